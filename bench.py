@@ -29,6 +29,12 @@ attention kernels do the same tile work on other values).  Such a line is the pe
 bound on what the group can reach — and says so in `config.emulated`.
 Weights are random-init (HF init, seed 2025), data is synthetic: there is no network for checkpoints/datasets.
 
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  `--full` adds what takes runs of its own:
+the per-kernel rooflines (`kernels`, `roofline.dominant_kernel`: HIP-event microbenchmarks of the hand-written kernels at
+the workload's shapes) and the CPU baseline (`cpu_baseline`: the oracle timed on the host cores).  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (see `dump_outputs`); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -547,6 +553,38 @@ def kernel_rooflines(workload: "Workload"):
     return out, allowed
 
 
+DUMP_SAMPLE_PER_TENSOR = 2048
+
+
+def dump_outputs(out_dir: str, stats: dict, trainer) -> dict:
+    """`--dump-outputs DIR`: what the last timed step computed, as DIR/<name>.npy — the statistics `Trainer.train_step`
+    returns (float64) and the optimizer state the step left behind (float32): the fp32 master weights and first moments at
+    DUMP_SAMPLE_PER_TENSOR positions per parameter drawn from a fixed seed (every position of a smaller parameter),
+    concatenated in the optimizer's parameter order.  Under a sharded engine: this rank's shards.  A few MB at 7B."""
+    opt = trainer.optimizer
+    if getattr(opt, "wait_updates", None):
+        opt.wait_updates()              # (updates pipelined under the next forward: the last step's has no next forward)
+    arrays = {k: v.detach().double().cpu().numpy() for k, v in stats.items() if isinstance(v, torch.Tensor)}
+    g = torch.Generator().manual_seed(0)
+    master, moment = [], []
+    for s in opt.state:
+        w, m = s["master"].reshape(-1), s["m"].reshape(-1)
+        n = w.numel()
+        idx = (torch.randint(0, n, (DUMP_SAMPLE_PER_TENSOR,), generator=g) if n > DUMP_SAMPLE_PER_TENSOR
+               else torch.arange(n)).to(w.device)
+        master.append(w[idx].float().cpu())
+        moment.append(m[idx].float().cpu())
+    arrays["master_weights_sample"] = torch.cat(master).numpy()
+    arrays["exp_avg_sample"] = torch.cat(moment).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB bound")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(gpus: int, argv=None) -> None:
     """`python bench.py --gpus N` (N > 1) WITHOUT a launcher: re-execute this command line under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -582,8 +620,12 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("TN_BENCH_WORKLOAD", "qwen2_audio_7b"))
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--seqlen", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-rooflines", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel rooflines (`kernels`) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (bench.dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-rooflines", action="store_true", help="with --full: leave out the per-kernel rooflines")
     ap.add_argument("--unfused-ce", action="store_true")
     ap.add_argument("--ce-chunk", type=int, default=None, help="tokens per lm_head+CE chunk (default: TrainConfig's)")
     ap.add_argument("--compact-lm-head", action="store_true",
@@ -715,6 +757,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t)
     ev_ms = ev0.elapsed_time(ev1) / args.steps
+    dumped = dump_outputs(args.dump_outputs, stats, trainer) if (args.dump_outputs and rank == 0) else None
 
     # reference convention: labels.numel() per data-parallel rank (train.py:345); the cp / tp peers of a rank work on the
     # SAME rows, so the job's tokens are dp x B x T.  An emulated rank reports its own share of them (1/cp of the
@@ -811,7 +854,7 @@ def main():
             "roofline": {"bound": "mfma", "achieved": round(fpt * (tps / gpus_in_job) / 1e12, 1), "peak": MFMA_PEAK / 1e12,
                          "unit": "TFLOP/s", "frac": round(mfu, 4), "traffic": None,
                          "note": "whole training step per GPU against the dense bf16 MFMA peak (reference MFU "
-                                 "formula); per-kernel rooflines of the hand-written HIP kernels in `kernels`"},
+                                 "formula); per-kernel rooflines of the hand-written HIP kernels in `kernels` (--full)"},
         }
         if wl.name.startswith("kimi_audio_7b"):
             line["mfu_convention"] = ("6*N + 12*L*H*Dh*T per token over the EXECUTED graph only: 28 decoder layers + text "
@@ -843,7 +886,7 @@ def main():
         elif args.workload != "tiny":
             try:
                 step_ms = elapsed / args.steps * 1e3
-                if args.no_kernel_rooflines:
+                if args.no_kernel_rooflines or not args.full:
                     # (the executed-FLOP fraction needs the allowed (query, key) pairs only, not the microbenchmarks:
                     #  VERDICT r4 #12 — with this switch the lines used to print the FORMULA value under that name)
                     allowed_pairs = allowed_attention_pairs(wl)
@@ -891,7 +934,7 @@ def main():
                                          "formula_frac": round(mfu, 4),
                                          "note": "whole training step per GPU against the dense bf16 MFMA peak: `frac` on the "
                                                  "FLOPs the step executes, `formula_frac` by the reference MFU formula; "
-                                                 "per-kernel rooflines of the hand-written HIP kernels in `kernels`"})
+                                                 "per-kernel rooflines of the hand-written HIP kernels in `kernels` (--full)"})
                 line["executed_flops_note"] = ("GEMM terms of the formula (6*N_wo_emb per token; tower on its 1500 frames "
                                                "per clip; an untied lm_head only on the rows it runs on) + attention on "
                                                "the allowed (query, key) pairs only, fwd + 2.5x bwd")
@@ -914,7 +957,9 @@ def main():
             else:
                 line["roofline"]["traffic_source"] = ("stale: profiles/" + os.path.basename(tfile) + " was taken with other "
                                                       "kernel sources / GEMM mode; re-run scripts/step_traffic.sh")
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl, n_params=int(trainer.num_params))
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

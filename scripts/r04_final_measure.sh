@@ -3,7 +3,7 @@
 # --kernel-trace --stats of the same command), whole-step HBM traffic (PMC, separate passes), then the bench line again so
 # that roofline.traffic is picked up with a matching source digest.   usage: bash scripts/r04_final_measure.sh <tag>
 R=$(pwd); tag=${1:-r04z}; out=$R/gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 python3 -c "
 import json; d=json.loads(open('$out/bench_default.json').read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['step_mfu'], d['roofline']['frac'], d['roofline'].get('traffic'))" | tee -a $out/summary.log
 cd /tmp

@@ -81,6 +81,25 @@ def _one_gpu_loss():
     return line["loss_per_sample_last"]
 
 
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without `--full`: K timed steps, no CPU baseline, the last
+    step's loss among the dumped arrays."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TN_FORCE_FSDP", "TN_DIST_BACKEND"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--workload", "tiny", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l][0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == set(line["dumped_outputs"]) and {"loss_per_sample", "master_weights_sample"} <= set(got)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert round(float(got["loss_per_sample"]), 5) == line["loss_per_sample_last"]
+
+
 def _devices():
     import torch
     return torch.cuda.device_count()
