@@ -356,6 +356,27 @@ int tn_gemm_bf16_tn(const void* A, const void* B, void* C, void* Ct, const void*
 void tn_gemm_set_persistent(int on);
 int tn_gemm_get_persistent(void);
 
+/* ---- Greedy decoding with a KV cache — touchnet/models/touch_audio/inference_touch_audio.py:177-192 (HF generate() with
+ *      use_cache=True, do_sample=False, num_beams=1, repetition_penalty, no_repeat_ngram_size; the per-token attention of
+ *      transformers/models/llama/modeling_llama.py:243-285 over past_key_values).
+ * attn_decode: q bf16 [B, Nh, D] and k_new / v_new bf16 [B, Nkv, D] of the new token (q, k_new rotated); caches bf16
+ *      [B, S_max, Nkv, D]; cache_len int32 [B] = entries valid before this call.  Writes k_new / v_new into slot
+ *      cache_len[b], attends over cache_len[b] + 1 keys (scale = softmax scale), writes o bf16 [B, Nh, D]; does NOT advance
+ *      cache_len.  cache_len[b] outside [0, S_max): row b's output is NaN, its cache untouched.  workspace: >=
+ *      tn_attn_decode_workspace_bytes(..) bytes, 16-byte aligned (NULL when that is 0).  -22 before any launch for NULL or
+ *      non-16-byte-aligned tensors, D not 64 / 128, Nh % Nkv != 0, Nh / Nkv > 16. */
+long long tn_attn_decode_workspace_bytes(int B, int Nh, int Nkv, int D, int S_max);
+int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
+                   void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream);
+/* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
+ *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
+ *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history
+ *      (0 = off), argmax (lowest id on ties); a finished row emits `pad`.  Then hist[b, hist_len[b]] = token,
+ *      hist_len[b]++, cache_len[b]++, and on `eos` finished[b] = 1, n_unfinished -= 1.  No host synchronisation.
+ *      -22 before any launch for NULL or misaligned pointers, V or S_hist out of range, ngram < 0, penalty <= 0. */
+int tn_greedy_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* finished, int* n_unfinished, int B,
+                   int V, int S_hist, float penalty, int ngram, int eos, int pad, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

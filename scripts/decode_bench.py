@@ -1,0 +1,182 @@
+"""KV-cache decoding on one MI355X: tn_attn_decode per call (µs, achieved TB/s) and greedy ASR decoding end to end on
+LlamaForASR-1B (random weights, eos unreachable: every run decodes max_new_tokens), against transformers' own bf16
+generate() (sdpa, same knobs, same weights).  Prints one JSON object per measurement.
+
+    python scripts/decode_bench.py [--skip-hf] [--layers 16] [--batch 12] [--new 256]
+
+bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
+row are noise beside it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+DEV = torch.device("cuda", 0)
+
+
+def _events_time(fn, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters * 1e3          # µs
+
+
+def bench_kernel(B, L, Nh, Nkv, D, iters=200):
+    import touchnet_amd.functional as F
+    S_max = L + 1
+    kc = torch.randn(B, S_max, Nkv, D, device=DEV, dtype=torch.bfloat16)
+    vc = torch.randn_like(kc)
+    q = torch.randn(B, Nh, D, device=DEV, dtype=torch.bfloat16)
+    kn = torch.randn(B, Nkv, D, device=DEV, dtype=torch.bfloat16)
+    cl = torch.full((B,), L - 1, dtype=torch.int32, device=DEV)           # L keys attended
+    flush = torch.empty(512 * 2 ** 20, dtype=torch.uint8, device=DEV)
+    with torch.no_grad():
+        for _ in range(10):
+            F.attn_decode(q, kn, kn, kc, vc, cl)
+        torch.cuda.synchronize()
+        hot = _events_time(lambda: F.attn_decode(q, kn, kn, kc, vc, cl), iters)
+        # cold: a 512 MiB write between calls evicts the caches from L2 / MALL; the flush is timed alone and subtracted
+        cold_total = _events_time(lambda: (flush.zero_(), F.attn_decode(q, kn, kn, kc, vc, cl)), 50)
+        flush_only = _events_time(lambda: flush.zero_(), 50)
+    nbytes = B * L * Nkv * D * 2 * 2
+    return dict(what="attn_decode", B=B, L=L, Nh=Nh, Nkv=Nkv, D=D, bytes=nbytes, us_back_to_back=round(hot, 2),
+                tbps_back_to_back=round(nbytes / hot / 1e6, 3), us_cold=round(cold_total - flush_only, 2),
+                tbps_cold=round(nbytes / (cold_total - flush_only) / 1e6, 3))
+
+
+def _model(layers):
+    from touchnet_amd.models.llama import DecoderConfig
+    from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
+    text = dict(model_type="llama", hidden_size=2048, intermediate_size=8192, num_attention_heads=32, num_key_value_heads=8,
+                head_dim=64, num_hidden_layers=layers, vocab_size=128256, rope_theta=500000.0, tie_word_embeddings=True,
+                rope_scaling={"factor": 32.0, "high_freq_factor": 4.0, "low_freq_factor": 1.0,
+                              "original_max_position_embeddings": 8192, "rope_type": "llama3"},
+                pad_token_id=128004, bos_token_id=128000, eos_token_id=128001, initializer_range=0.02, rms_norm_eps=1e-5)
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        m = TouchAudioForCausalLM(TouchAudioConfig(text_config=DecoderConfig.from_dict(text), input_size=400))
+    m.post_init()
+    return m.to(torch.bfloat16).eval(), text
+
+
+def bench_e2e(layers, B, new, skip_hf):
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.touch_audio.inference_touch_audio import build_prompts
+    m, text = _model(layers)
+    g = torch.Generator().manual_seed(1)
+    lens = torch.randint(60, 180, (B,), generator=g).tolist()      # AISHELL utterances: 2.4-7 s at 4 stacked 10 ms frames
+    feats = [torch.randn(n, 400, generator=g) * 0.5 for n in lens]
+    pr = build_prompts(feats, 128004, 128000)
+    cfg = G.GenerationConfig(max_new_tokens=new, eos_token_id=-1, pad_token_id=128004)      # eos unreachable
+    lm, proj = m.language_model, m.projector.weight
+    res = []
+    with torch.no_grad():
+        for _ in range(2):                                           # warm-up (GEMM algorithm selection, code objects)
+            G.generate(m, pr, G.GenerationConfig(max_new_tokens=8, eos_token_id=-1, pad_token_id=128004))
+        torch.cuda.synchronize()
+        P = [int(t.numel()) for t in pr.input_ids]
+        runs = []
+        for _ in range(3):
+            cache = G.KVCache.allocate(layers, B, max(P) + new, 8, 64, DEV)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            logits = G._prefill(lm, proj, pr, cache, DEV)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            import touchnet_amd.functional as F
+            F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, 1.5, 2,
+                          -1, 128004)
+            for _ in range(new - 1):
+                logits = G.decode_logits(lm, cache)
+                F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
+                              1.5, 2, -1, 128004)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            runs.append((t1 - t0, (t2 - t1) / (new - 1)))
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            G.generate(m, pr, cfg)
+            torch.cuda.synchronize()
+            runs[-1] = runs[-1] + (time.perf_counter() - t3,)
+        pre = min(r[0] for r in runs)
+        step = min(r[1] for r in runs)
+        total = min(r[2] for r in runs)
+        res.append(dict(what="touchnet_amd.generate", layers=layers, B=B, new_tokens=new, prompt_rows=lens,
+                        prefill_ms=round(pre * 1e3, 2), ms_per_decode_step=round(step * 1e3, 3),
+                        generate_total_ms=round(total * 1e3, 1)))
+    if not skip_hf:
+        import transformers
+        hf_cfg = transformers.LlamaConfig(vocab_size=128256, hidden_size=2048, intermediate_size=8192,
+                                          num_hidden_layers=layers, num_attention_heads=32, num_key_value_heads=8, head_dim=64,
+                                          rope_theta=500000.0, rope_scaling=text["rope_scaling"], tie_word_embeddings=True,
+                                          rms_norm_eps=1e-5, pad_token_id=128004, bos_token_id=128000,
+                                          max_position_embeddings=131072)
+        hf_cfg._attn_implementation = "sdpa"
+        with torch.device(DEV):
+            hf = transformers.LlamaForCausalLM(hf_cfg).to(torch.bfloat16).eval()
+        hf.load_state_dict({k: v for k, v in lm.state_dict().items()}, strict=False)
+        # the reference's batch: left-padded prompts, embed(ids) + projector(features)
+        T = max(P)
+        ids = torch.full((B, T), 128004, dtype=torch.int64)
+        fs = torch.zeros(B, T, 400)
+        mask = torch.zeros(B, T, dtype=torch.int64)
+        pos = torch.zeros(B, T, dtype=torch.int64)
+        for b in range(B):
+            n = P[b]
+            ids[b, T - n:] = pr.input_ids[b]
+            fs[b, T - n:] = pr.input_features[b]
+            mask[b, T - n:] = 1
+            pos[b, T - n:] = torch.arange(n)
+        ids, fs, mask, pos = ids.to(DEV), fs.to(DEV, torch.bfloat16), mask.to(DEV), pos.to(DEV)
+        with torch.no_grad():
+            emb = hf.model.embed_tokens(ids) + fs @ proj.t()
+            kw = dict(inputs_embeds=emb, attention_mask=mask, use_cache=True, do_sample=False, num_beams=1,
+                      repetition_penalty=1.5, no_repeat_ngram_size=2, pad_token_id=128004, eos_token_id=None,
+                      bos_token_id=128000)
+            hf.generate(**kw, max_new_tokens=8)
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(2):
+                t0 = time.perf_counter()
+                out = hf.generate(**kw, max_new_tokens=new, min_new_tokens=new)
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+        res.append(dict(what="transformers.generate (bf16, sdpa)", layers=layers, B=B, new_tokens=int(out.shape[1]),
+                        generate_total_ms=round(min(times) * 1e3, 1),
+                        ms_per_token_incl_prefill=round(min(times) * 1e3 / new, 3)))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--skip-hf", action="store_true")
+    ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--layers", type=int, default=16)
+    ap.add_argument("--batch", type=int, default=12)
+    ap.add_argument("--new", type=int, default=256)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench needs the MI355X")
+    from touchnet_amd import build
+    build.build()
+    print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    for B, L in ((64, 8192), (12, 600)):
+        for Nh, Nkv, D in ((32, 8, 64), (28, 4, 128)):
+            r = bench_kernel(B, L, Nh, Nkv, D)
+            print(json.dumps(r), flush=True)
+    if not a.skip_e2e:
+        for r in bench_e2e(a.layers, a.batch, a.new, a.skip_hf):
+            print(json.dumps(r), flush=True)
+
+
+if __name__ == "__main__":
+    main()

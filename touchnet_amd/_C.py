@@ -88,9 +88,13 @@ PROTOTYPES = {
     "tn_gemm_bf16_swiglu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _vp],
     "tn_gemm_set_persistent": [_i],
     "tn_gemm_get_persistent": [],
+    "tn_attn_decode_workspace_bytes": [_i, _i, _i, _i, _i],
+    "tn_attn_decode": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "tn_greedy_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp],
 }
 _RESTYPE = {"tn_gemm_set_persistent": None, "tn_version": C.c_char_p, "tn_sumsq_multi_chunk": C.c_longlong, "tn_adamw_multi_chunk": C.c_longlong,
-            "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_grouped_workspace_bytes": C.c_longlong}
+            "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_grouped_workspace_bytes": C.c_longlong,
+            "tn_attn_decode_workspace_bytes": C.c_longlong}
 
 # kernel-development entry points: exported by the library, deliberately NOT part of the C ABI (include/touchnet_amd.h)
 DEV_PROTOTYPES = {

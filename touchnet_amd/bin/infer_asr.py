@@ -1,0 +1,151 @@
+"""Greedy ASR decoding of a data list with a LlamaForASR (TouchAudioForCausalLM) checkpoint on one MI355X — the command of
+touchnet/models/touch_audio/inference_touch_audio.py (same inputs, same output lines), decoded by touchnet_amd.generation.
+
+    python -m touchnet_amd.bin.infer_asr --model_path CKPT_DIR --data_list data.list --output_dir OUT [--batch_size 12]
+        [--shard_index i --num_shards n]
+
+CKPT_DIR holds HF-format `*.safetensors` (the parameter names of TouchAudioForCausalLM are Hugging Face's) and a model
+config (`config.json` in the directory, else `../../model_config.json` as the reference reads it); the data config comes
+from `--data_config` or `CKPT_DIR/../../data_config.json` (fbank, 80 bins, stacking to the projector width when absent).
+`data.list`: one JSON object per line with at least "key" and "wav" (16-bit PCM wav).  Output:
+OUT/part_{i+1}_of_{n}, one JSON line per utterance: {"label": the input line, "predict_ids": [...], "predict": text} —
+"predict" only when CKPT_DIR has a tokenizer.  One GPU per process; `--shard_index / --num_shards` split the list
+without collectives.
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import json
+import os
+import types
+import wave
+
+import numpy as np
+import torch
+
+from touchnet_amd.data import functions as stages
+from touchnet_amd.generation import GenerationConfig
+from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
+from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
+
+_DATA_DEFAULTS = dict(audio_feat_type="fbank", audiofeat_num_mel_bins=80, audiofeat_dither=0.0, audiofeat_frame_length=25,
+                      audiofeat_frame_shift=10, audiofeat_n_fft=400, audiofeat_hop_length=160, audiofeat_padding=0,
+                      audiofeat_stack_length=None, audiofeat_stride_length=None, audiofeat_normalize=True,
+                      audio_resample_rate=16000)
+
+
+def _first(*paths):
+    for p in paths:
+        if p and os.path.exists(p):
+            return p
+    return None
+
+
+def load_model(model_path: str, device) -> TouchAudioForCausalLM:
+    from safetensors.torch import load_file
+    cfg_path = _first(os.path.join(model_path, "config.json"), os.path.join(model_path, "..", "..", "model_config.json"))
+    if cfg_path is None:
+        raise FileNotFoundError(f"no config.json / ../../model_config.json beside {model_path}")
+    with open(cfg_path) as f:
+        d = json.load(f)
+    cfg = TouchAudioConfig.from_dict(d)
+    for k in ("pad_token_id", "bos_token_id", "eos_token_id"):      # (top-level ids of an HF config reach the decoder)
+        if getattr(cfg.text_config, k) is None and d.get(k) is not None:
+            setattr(cfg.text_config, k, d[k])
+    model = TouchAudioForCausalLM(cfg)
+    sd = {}
+    files = sorted(glob.glob(os.path.join(model_path, "*.safetensors")))
+    if not files:
+        raise FileNotFoundError(f"no *.safetensors in {model_path}")
+    for f in files:
+        sd.update(load_file(f))
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    missing = [k for k in missing if not (k == "language_model.lm_head.weight" and cfg.text_config.tie_word_embeddings)]
+    if missing or unexpected:
+        raise RuntimeError(f"checkpoint does not match TouchAudioForCausalLM: missing {missing}, unexpected {unexpected}")
+    model.language_model.tie_weights()
+    return model.to(device).to(torch.bfloat16).eval()
+
+
+def data_config(args, model) -> types.SimpleNamespace:
+    d = dict(_DATA_DEFAULTS)
+    p = _first(args.data_config, os.path.join(args.model_path, "..", "..", "data_config.json"))
+    if p is not None:
+        with open(p) as f:
+            d.update(json.load(f))
+    if d["audiofeat_stack_length"] is None:
+        d["audiofeat_stack_length"] = max(1, model.config.input_size // int(d["audiofeat_num_mel_bins"]))
+    if d["audiofeat_stride_length"] is None:
+        d["audiofeat_stride_length"] = d["audiofeat_stack_length"]
+    return types.SimpleNamespace(**d)
+
+
+def read_wav(path: str) -> torch.Tensor:
+    """16-bit PCM wav -> int16 [1, N] (first channel)."""
+    with wave.open(path, "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError(f"{path}: 16-bit PCM only")
+        ch, rate = w.getnchannels(), w.getframerate()
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, ch)[:, 0].copy()
+    if rate != 16000:
+        raise ValueError(f"{path}: {rate} Hz; the device frontend is 16 kHz only")
+    return torch.from_numpy(pcm)[None]
+
+
+def features(wavs, dcfg) -> list:
+    """The device frontend stages of the data config: fbank / log-mel, then stacking."""
+    if dcfg.audio_feat_type == "fbank":
+        feat_stage = stages.audio_compute_fbank
+    elif dcfg.audio_feat_type == "log_mel_spectrogram":
+        feat_stage = stages.audio_compute_log_mel_spectrogram
+    else:
+        raise ValueError(f"unsupported audio_feat_type {dcfg.audio_feat_type!r}")
+    samples = [{"sample_rate": 16000, "waveform": w} for w in wavs]
+    return [s["audiofeat"] for s in stages.audiofeat_stack(feat_stage(iter(samples), dcfg), dcfg)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model_path", required=True)
+    ap.add_argument("--data_list", required=True)
+    ap.add_argument("--output_dir", required=True)
+    ap.add_argument("--data_config", default=None)
+    ap.add_argument("--batch_size", type=int, default=12)
+    ap.add_argument("--max_new_tokens", type=int, default=256)
+    ap.add_argument("--repetition_penalty", type=float, default=1.5)
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=2)
+    ap.add_argument("--shard_index", type=int, default=0)
+    ap.add_argument("--num_shards", type=int, default=1)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = load_model(args.model_path, device)
+    dcfg = data_config(args, model)
+    tokenizer = None
+    if _first(os.path.join(args.model_path, "tokenizer.json"), os.path.join(args.model_path, "tokenizer_config.json")):
+        from transformers import AutoTokenizer
+        tokenizer = AutoTokenizer.from_pretrained(args.model_path)
+    with open(args.data_list) as f:
+        items = [json.loads(line) for line in f if line.strip()]
+    items = items[args.shard_index::args.num_shards]
+    cfg = GenerationConfig(max_new_tokens=args.max_new_tokens, repetition_penalty=args.repetition_penalty,
+                           no_repeat_ngram_size=args.no_repeat_ngram_size)
+    os.makedirs(args.output_dir, exist_ok=True)
+    out_path = os.path.join(args.output_dir, f"part_{args.shard_index + 1}_of_{args.num_shards}")
+    with open(out_path, "w") as writer:
+        for i in range(0, len(items), args.batch_size):
+            batch = items[i:i + args.batch_size]
+            feats = features([read_wav(it["wav"]) for it in batch], dcfg)
+            ids = transcribe(model, feats, cfg)
+            for it, row in zip(batch, ids):
+                rec = {"label": json.dumps(it, ensure_ascii=False), "predict_ids": row}
+                if tokenizer is not None:
+                    rec["predict"] = tokenizer.decode(row, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+                writer.write(json.dumps(rec, ensure_ascii=False) + "\n")
+    return out_path
+
+
+if __name__ == "__main__":
+    main()

@@ -1518,3 +1518,20 @@ def feat_augment(feat: torch.Tensor, t_masks=(), f_masks=(), subs=(), out_rows: 
 def audiofeat_stack(feat: torch.Tensor, stack: int, stride: int, normalize: bool = True) -> torch.Tensor:
     """feat fp32 [T, F] -> fp32 [ceil(T/stride), F*stack] (functions.py:258-286)."""
     return L.audiofeat_stack(_c(feat).float(), int(stack), int(stride), bool(normalize))
+
+
+# ------------------------------------------------------------------------------------ KV-cache decoding (generation.py)
+def attn_decode(q, k_new, v_new, k_cache, v_cache, cache_len, scale: Optional[float] = None):
+    """Attention of ONE new token per row over a KV cache (the per-token attention of HF generate() with use_cache):
+    q [B, Nh, D], k_new / v_new [B, Nkv, D] (q and k rotated), caches bf16 [B, S_max, Nkv, D], cache_len int32 [B].
+    k_new / v_new are stored at slot cache_len[b]; returns o [B, Nh, D].  cache_len is advanced by `greedy_step`."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return L.attn_decode_(q, k_new, v_new, k_cache, v_cache, cache_len, float(scale))
+
+
+def greedy_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty: float = 1.0, ngram: int = 0,
+                eos: int = -1, pad: int = 0) -> None:
+    """Repetition penalty + no-repeat-n-gram ban + argmax of HF generate() on logits [B, V], appended to the device
+    history `hist` [B, S_hist] (int32); advances hist_len / cache_len, marks rows that emitted `eos` finished."""
+    L.greedy_step_(logits, hist, hist_len, cache_len, finished, n_unfinished, float(penalty), int(ngram), int(eos), int(pad))

@@ -882,7 +882,68 @@ def _(feat, quantizer, codebook):
     return feat.new_empty(feat.shape[0], dtype=torch.int64)
 
 
+# ===================================================================================================== KV-cache decoding
+def _no_grad_inputs(what, *ts):
+    if any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"{what}: inference only (no autograd formula); call it under torch.no_grad() on detached tensors")
+
+
+@custom_op(f"{NS}::attn_decode_", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def attn_decode_(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, cache_len: Tensor,
+                 scale: float) -> Tensor:
+    """One new token per row over a KV cache (tn_attn_decode): q [B, Nh, D], k_new / v_new [B, Nkv, D] (q, k rotated), caches
+    [B, S_max, Nkv, D] bf16, cache_len int32 [B].  Stores k_new / v_new at slot cache_len[b] of the caches and returns
+    o [B, Nh, D]; cache_len is not advanced."""
+    _no_grad_inputs("attn_decode_", q, k_new, v_new, k_cache, v_cache)
+    B, Nh, D = q.shape
+    S_max, Nkv = k_cache.shape[1], k_cache.shape[2]
+    if (q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16
+            or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16 or cache_len.dtype != torch.int32
+            or tuple(k_new.shape) != (B, Nkv, D) or tuple(v_new.shape) != (B, Nkv, D)
+            or tuple(k_cache.shape) != (B, S_max, Nkv, D) or tuple(v_cache.shape) != (B, S_max, Nkv, D)
+            or tuple(cache_len.shape) != (B,) or not k_cache.is_contiguous() or not v_cache.is_contiguous()):
+        raise _C.KernelError("attn_decode_: bf16 q [B, Nh, D], k_new / v_new [B, Nkv, D], contiguous caches "
+                             "[B, S_max, Nkv, D], int32 cache_len [B]")
+    q, k_new, v_new, cache_len = _c(q), _c(k_new), _c(v_new), _c(cache_len)
+    o = torch.empty_like(q)
+    nbytes = int(_lib().tn_attn_decode_workspace_bytes(B, Nh, Nkv, D, S_max))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    _C.check(_lib().tn_attn_decode(_p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(cache_len), _p(o), _p(ws),
+                                   B, Nh, Nkv, D, S_max, float(scale), _cur()), "tn_attn_decode")
+    return o
+
+
+@attn_decode_.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, cache_len, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+@custom_op(f"{NS}::greedy_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished"),
+           device_types="cuda")
+def greedy_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor, n_unfinished: Tensor,
+                 penalty: float, ngram: int, eos: int, pad: int) -> None:
+    """One greedy step of HF generate() (tn_greedy_step): logits [B, V] fp32 / bf16; hist int32 [B, S_hist], hist_len /
+    cache_len / finished int32 [B], n_unfinished int32 [1] — all advanced on the device."""
+    _no_grad_inputs("greedy_step_", logits)
+    B, V = logits.shape
+    for t, shape in ((hist_len, (B,)), (cache_len, (B,)), (finished, (B,)), (n_unfinished, (1,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _C.KernelError("greedy_step_: int32 hist_len / cache_len / finished [B], n_unfinished [1]")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != B or not hist.is_contiguous():
+        raise _C.KernelError("greedy_step_: int32 contiguous hist [B, S_hist]")
+    logits = _c(logits)
+    _C.check(_lib().tn_greedy_step(_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(finished), _p(n_unfinished), B, V,
+                                   hist.shape[1], float(penalty), int(ngram), int(eos), int(pad), _C.dcode(logits), _cur()),
+             "tn_greedy_step")
+
+
+@greedy_step_.register_fake
+def _(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty, ngram, eos, pad):
+    return None
+
+
 OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
-       "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize")
+       "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
+       "attn_decode_", "greedy_step_")

@@ -74,12 +74,15 @@ class Attention(nn.Module):
         self.o_proj = nn.Linear(self.num_heads * D, H, bias=False)
         self.scaling = D ** -0.5
 
-    def forward(self, x, cos, sin, mask, keep_rows=None, norm_src=None):
+    def forward(self, x, cos, sin, mask, keep_rows=None, norm_src=None, kv_out=None):
         """`keep_rows` (flat indices into B*T, last decoder layer only): the output projection runs on those rows only and
         the result is [1, len(keep_rows), H] — see DecoderModel.forward.  `norm_src`: x is the RMSNorm of that tensor
-        (functional.norm_source; op-level selective activation checkpointing)."""
+        (functional.norm_source; op-level selective activation checkpointing).  `kv_out` (a list, inference prefill): the
+        rotated keys and the values, [B, T, Nkv, D] each, are appended to it as a pair."""
         B, T, _ = x.shape
         cp = getattr(mask, "cp", None)
+        if kv_out is not None and cp is not None:
+            raise RuntimeError("kv_out is not available under context parallelism")
         if cp is not None and cp.need is not None:
             return self._forward_context_parallel(x, cos, sin, mask, cp)
         # one autograd node for the three projections of x: their weight gradients run as ONE GEMM in the forward
@@ -98,6 +101,8 @@ class Attention(nn.Module):
         q = q.view(B, T, self.num_heads, self.head_dim)
         k = k.view(B, T, self.num_kv_heads, self.head_dim)
         v = v.view(B, T, self.num_kv_heads, self.head_dim)
+        if kv_out is not None:
+            kv_out.append((k, v))
         if cp is not None:            # context parallel, all-gather rotate method (utils/context_parallel.py)
             a = ops().packed_attention_sharded(q, cp.gather_seq(k), cp.gather_seq(v), mask, cp.seq_shard(),
                                                self.scaling)
@@ -159,9 +164,10 @@ class DecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(config.hidden_size, config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, config.rms_norm_eps)
 
-    def forward(self, delta, residual, cos, sin, mask, keep_rows=None):
+    def forward(self, delta, residual, cos, sin, mask, keep_rows=None, kv_out=None):
         """`delta` is the previous sub-layer's output still to be added to the `residual` stream.
-        `keep_rows`: everything behind the attention core (o_proj, residual, norm, MLP) runs on those rows only."""
+        `keep_rows`: everything behind the attention core (o_proj, residual, norm, MLP) runs on those rows only.
+        `kv_out`: see Attention.forward."""
         # `_tn_recompute_rows` (set by parallelize.apply_ac for the reference's selective AC option "op"): the GEMM nodes
         # keep the residual stream instead of the norm outputs and recompute the row kernels (norms, SwiGLU product) in
         # their backward — functional.norm_source
@@ -172,7 +178,8 @@ class DecoderLayer(nn.Module):
         else:
             x, residual = self.input_layernorm(delta, residual)
         src = ops().norm_source(residual, self.input_layernorm.weight, self.input_layernorm.variance_epsilon) if sac else None
-        a = self.self_attn(x, cos, sin, mask, keep_rows, norm_src=src)
+        a = (self.self_attn(x, cos, sin, mask, keep_rows, norm_src=src) if kv_out is None
+             else self.self_attn(x, cos, sin, mask, keep_rows, norm_src=src, kv_out=kv_out))
         if keep_rows is not None:
             residual = residual.reshape(-1, residual.shape[-1]).index_select(0, keep_rows)[None]
         x, residual = self.post_attention_layernorm(a, residual)
@@ -226,7 +233,7 @@ class DecoderModel(nn.Module):
         return emb_c, pos_c, doc_c, keep_rows, rows, overflow
 
     def forward(self, input_ids=None, inputs_embeds=None, position_ids=None, attention_mask=None,
-                context_parallel=None, keep_rows=None, valid_rows_max=None):
+                context_parallel=None, keep_rows=None, valid_rows_max=None, kv_out=None):
         """With `context_parallel` (utils.context_parallel.ContextParallel): input_ids / inputs_embeds /
         position_ids are this rank's sequence shard [B, T/cp], `attention_mask` stays the GLOBAL [B, T]
         document-id tensor (it is tiny and every rank needs the tile metadata of the keys it attends to).
@@ -236,7 +243,10 @@ class DecoderModel(nn.Module):
         norm, MLP, final norm: 3/4 of that layer's GEMM work — is computed for the kept rows alone; all earlier layers and
         the last layer's q/k/v + attention see every row (they are the keys and values of later positions).  The caller
         keeps the rows that carry a label (ASR-SFT batches: ~5 % of the positions); results on those rows are what the
-        full computation gives."""
+        full computation gives.
+
+        `kv_out` (a list; the prefill of generation.generate): every layer appends its rotated keys and its values,
+        [B, T, Nkv, D] each, in the input's own row layout (padding slots are not dropped then)."""
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         B, T, _ = inputs_embeds.shape
@@ -244,7 +254,7 @@ class DecoderModel(nn.Module):
             position_ids = torch.arange(T, device=inputs_embeds.device).expand(B, T)
         sp = getattr(self, "_tn_sp", None)
         dropped = None
-        if (SKIP_PAD_ROWS and valid_rows_max is not None and context_parallel is None and sp is None
+        if (SKIP_PAD_ROWS and valid_rows_max is not None and context_parallel is None and sp is None and kv_out is None
                 and isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 2
                 and not attention_mask.dtype.is_floating_point):
             dropped = self._drop_pad_rows(inputs_embeds, position_ids, attention_mask, keep_rows, valid_rows_max)
@@ -264,13 +274,16 @@ class DecoderModel(nn.Module):
         # T/tp rows between the blocks; attention and MLP gather / reduce-scatter around their own bodies
         if sp is not None and keep_rows is not None:
             raise RuntimeError("keep_rows is not available under sequence parallelism")
+        if sp is not None and kv_out is not None:
+            raise RuntimeError("kv_out is not available under sequence parallelism")
+        kw = {} if kv_out is None else {"kv_out": kv_out}
         delta, residual = (inputs_embeds if sp is None else sp.scatter(inputs_embeds)), None
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
             if keep_rows is not None and i == last:
-                delta, residual = layer(delta, residual, cos, sin, mask, keep_rows)
+                delta, residual = layer(delta, residual, cos, sin, mask, keep_rows, **kw)
             else:
-                delta, residual = layer(delta, residual, cos, sin, mask)
+                delta, residual = layer(delta, residual, cos, sin, mask, **kw)
         h, _ = self.norm(delta, residual)
         if dropped is not None:
             # a bound below the real count dropped real tokens: NaN in every output (and through it every gradient)
