@@ -376,6 +376,24 @@ int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_
  *      -22 before any launch for NULL or misaligned pointers, V or S_hist out of range, ngram < 0, penalty <= 0. */
 int tn_greedy_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* finished, int* n_unfinished, int B,
                    int V, int S_hist, float penalty, int ngram, int eos, int pad, int dtype, void* stream);
+/* sample_step: one decoding step of HF generate() with the sampling warpers — what a Qwen2-Audio checkpoint's
+ *      generation_config.json asks of touchnet/models/qwen2_audio/inference_qwen2_audio.py (model.generate(**inputs,
+ *      max_length=..., use_cache=True)); transformers/generation/logits_process.py RepetitionPenaltyLogitsProcessor,
+ *      TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, then generation/utils.py's multinomial draw.
+ *      logits [B, V] (`dtype`), V <= 262144; hist / hist_len / cache_len / finished / n_unfinished as for greedy_step.
+ *      Per row: fp32 logits, repetition penalty over hist[b, :hist_len[b]] (each id once); with do_sample: l / temperature,
+ *      top_k (0 = off; ties at the k-th value stay), top_p (keep a token iff the softmax mass strictly above it is < top_p;
+ *      1 = off), then the first kept token in id order whose running sum of exp(l - max) exceeds u * (sum over the kept),
+ *      u in [0, 1) from Philox4x32-10 keyed by `seed` with counter (hist_len[b], row_key[b]) — or uniforms[b] when
+ *      `uniforms` (fp32 [B]) is not NULL; row_key int64 [B] (NULL: the row index).  Without do_sample: argmax (lowest id
+ *      on ties).  A finished row emits `pad`; then the bookkeeping of greedy_step, with up to 8 `eos_ids` (host array)
+ *      finishing a row.  n_kept (int32 [B], may be NULL): tokens left after top-k / top-p.  No host synchronisation.
+ *      -22 before any launch for NULL or misaligned pointers, V or S_hist out of range, penalty <= 0, n_eos outside
+ *      [0, 8], and with do_sample temperature <= 0, top_k < 0 or top_p outside (0, 1]. */
+int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* finished, int* n_unfinished,
+                   const long long* row_key, const float* uniforms, int* n_kept, int B, int V, int S_hist, float penalty,
+                   int do_sample, float temperature, int top_k, float top_p, unsigned long long seed, const int* eos_ids,
+                   int n_eos, int pad, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,11 @@ LlamaForASR-1B (random weights, eos unreachable: every run decodes max_new_token
 generate() (sdpa, same knobs, same weights).  Prints one JSON object per measurement.
 
     python scripts/decode_bench.py [--skip-hf] [--layers 16] [--batch 12] [--new 256]
+    python scripts/decode_bench.py --qwen2-audio-7b [--batch 12]
+
+--qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
+per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
+(decode_logits + tn_sample_step, top_k 50 / top_p 0.9, caches of ~300 tokens per row).
 
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
@@ -156,6 +161,57 @@ def bench_e2e(layers, B, new, skip_hf):
     return res
 
 
+def bench_qwen2_audio_7b(B, steps=32, iters=200):
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    V = 156032
+    g = torch.Generator(device=DEV).manual_seed(0)
+    logits = (torch.randn(B, V, device=DEV, generator=g) * 3).to(torch.bfloat16)
+    hist = torch.randint(0, V, (B, 512), device=DEV, generator=g, dtype=torch.int32)
+    z = lambda: torch.zeros(B, dtype=torch.int32, device=DEV)
+    fin, nu, keys = z(), torch.ones(1, dtype=torch.int32, device=DEV), torch.arange(B, device=DEV)
+    rows = []
+    for name, smp, k, p in (("top_k 20 + top_p 0.8", True, 20, 0.8), ("top_k 50 + top_p 0.9", True, 50, 0.9),
+                            ("top_p 0.9", True, 0, 0.9), ("greedy", False, 0, 1.0)):
+        hl, cl = torch.full((B,), 300, dtype=torch.int32, device=DEV), z()
+
+        def call():
+            hl.fill_(300)
+            F.sample_step(logits, hist, hl, cl, fin, nu, 1.1, smp, 0.7, k, p, 1, [151643, 151645], 151643, row_key=keys)
+        call()
+        us = _events_time(call, iters)
+        rows.append(dict(kernel="tn_sample_step", mode=name, B=B, V=V, us=round(us, 2)))
+    text = DecoderConfig.from_dict(dict(model_type="qwen2", hidden_size=4096, intermediate_size=11008, num_attention_heads=32,
+                                        num_key_value_heads=32, head_dim=128, num_hidden_layers=32, vocab_size=V,
+                                        rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=False,
+                                        initializer_range=0.02, eos_token_id=151643, pad_token_id=151643))
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        lm = PackedCausalLM(text)
+    lm.post_init()
+    lm = lm.to(torch.bfloat16).eval()
+    lens = [300] * B
+    prompts = G.Prompts([torch.randint(0, 150000, (n,)) for n in lens])
+    cache = G.KVCache.allocate(32, B, max(lens) + steps + 8, 32, 128, DEV)
+    with torch.no_grad():
+        logits = G._prefill(lm, None, prompts, cache, DEV)
+
+        def step():
+            F.sample_step(G.decode_logits(lm, cache), cache.hist, cache.hist_len, cache.cache_len, cache.finished,
+                          cache.n_unfinished, 1.1, True, 0.7, 50, 0.9, 1, [151643, 151645], 151643, row_key=keys)
+        F.sample_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, 1.1,
+                      True, 0.7, 50, 0.9, 1, [151643, 151645], 151643, row_key=keys)
+        step()
+        ms = _events_time(step, steps - 2) / 1e3
+    k50 = next(r["us"] for r in rows if r["mode"] == "top_k 50 + top_p 0.9")
+    rows.append(dict(e2e="qwen2_audio_7b_decode_step", B=B, ms_per_step=round(ms, 3),
+                     sample_share_top_k50_top_p=round(k50 / (ms * 1e3), 4),
+                     sample_share_top_p_only=round(next(r["us"] for r in rows if r.get("mode") == "top_p 0.9") /
+                                                   (ms * 1e3), 4)))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -163,12 +219,17 @@ def main():
     ap.add_argument("--layers", type=int, default=16)
     ap.add_argument("--batch", type=int, default=12)
     ap.add_argument("--new", type=int, default=256)
+    ap.add_argument("--qwen2-audio-7b", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.qwen2_audio_7b:
+        for r in bench_qwen2_audio_7b(a.batch):
+            print(json.dumps(r), flush=True)
+        return
     for B, L in ((64, 8192), (12, 600)):
         for Nh, Nkv, D in ((32, 8, 64), (28, 4, 128)):
             r = bench_kernel(B, L, Nh, Nkv, D)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TN_AMD_LIB: kernel-development hook (scripts/build_variant.sh builds -D variants of the same library)
 LIB_PATH = os.environ.get("TN_AMD_LIB") or os.path.join(_HERE, "_lib", "libtouchnet_amd.so")
 
-_vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
+_vp, _i, _f, _ll, _ull = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 PROTOTYPES = {
@@ -91,16 +91,19 @@ PROTOTYPES = {
     "tn_attn_decode_workspace_bytes": [_i, _i, _i, _i, _i],
     "tn_attn_decode": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "tn_greedy_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp],
+    "tn_sample_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _i, _f, _ull, _vp, _i, _i, _i,
+                       _vp],
 }
 _RESTYPE = {"tn_gemm_set_persistent": None, "tn_version": C.c_char_p, "tn_sumsq_multi_chunk": C.c_longlong, "tn_adamw_multi_chunk": C.c_longlong,
             "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_grouped_workspace_bytes": C.c_longlong,
-            "tn_attn_decode_workspace_bytes": C.c_longlong}
+            "tn_attn_decode_workspace_bytes": C.c_longlong, "tn_philox4x32_10": None}
 
 # kernel-development entry points: exported by the library, deliberately NOT part of the C ABI (include/touchnet_amd.h)
 DEV_PROTOTYPES = {
     "tn_attn_fwd_ablate": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],   # scripts/attn_ablate.py
     "tn_attn_fwd_stream_trace": [_vp],         # scripts/r06_attn_trace.py
     "tn_attn_set_fwd_schedule": [_i],
+    "tn_philox4x32_10": [_vp, _ull],          # the host twin of tn_sample_step's generator (tests)
     "tn_attn_set_bwd_dq": [_i],                # A/B of the dQ kernels inside one process (scripts/r06_attn_bwd_ab.py)      # A/B of the forward schedules inside one process (scripts/r06_attn_ab.py)
 }
 

@@ -1535,3 +1535,15 @@ def greedy_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penal
     """Repetition penalty + no-repeat-n-gram ban + argmax of HF generate() on logits [B, V], appended to the device
     history `hist` [B, S_hist] (int32); advances hist_len / cache_len, marks rows that emitted `eos` finished."""
     L.greedy_step_(logits, hist, hist_len, cache_len, finished, n_unfinished, float(penalty), int(ngram), int(eos), int(pad))
+
+
+def sample_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty: float = 1.0, do_sample: bool = True,
+                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, eos=(), pad: int = 0,
+                row_key=None, uniforms=None, n_kept=None) -> None:
+    """Repetition penalty, temperature, top-k, top-p and a seeded draw of HF generate() on logits [B, V] (argmax when
+    `do_sample` is False), appended to the device history `hist` [B, S_hist] (int32); advances hist_len / cache_len, marks
+    rows that emitted one of the `eos` ids (at most 8) finished.  The draw of row b depends only on (seed, row_key[b],
+    hist_len[b]); `uniforms` fp32 [B] fixes it instead."""
+    eos = [int(e) for e in ([eos] if isinstance(eos, int) else eos)]
+    L.sample_step_(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, uniforms, n_kept, float(penalty),
+                   bool(do_sample), float(temperature), int(top_k), float(top_p), int(seed), eos, int(pad))

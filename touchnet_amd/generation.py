@@ -12,11 +12,18 @@ repetition_penalty=1.5, no_repeat_ngram_size=2, max_new_tokens=256, eos / pad).
 There is no host synchronisation inside the loop: the host reads the count of unfinished rows every `check_every` steps.
 Device state invariant after every greedy step: cache_len[b] = hist_len[b] - 1 (the newest token is not cached yet; its
 position is cache_len[b]).
+
+Sampling (do_sample, several eos ids: what a Qwen2-Audio checkpoint's generation_config.json asks for,
+`GenerationConfig.from_hf`) runs the same loop with tn_sample_step in place of tn_greedy_step.  The caches start at
+`longest prompt + min(new tokens, cache_chunk)` rows and double when the host's step counter reaches their capacity (the
+host knows the step count: no sync), so a max_length of 70 000 does not allocate 70 000 rows per layer up front.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
-from typing import List, Optional
+import json
+import os
+from dataclasses import dataclass, fields
+from typing import Callable, List, Optional, Sequence, Union
 
 import torch
 
@@ -24,16 +31,88 @@ from . import _C
 from . import functional as F
 
 
+# generation_config.json keys this path does not implement, with the value that leaves them inert (HF's defaults)
+_UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "typical_p": 1.0, "min_p": None,
+                "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "top_h": None, "bad_words_ids": None, "force_words_ids": None,
+                "sequence_bias": None, "constraints": None, "min_length": 0, "min_new_tokens": None,
+                "suppress_tokens": None, "begin_suppress_tokens": None, "forced_bos_token_id": None,
+                "forced_eos_token_id": None, "encoder_repetition_penalty": 1.0, "encoder_no_repeat_ngram_size": 0,
+                "exponential_decay_length_penalty": None, "guidance_scale": None, "watermarking_config": None,
+                "renormalize_logits": False, "num_return_sequences": 1, "assistant_model": None,
+                "prompt_lookup_num_tokens": None, "max_time": None, "stop_strings": None, "dola_layers": None,
+                "diversity_penalty": 0.0}
+
+
 @dataclass
 class GenerationConfig:
-    """The knobs of the reference's generate() call (top_k / top_p / temperature are inert there: do_sample=False)."""
-    max_new_tokens: int = 256
+    """The knobs of the reference's generate() call (top_k / top_p / temperature are inert there: do_sample=False).
+    `from_hf` reads a checkpoint's generation_config.json instead."""
+    max_new_tokens: Optional[int] = 256      # None: max_length - the longest prompt (HF's rule)
     repetition_penalty: float = 1.5
     no_repeat_ngram_size: int = 2
-    eos_token_id: Optional[int] = None       # None: the model config's
+    eos_token_id: Optional[Union[int, List[int]]] = None       # None: the model config's; a list: any of them finishes
     pad_token_id: Optional[int] = None
     bos_token_id: Optional[int] = None
     check_every: int = 16                    # steps between two host reads of the unfinished count
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 50                          # 0: off (inert unless do_sample)
+    top_p: float = 1.0                       # 1: off (inert unless do_sample)
+    seed: int = 0                            # Philox key of the draws (with the row key and the step)
+    max_length: Optional[int] = None         # prompt + new tokens, used when max_new_tokens is None
+    cache_chunk: int = 1024                  # new-token rows of the first KV-cache allocation (it doubles on demand)
+
+    @classmethod
+    def from_hf(cls, path_or_dict, **overrides) -> "GenerationConfig":
+        """A generation_config.json (its path, its directory or its parsed dict) resolved as HF generate() resolves it:
+        HF's defaults for absent keys, the sampling warpers inert without do_sample, a file `max_new_tokens` taking
+        precedence over `max_length`.  Keys this path does not implement raise instead of being ignored.  `overrides`
+        (field names of this class) win over the file, except that the file's max_new_tokens still beats max_length."""
+        if isinstance(path_or_dict, dict):
+            d = dict(path_or_dict)
+        else:
+            p = str(path_or_dict)
+            if os.path.isdir(p):
+                p = os.path.join(p, "generation_config.json")
+            with open(p) as f:
+                d = json.load(f)
+        known = {f.name for f in fields(cls)}
+        bad = [k for k in overrides if k not in known]
+        if bad:
+            raise TypeError(f"GenerationConfig.from_hf: unknown overrides {bad}")
+        for k, inert in _UNSUPPORTED.items():
+            v = overrides.get(k, d.get(k, inert))
+            if v not in (inert, None, [], {}):
+                raise ValueError(f"generation config: {k} = {v!r} is not supported by this decoder "
+                                 f"(greedy or sampled search, one sequence per prompt)")
+        num = lambda k, default: overrides[k] if k in overrides else d.get(k, default)
+        cfg = cls(max_new_tokens=d.get("max_new_tokens"), repetition_penalty=float(num("repetition_penalty", 1.0)),
+                  no_repeat_ngram_size=int(num("no_repeat_ngram_size", 0)), eos_token_id=num("eos_token_id", None),
+                  pad_token_id=num("pad_token_id", None), bos_token_id=num("bos_token_id", None),
+                  do_sample=bool(num("do_sample", False)), temperature=float(num("temperature", 1.0)),
+                  top_k=int(num("top_k", 50) or 0), top_p=float(num("top_p", 1.0)), seed=int(num("seed", 0)),
+                  max_length=int(num("max_length", 20)), check_every=int(num("check_every", 16)),
+                  cache_chunk=int(num("cache_chunk", 1024)))
+        if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
+            cfg.max_new_tokens = overrides["max_new_tokens"]
+        if cfg.do_sample:
+            if not cfg.temperature > 0.0:
+                raise ValueError(f"generation config: temperature {cfg.temperature} must be > 0 when sampling")
+            if not 0.0 < cfg.top_p <= 1.0:
+                raise ValueError(f"generation config: top_p {cfg.top_p} must be in (0, 1]")
+            if cfg.top_k < 0:
+                raise ValueError(f"generation config: top_k {cfg.top_k} must be >= 0")
+        else:
+            cfg.temperature, cfg.top_k, cfg.top_p = 1.0, 0, 1.0        # the warpers are inert without do_sample
+        return cfg
+
+    def new_tokens(self, longest_prompt: int) -> int:
+        """The token budget of a batch: max_new_tokens, else max_length minus the longest prompt (HF's rule)."""
+        if self.max_new_tokens is not None:
+            return int(self.max_new_tokens)
+        if self.max_length is None:
+            raise ValueError("GenerationConfig: neither max_new_tokens nor max_length is set")
+        return int(self.max_length) - int(longest_prompt)
 
 
 @dataclass
@@ -67,26 +146,48 @@ class KVCache:
                    v=[torch.empty(B, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
                    cache_len=z(B), hist=z(B, S_max), hist_len=z(B), finished=z(B), n_unfinished=z(1))
 
+    @property
+    def capacity(self) -> int:
+        return self.hist.shape[1]
+
+    def grow(self, S_new: int) -> None:
+        """Reallocate caches and history with S_new >= S_max rows and copy the old contents (lengths are unchanged)."""
+        S = self.capacity
+        if S_new <= S:
+            return
+        def bigger(t):
+            n = t.new_empty(t.shape[0], S_new, *t.shape[2:]) if t.dim() > 2 else t.new_zeros(t.shape[0], S_new)
+            n[:, :S].copy_(t)
+            return n
+        self.k = [bigger(t) for t in self.k]
+        self.v = [bigger(t) for t in self.v]
+        self.hist = bigger(self.hist)
+
 
 def _parts(model):
-    """-> (PackedCausalLM, projector weight or None) of a TouchAudioForCausalLM or a plain PackedCausalLM."""
+    """-> (PackedCausalLM, projector weight or None) of a TouchAudioForCausalLM, a Qwen2-Audio model (its audio rows come
+    from an embedding builder) or a plain PackedCausalLM."""
     lm = getattr(model, "language_model", None)
     if lm is not None:
-        return lm, model.projector.weight
+        proj = getattr(model, "projector", None)
+        return lm, (proj.weight if proj is not None else None)
     return model, None
 
 
+def eos_ids(cfg: GenerationConfig, lm) -> List[int]:
+    """The eos ids of a generation (the config's, else the model's), as a list (possibly empty)."""
+    eos = cfg.eos_token_id if cfg.eos_token_id is not None else lm.config.eos_token_id
+    if eos is None:
+        return []
+    return [int(e) for e in eos] if isinstance(eos, (list, tuple)) else [int(eos)]
+
+
 def _special(cfg: GenerationConfig, lm):
-    c = lm.config
-    eos = cfg.eos_token_id if cfg.eos_token_id is not None else c.eos_token_id
-    pad = cfg.pad_token_id if cfg.pad_token_id is not None else c.pad_token_id
-    if isinstance(eos, (list, tuple)):
-        if len(eos) != 1:
-            raise ValueError("generate: one eos id only")
-        eos = eos[0]
+    eos = eos_ids(cfg, lm)
+    pad = cfg.pad_token_id if cfg.pad_token_id is not None else lm.config.pad_token_id
     if pad is None:
-        pad = eos if eos is not None else 0        # (HF: pad defaults to eos)
-    return (-1 if eos is None else int(eos)), int(pad)
+        pad = eos[0] if eos else 0                 # (HF: pad defaults to the first eos)
+    return eos, int(pad)
 
 
 def _check_model(model, lm):
@@ -101,9 +202,32 @@ def _check_model(model, lm):
                              "(D 64 / 128, Nh % Nkv == 0, Nh / Nkv <= 16)")
 
 
-def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device):
+def _embed_touch_audio(lm, proj_w, prompts: Prompts, ids, lens, Tp, device):
+    emb = lm.model.embed_tokens(ids)                                                       # [Tp, H]
+    if proj_w is not None and prompts.input_features is not None:
+        feats = torch.zeros(Tp, proj_w.shape[1], dtype=proj_w.dtype, device=device)
+        o = 0
+        for b, f in enumerate(prompts.input_features):
+            if f.shape[0] != lens[b]:
+                raise ValueError(f"prompt {b}: {f.shape[0]} feature rows for {lens[b]} ids")
+            feats[o:o + lens[b]] = f.to(device=device, dtype=proj_w.dtype)
+            o += lens[b]
+        emb = torch.addmm(emb, feats, proj_w.t())              # embed(ids) + projector(features): TouchAudio's forward
+    return emb
+
+
+_MAX_EOS = 8                                 # eos ids tn_sample_step takes
+
+
+# embedding builder of a prefill: (packed ids [Tp] on the device, prompt lengths, Tp) -> embeddings [Tp, H]
+EmbedFn = Callable[[torch.Tensor, List[int], int], torch.Tensor]
+
+
+def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device, embed: Optional[EmbedFn] = None):
     """Packed forward over all prompts (one row, one document each) -> logits [B, V] of every prompt's last position;
-    keys / values of every layer scattered into the caches."""
+    keys / values of every layer scattered into the caches.  `embed` builds the packed embeddings for a model of its own
+    (Qwen2-Audio: the audio tower's rows at the AUDIO positions); by default embed(ids), plus projector(features) for
+    TouchAudio."""
     lens = [int(t.numel()) for t in prompts.input_ids]
     B, T = len(lens), sum(lens)
     Tp = (T + 255) // 256 * 256
@@ -123,16 +247,10 @@ def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device):
     S_max = cache.k[0].shape[1]
     dst = torch.cat([torch.arange(n) + b * S_max for b, n in enumerate(lens)])
     ids, pos, doc, last, src, dst = (x.to(device, non_blocking=True) for x in (ids, pos, doc, last, torch.cat(src), dst))
-    emb = lm.model.embed_tokens(ids)                                                       # [Tp, H]
-    if proj_w is not None and prompts.input_features is not None:
-        feats = torch.zeros(Tp, proj_w.shape[1], dtype=proj_w.dtype, device=device)
-        o = 0
-        for b, f in enumerate(prompts.input_features):
-            if f.shape[0] != lens[b]:
-                raise ValueError(f"prompt {b}: {f.shape[0]} feature rows for {lens[b]} ids")
-            feats[o:o + lens[b]] = f.to(device=device, dtype=proj_w.dtype)
-            o += lens[b]
-        emb = torch.addmm(emb, feats, proj_w.t())              # embed(ids) + projector(features): TouchAudio's forward
+    if embed is not None:
+        emb = embed(ids, lens, Tp)                                                         # [Tp, H]
+    else:
+        emb = _embed_touch_audio(lm, proj_w, prompts, ids, lens, Tp, device)
     kv = []
     h = lm.model(inputs_embeds=emb[None], position_ids=pos[None], attention_mask=doc[None], keep_rows=last, kv_out=kv)
     for (k, v), kc, vc in zip(kv, cache.k, cache.v):
@@ -181,10 +299,15 @@ def decode_logits(lm, cache: KVCache) -> torch.Tensor:
 
 
 @torch.no_grad()
-def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, return_cache: bool = False):
-    """Greedy generation for a batch of prompts -> int64 [B, N] generated ids (the prompt excluded), `pad` after a row's
-    `eos` — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM or
-    PackedCausalLM, bf16, on the device."""
+def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, return_cache: bool = False,
+             row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None):
+    """Greedy or sampled generation for a batch of prompts -> int64 [B, N] generated ids (the prompt excluded), `pad`
+    after a row's eos — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM,
+    Qwen2AudioPackedForConditionalGeneration (with its `embed` builder) or PackedCausalLM, bf16, on the device.
+
+    Without do_sample and with at most one eos id every step is tn_greedy_step (repetition penalty, n-gram ban, argmax);
+    otherwise tn_sample_step (penalty, temperature, top-k, top-p, draw).  `row_keys` int64 [B] (default arange(B)) key
+    the draws with cfg.seed and the step: a row draws the same tokens whatever batch it is decoded in."""
     cfg = cfg or GenerationConfig()
     lm, proj_w = _parts(model)
     _check_model(model, lm)
@@ -197,36 +320,61 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     c = lm.config
     B = len(prompts)
     lens = [int(t.numel()) for t in prompts.input_ids]
-    n_new = int(cfg.max_new_tokens)
+    n_new = cfg.new_tokens(max(lens))
     if n_new <= 0:
         return torch.empty(B, 0, dtype=torch.int64, device=device)
-    S_max = max(lens) + n_new
-    cache = KVCache.allocate(len(lm.model.layers), B, S_max, c.num_key_value_heads, c.head_dim, device)
     penalty, ngram = float(cfg.repetition_penalty), int(cfg.no_repeat_ngram_size)
-    logits = _prefill(lm, proj_w, prompts, cache, device)
-    F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty, ngram,
-                  eos, pad)
+    greedy = not cfg.do_sample and len(eos) <= 1
+    if not greedy:
+        if ngram > 0:
+            raise ValueError("generate: no_repeat_ngram_size > 0 is only supported for greedy search with one eos id "
+                             f"(do_sample={cfg.do_sample}, eos ids {eos})")
+        if len(eos) > _MAX_EOS:
+            raise ValueError(f"generate: at most {_MAX_EOS} eos ids (got {len(eos)})")
+        if row_keys is None:
+            row_keys = torch.arange(B, dtype=torch.int64, device=device)
+        row_keys = row_keys.to(device=device, dtype=torch.int64).contiguous()
+        if tuple(row_keys.shape) != (B,):
+            raise ValueError(f"generate: row_keys must have shape [{B}]")
+    chunk = max(1, int(cfg.cache_chunk))
+    cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
+                             device)
+    S_full = max(lens) + n_new
+
+    def step(logits):
+        if greedy:
+            F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
+                          ngram, eos[0] if eos else -1, pad)
+        else:
+            F.sample_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
+                          cfg.do_sample, cfg.temperature, cfg.top_k, cfg.top_p, cfg.seed, eos, pad, row_key=row_keys)
+
+    step(_prefill(lm, proj_w, prompts, cache, device, embed))
     steps = 1
     while steps < n_new:
         if steps % max(1, int(cfg.check_every)) == 0 and int(cache.n_unfinished.item()) == 0:
             break
-        logits = decode_logits(lm, cache)
-        F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
-                      ngram, eos, pad)
+        # the next step writes key / value slot lens[b] + steps - 1 and history slot lens[b] + steps
+        if max(lens) + steps >= cache.capacity:
+            cache.grow(min(S_full, 2 * cache.capacity))
+        step(decode_logits(lm, cache))
         steps += 1
     idx = torch.tensor(lens, dtype=torch.int64, device=device)[:, None] + torch.arange(steps, device=device)[None]
     out = cache.hist.gather(1, idx).to(torch.int64)
     # HF stops at the first step after which every row is finished: drop the all-pad columns the check interval added
-    if eos >= 0:
-        is_eos = (out == eos)
+    if eos:
+        is_eos = torch.isin(out, torch.tensor(eos, dtype=torch.int64, device=device))
         first = torch.where(is_eos.any(1), is_eos.to(torch.int8).argmax(1), torch.full_like(out[:, 0], steps - 1))
         out = out[:, :int(first.max()) + 1]
     return (out, cache) if return_cache else out
 
 
-def trim_at_eos(ids: torch.Tensor, eos: int) -> List[List[int]]:
-    """[B, N] generated ids -> per row the ids in front of the first eos (the eos and the padding behind it dropped)."""
+def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[int]]:
+    """[B, N] generated ids -> per row the ids in front of the first eos (the eos and the padding behind it dropped);
+    `eos` one id or several."""
+    stop = {int(eos)} if isinstance(eos, int) else {int(e) for e in eos}
     rows = []
     for r in ids.tolist():
-        rows.append(r[:r.index(eos)] if eos in r else r)
+        cut = next((i for i, t in enumerate(r) if t in stop), len(r))
+        rows.append(r[:cut])
     return rows

@@ -13,6 +13,7 @@ returns an EMPTY placeholder and the autograd formula keeps the input itself.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import List, Optional, Tuple
 
@@ -942,8 +943,52 @@ def _(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty, ngram,
     return None
 
 
+MAX_EOS = 8
+
+
+@custom_op(f"{NS}::sample_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished"),
+           device_types="cuda")
+def sample_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor, n_unfinished: Tensor,
+                 row_key: Optional[Tensor], uniforms: Optional[Tensor], n_kept: Optional[Tensor], penalty: float,
+                 do_sample: bool, temperature: float, top_k: int, top_p: float, seed: int, eos: List[int],
+                 pad: int) -> None:
+    """One decoding step of HF generate() with the sampling warpers (tn_sample_step): logits [B, V] fp32 / bf16; hist int32
+    [B, S_hist], hist_len / cache_len / finished int32 [B], n_unfinished int32 [1] — all advanced on the device.  row_key
+    int64 [B] keys the draws (None: the row index); uniforms fp32 [B] replaces the generator; n_kept int32 [B] receives the
+    number of tokens top-k / top-p kept (None: not written)."""
+    _no_grad_inputs("sample_step_", logits)
+    B, V = logits.shape
+    for t, shape in ((hist_len, (B,)), (cache_len, (B,)), (finished, (B,)), (n_unfinished, (1,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _C.KernelError("sample_step_: int32 hist_len / cache_len / finished [B], n_unfinished [1]")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != B or not hist.is_contiguous():
+        raise _C.KernelError("sample_step_: int32 contiguous hist [B, S_hist]")
+    for name, t, dt in (("row_key", row_key, torch.int64), ("uniforms", uniforms, torch.float32),
+                        ("n_kept", n_kept, torch.int32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (B,) or not t.is_contiguous()):
+            raise _C.KernelError(f"sample_step_: {name} must be a contiguous {dt} [B] tensor")
+    if len(eos) > MAX_EOS:
+        raise _C.KernelError(f"sample_step_: at most {MAX_EOS} eos ids")
+    if do_sample and not (temperature > 0.0 and top_k >= 0 and 0.0 < top_p <= 1.0):
+        raise _C.KernelError("sample_step_: temperature > 0, top_k >= 0 and 0 < top_p <= 1 when sampling")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise _C.KernelError("sample_step_: seed must fit in 64 unsigned bits")
+    logits = _c(logits)
+    eos_arr = (ctypes.c_int * max(1, len(eos)))(*[int(e) for e in eos])
+    _C.check(_lib().tn_sample_step(_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(finished), _p(n_unfinished),
+                                   _p(row_key), _p(uniforms), _p(n_kept), B, V, hist.shape[1], float(penalty),
+                                   int(bool(do_sample)), float(temperature), int(top_k), float(top_p), int(seed), eos_arr,
+                                   len(eos), int(pad), _C.dcode(logits), _cur()), "tn_sample_step")
+
+
+@sample_step_.register_fake
+def _(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, uniforms, n_kept, penalty, do_sample, temperature,
+      top_k, top_p, seed, eos, pad):
+    return None
+
+
 OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
-       "attn_decode_", "greedy_step_")
+       "attn_decode_", "greedy_step_", "sample_step_")
