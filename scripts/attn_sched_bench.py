@@ -1,5 +1,5 @@
-"""Forward-attention schedule comparison: run once per TN_ATTN_FWD_SCHEDULE value (0 = baseline 4-wave blocks,
-1 = ping-pong 8-wave blocks).  Prints ms and dense-equivalent TFLOP/s per case."""
+"""Forward and backward attention over causal / packed-document masks at T = 8192 (the kernels the shape selects).
+Prints ms and dense-equivalent TFLOP/s per case."""
 import os
 import sys
 
@@ -34,7 +34,6 @@ def flops(doc, Nh, D):
     return 4.0 * tot * Nh * D
 
 
-sched = os.environ.get("TN_ATTN_FWD_SCHEDULE", "default")
 for (B, T, Nh, Nkv, D, mean) in ((2, 8192, 32, 32, 128, 0), (2, 8192, 32, 32, 128, 790), (2, 8192, 32, 32, 128, 100),
                                  (2, 8192, 32, 32, 64, 0), (4, 8192, 28, 4, 64, 400), (2, 8192, 32, 8, 64, 790)):
     q = torch.randn(B, T, Nh, D, dtype=bf, device=dev)
@@ -51,7 +50,7 @@ for (B, T, Nh, Nkv, D, mean) in ((2, 8192, 32, 32, 128, 0), (2, 8192, 32, 32, 12
         e.record()
         torch.cuda.synchronize()
     ms = s.elapsed_time(e) / 20
-    # backward (delta + dK/dV + dQ kernels)
+    # backward (dQ + dK/dV kernels)
     qg, kg, vg = [x.clone().requires_grad_() for x in (q, k, v)]
     out = F.packed_attention(qg, kg, vg, mask)
     do = torch.randn_like(out)
@@ -64,5 +63,5 @@ for (B, T, Nh, Nkv, D, mean) in ((2, 8192, 32, 32, 128, 0), (2, 8192, 32, 32, 12
     torch.cuda.synchronize()
     msb = s.elapsed_time(e) / 10
     fl = flops(doc, Nh, D)
-    print(f"sched={sched} B{B} T{T} Nh{Nh}/{Nkv} D{D} docs~{mean or 'causal'}: fwd {ms:.3f} ms {fl / ms / 1e9:.1f} TFLOP/s"
+    print(f"B{B} T{T} Nh{Nh}/{Nkv} D{D} docs~{mean or 'causal'}: fwd {ms:.3f} ms {fl / ms / 1e9:.1f} TFLOP/s"
           f" | bwd {msb:.3f} ms {2.5 * fl / msb / 1e9:.1f} TFLOP/s", flush=True)

@@ -3,8 +3,8 @@
 # read carries no alias metadata (attn_common.h, i32x4_t).  That silently turns the counted-vmcnt stage ring of the
 # attention backward kernels into a serial load -> compute loop.  This check compiles attn_bwd.hip to ISA and fails if a
 # `s_waitcnt vmcnt(0)` sits directly in front of a ds_read_b128 (the MFMA "row" operand / statistics reads) inside the
-# stage loops of the dK/dV and dQ kernels.  (The transpose-read builtin still gets such a wait; at the ring depth in use,
-# one stage, it costs nothing — see DESIGN.md 5.2.)
+# stage loops of the dK/dV, dQ and stream forward kernels.  (The transpose-read builtin still gets such a wait; at the
+# ring depth in use, one stage, it costs nothing — see DESIGN.md 5.2.)
 # usage: scripts/check_dma_waits.sh   -> exit 0 / 1
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
@@ -18,10 +18,8 @@ python3 - "$tmp/bwd.s" <<'PY'
 import re, sys
 text = open(sys.argv[1]).read()
 bad = 0
-for m in re.finditer(r'^(_ZN2tn\d+attn_(?:bwd_kv|bwd_dq|bwd_dq_stream|fwd_stream)_kernel\S*):.*?s_endpgm', text, re.S | re.M):
+for m in re.finditer(r'^(_ZN2tn\d+attn_(?:bwd_kv|bwd_dq_stream|fwd_stream)_kernel\S*):.*?s_endpgm', text, re.S | re.M):
     name, body = m.group(1), m.group(0).split('\n')
-    if 'fwd_stream_kernelILi128ELb1E' in name:      # the TRACE instantiation (s_memtime stamps + stores: development only)
-        continue
     ins = [l.strip() for l in body if l.strip() and not l.strip().startswith((';', '.'))]
     # stage loop = everything after the first LDS-DMA instruction
     first = next((i for i, l in enumerate(ins) if l.startswith('buffer_load_dword ') and l.endswith('lds')), None)

@@ -1,6 +1,7 @@
 """Compile-time (CPU, hipcc cross-compiles gfx950) checks on the generated ISA of kernels whose speed depends on a
 compiler behaviour that the source cannot express."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -10,15 +11,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
-def test_attention_backward_stage_ring_is_not_serialised_by_alias_waits():
-    """The LDS-DMA stage ring of the dK/dV and dQ kernels relies on counted vmcnt waits.  hipcc inserts a full
-    `s_waitcnt vmcnt(0)` in front of LDS reads without alias metadata while a DMA is pending (attn_common.h, i32x4_t;
-    DESIGN.md 5.2): the check fails if such a wait appears in front of a row-operand read inside the stage loops."""
+def test_attention_stage_loops_are_not_serialised_by_alias_waits():
+    """The LDS-DMA stage rings of the dK/dV, dQ and stream forward kernels rely on counted vmcnt waits.  hipcc inserts a
+    full `s_waitcnt vmcnt(0)` in front of LDS reads without alias metadata while a DMA is pending (attn_common.h,
+    i32x4_t): the check fails if such a wait appears in front of a row-operand read inside the stage
+    loops, or if the set of stage-loop kernels it inspected is not exactly the attention's seven."""
     r = subprocess.run(["bash", os.path.join(ROOT, "scripts", "check_dma_waits.sh")], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("attn_bwd_") >= 7, r.stdout      # two dK/dV (D=128) + one (D=64) + two dQ + two stream dQ kernels
-    assert r.stdout.count("attn_fwd_stream") >= 2, r.stdout
+    hits = {}                       # "kernel<template args>" -> alias waits found in its stage loop
+    for line in r.stdout.splitlines():
+        m = re.match(r"_ZN2tn\d+(attn_\w+?_kernel)I((?:Li\d+E)+)E\S*: (\d+) vmcnt", line)
+        if m:
+            hits[m.group(1) + "<" + ",".join(re.findall(r"Li(\d+)E", m.group(2))) + ">"] = int(m.group(3))
+    # every stage-loop kernel of the attention, each with no hit
+    assert hits == {"attn_bwd_kv_kernel<128,0>": 0, "attn_bwd_kv_kernel<128,1>": 0, "attn_bwd_kv_kernel<64,2>": 0,
+                    "attn_bwd_dq_stream_kernel<128>": 0, "attn_bwd_dq_stream_kernel<64>": 0,
+                    "attn_fwd_stream_kernel<128>": 0, "attn_fwd_stream_kernel<64>": 0}, r.stdout
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")

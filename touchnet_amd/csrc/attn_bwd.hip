@@ -1,66 +1,26 @@
 // Packed (document-masked, causal) flash attention BACKWARD for gfx950 — MFMA 32x32x16 bf16.
 //
-// Same masking / layout contract as attn_fwd.hip.  All kernels are deterministic (no atomics):
-//   1. delta[b,h,t] = sum_d dO[b,t,h,d] * O[b,t,h,d]                                (HBM-bound)
+// Same masking / layout contract as attn_fwd.hip.  All kernels are deterministic (no atomics).  One call runs:
+//   1. dQ (attn_bwd_dq_stream.hip): a workgroup owns 128 query rows of one head and walks KV tiles exactly like the
+//      forward: S^T = K Q^T, dP^T = V dO^T, dQ^T += K^T dS^T, one 32-row KV block at a time.  It also forms
+//      delta[b,h,t] = sum_d dO[b,t,h,d] * O[b,t,h,d] from the dO / O rows it loads anyway, for the pass behind it.
 //   2. dK / dV: a workgroup owns 128 KV rows of one KV head (32 per wave, K/V rows held in registers as MFMA
 //      B operands) and walks the 64-row query tiles of every query head of its GQA group that can see them:
 //          S = Q K^T,  P = exp2(S*c - LSE2),  dP = dO V^T,  dS = P o (dP - delta),
 //          dV^T += dO^T P,   dK^T += Q^T dS
 //      S is computed un-transposed here so that the contraction index of the last two products (q) is the
-//      in-lane index of P / dS.  MODE selects what one launch accumulates:
+//      in-lane index of P / dS.  Causal D = 128 runs both in ONE pass (attn_bwd_fused.hip); this file's kernel,
+//      whose MODE selects what one launch accumulates, runs the rest:
 //        D = 64 : one kernel does both (2 waves/SIMD)
-//        D = 128: a dV launch and a dK launch.  Keeping dK and dV accumulators (128 regs) plus K and V
+//        D = 128 (bidirectional): a dV launch and a dK launch.  Keeping dK and dV accumulators (128 regs) plus K and V
 //                 operands (64) resident needs the 512-register file at 1 wave/SIMD and made hipcc shuttle
 //                 ~14 v_accvgpr moves per MFMA (measured: 15 VALU per MFMA, SQ_INSTS_VALU / SQ_INSTS_MFMA);
 //                 two lean kernels at 2 waves/SIMD recompute S once more (+25 % MFMA) and are faster.
-//   3. dQ: a workgroup owns 128 query rows of one head and walks KV tiles exactly like the forward:
-//      S^T = K Q^T, dP^T = V dO^T, dQ^T += K^T dS^T, one 32-row KV block at a time.
 // Recomputing S in each pass buys determinism and needs no fp32 dQ scratch; the reference's
 // flex_attention backward has the same two-loop structure (inductor-generated Triton template).
 #include "attn_common.h"
 
-// Timing experiments only (scripts/build_variant.sh <name> -DTN_BWD_ABL=3; results are wrong): no MFMA / softmax work,
-// the staging skeleton alone.  (Values 1 and 2 — no in-loop loads / no barriers — existed for the register-staged kernels
-// this file replaced; their numbers are quoted in the dK/dV kernel's header.)
-#ifndef TN_BWD_ABL
-#define TN_BWD_ABL 0
-#endif
-// dK/dV stream: query rows per stage (32 or 64) and ring depth
-#ifndef TN_KV_BQ
-#define TN_KV_BQ 64
-#endif
-#ifndef TN_KV_NST
-#define TN_KV_NST 2
-#endif
-
 namespace tn {
-
-// ------------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
-                                                         float* __restrict__ delta, int B, int T, int Nh) {
-  constexpr int LPR = D / 8;        // lanes per (token, head) row
-  const size_t rows = (size_t)B * T * Nh;
-  const size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / LPR;
-  const int sub = threadIdx.x % LPR;
-  float acc = 0.f;
-  if (row < rows) {
-    Vec16<bf16_t> a, g;
-    float af[8], gf[8];
-    a.load(O + row * D + sub * 8);
-    g.load(dO + row * D + sub * 8);
-    a.unpack(af);
-    g.unpack(gf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc += af[j] * gf[j];
-  }
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (row < rows && sub == 0) {
-    const size_t h = row % Nh, t = (row / Nh) % T, b = row / ((size_t)Nh * T);
-    delta[(b * Nh + h) * T + t] = acc;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // dK / dV.   MODE 0: dV only   1: dK only   2: both
@@ -70,7 +30,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
 // registers, no LDS store instructions) into a ring of NST slots, NST - 1 stages ahead of the one being computed, with
 // counted vmcnt waits and ONE raw barrier per stage.  Why: with register staging the prefetch distance was one tile
 // and the per-tile {wait for HBM/L2, store, 2 barriers} skeleton alone took 134 of the dV kernel's 281 us on the
-// headline workload (scripts/attn_ktimes.sh, -DTN_BWD_ABL variants of the previous kernel: no loads/stores 224 us, no
+// headline workload (scripts/attn_ktimes.sh, ablation builds of the previous kernel: no loads/stores 224 us, no
 // barriers either 206 us, no MFMA/softmax 134 us).  The per-tile document-id statistics come from an LDS window
 // filled once per workgroup instead of dependent scalar loads per tile.
 // ------------------------------------------------------------------------------------------------
@@ -97,7 +57,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, const int* __restrict__ doc, AttnMeta meta, QView qv, int T,
     int Nh, int Nkv, float scale, float scale_log2) {
   constexpr bool DO_DV = MODE != 1, DO_DK = MODE != 0;
-  constexpr int BNK = 128, BQ = TN_KV_BQ, NST = TN_KV_NST, SPT = kTile / BQ;   // SPT stages per 64-position q tile
+  constexpr int BNK = 128, BQ = 64, NST = 2, SPT = kTile / BQ;   // SPT stages per 64-position q tile
   constexpr int KSTEPS = D / 16, DBLK = D / 32;
   using Tile = PTile<BQ, D>;
   constexpr int IMGB = Tile::SIZE * 2;          // bytes of one panel image
@@ -378,7 +338,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
     const float* lse_s = reinterpret_cast<const float*>(smem + slot * STAGEB + 2 * IMGB);
     const float* delta_s = lse_s + 64;
     const int* docq = reinterpret_cast<const int*>(lse_s + 128);
-    if (uniform(TN_BWD_ABL != 3 && (bidir || cur.qsb + BQ - 1 >= wk0) && tile_may_interact(cur.mp, cur.mx, wminpos, wmax))) {
+    if (uniform((bidir || cur.qsb + BQ - 1 >= wk0) && tile_may_interact(cur.mp, cur.mx, wminpos, wmax))) {
       const bool q_uniform = w_uniform && cur.mn == cur.mx && cur.mx == wmax && cur.left == BQ;
       // The work on one 32-row half (qs) of the stage, in pieces.  (Issuing both halves of an interior stage as ONE
       // straight-line block — S of half 1 under the exponentials of half 0 — measured 3-9 % SLOWER: 226 -> 242 VGPRs.)
@@ -526,270 +486,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// dQ
-// ------------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
-    const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
-    const bf16_t* __restrict__ dO, const float* __restrict__ LSE2, float* __restrict__ Delta,
-    bf16_t* __restrict__ dQ, const int* __restrict__ doc, AttnMeta meta, QView qv, int T, int Nh, int Nkv,
-    float scale, float scale_log2, const bf16_t* __restrict__ O) {
-  // O != null: this kernel ALSO forms delta = rowsum(dO o O) of its 128 query rows — it holds the dO rows in registers
-  // anyway — and writes it to `Delta` for the dK / dV pass, which is launched BEHIND it (round 5: the separate
-  // attn_delta_kernel pass, 64 launches and 2.5 ms per Qwen2-Audio step, is gone).  O == null: `Delta` is read.
-  constexpr int BM = 128, BN = 64, NST = 2;
-  constexpr int KSTEPS = D / 16, DBLK = D / 32;
-  using Tile = PTile<BN, D>;
-  constexpr int IMGB = Tile::SIZE * 2;          // bytes of one panel image
-  constexpr int NPC = Tile::NP * (BN / 16);     // 1-KiB DMA pieces per image
-  constexpr int PPW = NPC / 4;                  // pieces per wave and image
-  constexpr int IPS = 2 * PPW + 1;              // DMA instructions per wave and stage
-  constexpr int STAGEB = 2 * IMGB + 4 * 256;    // {K image | V image | doc ids[64] | 3 spare rows}
-  constexpr int WIN = 256;                      // kv tiles whose statistics are kept in LDS
-  // K image: rows -> A of S^T = K Q^T, transposed -> A of dQ^T += K^T dS^T;  V image: rows -> A of dP^T = V dO^T.
-  // Stages = the kv tiles this workgroup meets, streamed by LDS-DMA exactly like the dK/dV kernel's (one LDS variable,
-  // see there).
-  __shared__ __attribute__((aligned(1024))) char smem[NST * STAGEB + WIN * 16];
-  i32x4_t* kstat = reinterpret_cast<i32x4_t*>(smem + NST * STAGEB);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int h = head_of_slot(blockIdx.x, Nh, Nkv), b = blockIdx.z;
-  const int hk = h / (Nh / Nkv);
-  int lq0, q0, qleft;
-  qv.tile(gridDim.y - 1 - blockIdx.y, BM, lq0, q0, qleft);
-  const int wq0 = q0 + 32 * wave;          // global position of the wave's first query row
-  const int qrow = wq0 + l31;              // global position
-  const int lrow = lq0 + 32 * wave + l31;  // row in the local Q / dO / dQ / LSE / delta buffers
-  const bool qvalid = (32 * wave + l31 < qleft) && (qrow < T);
-
-  bf16x8_t qreg[KSTEPS], doreg[KSTEPS];
-  float dsum = 0.f;                         // this lane's share of rowsum(dO o O): slots 8 hi .. 8 hi + 7 of every k-step
-  {
-    const size_t off = (((size_t)b * qv.rpb + (qvalid ? lrow : 0)) * Nh + h) * D + 8 * hi;
-    uint4 orow[KSTEPS];                     // (all loads of the row are issued before the first use: ONE memory round trip)
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) {
-      uint4 a = make_uint4(0, 0, 0, 0), c = make_uint4(0, 0, 0, 0);
-      orow[s] = make_uint4(0, 0, 0, 0);
-      if (qvalid) {
-        a = *reinterpret_cast<const uint4*>(Q + off + 16 * s);
-        c = *reinterpret_cast<const uint4*>(dO + off + 16 * s);
-        if (O != nullptr) orow[s] = *reinterpret_cast<const uint4*>(O + off + 16 * s);
-      }
-      qreg[s] = as_bf16x8(a);
-      doreg[s] = as_bf16x8(c);
-    }
-    if (O != nullptr) {
-#pragma unroll
-      for (int s = 0; s < KSTEPS; ++s) {
-        Vec16<bf16_t> ov, gv;
-        float of[8], gf[8];
-        ov.raw = orow[s];
-        const u32x4_t g4 = __builtin_bit_cast(u32x4_t, doreg[s]);
-        gv.raw = make_uint4(g4.x, g4.y, g4.z, g4.w);
-        ov.unpack(of);
-        gv.unpack(gf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dsum += of[e] * gf[e];
-      }
-    }
-  }
-  const int dq = qvalid ? doc[(size_t)b * T + qrow] : 0;
-  const float lse2 = qvalid ? LSE2[((size_t)b * Nh + h) * qv.rpb + lrow] : INFINITY;
-  float delta;
-  if (O != nullptr) {
-    delta = dsum + __shfl_xor(dsum, 32, 64);            // (both 32-lane halves hold the same rows)
-    if (qvalid && hi == 0) Delta[((size_t)b * Nh + h) * qv.rpb + lrow] = delta;
-  } else {
-    delta = qvalid ? Delta[((size_t)b * Nh + h) * qv.rpb + lrow] : 0.f;
-  }
-
-  const int* m_min = meta.tmin + (size_t)b * meta.nt;
-  const int* m_max = meta.tmax + (size_t)b * meta.nt;
-  const int* m_minpos = meta.tminpos + (size_t)b * meta.nt;
-  const int t0 = q0 / kTile, t1 = min(t0 + 1, meta.nt - 1);
-  const bool bidir = qv.bidir != 0;
-  const int j_hi = bidir ? max(t1, max(meta.kv_hi[(size_t)b * meta.nt + t0], meta.kv_hi[(size_t)b * meta.nt + t1])) : t1;
-  const int qcap = bidir ? 0x7fffffff : qrow;               // `kv <= qcap`: the causal term of the predicate
-  // statistics window: the WIN tiles that END at the diagonal are the ones a packed batch needs; a longer reach (plain
-  // causal beyond 16 k positions) starts below it and refills the window on the way up
-  const int j_lo = min(meta.q_lo[(size_t)b * meta.nt + t0], meta.q_lo[(size_t)b * meta.nt + t1]);
-  int win_lo = max(j_lo, 0);
-  auto fill_window = [&]() {
-    for (int i = tid; i < WIN; i += 256) {
-      const int t = win_lo + i;
-      if (t < meta.nt) kstat[i] = i32x4_t{m_minpos[t], m_max[t], m_min[t], 0};
-    }
-  };
-  fill_window();
-  const int bminpos = min(m_minpos[t0], m_minpos[t1]);
-  const int bmax = max(m_max[t0], m_max[t1]);
-  int wminpos, wmax;
-  wave_id_range(dq, wminpos, wmax);
-  const bool w_has_zero = __any(dq == 0);
-  __syncthreads();
-
-  struct KStage {
-    int valid, j, mn, mx, mp;
-  };
-  int sc_j = j_lo;
-  auto next = [&]() {
-    KStage d = {0, 0, 0, 0, 0};
-    while (sc_j <= j_hi) {
-      const int jj = sc_j++;
-      if (jj >= win_lo + WIN) {            // (workgroup-uniform: every wave runs the same scan)
-        __syncthreads();
-        win_lo = jj;
-        fill_window();
-        __syncthreads();
-      }
-      const int4 st = scalarize(kstat[jj - win_lo]);
-      if (!tile_may_interact(bminpos, bmax, st.x, st.y)) continue;
-      d.valid = 1;
-      d.j = jj;
-      d.mp = st.x;
-      d.mx = st.y;
-      d.mn = st.z;
-      break;
-    }
-    return d;
-  };
-
-  const size_t krow_elems = (size_t)Nkv * D;
-  const uint32_t k_bytes = (uint32_t)min((size_t)T * krow_elems * 2, (size_t)0x7fffffff);
-  const __amdgpu_buffer_rsrc_t rk =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(K + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(V + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdoc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(doc + (size_t)b * T), 0, (uint32_t)T * 4, 0x00020000);
-  const int rr = lane >> 2;
-  const uint32_t voff = (uint32_t)(((size_t)rr * krow_elems + 8 * ((lane & 3) ^ ((rr >> 2) & 3))) * 2);
-  constexpr uint32_t OOB = 0x80000000u;
-  auto issue = [&](const KStage& d, int slot) {      // always IPS instructions; an invalid stage reads nothing
-    char* st = smem + slot * STAGEB;
-    const int k0 = d.j * BN;
-    const int left = d.valid ? min(T - k0, BN) : 0;
-    const uint32_t base = (uint32_t)(((size_t)k0 * Nkv + hk) * D * 2);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int pc = wave + 4 * i, panel = pc % Tile::NP, rh = pc / Tile::NP;
-      const uint32_t vo = (16 * rh + rr < left) ? voff : OOB;
-      const uint32_t so = base + (uint32_t)((16 * rh * krow_elems + 32 * panel) * 2);
-      char* dst = st + panel * (Tile::PSTRIDE * 2) + rh * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)dst, 16, vo, so, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(dst + IMGB), 16, vo, so, 0, 0);
-    }
-    const uint32_t va = lane < left ? (uint32_t)lane * 4 : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rdoc, (lds_ptr_t)(st + 2 * IMGB + 256 * wave), 4, va, (uint32_t)k0 * 4, 0,
-                                             0);
-  };
-
-  f32x16_t dqacc[DBLK];
-#pragma unroll
-  for (int i = 0; i < DBLK; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dqacc[i][r] = 0.f;
-
-  const PRowReader<BN, D> rrd(l31, hi);
-  const PTrReader<BN, D> trd(lane);
-  const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-  KStage ring[NST - 1];
-#pragma unroll
-  for (int i = 0; i < NST - 1; ++i) {
-    ring[i] = next();
-    issue(ring[i], i);
-  }
-  int slot = 0;
-  while (ring[0].valid) {
-    const KStage cur = ring[0];
-    const KStage ahead = next();
-    wait_vmcnt<(NST - 2) * IPS>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue(ahead, (slot + NST - 1) % NST);
-
-    const bf16_t* Ks = reinterpret_cast<const bf16_t*>(smem + slot * STAGEB);
-    const bf16_t* Vs = Ks + Tile::SIZE;
-    const int* docs = reinterpret_cast<const int*>(smem + slot * STAGEB + 2 * IMGB);
-    const int k0 = cur.j * BN;
-    if (uniform(TN_BWD_ABL != 3 && (bidir || k0 <= wq0 + 31) && tile_may_interact(wminpos, wmax, cur.mp, cur.mx))) {
-      const bool need_mask = uniform(!(cur.mn == cur.mx && cur.mx == wminpos && wminpos == wmax && !w_has_zero &&
-                                       (bidir || k0 + BN - 1 <= wq0)));
-#pragma unroll
-      for (int blk = 0; blk < 2; ++blk) {
-        if (uniform(bidir || k0 + 32 * blk <= wq0 + 31)) {    // else: this 32-row KV block is above the diagonal
-          f32x16_t sacc = mfma32(rrd.operand(Ks, 32 * blk, 0), qreg[0], zero16);
-          f32x16_t dpacc = mfma32(rrd.operand(Vs, 32 * blk, 0), doreg[0], zero16);
-#pragma unroll
-          for (int s = 1; s < KSTEPS; ++s) {
-            sacc = mfma32(rrd.operand(Ks, 32 * blk, s), qreg[s], sacc);
-            dpacc = mfma32(rrd.operand(Vs, 32 * blk, s), doreg[s], dpacc);
-          }
-          float ds[16];
-          auto dscore = [&](auto masked) {
-            constexpr bool MASK = decltype(masked)::value;
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-              int dkk[4] = {0, 0, 0, 0};
-              if (MASK) {
-                const i32x4_t dk = *reinterpret_cast<const i32x4_t*>(docs + 32 * blk + 8 * r4 + 4 * hi);
-                dkk[0] = dk.x; dkk[1] = dk.y; dkk[2] = dk.z; dkk[3] = dk.w;
-              }
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const int r = 4 * r4 + e;
-                float pv = fast_exp2(sacc[r] * scale_log2 - lse2);
-                if (MASK) {
-                  const int kv = k0 + 32 * blk + 8 * r4 + 4 * hi + e;
-                  pv = ((kv <= qcap) & (dkk[e] == dq) & (dq > 0)) ? pv : 0.f;
-                }
-                ds[r] = pv * (dpacc[r] - delta);
-              }
-            }
-          };
-          if (need_mask) dscore(std::true_type{}); else dscore(std::false_type{});
-#pragma unroll
-          for (int sp = 0; sp < 2; ++sp) {
-            const u32x4_t u = {pack2bf(ds[8 * sp + 0], ds[8 * sp + 1]), pack2bf(ds[8 * sp + 2], ds[8 * sp + 3]),
-                               pack2bf(ds[8 * sp + 4], ds[8 * sp + 5]), pack2bf(ds[8 * sp + 6], ds[8 * sp + 7])};
-            const bf16x8_t dsb = __builtin_bit_cast(bf16x8_t, u);
-#pragma unroll
-            for (int db = 0; db < DBLK; ++db)       // dQ^T[d, q] += K^T[d, kv] dS^T[kv, q]
-              dqacc[db] = mfma32(trd.operand(Ks, db, 32 * blk + 16 * sp), dsb, dqacc[db]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i + 1 < NST - 1; ++i) ring[i] = ring[i + 1];
-    ring[NST - 2] = ahead;
-    slot = (slot + 1) % NST;
-  }
-  wait_vmcnt<0>();      // (the zero-fill tail DMAs)
-
-  if (qvalid) {
-    bf16_t* op = dQ + (((size_t)b * qv.rpb + lrow) * Nh + h) * D;
-#pragma unroll
-    for (int db = 0; db < DBLK; ++db) {
-#pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) {
-        uint2 o;
-        o.x = pack2bf(dqacc[db][4 * r4 + 0] * scale, dqacc[db][4 * r4 + 1] * scale);
-        o.y = pack2bf(dqacc[db][4 * r4 + 2] * scale, dqacc[db][4 * r4 + 3] * scale);
-        *reinterpret_cast<uint2*>(op + 32 * db + 8 * r4 + 4 * hi) = o;
-      }
-    }
-  }
-}
-
-}  // namespace tn
-
-namespace tn {
 // attn_bwd_dq_stream.hip: the dQ pass on precomputed tile lists, Q / dO by LDS-DMA, batched operand reads, whole-row stores
 void launch_attn_bwd_dq_stream(const bf16_t* Q, const bf16_t* K, const bf16_t* V, const bf16_t* dO, const float* lse2,
                                float* delta, bf16_t* dQ, const int* doc, AttnMeta m, QView qv, int B, int T, int Nh,
@@ -809,23 +505,6 @@ extern "C" {
 int tn_rope_apply(const void* q, const void* k, void* q_out, void* k_out, const void* cos_t, const void* sin_t, int n,
                   int hq, int hk, int D, int backward, int dtype, void* stream);      // (norm_act.hip)
 
-// TN_ATTN_BWD_KV=split restores the two-launch dV / dK scheme for D = 128 (kernel-development A/B switch, read per call)
-static bool bwd_kv_split() {
-  const char* e = getenv("TN_ATTN_BWD_KV");
-  return e != nullptr && e[0] == 's';
-}
-
-// dQ kernel selection: 1 = attn_bwd_dq_stream.hip (default), 0 = this file's kernel (the reference the stream kernel is
-// compared against).  TN_ATTN_BWD_DQ = 0 / 1 forces one; tn_attn_set_bwd_dq (development entry point) overrides per process.
-static int g_bwd_dq_override = -1;
-static int bwd_dq_mode() {
-  static int mode = [] {
-    const char* e = getenv("TN_ATTN_BWD_DQ");
-    return e ? atoi(e) : 1;
-  }();
-  return g_bwd_dq_override >= 0 ? g_bwd_dq_override : mode;
-}
-
 static int attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
                            const float* lse2, float* delta, void* dq, void* dk, void* dv, const int* doc,
                            const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, QView qv,
@@ -837,68 +516,32 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
   const AttnMeta m = make_attn_meta(meta, B, T);
   hipStream_t st = (hipStream_t)stream;
   const float sl2 = scale * 1.4426950408889634f;
-  const size_t rows = (size_t)B * qv.rpb * Nh;
-  dim3 gq(Nh, qv.tiles(0, 128) + qv.tiles(1, 128), B), gk(Nkv, (T + 127) / 128, B), block(256);
+  dim3 gk(Nkv, (T + 127) / 128, B), block(256);
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v, *dO = (const bf16_t*)dout;
-  // TN_ATTN_DELTA_KERNEL=1: the round-4 order (separate delta pass, dK / dV, dQ) for A/B runs; default: dQ first — it forms
-  // delta from the dO / O rows it loads anyway and leaves it for the dK / dV pass behind it
-  static const bool delta_pass = [] { const char* e = getenv("TN_ATTN_DELTA_KERNEL"); return e && e[0] == '1'; }();
-  const bf16_t* O_ = delta_pass ? nullptr : (const bf16_t*)o;
-  (void)rows;
-  const bool dq_stream = bwd_dq_mode() == 1;
-  // rope_cos / rope_sin (tn_attn_bwd_rope): dq / dk are wanted as gradients of the UN-rotated q / k.  The default D = 128
+  // rope_cos / rope_sin (tn_attn_bwd_rope): dq / dk are wanted as gradients of the UN-rotated q / k.  The causal D = 128
   // kernels rotate back in their epilogues; every other combination runs as it is and the row kernel follows (same bits).
   const bool rope = rope_cos != nullptr;
-  const bool rope_fused = rope && D == 128 && dq_stream && !delta_pass && !(bwd_kv_split() || qv.bidir) && qv.nseg == 1 &&
-                          qv.rpb == T;
+  const bool rope_fused = rope && D == 128 && !qv.bidir && qv.nseg == 1 && qv.rpb == T;
   const bf16_t* rc = rope_fused ? (const bf16_t*)rope_cos : nullptr;
   const bf16_t* rs = rope_fused ? (const bf16_t*)rope_sin : nullptr;
-  auto launch_dq = [&]() {
-    if (dq_stream)
-      launch_attn_bwd_dq_stream(Q, K, V, dO, lse2, delta, (bf16_t*)dq, doc, m, qv, B, T, Nh, Nkv, D, scale, sl2, O_, rc, rs,
-                                st);
-    else if (D == 128)
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), gq, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dq, doc, m,
-                         qv, T, Nh, Nkv, scale, sl2, O_);
-    else
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<64>), gq, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dq, doc, m,
-                         qv, T, Nh, Nkv, scale, sl2, O_);
-  };
-  if (D == 128) {
-    if (delta_pass)
-      hipLaunchKernelGGL((attn_delta_kernel<128>), dim3((rows * 16 + 255) / 256), block, 0, st, (const bf16_t*)o, dO,
-                         delta, B, qv.rpb, Nh);
-    else
-      launch_dq();
-    if (bwd_kv_split() || qv.bidir) {          // (the fused pass is causal only)
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<128, 0>), gk, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dk,
-                         (bf16_t*)dv, doc, m, qv, T, Nh, Nkv, scale, sl2);
-      hipLaunchKernelGGL((attn_bwd_kv_kernel<128, 1>), gk, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dk,
-                         (bf16_t*)dv, doc, m, qv, T, Nh, Nkv, scale, sl2);
-    } else {
-      launch_attn_bwd_kv_fused128(Q, K, V, dO, lse2, delta, (bf16_t*)dk, (bf16_t*)dv, doc, m, qv, B, T, Nh, Nkv, scale,
-                                  sl2, rc, rs, st);
-    }
-    if (delta_pass) launch_dq();
-  } else {
-    if (delta_pass)
-      hipLaunchKernelGGL((attn_delta_kernel<64>), dim3((rows * 8 + 255) / 256), block, 0, st, (const bf16_t*)o, dO,
-                         delta, B, qv.rpb, Nh);
-    else
-      launch_dq();
+  // dQ first: it forms delta from the dO / O rows it loads anyway and leaves it for the dK / dV pass behind it
+  launch_attn_bwd_dq_stream(Q, K, V, dO, lse2, delta, (bf16_t*)dq, doc, m, qv, B, T, Nh, Nkv, D, scale, sl2,
+                            (const bf16_t*)o, rc, rs, st);
+  if (D == 64) {
     hipLaunchKernelGGL((attn_bwd_kv_kernel<64, 2>), gk, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dk,
                        (bf16_t*)dv, doc, m, qv, T, Nh, Nkv, scale, sl2);
-    if (delta_pass) launch_dq();
+  } else if (qv.bidir) {                       // (the fused pass is causal only)
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<128, 0>), gk, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dk,
+                       (bf16_t*)dv, doc, m, qv, T, Nh, Nkv, scale, sl2);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<128, 1>), gk, block, 0, st, Q, K, V, dO, lse2, delta, (bf16_t*)dk,
+                       (bf16_t*)dv, doc, m, qv, T, Nh, Nkv, scale, sl2);
+  } else {
+    launch_attn_bwd_kv_fused128(Q, K, V, dO, lse2, delta, (bf16_t*)dk, (bf16_t*)dv, doc, m, qv, B, T, Nh, Nkv, scale,
+                                sl2, rc, rs, st);
   }
   TN_LAUNCH_CHECK();
   if (rope && !rope_fused)
     return tn_rope_apply(dq, dk, dq, dk, rope_cos, rope_sin, B * T, Nh, Nkv, D, 1, 1 /* bf16 */, stream);
-  return TN_OK;
-}
-
-// Development entry point (NOT part of the C ABI): dQ kernel for A/B runs inside one process (-1 = TN_ATTN_BWD_DQ / default).
-int tn_attn_set_bwd_dq(int mode) {
-  g_bwd_dq_override = mode;
   return TN_OK;
 }
 

@@ -1,5 +1,5 @@
 // Packed (document-masked) flash attention BACKWARD, dQ pass, for gfx950 — the treatment attn_fwd_stream.hip gave the
-// forward, applied to attn_bwd.hip's dQ kernel (same maths, same tile walk, same outputs):
+// forward, applied to the round-5 dQ kernel it replaced (same maths, same tile walk, same outputs):
 //   * the KV tiles a query tile meets and the id statistics of each wave's rows come from the mask metadata
 //     (attn_common.h klist / qstat) instead of an LDS window + scan inside every workgroup;
 //   * each wave fetches ITS 32 Q rows and 32 dO rows by LDS-DMA (64-byte runs per row) into a private piece of the ring

@@ -33,12 +33,6 @@
 
 #include "attn_common.h"
 
-// Timing experiments only (scripts/r04_fkv_ablate.sh builds variants with -DTN_FKV_ABL=<bits>; results are wrong):
-// 1 no LDS-DMA in the trips, 2 no barrier, 4 no softmax arithmetic, 8 no LDS reads, 16 no MFMAs, 32 no lgkmcnt waits
-#ifndef TN_FKV_ABL
-#define TN_FKV_ABL 0
-#endif
-
 namespace tn {
 
 namespace fusedkv {
@@ -74,9 +68,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 template <int BLK, bool FIRST>
 __device__ __forceinline__ void acc_mfma(bf16x8_t a, bf16x8_t b) {
 #define TN_M(...)                                                                                                     \
-  if constexpr ((TN_FKV_ABL & 16) != 0)                                                                               \
-    asm volatile("" ::"v"(a), "v"(b));                                                                                \
-  else if constexpr (FIRST)                                                                                           \
+  if constexpr (FIRST)                                                                                                \
     asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b),             \
                  "n"(16 * BLK), "n"(16 * BLK + 15) : __VA_ARGS__);                                                    \
   else                                                                                                                \
@@ -110,19 +102,11 @@ __device__ __forceinline__ float acc_read() {
 // behind that read; one statement, so hipcc has no boundary to pad between the wait and the MFMA).
 template <int K>
 __device__ __forceinline__ void mfma_first(f32x16_t& d, u32x4_t a, bf16x8_t b) {
-  constexpr int W = (TN_FKV_ABL & 32) ? 15 : K;
-  if constexpr ((TN_FKV_ABL & 16) != 0)
-    asm volatile("s_waitcnt lgkmcnt(%3)" : "=&v"(d) : "v"(a), "v"(b), "n"(W));
-  else
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b), "n"(W));
+  asm volatile("s_waitcnt lgkmcnt(%3)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b), "n"(K));
 }
 template <int K>
 __device__ __forceinline__ void mfma_acc(f32x16_t& d, u32x4_t a, bf16x8_t b) {
-  constexpr int W = (TN_FKV_ABL & 32) ? 15 : K;
-  if constexpr ((TN_FKV_ABL & 16) != 0)
-    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(d) : "v"(a), "v"(b), "n"(W));
-  else
-    asm volatile("s_waitcnt lgkmcnt(%3)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b), "n"(W));
+  asm volatile("s_waitcnt lgkmcnt(%3)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b), "n"(K));
 }
 // >= 13 wait states between the last MFMA of a chain and the first VALU read of its result
 __device__ __forceinline__ void mfma_result_pad(f32x16_t& d) { asm volatile("s_nop 7\n\ts_nop 4" : "+v"(d)); }
@@ -130,16 +114,14 @@ __device__ __forceinline__ void mfma_result_pad(f32x16_t& d) { asm volatile("s_n
 template <int OFF>
 __device__ __forceinline__ u32x2_t ds_tr16(uint32_t addr) {
   u32x2_t r;
-  if constexpr ((TN_FKV_ABL & 8) != 0) asm volatile("" : "=v"(r) : "v"(addr));
-  else asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
   return r;
 }
 
 template <class V, int OFF>
 __device__ __forceinline__ V ds_b128(uint32_t addr) {
   V r;
-  if constexpr ((TN_FKV_ABL & 8) != 0) asm volatile("" : "=v"(r) : "v"(addr));
-  else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
   return r;
 }
 
@@ -456,18 +438,19 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
     // my pieces of stage n have landed (stage n + 1 may stay in flight) ...
     wait_vmcnt<IPS>();
     // ... everybody's have, and everybody has left stage c - 1: its slot takes the stage three ahead
-    if constexpr ((TN_FKV_ABL & 2) == 0) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if constexpr ((TN_FKV_ABL & 1) == 0) issue(ahead, sb_a);
-    auto ds_elem = [&](auto R) {               // dS = P o (dP - delta), element R of stage c
+    issue(ahead, sb_a);
+    // (captures listed: their order is the closure's layout, and hipcc's schedule of the trip follows it)
+    auto ds_elem = [&dPc, &pf, &de4, &dsf](auto R) {      // dS = P o (dP - delta), element R of stage c
       constexpr int r = decltype(R)::value;
-      float v = (TN_FKV_ABL & 4) ? dPc[r] : pf[r] * (dPc[r] - de4[r >> 2][r & 3]);
+      float v = pf[r] * (dPc[r] - de4[r >> 2][r & 3]);
       asm volatile("" : "+v"(v));              // (one element per statement: no v_pk_*_f32 packing beside the MFMAs)
       dsf[r] = v;
     };
     auto p_elem = [&](auto R) {                // P = exp2(S c - LSE2), element R of stage n
       constexpr int r = decltype(R)::value;
-      float pv = (TN_FKV_ABL & 4) ? S[r] : fast_exp2(S[r] * scale_log2 - le4[r >> 2][r & 3]);
+      float pv = fast_exp2(S[r] * scale_log2 - le4[r >> 2][r & 3]);
       if constexpr (MASK) {
         const int o = 8 * (r >> 2) + 4 * hi + (r & 3);
         pv = ((kvrow <= qsb_n + o) & (qd4[r >> 2][r & 3] == dkdoc) & (dkdoc > 0)) ? pv : 0.f;

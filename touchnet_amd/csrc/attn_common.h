@@ -144,57 +144,7 @@ __device__ __forceinline__ bool tile_may_interact(int qminpos, int qmax, int kmi
   return !(qminpos == 0x7fffffff || kminpos == 0x7fffffff || kmax < qminpos || kminpos > qmax);
 }
 
-// ---- KV-tile list in LDS --------------------------------------------------------------------------------------
-// The tile loops used to walk the metadata arrays themselves: per tile two or three DEPENDENT scalar global loads
-// (interaction test of the next tile, then of the current one), ~1-2 k cycles of latency each way (s_memtime trace of
-// the ping-pong forward: QK^T segment 2100 -> 860 cycles without them).  Instead the workgroup compacts, ONCE per
-// chunk of tiles (the caller's list capacity), the tiles of [lo, hi] that may interact with its query id range into LDS:
-//   entry = {tile, min id, max id, min positive id};  entries [n, n + 4) = sentinels {hi_all + 1, 0, 0, 0}.
-// NT = threads per workgroup (all must call; contains barriers).  Returns n (wave-uniform, in an SGPR).
-constexpr int kListCap = 1024;
-
-template <int NT>
-__device__ __forceinline__ int build_kv_list(int4* list, int* wcount, int lo, int hi, int sentinel, int bminpos,
-                                             int bmax, const int* m_min, const int* m_max, const int* m_minpos,
-                                             int tid, int kv_tpc = 0, unsigned long long kv_mask = ~0ull) {
-  constexpr int NW = NT / 64;
-  const int lane = tid & 63, wave = tid >> 6;
-  int n = 0;
-  for (int base = lo; base <= hi; base += NT) {
-    const int j = base + tid;
-    int mn = 0, mx = 0, mp = 0;
-    bool ok = false;
-    if (j <= hi) {
-      mn = m_min[j];
-      mx = m_max[j];
-      mp = m_minpos[j];
-      ok = tile_may_interact(bminpos, bmax, mp, mx) && (kv_tpc == 0 || ((kv_mask >> (j / kv_tpc)) & 1ull));
-    }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int before = n, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const int c = wcount[w];
-      before += w < wave ? c : 0;
-      total += c;
-    }
-    if (ok) list[before + __popcll(bal & ((1ull << lane) - 1ull))] = make_int4(j, mn, mx, mp);
-    n += __builtin_amdgcn_readfirstlane(total);
-    __syncthreads();
-  }
-  if (tid < 4) list[n + tid] = make_int4(sentinel, 0, 0, 0);
-  __syncthreads();
-  return n;
-}
-
-// list entry i as four scalars (one broadcast LDS read + 4 readfirstlane)
-__device__ __forceinline__ int4 list_entry(const int4* list, int i) {
-  const int4 e = list[i];
-  return make_int4(__builtin_amdgcn_readfirstlane(e.x), __builtin_amdgcn_readfirstlane(e.y),
-                   __builtin_amdgcn_readfirstlane(e.z), __builtin_amdgcn_readfirstlane(e.w));
-}
+// a list entry as four scalars (4 readfirstlane)
 __device__ __forceinline__ int4 scalarize(i32x4_t e) {
   return make_int4(__builtin_amdgcn_readfirstlane(e.x), __builtin_amdgcn_readfirstlane(e.y),
                    __builtin_amdgcn_readfirstlane(e.z), __builtin_amdgcn_readfirstlane(e.w));
@@ -311,33 +261,6 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t b
   const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
-
-// Stage a [R rows][D] bf16 tile (source row stride `ld` elements, rows >= rows_valid zero-filled) into a PTile image:
-// full-row coalesced 16-byte global loads now, 16-byte LDS stores later.
-template <int R, int D, int NT>
-struct PStage {
-  static constexpr int CPR = D / 8;
-  static constexpr int N = (R * CPR + NT - 1) / NT;
-  static constexpr bool EXACT = (R * CPR) % NT == 0;
-  uint4 v[N];
-  __device__ __forceinline__ void load(const bf16_t* src, size_t ld, int rows_valid, int tid) {
-    const __amdgpu_buffer_rsrc_t rs = tile_rsrc(src, ld, rows_valid < R ? rows_valid : R, D);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const int c = tid + i * NT;
-      const int r = c / CPR, cc = c % CPR;
-      v[i] = buf_load16(rs, (EXACT || c < R * CPR) ? (uint32_t)((r * ld + cc * 8) * 2) : 0xffffffffu);
-    }
-  }
-  __device__ __forceinline__ void store(bf16_t* dst, int tid) const {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const int c = tid + i * NT;
-      const int r = c / CPR, cc = c % CPR;
-      if (EXACT || c < R * CPR) *reinterpret_cast<uint4*>(dst + PTile<R, D>::chunk_off(r, cc)) = v[i];
-    }
-  }
-};
 
 // The TRANSPOSED rotary rotation — what tn_rope_apply(backward = 1) applies to the gradient of a rotated q / k row — of one
 // 16-byte chunk of a gradient row in a backward kernel's epilogue: `own` = the lane's 8 columns, `other` = the same 8

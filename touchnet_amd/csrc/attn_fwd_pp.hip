@@ -1,8 +1,8 @@
 // Packed (document-masked, causal) flash attention FORWARD — "ping-pong" variant for gfx950.
 //
-// Same contract, layouts and MFMA conventions as attn_fwd.hip; what changes is the SCHEDULE.  Ablation of the
-// baseline kernel (scripts/attn_ablate.py) showed that the phases of a wave (QK^T MFMAs | softmax VALU | P.V
-// MFMAs | staging | barrier) add up to the total: with 2 waves per SIMD nothing overlaps, and an 8-wave block in
+// Same contract, layouts and MFMA conventions as attn_fwd_stream.hip; what changes is the SCHEDULE.  Ablation of
+// the original one-group kernel (retired) showed that the phases of a wave (QK^T MFMAs | softmax VALU |
+// P.V MFMAs | staging | barrier) add up to the total: with 2 waves per SIMD nothing overlaps, and an 8-wave block in
 // lockstep is even slower.  Here a 512-thread workgroup owns 256 query rows as two groups of 4 waves
 // (one wave of each group per SIMD) that run ONE PHASE APART:
 //
@@ -18,33 +18,6 @@
 #include "attn_common.h"
 
 namespace tn {
-
-#ifdef TN_PP_TRACE   // kernel-development instrumentation (scripts/build_variant.sh ... -DTN_PP_TRACE), never in the product build
-__device__ unsigned long long g_pp_trace[2][192][8];
-__device__ unsigned long long g_pp_blocks[8192][2];   // per workgroup: s_memrealtime at entry / exit
-#define PP_STAMP(slot)                                                                          \
-  do {                                                                                          \
-    if (trace_on && t < 192) g_pp_trace[grp][t][slot] = __builtin_amdgcn_s_memtime();           \
-  } while (0)
-#else
-#define PP_STAMP(slot) \
-  do {                 \
-  } while (0)
-#endif
-
-// kernel-development ablations (variants only): -DTN_PP_NOMFMA keeps the operand reads but drops the MFMAs,
-// -DTN_PP_NOLDS keeps the MFMAs but feeds them registers instead of LDS operands.  Output is garbage.
-#if defined(TN_PP_NOMFMA)
-#define PP_MFMA(a, b, c) (keep_alive(a), (c))
-#else
-#define PP_MFMA(a, b, c) mfma32(as_bf16x8(a), b, c)
-#endif
-#if defined(TN_PP_NOLDS)
-#define PP_LDS16(p, dflt) (dflt)
-#else
-#define PP_LDS16(p, dflt) (*reinterpret_cast<const uint4*>(p))
-#endif
-__device__ __forceinline__ void keep_alive(uint4 v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
 
 // LDS image of V^T for the P.V operand: element (d, kv) at  d * (R + 8) + 4 * pos(kv >> 2) + (kv & 3)  with
 // pos(g) = 4 * (g >> 2) + bitswap2(g & 3): the two 4-kv groups {g, g + 2} that one lane-half contracts in one MFMA
@@ -80,14 +53,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
   bf16_t* const Vbuf = smem + 3 * KSLOT;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef TN_PP_TRACE
-  const int lin_block = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  if (tid == 0 && lin_block < 8192) {
-    g_pp_blocks[lin_block][0] = __builtin_amdgcn_s_memrealtime();
-    g_pp_trace[0][191][0] = __builtin_amdgcn_s_memtime();       // (clock-ratio probe, any block)
-    g_pp_trace[0][191][1] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
   const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);   // 0 = group A, 1 = group B (one phase behind); SGPR
   const int gtid = tid & 255;               // thread index inside the group (staging work split)
   const int l31 = lane & 31, hi = lane >> 5;
@@ -261,14 +226,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
     const bf16_t* kp = Ks + l31 * KLD + 8 * hi;
     constexpr int NQK = 2 * KSTEPS, QRING = NQK < 8 ? NQK : 8;   // op i: K block i&1, contraction step i>>1
     uint4 kf[QRING];
-    const uint4 dflt = make_uint4(lane, tid, l31, hi);
 #pragma unroll
-    for (int i = 0; i < QRING; ++i) kf[i] = PP_LDS16(kp + (i & 1) * 32 * KLD + 16 * (i >> 1), dflt);
+    for (int i = 0; i < QRING; ++i) kf[i] = *reinterpret_cast<const uint4*>(kp + (i & 1) * 32 * KLD + 16 * (i >> 1));
     __builtin_amdgcn_sched_barrier(0);      // (pins the order: the scheduler otherwise sinks the reads again)
 #pragma unroll
     for (int i = 0; i < NQK; ++i) {
-      sacc[i & 1] = PP_MFMA(kf[i % QRING], qreg[i >> 1], i < 2 ? zero16 : sacc[i & 1]);
-      if (i + QRING < NQK) kf[i % QRING] = PP_LDS16(kp + ((i + QRING) & 1) * 32 * KLD + 16 * ((i + QRING) >> 1), dflt);
+      sacc[i & 1] = mfma32(as_bf16x8(kf[i % QRING]), qreg[i >> 1], i < 2 ? zero16 : sacc[i & 1]);
+      if (i + QRING < NQK)
+        kf[i % QRING] = *reinterpret_cast<const uint4*>(kp + ((i + QRING) & 1) * 32 * KLD + 16 * ((i + QRING) >> 1));
       if (stage && i >= 1 && i <= 5) issue_piece(i - 1);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -308,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
     mx = max3(mx, mxs[3], sacc[1][7]);
     mx = max3(mx, sacc[1][15], sacc[1][15]);
     mx = half_swap_max(mx) * scale_log2;
-    if (uniform(!__all(mx - m_run <= 8.f))) {             // deferred rescale, see attn_fwd.hip
+    if (uniform(!__all(mx - m_run <= 8.f))) {             // deferred rescale, see attn_fwd_stream.hip
       const float m_new = fmaxf(m_run, mx);
       const float alpha = fast_exp2(m_run - m_new);
       m_run = m_new;
@@ -349,15 +314,15 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
     // 4 (16-kv sub-block) x DBLK MFMAs; operand ring of RING fragments, consecutive MFMAs hit different accumulators
     constexpr int NOP = 4 * DBLK, RING = NOP < 8 ? NOP : 8;
     uint4 vf[RING];
-    const uint4 dflt = make_uint4(lane, tid, l31, hi);
 #pragma unroll
-    for (int i = 0; i < RING; ++i) vf[i] = PP_LDS16(vp + (i % DBLK) * 32 * VLD + 16 * (i / DBLK), dflt);
+    for (int i = 0; i < RING; ++i) vf[i] = *reinterpret_cast<const uint4*>(vp + (i % DBLK) * 32 * VLD + 16 * (i / DBLK));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NOP; ++i) {
       const int db = i % DBLK, g = i / DBLK;              // g: 16-kv sub-block = (blk, sp)
-      oacc[db] = PP_MFMA(vf[i % RING], pb[g >> 1][g & 1], oacc[db]);
-      if (i + RING < NOP) vf[i % RING] = PP_LDS16(vp + ((i + RING) % DBLK) * 32 * VLD + 16 * ((i + RING) / DBLK), dflt);
+      oacc[db] = mfma32(as_bf16x8(vf[i % RING]), pb[g >> 1][g & 1], oacc[db]);
+      if (i + RING < NOP)
+        vf[i % RING] = *reinterpret_cast<const uint4*>(vp + ((i + RING) % DBLK) * 32 * VLD + 16 * ((i + RING) / DBLK));
       if (stage && i < 8) store_piece(G, i, kbase, vbase, dbase);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -394,30 +359,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
     auto main_loop = [&](auto G) __attribute__((always_inline)) {
       constexpr int grp_c = decltype(G)::value;
       if (grp_c == 1) __syncthreads();
-#ifdef TN_PP_TRACE
-      const bool trace_on = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && (tid & 255) == 0;
-#endif
       for (int t = 0; t < n; ++t) {
-        PP_STAMP(0);
         const int4 e_nxt = tlist[t + 1];    // (vector read now, scalarised at the end of the iteration)
         const int js = __builtin_amdgcn_readfirstlane(tlist[ps].x);
         const int kst = kslot == 0 ? 2 : kslot - 1;       // (t + 2) % 3
         pv(G, IC<1>{}, (t - 1) & 1, k_spot(kst), v_spot(t & 1), d_spot(kst));
-        PP_STAMP(1);
         issue_setup(stage_src, js);
         ++ps;
         qk(e_cur, kslot);
-        PP_STAMP(2);
         __syncthreads();
-        PP_STAMP(3);
         softmax();
-        PP_STAMP(4);
         e_cur = make_int4(__builtin_amdgcn_readfirstlane(e_nxt.x), __builtin_amdgcn_readfirstlane(e_nxt.y),
                           __builtin_amdgcn_readfirstlane(e_nxt.z), __builtin_amdgcn_readfirstlane(e_nxt.w));
         kslot = kslot == 2 ? 0 : kslot + 1;
-        PP_STAMP(6);
         __syncthreads();
-        PP_STAMP(7);
       }
       pv(G, IC<0>{}, (n - 1) & 1, nullptr, nullptr, nullptr);   // drain: P.V of the last tile
       __syncthreads();
@@ -427,15 +382,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
   }
 
   // ---- epilogue
-#ifdef TN_PP_TRACE
-  if (tid == 0 && lin_block < 8192) {
-    g_pp_blocks[lin_block][1] = __builtin_amdgcn_s_memrealtime();
-    if (lin_block == 8191 || lin_block == gridDim.x * gridDim.y * gridDim.z - 1) {
-      g_pp_trace[0][191][2] = __builtin_amdgcn_s_memtime();
-      g_pp_trace[0][191][3] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
-#endif
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
   if (qvalid) {
@@ -457,15 +403,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
 }  // namespace tn
 
 using namespace tn;
-
-#ifdef TN_PP_TRACE
-extern "C" int tn_debug_pp_trace(void* dst) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tn::g_pp_trace), sizeof(unsigned long long) * 2 * 192 * 8);
-}
-extern "C" int tn_debug_pp_blocks(void* dst) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tn::g_pp_blocks), sizeof(unsigned long long) * 8192 * 2);
-}
-#endif
 
 // called from attn_fwd.hip's launcher
 int tn_attn_fwd_pp_launch(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,

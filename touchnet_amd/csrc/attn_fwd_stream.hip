@@ -2,9 +2,10 @@
 // (those: attn_fwd_pp.hip): LDS-DMA ring for K / V, nothing a workgroup needs to know computed inside it.
 //
 // Why (profiles/r05x_attn_fwd_ablation_short_documents.log, profiles/r06a_*): on the headline's ~790-token documents a
-// workgroup of attn_fwd.hip meets ~9 KV tiles; a wave's life there was 23 % prologue (four DEPENDENT memory round trips:
-// row ids -> tile range -> tile list -> first K/V tile), 8 % epilogue (8 bytes per lane at a row stride: store-issue
-// bound) and 68 % tile trips in which every MFMA of the QK^T chain waited for its own LDS read.  Here, per workgroup:
+// workgroup of the retired schedule-0 forward meets ~9 KV tiles; a wave's life there was 23 % prologue (four DEPENDENT
+// memory round trips: row ids -> tile range -> tile list -> first K/V tile), 8 % epilogue (8 bytes per lane at a row
+// stride: store-issue bound) and 68 % tile trips in which every MFMA of the QK^T chain waited for its own LDS read.
+// Here, per workgroup:
 //   * what it has to do comes from the mask metadata, worked out ONCE per batch for all layers and heads
 //     (attn_common.h klist / qstat): the list of KV tiles of its query tile and the id statistics of each wave's rows.
 //     Two round trips are left: {list, statistics, Q rows} and the first K / V tile;
@@ -20,38 +21,24 @@
 //     instruction.
 // Measured on one box, interleaved (profiles/r06a_attn_fwd_stream_vs_base_same_box.log): 286 -> 238 us on the decoder's
 // shape, 257 -> 216 us on the audio tower's, 1217 -> 1107 us on plain causal 2 x 8192; same tiles, same MFMA and
-// softmax sequence as attn_fwd.hip (outputs equal to the last bf16 digit but for the summation order of the row sums).
+// softmax sequence as schedule 0 (outputs equal to the last bf16 digit but for the summation order of the row sums).
 // Also measured, and NOT kept: several heads of a query tile per workgroup sharing the list, with the stream crossing
 // head seams (1.00 / 1.15 / 1.33 x the time at 2 / 4 / 8 heads: fewer, longer workgroups balance worse over the CUs than
 // the shared prologue saves); records sorted heaviest-first (attn_common.h).
 //
-// Maths, masking rules, layouts and the output contract are those of attn_fwd.hip (reference semantics:
+// Layouts and the output contract: attn_fwd.hip (reference semantics:
 // transformers/integrations/flex_attention.py:190-201,264-340 via touchnet/models/kimi_audio/modeling_kimi_audio.py:582-585
 // and touchnet/models/qwen2_audio/__init__.py:190-193).
-#include <stdlib.h>
-
 #include "attn_stream.h"
 
 namespace tn {
 
-// TRACE (timing experiments, scripts/r06_attn_trace.py): lane 0 of every wave stamps s_memtime at the marked points into
-// trace[(workgroup * 4 + wave) * 64 + event]
-template <int D, bool TRACE = false>
+template <int D>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
     float* __restrict__ LSE2, const int* __restrict__ doc, AttnMeta meta, QView qv, int T, int Nh, int Nkv,
-    float scale_log2, unsigned long long* __restrict__ trace) {
+    float scale_log2) {
   using namespace fstream;
-  int tev = 0;
-  auto stamp = [&]() {
-    if constexpr (TRACE) {
-      const unsigned long long t = __builtin_readcyclecounter();
-      const int wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-      if ((threadIdx.x & 63) == 0 && tev < 64) trace[((size_t)wg * 4 + (threadIdx.x >> 6)) * 64 + tev] = t;
-      ++tev;
-    }
-  };
-  stamp();                                                   // 0: entry
   constexpr int BM = 128, BN = 64, NST = 2;
   constexpr int KSTEPS = D / 16, DBLK = D / 32;
   using Tile = PTile<BN, D>;
@@ -139,11 +126,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
   const int t0 = q0 / kTile, t1 = min(t0 + BM / kTile - 1, meta.nt - 1);
   const int n_pre = __builtin_amdgcn_readfirstlane(kl_head.x);
   const bool pre = n_pre <= kListPre;                    // the stored list is complete: use it
-  stamp();                                                   // 1: round trip A is back
   int bminpos = 0x7fffffff, bmax = 0, j_lo = meta.nt, j_hi = t1;
   if (!pre) {
     // ---- long lists, bidirectional masks, key-chunk restrictions: the tile range from the metadata of the two 64-row
-    // halves of the query tile, the list built here in chunks of CAP (as attn_fwd.hip)
+    // halves of the query tile, the list built here in chunks of CAP
     for (int t = t0; t <= t1; ++t) {
       bminpos = min(bminpos, m_minpos[t]);
       bmax = max(bmax, m_max[t]);
@@ -153,7 +139,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
       for (int t = t0; t <= t1; ++t) j_hi = max(j_hi, meta.kv_hi[(size_t)b * meta.nt + t]);
   }
   const int qcap = bidir ? 0x7fffffff : qrow;          // `kv <= qcap`: the causal term of the predicate
-  stamp();                                                   // 2: tile range known
 
   // tiles of [lo, hi] that may interact with this query tile -> list entries {tile, min id, max id, min positive id}
   auto build_list = [&](int lo, int hi_t) {
@@ -242,7 +227,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qreg[s]));
   }
-  stamp();                                                   // 3: Q in registers, list in LDS
 
   f32x16_t oacc[DBLK];
 #pragma unroll
@@ -261,11 +245,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
       const i32x4_t e_nn = tlist[i + 2];                  // (vector read now, scalarised at the hand-over)
       // my pieces of this stage have landed ...
       wait_vmcnt<0>();
-      stamp();                                             // trip: my pieces have landed
       // ... everybody's have, and everybody has left the previous stage: its slot takes the next one
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      stamp();                                             // trip: through the barrier
       // K "row" operands: inline-asm reads in batches of four fragments (k-steps 2 g, 2 g + 1 of both 32-row blocks), two
       // batches in flight — left to hipcc, every MFMA of the chain waited for its own read (read, lgkmcnt(0), MFMA:
       // sixteen exposed LDS latencies per tile).  The first two batches leave before the DMA of the next stage is
@@ -371,7 +353,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
           mx = max3(mx, sacc[1][15], sacc[1][15]);
         }
         mx = half_max(mx) * scale_log2;
-        // Deferred rescale (threshold 8 in the log2 domain), as attn_fwd.hip
+        // Deferred rescale (threshold 8 in the log2 domain): while no row's running max grows by more than 2^8 the old
+        // reference max stays, P <= 256 is exact enough in bf16 and the 16*DBLK-register O rescale is skipped.
         if (uniform(!__all(mx - m_run <= 8.f))) {
           const float m_new = fmaxf(m_run, mx);
           const float alpha = fast_exp2(m_run - m_new);
@@ -449,7 +432,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
         vt_mfma(I3{}, I1{});
 #undef TN_VT_RETIRE
       }
-      stamp();                                             // trip: computed
       // ---- hand-over
       e_cur = e_nxt;
       e_nxt = scalarize(e_nn);
@@ -486,33 +468,22 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
     }
     if (qvalid && hi == 0) LSE2[((size_t)b * Nh + h) * qv.rpb + lrow] = l_tot > 0.f ? m_run + log2f(l_tot) : INFINITY;
   }
-  stamp();                                         // exit
 }
 
 }  // namespace tn
 
 using namespace tn;
 
-static unsigned long long* g_stream_trace = nullptr;      // tn_attn_fwd_stream_trace (development entry point)
-
 int tn_attn_fwd_stream_launch(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                               AttnMeta m, QView qv, int B, int T, int Nh, int Nkv, int D, float sl2, hipStream_t st) {
   dim3 grid(Nh, qv.tiles(0, 128) + qv.tiles(1, 128), B), block(256);
-#define TN_LAUNCH(DD, TT)                                                                                              \
-  hipLaunchKernelGGL((attn_fwd_stream_kernel<DD, TT>), grid, block, 0, st, (const bf16_t*)q, (const bf16_t*)k,         \
-                     (const bf16_t*)v, (bf16_t*)o, lse2, doc, m, qv, T, Nh, Nkv, sl2, g_stream_trace)
-  if (D == 128 && g_stream_trace) TN_LAUNCH(128, true);
-  else if (D == 128) TN_LAUNCH(128, false);
-  else if (D == 64) TN_LAUNCH(64, false);
+#define TN_LAUNCH(DD)                                                                                                  \
+  hipLaunchKernelGGL((attn_fwd_stream_kernel<DD>), grid, block, 0, st, (const bf16_t*)q, (const bf16_t*)k,             \
+                     (const bf16_t*)v, (bf16_t*)o, lse2, doc, m, qv, T, Nh, Nkv, sl2)
+  if (D == 128) TN_LAUNCH(128);
+  else if (D == 64) TN_LAUNCH(64);
   else return TN_EINVAL;
 #undef TN_LAUNCH
   TN_LAUNCH_CHECK();
-  return TN_OK;
-}
-
-// Development entry point (NOT part of the C ABI): D = 128 launches of the stream forward stamp s_memtime per wave into
-// `buf` (uint64 [workgroups * 4 * 64]) until it is reset with nullptr.
-extern "C" int tn_attn_fwd_stream_trace(void* buf) {
-  g_stream_trace = (unsigned long long*)buf;
   return TN_OK;
 }

@@ -14,7 +14,6 @@ returns an EMPTY placeholder and the autograd formula keeps the input itself.
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import List, Optional, Tuple
 
 import torch
@@ -362,9 +361,6 @@ def _(q, k, v, o, do, lse2, doc, meta, scale):
     return e(q), e(k), e(v)
 
 
-_STACKED_BWD = os.environ.get("TN_ATTN_BWD_STACKED", "1") != "0"      # (A/B switch)
-
-
 @custom_op(f"{NS}::attn_bwd_stacked", mutates_args=(), device_types="cuda")
 def attn_bwd_stacked(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
                      scale: float) -> Tensor:
@@ -429,7 +425,7 @@ def _attn_backward(ctx, do, _dlse):
     q, k, v, o, lse2, doc, meta = ctx.saved_tensors
     if do is None:
         do = torch.zeros_like(o)
-    if q.shape == k.shape and _STACKED_BWD:                  # multi-head attention: one buffer, three slices
+    if q.shape == k.shape:                  # multi-head attention: one buffer, three slices
         dq, dk, dv = attn_bwd_stacked(q, k, v, o, do, lse2, doc, meta, ctx.scale).unbind(0)
     else:
         dq, dk, dv = attn_bwd(q, k, v, o, do, lse2, doc, meta, ctx.scale)
