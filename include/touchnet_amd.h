@@ -395,6 +395,22 @@ int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len,
                    int do_sample, float temperature, int top_k, float top_p, unsigned long long seed, const int* eos_ids,
                    int n_eos, int pad, int dtype, void* stream);
 
+/* ---- Kimi-Audio's speech tokenizer (GLM-4-voice WhisperVQEncoder, touchnet/models/kimi_audio/modeling_kimi_audio.py:140-319,
+ *      run by MoonshotKimiaForCausalLM.prepare_audio_input_embs under no_grad, :957-963).  Forward only: it is frozen.
+ * attn_block_causal_fwd: the layers' self-attention under get_block_causal_attention_mask (:226-242, applied :293-301):
+ *      allowed(i, j) = m[j] && j / block <= i / block.  q / k / v / o bf16 [B, T, Nh, D], D = 64, Nh == Nkv; position t of
+ *      row b belongs to the clip starting at seg_start[b, t] (row-local) whose valid keys end at key_end[b, t] (exclusive;
+ *      int32 [B, T] each): query i attends to keys [s, min(key_end, s + ((i - s) / block + 1) * block)), s = seg_start;
+ *      fp32 softmax; a row with no such key writes 0.  -22 before any launch for D != 64, block < 1, NULL or misaligned
+ *      (q / k / v 16-byte, o 8-byte) pointers. */
+int tn_attn_block_causal_fwd(const void* q, const void* k, const void* v, void* o, const int* seg_start, const int* key_end,
+                             int B, int T, int Nh, int D, int block, float scale, void* stream);
+/* vq_nearest: `vector_quantize` (:85-98): ids[r] = argmin_c (cnorm[c] - 2 x[r] . c), the first index on ties (torch.min);
+ *      x bf16 [M, d], codebook bf16 [V, d] (16-byte aligned), cnorm fp32 [V] = |c|^2, d % 64 == 0; bf16 MFMA products
+ *      with fp32 accumulation, no [M, V] buffer; ids int64 [M] (also the scratch of the cross-workgroup 64-bit min, so
+ *      the result is deterministic).  -22 before any launch for d % 64 != 0, V < 1, NULL or misaligned pointers. */
+int tn_vq_nearest(const void* x, const void* codebook, const float* cnorm, long long* ids, int M, int V, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1547,3 +1547,46 @@ def sample_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penal
     eos = [int(e) for e in ([eos] if isinstance(eos, int) else eos)]
     L.sample_step_(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, uniforms, n_kept, float(penalty),
                    bool(do_sample), float(temperature), int(top_k), float(top_p), int(seed), eos, int(pad))
+
+
+# ------------------------------------------------------------------------------------ Kimi-Audio speech tokenizer (frozen)
+@dataclass
+class BlockCausalMask:
+    """Device-side form of the speech tokenizer's block-causal key mask (`get_block_causal_attention_mask`,
+    touchnet/models/kimi_audio/modeling_kimi_audio.py:226-242) for rows that may hold several clips back to back:
+    position t of row b belongs to the clip starting at seg_start[b, t] whose valid keys end at key_end[b, t]."""
+    seg_start: torch.Tensor   # int32 [B, T]
+    key_end: torch.Tensor     # int32 [B, T]
+    block: int
+    B: int
+    T: int
+
+
+def block_causal_mask(seg_start: torch.Tensor, key_end: torch.Tensor, block: int) -> BlockCausalMask:
+    B, T = seg_start.shape
+    return BlockCausalMask(_c(seg_start).to(torch.int32), _c(key_end).to(torch.int32), int(block), B, T)
+
+
+def block_causal_attention(q, k, v, mask: BlockCausalMask, scale: Optional[float] = None):
+    """softmax(scale * Q K^T + block-causal key mask) V, forward only (tn_attn_block_causal_fwd): q / k / v bf16
+    [B, T, Nh, 64] -> [B, T, Nh, 64].  Query i of a clip starting at s sees the clip's valid keys j with
+    (j - s) // block <= (i - s) // block; padded query rows are ordinary rows."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    if tuple(q.shape[:2]) != (mask.B, mask.T):
+        raise _C.KernelError(f"mask built for {(mask.B, mask.T)}, got q {tuple(q.shape[:2])}")
+    return L.attn_block_causal_fwd(q, k, v, mask.seg_start, mask.key_end, mask.block, float(scale))
+
+
+def vq_nearest(x: torch.Tensor, codebook: torch.Tensor, cnorm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Nearest codebook row of every row of x (`vector_quantize`, modeling_kimi_audio.py:85-98; tn_vq_nearest): x bf16
+    [M, d], codebook bf16 [V, d], d % 64 == 0 -> ids int64 [M], the first index on ties.  `cnorm` = fp32 |c|^2 [V]
+    (computed here when None; callers with a frozen codebook pass it once computed)."""
+    if cnorm is None:
+        cnorm = codebook_sqnorm(codebook)
+    return L.vq_nearest(x, codebook, cnorm)
+
+
+def codebook_sqnorm(codebook: torch.Tensor) -> torch.Tensor:
+    """fp32 |c|^2 [V] of a codebook: the per-code constant of the nearest-code distance (once per frozen codebook)."""
+    return codebook.detach().float().pow(2).sum(1)

@@ -983,8 +983,56 @@ def _(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, unifor
     return None
 
 
+# ===================================================================================================== speech tokenizer (frozen)
+@custom_op(f"{NS}::attn_block_causal_fwd", mutates_args=(), device_types="cuda")
+def attn_block_causal_fwd(q: Tensor, k: Tensor, v: Tensor, seg_start: Tensor, key_end: Tensor, block: int,
+                          scale: float) -> Tensor:
+    """Block-causal attention of the Kimi-Audio speech tokenizer (tn_attn_block_causal_fwd): q / k / v bf16 [B, T, Nh, 64];
+    seg_start / key_end int32 [B, T]: query i attends to keys [s, min(key_end, s + ((i - s) // block + 1) * block)),
+    s = seg_start[i].  Forward only (no autograd formula: the tokenizer is frozen)."""
+    _no_grad_inputs("attn_block_causal_fwd", q, k, v)
+    B, T, Nh, D = q.shape
+    if (q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16 or D != 64
+            or tuple(k.shape) != (B, T, Nh, D) or tuple(v.shape) != (B, T, Nh, D)
+            or seg_start.dtype != torch.int32 or key_end.dtype != torch.int32
+            or tuple(seg_start.shape) != (B, T) or tuple(key_end.shape) != (B, T) or block < 1):
+        raise _C.KernelError("attn_block_causal_fwd: bf16 q / k / v [B, T, Nh, 64] (Nh == Nkv), int32 seg_start / key_end "
+                             "[B, T], block >= 1")
+    q, k, v, s, e = _c(q), _c(k), _c(v), _c(seg_start), _c(key_end)
+    o = torch.empty_like(q)
+    _C.check(_lib().tn_attn_block_causal_fwd(_p(q), _p(k), _p(v), _p(o), _p(s), _p(e), B, T, Nh, D, int(block),
+                                             float(scale), _cur()), "tn_attn_block_causal_fwd")
+    return o
+
+
+@attn_block_causal_fwd.register_fake
+def _(q, k, v, seg_start, key_end, block, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+@custom_op(f"{NS}::vq_nearest", mutates_args=(), device_types="cuda")
+def vq_nearest(x: Tensor, codebook: Tensor, cnorm: Tensor) -> Tensor:
+    """ids int64 [M] = argmin_c (cnorm[c] - 2 x[r] . c), first index on ties (tn_vq_nearest): x bf16 [M, d], codebook bf16
+    [V, d], cnorm fp32 [V] = |c|^2, d % 64 == 0.  Forward only."""
+    _no_grad_inputs("vq_nearest", x, codebook)
+    if (x.dim() != 2 or codebook.dim() != 2 or x.dtype != torch.bfloat16 or codebook.dtype != torch.bfloat16
+            or x.shape[1] != codebook.shape[1] or x.shape[1] % 64 != 0 or codebook.shape[0] < 1
+            or cnorm.dtype != torch.float32 or tuple(cnorm.shape) != (codebook.shape[0],)):
+        raise _C.KernelError("vq_nearest: bf16 x [M, d] and codebook [V, d] with d % 64 == 0, fp32 cnorm [V]")
+    x, cb, cn = _c(x), _c(codebook), _c(cnorm)
+    M, d = x.shape
+    ids = torch.empty(M, dtype=torch.int64, device=x.device)
+    _C.check(_lib().tn_vq_nearest(_p(x), _p(cb), _p(cn), _p(ids), M, cb.shape[0], d, _cur()), "tn_vq_nearest")
+    return ids
+
+
+@vq_nearest.register_fake
+def _(x, codebook, cnorm):
+    return x.new_empty(x.shape[0], dtype=torch.int64)
+
+
 OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
-       "attn_decode_", "greedy_step_", "sample_step_")
+       "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest")

@@ -13,9 +13,9 @@ In scope: the decoder (the packed hot path: document-masked attention, fused nor
 over V = 168448 on the labelled rows) AND — round 4 — the audio-input side of `prepare_audio_input_embs` (`:933-985`):
 the Whisper-large-v3 speech encoder on `whisper_input_features` (`WhisperSpeechEncoder`: the Qwen2-Audio tower's blocks
 with BIDIRECTIONAL attention and no pooling), the x4 reshape + `vq_adaptor` (`:322-334`), the embeddings of the discrete
-speech-tokenizer ids x sqrt(2), and the scatter between the media markers (index arithmetic, no host sync).  Still the
-loader's: the GLM-4-voice VQ tokenizer (`WhisperVQEncoder`, frozen, `:859-860, 957-963`) — its ids enter as
-`speech_tokenizer_ids`.
+speech-tokenizer ids x sqrt(2), and the scatter between the media markers (index arithmetic, no host sync).  With a
+`speech_tokenizer_config` the model also holds the frozen GLM-4-voice VQ tokenizer (`WhisperVQEncoder`, `:856-857,
+957-963`; speech_tokenizer.py) and computes the ids itself when the batch carries none.
 """
 from __future__ import annotations
 
@@ -30,6 +30,7 @@ from ..llama.configuration import DecoderConfig
 from ..llama.modeling_llama import DecoderLayer, RMSNorm, RotaryEmbedding
 from ..qwen2_audio.modeling_qwen2_audio import AudioEncoderConfig, LayerNorm, Qwen2AudioEncoder
 from ..backend import ops
+from .speech_tokenizer import WhisperVQConfig, WhisperVQEncoder
 
 
 @dataclass
@@ -44,6 +45,7 @@ class KimiAudioConfig(DecoderConfig):
     use_whisper_feature: bool = False
     kimia_adaptor_input_dim: int = 5120
     speech_encoder_config: Optional[dict] = None      # WhisperConfig keys; None = whisper-large-v3's encoder
+    speech_tokenizer_config: Optional[dict] = None    # WhisperVQConfig keys; None = no tokenizer (ids come with the batch)
 
     def __post_init__(self):
         self.model_type = "qwen2"            # Qwen2DecoderLayer: q/k/v carry a bias
@@ -52,6 +54,11 @@ class KimiAudioConfig(DecoderConfig):
 
     def speech_encoder_dims(self) -> AudioEncoderConfig:
         return AudioEncoderConfig.from_dict(self.speech_encoder_config or {})     # (defaults = whisper-large-v3)
+
+    def speech_tokenizer_dims(self) -> Optional[WhisperVQConfig]:
+        if self.speech_tokenizer_config is None:
+            return None
+        return WhisperVQConfig.from_dict(self.speech_tokenizer_config)
 
 
 class WhisperSpeechEncoder(Qwen2AudioEncoder):
@@ -142,6 +149,9 @@ class KimiAudioPackedForCausalLM(nn.Module):
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.mimo_output = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.speech_encoder = WhisperSpeechEncoder(config.speech_encoder_dims()) if config.use_whisper_feature else None
+        vq = config.speech_tokenizer_dims()
+        # (`:856-857`: frozen; replicated under tensor parallelism like the speech encoder, its kernels are deterministic)
+        self.speech_tokenizer = WhisperVQEncoder(vq) if vq is not None else None
 
     def prepare_audio_input_embs(self, audio_input_ids, audio_input_embs, whisper_input_features, speech_tokenizer_ids):
         """`:933-985`.  whisper_input_features [n, mel, frames]: one 30 s-padded clip per media-marker pair, in the order
@@ -186,21 +196,29 @@ class KimiAudioPackedForCausalLM(nn.Module):
             elif isinstance(m, nn.Conv1d):
                 nn.init.normal_(m.weight, mean=0.0, std=std)
                 nn.init.zeros_(m.bias)
+        if self.speech_tokenizer is not None:
+            self.speech_tokenizer.reset_parameters()
+            self.speech_tokenizer.requires_grad_(False)
 
     def forward(self, text_input_ids=None, audio_input_ids=None, audio_input_embs=None, attention_mask=None,
                 position_ids=None, labels=None, sentence_lens=None, num_sentence=None, shift_labels=None,
                 compute_audio_logits: bool = False, ce_chunk_tokens: int = 4096, ce_compact=False,
                 labelled_rows_max=None, whisper_input_features=None, whisper_attention_mask=None,
-                speech_tokenizer_ids=None, **unused):
+                speech_tokenizer_ids=None, clip_tokens=None, **unused):
         """`audio_input_ids` / `text_input_ids` int64 [B, T]: the two aligned token streams of the Kimi-Audio prompt
         format (`processing_kimi_audio.py:112-116`); `audio_input_embs` [B, T, H] replaces the audio-token embeddings
         where the caller has merged continuous Whisper features into them.  `attention_mask` = document ids.
         `whisper_input_features` (+ `speech_tokenizer_ids`): the reference batch's own keys (`:1022-1029`): with
         `use_whisper_feature` the speech encoder / adaptor / marker scatter run here (`prepare_audio_input_embs`);
-        `whisper_attention_mask` is accepted and — like in transformers' WhisperEncoder — not used."""
+        The speech encoder ignores `whisper_attention_mask` like transformers' WhisperEncoder; without
+        `speech_tokenizer_ids` the model's own tokenizer computes the ids (`:957-963`) with it as the key mask (None = every
+        frame valid), on the frames the first `clip_tokens[i]` ids of clip i need when the batch carries those host counts."""
         emb = self.model.embed_tokens
         x = audio_input_embs if audio_input_embs is not None else emb(audio_input_ids)
         if self.speech_encoder is not None and whisper_input_features is not None:
+            if speech_tokenizer_ids is None and self.speech_tokenizer is not None:
+                speech_tokenizer_ids = self.speech_tokenizer(whisper_input_features, whisper_attention_mask,
+                                                             clip_tokens=clip_tokens)
             if speech_tokenizer_ids is None:
                 raise ValueError("whisper_input_features need speech_tokenizer_ids: the frozen GLM-4-voice tokenizer "
                                  "(modeling_kimi_audio.py:957-963) runs in the loader, its ids are an input here")

@@ -13,9 +13,11 @@ and the reference's batching rule: samples are collected until `longest x (n + 1
 `dataset_batchsize x dataset_text_seqlen`, then right-padded per row (pad id / 0 / -100 / 1) — one sample, i.e. one media
 marker pair, per row (`create_mask_between_markers` relies on it).  The log-mel runs on the DEVICE (tn_log_mel).
 
-Beyond the reference's keys the batch may carry `speech_tokenizer_ids` [n, 375]: the reference model runs the frozen
-GLM-4-voice tokenizer inside its forward (modeling_kimi_audio.py:957-963); here that is the loader's job — pass
-`speech_tokenizer=callable(features [128, 3000], mask [3000]) -> ids [375]` — and the model takes the ids as an input.
+Beyond the reference's keys the batch carries `clip_tokens`: the host list of `num_audio_tokens` per clip, the ids the
+model reads of each clip.  The frozen GLM-4-voice tokenizer runs inside the model's forward like the reference's
+(modeling_kimi_audio.py:957-963; a model built with `speech_tokenizer_config`), which uses the counts to skip the frames
+no read id depends on.  A loader may still supply the ids itself — `speech_tokenizer=callable(features [128, 3000],
+mask [3000]) -> ids [375]` adds `speech_tokenizer_ids` [n, 375] — and the model then takes them as they are.
 """
 from __future__ import annotations
 
@@ -79,6 +81,7 @@ def _emit(buf, pad_id):
            "sentence_lens": _pad([[b["slen"]] * len(b["labels"]) for b in buf], 1)}
     out["position_ids"] = torch.arange(out["labels"].shape[1]).expand_as(out["labels"]).contiguous()
     out["labelled_rows_max"] = int(sum(b["slen"] for b in buf))              # response + eos rows (host int, no sync)
+    out["clip_tokens"] = [int(b["n_audio"]) for b in buf]                    # ids read per clip (host ints, no sync)
     if all(b.get("speech_ids") is not None for b in buf):
         out["speech_tokenizer_ids"] = torch.stack([b["speech_ids"] for b in buf])
     return out
@@ -110,7 +113,7 @@ def batch_kimi_audio(data, config, processor, tokenizer, speech_tokenizer=None):
         if length < config.text_min_length_in_tokens_for_filter or length > config.text_max_length_in_tokens_for_filter:
             continue                                                              # :128-132
         item = {"text": text, "audio": audio, "labels": labels, "slen": slen, "features": mel.t().contiguous(),
-                "mask": mask.to(mel.device)}
+                "mask": mask.to(mel.device), "n_audio": n_audio}
         if speech_tokenizer is not None:
             item["speech_ids"] = speech_tokenizer(item["features"], item["mask"])
         longest = max(longest, length)

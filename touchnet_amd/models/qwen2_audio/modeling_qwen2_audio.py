@@ -92,11 +92,14 @@ class EncoderAttention(nn.Module):
         q = q.view(B, T, self.num_heads, self.head_dim)
         k = k.view(B, T, self.num_heads, self.head_dim)
         v = v.view(B, T, self.num_heads, self.head_dim)
-        # (causal: the Qwen2-Audio tower as the reference forces it; bidirectional: Whisper's own encoder, Kimi-Audio)
-        attend = ops().packed_attention if self.causal else ops().bidirectional_attention
-        a = attend(q, k, v, mask, self.head_dim ** -0.5)
+        a = self.attend(q, k, v, mask)
         return ops().linear_group(a.view(B, T, C), [(self.out_proj.weight, self.out_proj.bias)], wgrad="nt",
                                   dgrad_tn=False)[0]
+
+    def attend(self, q, k, v, mask):
+        # (causal: the Qwen2-Audio tower as the reference forces it; bidirectional: Whisper's own encoder, Kimi-Audio)
+        attend = ops().packed_attention if self.causal else ops().bidirectional_attention
+        return attend(q, k, v, mask, self.head_dim ** -0.5)
 
 
 class EncoderLayer(nn.Module):
