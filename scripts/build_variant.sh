@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build an experimental variant of libtouchnet_amd.so with extra hipcc flags (e.g. -DTN_GEMM_ABLATE=1) into
+# Build an experimental variant of libtouchnet_amd.so with extra hipcc flags (e.g. -DNDEBUG, or a macro of the experiment at hand) into
 # touchnet_amd/_lib/variants/<name>/libtouchnet_amd.so; select it at run time with TN_AMD_LIB=<path>.
 # usage: scripts/build_variant.sh <name> [extra hipcc flags...]
 set -e

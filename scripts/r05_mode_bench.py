@@ -2,7 +2,7 @@
 W read as stored, ds_read_b64_tr_b16) slower than the row mode on a pre-transposed W, and by how much?  (If it were, one
 transposed weight copy per step — 14 GB of traffic — could buy it back.)  Also the weight-gradient mode against row mode
 on pre-transposed operands.
-    python scripts/r05_mode_bench.py [rounds [iters]]      (short runs for the PMC passes of scripts/r05_gemm16_pmc.sh)"""
+    python scripts/r05_mode_bench.py [rounds [iters]]      (short runs for PMC passes)"""
 import os
 import sys
 

@@ -31,55 +31,42 @@ def test_attention_stage_loops_are_not_serialised_by_alias_waits():
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
-def test_gemm_accumulators_stay_out_of_the_compilers_hands(tmp_path):
-    """The four-wave GEMM keeps its 256 accumulators in the LITERAL registers a[0:255] (asm MFMAs that list them as
-    clobbers, csrc/gemm.hip `acc_mfma`).  That is only sound while hipcc itself never touches the accumulator file:
-    no spill, no scratch, every v_accvgpr_* inside an inline-asm region; and the stage loops must hold nothing but the
-    hand-placed waits (a compiler-inserted `s_waitcnt vmcnt(N)` in front of an LDS read drains the DMA ring)."""
-    import re
+def test_gemm_library_holds_exactly_the_kernels_the_product_launches(tmp_path):
+    """csrc/gemm.hip compiled with the library's own flags holds the 21 kernels `launch` and the fused entry points reach,
+    no development variant beside them, and none of them spills a vector register or uses scratch.  (SGPR spills are not
+    zero — up to 14 per kernel — and are not asserted.)"""
+    import itertools
+
+    from touchnet_amd import build
     out = tmp_path / "gemm.s"
-    # (the four-wave geometry is variant 2003 of the source; the product library is built with the eight-wave default)
-    r = subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-result", "-S",
-                        "-DTN_GEMM_DEFAULT_VARIANT=2003",
-                        "--cuda-device-only", os.path.join(ROOT, "touchnet_amd", "csrc", "gemm.hip"), "-o", str(out)],
+    r = subprocess.run(["hipcc", *build.FLAGS, "-S", "--cuda-device-only",
+                        os.path.join(ROOT, "touchnet_amd", "csrc", "gemm.hip"), "-o", str(out)],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr
     text = out.read_text()
-    kernels = re.findall(r"^(_ZN2tn4gemm12gemm4_kernel\S*):(.*?)s_endpgm", text, re.S | re.M)
-    assert len(kernels) == 6                       # 3 operand-mode pairs x with / without the transposed copy
-    for name, body in kernels:
-        in_asm, mine, theirs, mfma_outside = False, 0, 0, 0
-        for line in body.split("\n"):
-            t = line.strip()
-            if t.startswith(";;#ASMSTART") or t.startswith(";#ASMSTART"):
-                in_asm = True
-            elif t.startswith(";;#ASMEND") or t.startswith(";#ASMEND"):
-                in_asm = False
-            elif t.startswith("v_accvgpr"):
-                mine, theirs = mine + in_asm, theirs + (not in_asm)
-            elif t.startswith("v_mfma") and not in_asm:
-                mfma_outside += 1
-            assert not t.startswith("scratch_"), (name, t)
-        assert theirs == 0 and mfma_outside == 0 and mine == 3 * 256, (name, mine, theirs, mfma_outside)
-    for field in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
-        for m in re.finditer(rf"\.name:\s+_ZN2tn4gemm12gemm4_kernel.*?\.{field}:\s+(\d+)", text, re.S):
-            pass
-    meta = re.findall(r"\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", text, re.S)
-    assert meta and all(int(a) == 0 and int(b) == 0 for a, b in meta), meta
-    # stage loops: the innermost loops with 64 MFMAs hold exactly four lgkmcnt(0) waits + one vmcnt(8), nothing else
-    for name, body in kernels:
-        ins = [l.strip() for l in body.split("\n") if l.strip() and not l.strip().startswith(";")]
-        labels = {m.group(1): i for i, l in enumerate(ins) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
-        found = 0
-        for i, l in enumerate(ins):
-            m = re.match(r"s_c?branch\S*\s+(\.LBB\d+_\d+)", l)
-            if m and labels.get(m.group(1), len(ins)) < i:
-                seg = ins[labels[m.group(1)]:i + 1]
-                if sum(x.startswith("v_mfma") for x in seg) == 64:
-                    found += 1
-                    waits = sorted(x for x in seg if x.startswith("s_waitcnt"))
-                    assert waits == ["s_waitcnt lgkmcnt(0)"] * 4 + ["s_waitcnt vmcnt(8)"], (name, waits)
-        assert found == 4, (name, found)            # one stage loop per wave
+    PLAIN, GROUPED, SWIGLU_FWD, SWIGLU_BWD, BIASG, ROPE, GELU_FWD, GELU_BWD = range(8)      # csrc/gemm.hip EPI_*
+    ROW, KMAJ = 0, 1
+    b = lambda *flags: "".join(f"Lb{int(f)}E" for f in flags)
+    # gemm16_kernel<AK, BK, EPI>: row-stored A, forward (B row-stored) and input-gradient (B contraction-major) products
+    want = {f"_ZN2tn4gemm13gemm16_kernelI{b(ROW, bk)}Li{epi}EEEvNS0_6ParamsE"
+            for bk, epi in [(ROW, PLAIN), (ROW, SWIGLU_FWD), (ROW, ROPE), (ROW, GELU_FWD),
+                            (KMAJ, PLAIN), (KMAJ, SWIGLU_BWD), (KMAJ, GELU_BWD)]}
+    # gemm_kernel<AK, BK, HAS_CT, SPLITK, OUT_F32, EPI>
+    CT, SPLITK, NONE = (1, 0), (0, 1), (0, 0)
+    modes = [(ROW, bk, *m, 0, PLAIN) for bk in (ROW, KMAJ) for m in (CT, SPLITK)]                       # 4
+    modes += [(KMAJ, KMAJ, *NONE, f32, epi) for epi, f32 in itertools.product((PLAIN, GROUPED, BIASG), (0, 1))]   # 6
+    modes += [(KMAJ, KMAJ, *SPLITK, 0, PLAIN), (KMAJ, KMAJ, *SPLITK, 0, BIASG), (KMAJ, KMAJ, *CT, 0, PLAIN)]      # 3
+    want |= {f"_ZN2tn4gemm11gemm_kernelI{b(*m[:5])}Li{m[5]}EEEvNS0_6ParamsE" for m in modes}
+    want.add("_ZN2tn4gemm20splitk_reduce_kernelEPKfiiiiiiiPtxPKtiiS2_S3_")
+    assert len(want) == 21
+    meta = text[text.find("amdhsa.kernels"):]
+    found = {}
+    for ent in meta.split("- .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", ent).group(1)
+        found[name] = (int(re.search(r"\.vgpr_spill_count:\s+(\d+)", ent).group(1)),
+                       int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", ent).group(1)))
+    assert set(found) == want, (sorted(set(found) - want), sorted(want - set(found)))
+    assert all(v == (0, 0) for v in found.values()), {k: v for k, v in found.items() if v != (0, 0)}
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
@@ -147,8 +134,8 @@ def test_fused_dkdv_accumulators_and_stage_ring(tmp_path):
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 def test_product_gemm_kernels_keep_their_stage_loops_clean(tmp_path):
-    """Every instantiation of the product GEMM (csrc/gemm.hip: `gemm_kernel` with its epilogue modes — plain, grouped, SwiGLU
-    forward / backward, bias gradient, RoPE — and `gemm16_kernel`, the 16x16x32 variant, with the GELU epilogues of round 6)
+    """Every instantiation of the product GEMM (csrc/gemm.hip: `gemm_kernel` with its epilogue modes — plain, grouped, bias
+    gradient — and `gemm16_kernel`, the 16x16x32 kernel, plain and with the SwiGLU forward / backward, RoPE and GELU epilogues)
     compiled for gfx950: no scratch, no
     VGPR spill (a fused epilogue must not push the main loop out of the register file); each kernel issues ONE MFMA shape;
     and its stage loops hold no `s_waitcnt vmcnt` but the hand-counted `vmcnt(4)` of the five-slot LDS-DMA ring (a
@@ -163,7 +150,7 @@ def test_product_gemm_kernels_keep_their_stage_loops_clean(tmp_path):
     kernels = re.findall(r"^(_ZN2tn4gemm(?:11gemm_kernel|13gemm16_kernel)\S*):(.*?)s_endpgm", text, re.S | re.M)
     names = [n for n, _ in kernels]
     # (gemm16: plain x 2 operand modes, SwiGLU forward / backward, RoPE, GELU forward / backward)
-    assert sum("gemm16_kernel" in n for n in names) == 7 and sum("11gemm_kernel" in n for n in names) >= 14, names
+    assert sum("gemm16_kernel" in n for n in names) == 7 and sum("11gemm_kernel" in n for n in names) == 13, names
     meta = text[text.find("amdhsa.kernels"):]
     for ent in meta.split("- .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", ent).group(1)

@@ -8,10 +8,19 @@
 //   KMAJ   X[K, R]  contraction-major      (row pitch ld)   — W in dX = dY W, dY and x in dW = dY^T x
 // so the three GEMMs of a linear layer (transformers' LlamaMLP / LlamaAttention projections as swapped at
 // touchnet/models/llama/__init__.py:11-15) read nn.Linear's own tensors: no transposed copies of
-// W, dY or x are ever made (round 2 ran 480 standalone transpose launches per step for a ROW-only kernel).  Several
-// segments = one accumulator over several (A, B) pairs: dX = dQ Wq + dK Wk + dV Wv is ONE launch without bf16 round trips.
+// W, dY or x are ever made (a ROW-only kernel needed 480 standalone transpose launches per step).  Several segments = one
+// accumulator over several (A, B) pairs: dX = dQ Wq + dK Wk + dV Wv is ONE launch without bf16 round trips.
 //
-// Structure (MI355X-first; numbers from MI355X_MICROARCH.md):
+// Two kernels, one stage ring, and nothing that selects among alternatives: which one a product runs on follows from its
+// shape (`launch` below states the rule).
+//   Kernel16  v_mfma_f32_16x16x32_bf16  row-stored A — every forward and input-gradient product, with the fused SwiGLU /
+//                                       RoPE / GELU epilogues
+//   Kernel    v_mfma_f32_32x32x16_bf16  contraction-major A (the weight gradients: plain, grouped, with the bias
+//                                       gradient, fp32 output), split-K units, products with a transposed copy
+// The measured alternatives (a half-stage ring, a four-wave geometry with the accumulators in AGPRs, other DMA placements)
+// are history: DESIGN.md 5.5 has what they showed.
+//
+// Structure of Kernel (MI355X-first; numbers from MI355X_MICROARCH.md; Kernel16 differs in the MFMA shape only, see there):
 //  * 256 x 256 output tile per 512-thread workgroup (8 waves = 2(M) x 4(N), wave tile 128 x 64 = 4 x 2 blocks of
 //    v_mfma_f32_32x32x16_bf16, 128 accumulator registers), one workgroup per CU, two waves per SIMD.
 //  * K is consumed in 64-deep operand stages of 32 KB that reach LDS by LDS-DMA (buffer_load_dwordx4 ... lds: no staging
@@ -27,7 +36,7 @@
 //    ONE barrier per stage, in front of its LAST 16-deep quarter (fragments of quarter q+1 are read while quarter q's
 //    8 MFMAs run, so the matrix pipe does not drain across it).  The barrier of stage t frees two slots, which take
 //    B(t+2) (due one stage later) and A(t+3) (due two stages later); their 8 pieces per wave are placed between the
-//    MFMAs of the following quarters by a compile-time table (PLACE) — never a vmcnt(0) in the loop:
+//    MFMAs of the following quarters by a compile-time table (kPieceB / kPieceA) — never a vmcnt(0) in the loop:
 //      wait at the barrier of stage t, in flight oldest first: A(t+1), B(t+1), A(t+2) -> vmcnt(4) = A(t+2) may remain.
 //  * Out-of-range rows (M, N not multiples of 256) and exhausted operand streams are zero-filled by the buffer
 //    descriptor's bounds check (an exhausted stream's descriptor has length 0: no memory traffic).
@@ -71,7 +80,7 @@ struct Grp {
   int stages;          // ceil(K / 64)
 };
 
-// What the epilogue does with a finished tile:
+// What the epilogue does with a finished tile (Kernel: PLAIN, GROUPED, BIASG; Kernel16: PLAIN and the fused ones):
 //   EPI_PLAIN       C = acc (+ bias) (+ C), optional transposed copy
 //   EPI_GROUPED     the same per product of a grouped launch (no bias / transposed copy)
 //   EPI_SWIGLU_FWD  the MLP's gate and up products as ONE launch: an output tile is 256 rows x (128 gate columns + 128 up
@@ -94,7 +103,7 @@ struct Grp {
 //                   the natural layout already has that).  (acc + bias) is rounded to bf16 first, as the separate
 //                   projection leaves it, then rotated with the row kernel's arithmetic: bit-identical, one pass over
 //                   q and k through HBM less per layer
-//   EPI_GELU_FWD    (round 6, the audio tower's fc1) C = x W^T + bias AND C2 = gelu(C): the activation pass read C again
+//   EPI_GELU_FWD    (the audio tower's fc1) C = x W^T + bias AND C2 = gelu(C): the activation pass read C again
 //   EPI_GELU_BWD    (the tower's fc2 input gradient) the product d(act) = dY W never reaches HBM: C = d(act) o gelu'(E1),
 //                   E1 = the saved fc1 output (pitch lde) — the GELU backward pass read both and wrote C
 constexpr int EPI_PLAIN = 0, EPI_GROUPED = 1, EPI_SWIGLU_FWD = 2, EPI_SWIGLU_BWD = 3, EPI_BIASG = 4, EPI_ROPE = 5;
@@ -109,7 +118,7 @@ struct Params {
   const bf16_t* bias;  // optional [N]
   long long ldc, ldct;
   int accumulate;      // C += result
-  // C = result + ADDEND (round 6: the residual stream added in the o_proj / down_proj epilogue — `hidden_states = residual
+  // C = result + ADDEND (the residual stream added in the o_proj / down_proj epilogue — `hidden_states = residual
   // + hidden_states` of the HF decoder layers — so that the norm behind it reads ONE tensor): same arithmetic as
   // accumulate (the product rounded to bf16, added in fp32, rounded), the other term read from here instead of from C
   const bf16_t* addend;
@@ -165,39 +174,25 @@ __device__ __forceinline__ void tile_of_block(int bid, int nbm, int nbn, int& tm
 
 typedef f32x16_t Acc[4][2];
 
-// Timing experiments (scripts/build_gemm_variant.sh <name> -DTN_GEMM_ABLATE=n; results are garbage for n != 0):
-//   1 no DMA in the loop   2 no fragment reads in the loop   3 no MFMA   4 no epilogue   5 no barrier in the loop
-//   6 every DMA piece reads the tile's first rows (L1 / L2 hits only)   7 no vmcnt wait in front of the barrier (4-wave kernel)
-#ifndef TN_GEMM_ABLATE
-#define TN_GEMM_ABLATE 0
-#endif
-
 // Where the 8 DMA pieces a wave issues per stage go, as positions 0..31 in the stream of MFMAs that follows the barrier
-// which freed their slots (0-7 = last quarter of stage t, 8-31 = quarters 0-2 of stage t+1).  All B positions must be
-// below all A positions (the vmcnt arithmetic above relies on B(t+2) being older than A(t+3)).
-//   0  burst right behind the barrier (the round-2 kernel)      1  B every other MFMA, A spread over the next two quarters
-//   2  everything every fourth MFMA                              3  B in the last quarter, A one per following quarter pair
-template <int PLACE> struct Place;
-template <> struct Place<0> { static constexpr int B[4] = {0, 1, 2, 3}, A[4] = {4, 5, 6, 7}; };
-template <> struct Place<1> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {9, 13, 17, 21}; };
-template <> struct Place<2> { static constexpr int B[4] = {0, 4, 8, 12}, A[4] = {16, 20, 24, 28}; };
-template <> struct Place<3> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {8, 12, 16, 20}; };
-template <> struct Place<4> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {8, 10, 12, 14}; };
-template <> struct Place<5> { static constexpr int B[4] = {0, 1, 2, 3}, A[4] = {9, 13, 17, 21}; };
-template <> struct Place<6> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {14, 18, 22, 26}; };
-template <> struct Place<7> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {18, 22, 26, 30}; };   // (round 5, Kernel16 sweep)
-template <> struct Place<8> { static constexpr int B[4] = {1, 3, 5, 7}, A[4] = {14, 18, 22, 26}; };
-template <> struct Place<9> { static constexpr int B[4] = {0, 2, 4, 6}, A[4] = {16, 20, 24, 28}; };
-// (Kernel16: a position = two MFMAs; a quarter's fragment reads sit behind its MFMAs 0..7 = its positions 0..3 — tables 10, 11
-//  put every piece into the read-free second half of a quarter)
-template <> struct Place<10> { static constexpr int B[4] = {4, 5, 6, 7}, A[4] = {12, 14, 20, 22}; };
-template <> struct Place<11> { static constexpr int B[4] = {4, 5, 6, 7}, A[4] = {13, 15, 21, 23}; };
+// which freed their slots (0-7 = last quarter of stage t, 8-31 = quarters 0-2 of stage t+1; Kernel16: a position = two
+// MFMAs).  B(t+2) is due one stage later: every other MFMA right behind the barrier; A(t+3) is due two stages later: spread
+// over the following quarters instead of bunched behind the barrier.  All B positions must be below all A positions (the
+// vmcnt arithmetic of the stage loop relies on B(t+2) being older than A(t+3)).
+constexpr int kPieceB[4] = {0, 2, 4, 6}, kPieceA[4] = {14, 18, 22, 26};
+static_assert(kPieceB[3] < kPieceA[0], "every B piece is issued before the first A piece");
 
-// piece index issued at position `pos` for the given table, or -1
-template <int PLACE, bool IS_A> constexpr int piece_at(int pos) {
+// piece index issued at position `pos`, or -1
+template <bool IS_A> constexpr int piece_at(int pos) {
   for (int i = 0; i < 4; ++i)
-    if ((IS_A ? Place<PLACE>::A[i] : Place<PLACE>::B[i]) == pos) return i;
+    if ((IS_A ? kPieceA[i] : kPieceB[i]) == pos) return i;
   return -1;
+}
+// pieces with positions 0..7: issued in one burst where no MFMA stream runs (prologue; behind a tile's epilogue)
+constexpr int early_piece_count() {
+  int n = 0;
+  for (int i = 0; i < 4; ++i) n += (kPieceB[i] < 8) + (kPieceA[i] < 8);
+  return n;
 }
 
 // ---- operand stream: which bytes the next operand stage comes from -------------------------------------------------------
@@ -221,7 +216,7 @@ struct Stream {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int row = wave * 32 + q * 8 + (lane >> 3);
-        voff[q] = (TN_GEMM_ABLATE == 6 ? (row & 7) : row) * ld2 + (((lane & 7) ^ ((row >> 1) & 7)) << 4);
+        voff[q] = row * ld2 + (((lane & 7) ^ ((row >> 1) & 7)) << 4);
       }
     } else {
       // piece q = k-rows 8 wave + 2 q + (lane >> 5) of the stage; the lane's 16-byte slot u = lane & 31 of the 512-byte
@@ -231,7 +226,7 @@ struct Stream {
         const int k = wave * 8 + q * 2 + (lane >> 5);
         const int u = lane & 31;
         const int ch = M16 ? ((u & 3) ^ (((k >> 3) & 1) << 1)) : (u & 3);
-        voff[q] = (TN_GEMM_ABLATE == 6 ? (k & 1) : k) * ld2 + ((((u >> 2) ^ (k & 3)) << 6) | (ch << 4));
+        voff[q] = k * ld2 + ((((u >> 2) ^ (k & 3)) << 6) | (ch << 4));
       }
     }
   }
@@ -277,24 +272,12 @@ __device__ __forceinline__ u32x2_t ds_tr16(uint32_t addr) {
   return r;
 }
 
-template <int OFF>
-__device__ __forceinline__ u32x4_t ds_b128(uint32_t addr) {
-  u32x4_t r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-
-template <bool AK, bool BK, int PLACE, int ASYM, int ILV, bool HAS_CT, bool SPLITK = false, bool OUT_F32 = false,
-          int EPI = EPI_PLAIN>
+template <bool AK, bool BK, bool HAS_CT, bool SPLITK = false, bool OUT_F32 = false, int EPI = EPI_PLAIN>
 struct Kernel {
-  static_assert(EPI == EPI_PLAIN || EPI == EPI_BIASG || (!HAS_CT && !SPLITK), "fused epilogues: whole tiles, no transposed copy");
+  static_assert(EPI == EPI_PLAIN || EPI == EPI_GROUPED || EPI == EPI_BIASG,
+                "Kernel: plain / grouped / bias-gradient epilogues (the fused ones are Kernel16's)");
+  static_assert(EPI != EPI_GROUPED || (!HAS_CT && !SPLITK), "grouped launch: whole tiles, no transposed copy");
   static_assert(EPI != EPI_BIASG || (AK && BK && !HAS_CT), "bias gradient: weight-gradient mode");
-  static_assert(EPI != EPI_ROPE || (!AK && !BK && !OUT_F32), "RoPE epilogue: x W^T layout");
-  static_assert(EPI != EPI_SWIGLU_FWD || (!AK && !BK && !OUT_F32), "SwiGLU forward: x W^T layout");
-  static_assert(EPI != EPI_SWIGLU_BWD || (!AK && BK && !OUT_F32), "SwiGLU backward: dY W layout");
-  static constexpr int BN_EFF = EPI == EPI_SWIGLU_FWD ? 128 : BN;   // output columns per tile (per matrix)
-  // DMA wave w of the SwiGLU forward fetches rows [32 (w >> 1), + 32) of its matrix's 128-row panel: per-lane offsets as
-  // for wave 0 (the bank swizzle only involves row bits below 32)
   struct Out {
     bf16_t* C;
     long long ldc;
@@ -361,11 +344,12 @@ struct Kernel {
     }
   }
 
-  // ---- the kernel body; HALF = 0 for waves 0-3, 1 for waves 4-7 (ASYM shifts the younger half's DMA positions by one
-  //      MFMA so that the two waves of a SIMD, which leave every barrier together, do not issue their pieces in the same gap)
-  template <int HALF>
+  // (The kernel enters its body through this one extra call level on purpose: hipcc's result depends on the inlining depth —
+  //  called directly, the two unsplit EPI_BIASG kernels come out with the same instructions but two waits of the bias-sum
+  //  store placed elsewhere.  Everything is inlined either way.)
+  static __device__ __forceinline__ void run(const Params& p, char* smem) { body(p, smem); }
+
   static __device__ __forceinline__ void body(const Params& p, char* smem) {
-    constexpr int SH = ASYM ? HALF : 0;
     const int tid = threadIdx.x;
     int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -389,7 +373,7 @@ struct Kernel {
         tile_of_block(u, p.nbm, p.nbn, tm, tn);
       }
       m0 = tm * BM;
-      n0 = tn * BN_EFF;
+      n0 = tn * BN;
     };
     auto origin = [&](int k, int& m0, int& n0) {
       int g;
@@ -433,17 +417,6 @@ struct Kernel {
         int g;
         origin_g(kb, m0, n0, g);
         sB.open(p.seg[g].B, p.seg[g].ldb, p.seg[g].K, p.grp[g].N, n0, wave, lane);
-      } else if constexpr (EPI == EPI_SWIGLU_FWD) {
-        // LDS rows [32 w, 32 w + 32) of the B image = rows n0 + 32 (w >> 1) .. of gate_proj (w even) / up_proj (w odd)
-        sB.open((wave & 1) ? p.seg[1].B : p.seg[0].B, p.seg[0].ldb, p.seg[0].K, p.N, n0 + (wave >> 1) * 32, 0, lane);
-      } else if constexpr (EPI == EPI_ROPE) {
-        // D = 128: LDS rows [32 w, 32 w + 32) = W rows of head n0 / 128 + (w >> 2), columns 64 (w & 1) + 32 ((w >> 1) & 1) ..:
-        // reader wave wc = w >> 1 then holds (c, c + 64) pairs in its blocks j = 0 / 1.  D = 64: the plain order.
-        if (p.rope_d == 128)
-          sB.open(p.seg[0].B, p.seg[0].ldb, p.seg[0].K, p.N, n0 + (wave >> 2) * 128 + (wave & 1) * 64 + ((wave >> 1) & 1) * 32,
-                  0, lane);
-        else
-          sB.open(p.seg[0].B, p.seg[0].ldb, p.seg[0].K, p.N, n0, wave, lane);
       } else {
         sB.open(p.seg[s].B, p.seg[s].ldb, p.seg[s].K, p.N, n0, wave, lane);
       }
@@ -509,11 +482,7 @@ struct Kernel {
       read_frag(QC, std::integral_constant<int, 5>{}, sa, sb, a, b);
     };
     auto mma = [&](const Frags<AK, 4>& a, const Frags<BK, 2>& b, int i, int j) {
-#if TN_GEMM_ABLATE == 3
-      asm volatile("" ::"v"(a.v[i]), "v"(b.v[j]));
-#else
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b.v[j], a.v[i], acc[i][j], 0, 0, 0);
-#endif
     };
 
     // EPI_BIASG: this wave's share of the A panel's column sums — block wc of the four A fragments (32 rows of dY^T), the
@@ -534,16 +503,12 @@ struct Kernel {
       else add(a.v[3]);
     };
 
-    // One quarter: the 8 MFMAs of (ca, cb); the fragments of quarter NQ of slots (nsa, nsb) are read into (na, nb) either
-    // all in front (ILV = 0) or one behind each of the first six MFMAs (ILV = 1); the DMA pieces the placement table
-    // puts at positions P0 .. P0 + 7 go behind their MFMA (P0 < 0: none).  dst_b / dst_a = slots the open piece set fills.
+    // One quarter: the 8 MFMAs of (ca, cb); the fragments of quarter NQ of slots (nsa, nsb) are read into (na, nb), one
+    // behind each of the first six MFMAs; the DMA pieces the placement table puts at positions P0 .. P0 + 7 go behind
+    // their MFMA (P0 < 0: none).  dst_b / dst_a = slots the open piece set fills.
     auto quarter = [&](auto NQC, auto P0C, const Frags<AK, 4>& ca, const Frags<BK, 2>& cb, Frags<AK, 4>& na,
                        Frags<BK, 2>& nb, int nsa, int nsb, int dst_b, int dst_a) {
       constexpr int P0 = decltype(P0C)::value;
-      if constexpr (ILV == 0 && TN_GEMM_ABLATE != 2) {
-        read_all(NQC, nsa, nsb, na, nb);
-        TN_PIN();
-      }
       if constexpr (EPI == EPI_BIASG) {
         if (bias_on) bias_accum(ca);
         TN_PIN();
@@ -552,19 +517,19 @@ struct Kernel {
         constexpr int m = decltype(MC)::value;
         mma(ca, cb, m >> 1, m & 1);
         TN_PIN();
-        if constexpr (ILV == 1 && m < 6 && TN_GEMM_ABLATE != 2) {
+        if constexpr (m < 6) {
           read_frag(NQC, std::integral_constant<int, m>{}, nsa, nsb, na, nb);
           TN_PIN();
         }
-        constexpr int pb = P0 < 0 ? -1 : piece_at<PLACE, false>(P0 + m - SH);
-        constexpr int pa = P0 < 0 ? -1 : piece_at<PLACE, true>(P0 + m - SH);
+        constexpr int pb = P0 < 0 ? -1 : piece_at<false>(P0 + m);
+        constexpr int pa = P0 < 0 ? -1 : piece_at<true>(P0 + m);
         if constexpr (pb >= 0) {
-          if constexpr (TN_GEMM_ABLATE != 1) piece_b(dst_b, pb);
+          piece_b(dst_b, pb);
           if constexpr (pb == 3) adv_b();
           TN_PIN();
         }
         if constexpr (pa >= 0) {
-          if constexpr (TN_GEMM_ABLATE != 1) piece_a(dst_a, pa);
+          piece_a(dst_a, pa);
           if constexpr (pa == 3) adv_a();
           TN_PIN();
         }
@@ -582,7 +547,7 @@ struct Kernel {
     auto early_pieces = [&](int dst_b, int dst_a) {
       auto one = [&](auto MC) {
         constexpr int m = decltype(MC)::value;
-        constexpr int pb = piece_at<PLACE, false>(m - SH), pa = piece_at<PLACE, true>(m - SH);
+        constexpr int pb = piece_at<false>(m), pa = piece_at<true>(m);
         if constexpr (pb >= 0) {
           piece_b(dst_b, pb);
           if constexpr (pb == 3) adv_b();
@@ -620,11 +585,8 @@ struct Kernel {
     for (int q = 0; q < 4; ++q) piece_a(2, q);
     adv_a();
     early_pieces(3, 4);
-    constexpr int kEarly = (Place<PLACE>::B[0] + SH < 8) + (Place<PLACE>::B[1] + SH < 8) + (Place<PLACE>::B[2] + SH < 8) +
-                           (Place<PLACE>::B[3] + SH < 8) + (Place<PLACE>::A[0] + SH < 8) + (Place<PLACE>::A[1] + SH < 8) +
-                           (Place<PLACE>::A[2] + SH < 8) + (Place<PLACE>::A[3] + SH < 8);
     // A(0), B(0) must have landed; everything issued behind them may stay in flight
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + kEarly) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + early_piece_count()) : "memory");
     __builtin_amdgcn_s_barrier();
     int sa = 0, sb = 1;                         // slots of A(t), B(t)
     int pa = 4, pb = 3;                         // slots the piece set opened at the previous barrier fills (A part, B part)
@@ -648,7 +610,7 @@ struct Kernel {
       wait_frags(ao, bo);                                 // (asm reads retired here; ROW reads by the next line)
       __builtin_amdgcn_s_waitcnt(0xc07f);                 // my reads of stage t are complete (quarter 3 is in registers)
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");    // A(t+1), B(t+1) landed; A(t+2) may still be in flight
-      if constexpr (TN_GEMM_ABLATE != 5) __builtin_amdgcn_s_barrier();   // stage t+1 visible; slots sa, sb free
+      __builtin_amdgcn_s_barrier();                       // stage t+1 visible; slots sa, sb free
       __builtin_amdgcn_s_setprio(1);
       if constexpr (!LAST) {
         // last quarter of stage t: the new piece set {B(t+2) -> slot sa, A(t+3) -> slot sb} opens (positions 0..7)
@@ -718,21 +680,10 @@ struct Kernel {
           const Out o = {p.C, p.ldc, p.M, p.N};
           epilogue_f32(p, o, acc, m0 + wr * 128, n0 + wc * 64, lane);
         }
-      } else if constexpr (EPI == EPI_SWIGLU_FWD) {
-        epilogue_swiglu_fwd(p, acc, smem + (wave < 4 ? pb : pa) * SLOT + (wave & 3) * 8192, m0 + wr * 128, n0 + wc * 32,
-                            lane);
-      } else if constexpr (EPI == EPI_SWIGLU_BWD) {
-        epilogue_swiglu_bwd(p, acc, smem + (wave < 4 ? pb : pa) * SLOT + (wave & 3) * 8192, m0 + wr * 128, n0 + wc * 64,
-                            lane);
-      } else if constexpr (EPI == EPI_ROPE) {
-        const bool d128 = p.rope_d == 128;
-        const int col_a = d128 ? n0 + (wc >> 1) * 128 + (wc & 1) * 32 : n0 + wc * 64;     // block j = 0; j = 1: + D / 2
-        epilogue_rope(p, acc, smem + (wave < 4 ? pb : pa) * SLOT + (wave & 3) * 8192, m0 + wr * 128, col_a,
-                      d128 ? (wc & 1) * 32 : 0, lane);
       } else if constexpr (EPI == EPI_GROUPED) {
         const Out o = {p.grp[grp].C, p.grp[grp].ldc, p.grp[grp].M, p.grp[grp].N};
         epilogue(p, o, acc, smem + (wave < 4 ? pb : pa) * SLOT + (wave & 3) * 8192, m0 + wr * 128, n0 + wc * 64, lane);
-      } else if constexpr (TN_GEMM_ABLATE != 4) {
+      } else {
         const Out o = {p.C, p.ldc, p.M, p.N};
         epilogue(p, o, acc, smem + (wave < 4 ? pb : pa) * SLOT + (wave & 3) * 8192, m0 + wr * 128, n0 + wc * 64, lane);
       }
@@ -745,17 +696,8 @@ struct Kernel {
       ra = Reader<AK, 4>(lane, wr * 128);
       rb = Reader<BK, 2>(lane, wc * 64);
       sA.set_voff(wave, lane);
-      sB.set_voff((EPI == EPI_SWIGLU_FWD || (EPI == EPI_ROPE && p.rope_d == 128)) ? 0 : wave, lane);
+      sB.set_voff(wave, lane);
       early_pieces(pb, pa);
-    }
-  }
-
-  static __device__ __forceinline__ void run(const Params& p, char* smem) {
-    if constexpr (ASYM) {
-      if (__builtin_amdgcn_readfirstlane(threadIdx.x) < 256) body<0>(p, smem);
-      else body<1>(p, smem);
-    } else {
-      body<0>(p, smem);
     }
   }
 
@@ -799,231 +741,6 @@ struct Kernel {
           const f32x4_t v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
           *reinterpret_cast<f32x4_t*>(base + m * BN + n) = v;
         }
-    }
-  }
-
-  // ---- fused SwiGLU epilogues ------------------------------------------------------------------------------------------
-  // Arithmetic = tn::swiglu_fwd_kernel / swiglu_bwd_kernel (csrc/norm_act.hip) on the bf16-ROUNDED products, as the
-  // separate passes saw them: silu(gate) rounded to bf16 before the product (what the eager path materialises), so the
-  // fused and the unfused MLP agree bit for bit.
-  static __device__ __forceinline__ float sigm(float x) { return sigmoid_fast(x); }
-  static __device__ __forceinline__ float lo16(uint32_t w) { return __uint_as_float(w << 16); }
-  static __device__ __forceinline__ float hi16(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-  static __device__ __forceinline__ float rbf(float v) { return __uint_as_float(((uint32_t)f2bf(v)) << 16); }
-
-  // Forward.  The wave holds gate (acc[i][0]) and up (acc[i][1]) of rows wm0 .. wm0 + 127, columns wn0 .. wn0 + 31.
-  // Three trips through its 8 KB park ([64 rows][64 columns] bf16, 128-byte rows, 16-byte chunk ^= row & 7):
-  //   1, 2  rows half * 64 ..: columns 0-31 = gate, 32-63 = up  -> 64-byte row segments of C (gate) and C2 (up)
-  //   3     act of ALL 128 rows: columns 0-31 = rows 0-63, columns 32-63 = rows 64-127 -> 64-byte row segments of C3
-  static __device__ __forceinline__ void epilogue_swiglu_fwd(const Params& p, Acc& acc, char* park, int wm0, int wn0,
-                                                             int lane) {
-    const int l31 = lane & 31, hi = lane >> 5;
-    // (the per-lane choice between the two outputs as integer arithmetic on pointers held in registers: written as
-    //  `c < 4 ? p.C : p.C2` hipcc selects between the two kernel-argument ADDRESSES and re-loads the pointer per store)
-    const uintptr_t c_gate = (uintptr_t)p.C, c_up = (uintptr_t)p.C2;
-    bf16_t* const gu_base = reinterpret_cast<bf16_t*>(c_gate + ((lane & 4) ? c_up - c_gate : (uintptr_t)0));
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = half * 2 + ii;
-        const int row = ii * 32 + l31;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int chunk = (j * 4 + g) ^ (row & 7);
-            const u32x2_t pk = {pack2bf(acc[i][j][4 * g], acc[i][j][4 * g + 1]),
-                                pack2bf(acc[i][j][4 * g + 2], acc[i][j][4 * g + 3])};
-            *reinterpret_cast<u32x2_t*>(park + row * 128 + chunk * 16 + hi * 8) = pk;
-          }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 4
-      for (int it = 0; it < 8; ++it) {
-        const int row = it * 8 + (lane >> 3), c = lane & 7;
-        const u32x4_t pv = *reinterpret_cast<const u32x4_t*>(park + row * 128 + ((c ^ (row & 7)) << 4));
-        const int m = wm0 + half * 64 + row, n = wn0 + (c & 3) * 8;
-        if (m < p.M && n < p.N)
-          *reinterpret_cast<uint4*>(gu_base + (long long)m * p.ldc + n) = make_uint4(pv.x, pv.y, pv.z, pv.w);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = (i & 1) * 32 + l31;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float h[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float gf = rbf(acc[i][0][4 * g + e]), uf = rbf(acc[i][1][4 * g + e]);
-          h[e] = rbf(gf * sigm(gf)) * uf;
-        }
-        const int chunk = ((i >> 1) * 4 + g) ^ (row & 7);
-        const u32x2_t pk = {pack2bf(h[0], h[1]), pack2bf(h[2], h[3])};
-        *reinterpret_cast<u32x2_t*>(park + row * 128 + chunk * 16 + hi * 8) = pk;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 4
-    for (int it = 0; it < 8; ++it) {
-      const int row = it * 8 + (lane >> 3), c = lane & 7;
-      const u32x4_t pv = *reinterpret_cast<const u32x4_t*>(park + row * 128 + ((c ^ (row & 7)) << 4));
-      const int m = wm0 + (c >> 2) * 64 + row, n = wn0 + (c & 3) * 8;
-      if (m < p.M && n < p.N)
-        *reinterpret_cast<uint4*>(p.C3 + (long long)m * p.ldc + n) = make_uint4(pv.x, pv.y, pv.z, pv.w);
-    }
-  }
-
-  // RoPE.  The wave holds columns col_a .. + 31 (acc[i][0]) and col_a + D/2 .. + 31 (acc[i][1]) of rows wm0 .. + 127: both
-  // members of every rotary pair in one lane; c0 = the first pair's index inside the head (table column).
-  static __device__ __forceinline__ void epilogue_rope(const Params& p, Acc& acc, char* park, int wm0, int col_a, int c0,
-                                                       int lane) {
-    const int l31 = lane & 31, hi = lane >> 5;
-    const int half = p.rope_d >> 1;
-    const int col_b = col_a + half;
-    // every table / bias element of the tile is requested up front (32 + 8 loads in flight per lane, ONE wait per 64-row
-    // half) — issued one (row block, column quad) at a time the epilogue paid a memory round trip per quad
-    uint2 bwa[4], bwb[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int q = 8 * g + 4 * hi;
-      bwa[g] = bwb[g] = make_uint2(0, 0);
-      if (p.bias != nullptr) {
-        bwa[g] = *reinterpret_cast<const uint2*>(p.bias + min(col_a + q, p.N - 4));
-        bwb[g] = *reinterpret_cast<const uint2*>(p.bias + min(col_b + q, p.N - 4));
-      }
-    }
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      uint2 cw[2][4], sw[2][4];
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int m = min(wm0 + (hf * 2 + ii) * 32 + l31, p.M - 1);         // (rows >= M are never stored)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const long long o = (long long)m * half + c0 + 8 * g + 4 * hi;
-          cw[ii][g] = *reinterpret_cast<const uint2*>(p.rope_cos + o);
-          sw[ii][g] = *reinterpret_cast<const uint2*>(p.rope_sin + o);
-        }
-      }
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = hf * 2 + ii;
-        const int row = ii * 32 + l31;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float ba[4] = {lo16(bwa[g].x), hi16(bwa[g].x), lo16(bwa[g].y), hi16(bwa[g].y)};
-          const float bb[4] = {lo16(bwb[g].x), hi16(bwb[g].x), lo16(bwb[g].y), hi16(bwb[g].y)};
-          const float cf[4] = {lo16(cw[ii][g].x), hi16(cw[ii][g].x), lo16(cw[ii][g].y), hi16(cw[ii][g].y)};
-          const float sf[4] = {lo16(sw[ii][g].x), hi16(sw[ii][g].x), lo16(sw[ii][g].y), hi16(sw[ii][g].y)};
-          float ya[4], yb[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            rope_rotate(rbf(acc[i][0][4 * g + e] + ba[e]), rbf(acc[i][1][4 * g + e] + bb[e]), cf[e], sf[e], ya[e], yb[e]);
-          const u32x2_t pa_ = {pack2bf(ya[0], ya[1]), pack2bf(ya[2], ya[3])};
-          const u32x2_t pb_ = {pack2bf(yb[0], yb[1]), pack2bf(yb[2], yb[3])};
-          *reinterpret_cast<u32x2_t*>(park + row * 128 + ((g ^ (row & 7)) << 4) + hi * 8) = pa_;
-          *reinterpret_cast<u32x2_t*>(park + row * 128 + (((4 + g) ^ (row & 7)) << 4) + hi * 8) = pb_;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 4
-      for (int it = 0; it < 8; ++it) {
-        const int row = it * 8 + (lane >> 3), c = lane & 7;
-        const u32x4_t pv = *reinterpret_cast<const u32x4_t*>(park + row * 128 + ((c ^ (row & 7)) << 4));
-        const int m = wm0 + hf * 64 + row, n = (c < 4 ? col_a : col_b) + (c & 3) * 8;
-        if (m < p.M && n < p.N)
-          *reinterpret_cast<uint4*>(p.C + (long long)m * p.ldc + n) = make_uint4(pv.x, pv.y, pv.z, pv.w);
-      }
-    }
-  }
-
-  // Backward.  acc = d(act) of the wave's 128 x 64 tile.  Per 64-row half: the gate and up rows come in as full 128-byte
-  // lines (16 bytes per lane), go through the park into the accumulator layout (row = lane, 4 consecutive columns per
-  // register quad), d(gate) / d(up) are formed in registers and leave through the park like any other tile.
-  static __device__ __forceinline__ void epilogue_swiglu_bwd(const Params& p, Acc& acc, char* park, int wm0, int wn0,
-                                                             int lane) {
-    const int l31 = lane & 31, hi = lane >> 5;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      uint4 gv[8], uv[8];
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int row = it * 8 + (lane >> 3), c = lane & 7;
-        const int m = wm0 + half * 64 + row, n = wn0 + c * 8;
-        const bool in = m < p.M && n < p.N;
-        const long long off = (long long)m * p.lde + n;
-        gv[it] = in ? *reinterpret_cast<const uint4*>(p.E1 + off) : make_uint4(0, 0, 0, 0);
-        uv[it] = in ? *reinterpret_cast<const uint4*>(p.E2 + off) : make_uint4(0, 0, 0, 0);
-      }
-      u32x2_t gq[2][2][4], uq[2][2][4];
-      auto through_park = [&](const uint4 (&src)[8], u32x2_t (&dst)[2][2][4]) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int row = it * 8 + (lane >> 3), c = lane & 7;
-          const u32x4_t v = {src[it].x, src[it].y, src[it].z, src[it].w};
-          *reinterpret_cast<u32x4_t*>(park + row * 128 + ((c ^ (row & 7)) << 4)) = v;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-          const int row = ii * 32 + l31;
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              dst[ii][j][g] =
-                  *reinterpret_cast<const u32x2_t*>(park + row * 128 + (((j * 4 + g) ^ (row & 7)) << 4) + hi * 8);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      };
-      through_park(gv, gq);
-      through_park(uv, uq);
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = half * 2 + ii;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            float dg[4], du[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const uint32_t wg = e < 2 ? gq[ii][j][g].x : gq[ii][j][g].y, wu = e < 2 ? uq[ii][j][g].x : uq[ii][j][g].y;
-              const float gf = (e & 1) ? hi16(wg) : lo16(wg), uf = (e & 1) ? hi16(wu) : lo16(wu);
-              const float d = rbf(acc[i][j][4 * g + e]);
-              const float sg = sigm(gf);
-              const float silu = gf * sg;
-              du[e] = d * silu;
-              dg[e] = d * uf * (sg + silu * (1.f - sg));
-            }
-            gq[ii][j][g] = u32x2_t{pack2bf(dg[0], dg[1]), pack2bf(dg[2], dg[3])};
-            uq[ii][j][g] = u32x2_t{pack2bf(du[0], du[1]), pack2bf(du[2], du[3])};
-          }
-      }
-      auto out_park = [&](const u32x2_t (&src)[2][2][4], bf16_t* C) {
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-          const int row = ii * 32 + l31;
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              *reinterpret_cast<u32x2_t*>(park + row * 128 + (((j * 4 + g) ^ (row & 7)) << 4) + hi * 8) = src[ii][j][g];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 4
-        for (int it = 0; it < 8; ++it) {
-          const int row = it * 8 + (lane >> 3), c = lane & 7;
-          const u32x4_t pv = *reinterpret_cast<const u32x4_t*>(park + row * 128 + ((c ^ (row & 7)) << 4));
-          const int m = wm0 + half * 64 + row, n = wn0 + c * 8;
-          if (m < p.M && n < p.N)
-            *reinterpret_cast<uint4*>(C + (long long)m * p.ldc + n) = make_uint4(pv.x, pv.y, pv.z, pv.w);
-        }
-      };
-      out_park(gq, p.C);
-      out_park(uq, p.C2);
     }
   }
 
@@ -1123,19 +840,20 @@ struct Kernel {
   }
 };
 
-template <bool AK, bool BK, int PLACE, int ASYM, int ILV, bool HAS_CT, bool SPLITK = false, bool OUT_F32 = false,
-          int EPI = EPI_PLAIN>
+template <bool AK, bool BK, bool HAS_CT, bool SPLITK = false, bool OUT_F32 = false, int EPI = EPI_PLAIN>
 __global__ __launch_bounds__(NT, 2) void gemm_kernel(const Params p) {
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
-  Kernel<AK, BK, PLACE, ASYM, ILV, HAS_CT, SPLITK, OUT_F32, EPI>::run(p, smem);
+  Kernel<AK, BK, HAS_CT, SPLITK, OUT_F32, EPI>::run(p, smem);
 }
 
 // =====================================================================================================================
 // Kernel16: the same workgroup geometry, stage ring, DMA placement and persistent tile walk as Kernel above, with
-// v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_32x32x16_bf16.  Why (round 5, profiles/r05p_*): with operands in
+// v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_32x32x16_bf16.  Why (profiles/r05p_*): with operands in
 // registers only the 32x32x16 shape SUSTAINS 1.73-1.78 PF on this chip — the 1.67 GHz the GEMM was always measured at —
 // and the 16x16x32 shape 1.98-1.99 PF (half the accumulator register traffic per flop): the "power limit" of the
-// kernel was its instruction shape (hipBLASLt's gfx950 kernels issue 16x16x32).
+// kernel was its instruction shape (hipBLASLt's gfx950 kernels issue 16x16x32).  Products with a row-stored A gain 5-7 %
+// (forward) / 2-3 % (input gradient); the weight-gradient mode (both operands through transpose reads) gains nothing and
+// stays on Kernel.
 //  * wave tile 128 x 64 = 8 x 4 blocks of 16 x 16, accumulators f32x4 [8][4] (the same 128 registers)
 //  * a 64-deep stage = two 32-deep halves; a "quarter" = 16 MFMAs = A blocks 4 part .. 4 part + 3 (part = quarter & 1) of
 //    half quarter >> 1 against the half's four B blocks.  Fragment sets: 4 A fragments per quarter (double buffered),
@@ -1149,18 +867,15 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const Params p) {
 //  * result of mfma(b, a): lane holds column m = l & 15 of its 16 x 16 block, registers r = rows n = 4 (l >> 4) + r
 // =====================================================================================================================
 typedef f32x4_t Acc16[8][4];
-#ifndef TN_G16_RSTEP
-#define TN_G16_RSTEP 1
-#endif
 
-template <bool AK, bool BK, int PLACE, int EPI = EPI_PLAIN>
+template <bool AK, bool BK, int EPI = EPI_PLAIN>
 struct Kernel16 {
   static_assert(EPI == EPI_PLAIN || EPI == EPI_SWIGLU_FWD || EPI == EPI_SWIGLU_BWD || EPI == EPI_ROPE ||
                     EPI == EPI_GELU_FWD || EPI == EPI_GELU_BWD,
                 "Kernel16: plain / SwiGLU / RoPE / GELU epilogues (the weight-gradient modes stay on Kernel)");
   static_assert(EPI != EPI_GELU_FWD || !BK, "GELU forward: x W^T layout");
   static_assert(EPI != EPI_GELU_BWD || BK, "GELU backward: dY W layout");
-  static_assert(!AK, "Kernel16 is used where it is faster: row-stored A (forward and input-gradient products)");
+  static_assert(!AK, "Kernel16: row-stored A (forward and input-gradient products)");
   static_assert(EPI != EPI_SWIGLU_FWD || !BK, "SwiGLU forward: x W^T layout");
   static_assert(EPI != EPI_SWIGLU_BWD || BK, "SwiGLU backward: dY W layout");
   static_assert(EPI != EPI_ROPE || !BK, "RoPE epilogue: x W^T layout");
@@ -1173,9 +888,6 @@ struct Kernel16 {
   struct F4 {
     bf16x8_t v[4];
     u32x2_t h[KMAJ ? 4 : 1][2];
-#ifdef TN_G16_ASMROW
-    u32x4_t r[4];
-#endif
   };
   // per-lane LDS offsets.  ROW: x[half]; block b of the wave's rows at + b * 2048.  KMAJ: x[G] for the 64-byte group G of
   // the wave's 32-row pairs, x ^ 32 for the odd 16-row block of the pair; k-row offsets are compile-time.
@@ -1199,12 +911,7 @@ struct Kernel16 {
     template <int H, int BLK, int I>
     __device__ __forceinline__ void read(const char* smem, int sbase, F4<KMAJ>& f) const {
       if constexpr (!KMAJ) {
-#ifdef TN_G16_ASMROW   // diagnostic: row fragments as asm reads retired by ONE lgkmcnt(0) per set, like the transpose reads
-        const uint32_t a = (uint32_t)(size_t)(lds_ptr_t)smem + (uint32_t)(sbase + x[H]);
-        f.r[I] = ds_b128<BLK * 2048>(a);
-#else
         f.v[I] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(smem + sbase + x[H] + BLK * 2048));
-#endif
       } else {
         const uint32_t a = (uint32_t)(size_t)(lds_ptr_t)smem + (uint32_t)(sbase + (x[BLK >> 1] ^ ((BLK & 1) * 32)));
         f.h[I][0] = ds_tr16<(32 * H) * 512>(a);
@@ -1214,13 +921,6 @@ struct Kernel16 {
   };
   template <bool KMAJ>
   static __device__ __forceinline__ void retire(F4<KMAJ>& f) {
-#ifdef TN_G16_ASMROW
-    if constexpr (!KMAJ) {
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.r[0]), "+v"(f.r[1]), "+v"(f.r[2]), "+v"(f.r[3]));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) f.v[i] = __builtin_bit_cast(bf16x8_t, f.r[i]);
-    }
-#endif
     if constexpr (KMAJ) {
       asm volatile("s_waitcnt lgkmcnt(0)"
                    : "+v"(f.h[0][0]), "+v"(f.h[0][1]), "+v"(f.h[1][0]), "+v"(f.h[1][1]), "+v"(f.h[2][0]), "+v"(f.h[2][1]),
@@ -1256,8 +956,11 @@ struct Kernel16 {
       sA.open(p.seg[s].A, p.seg[s].lda, p.seg[s].K, p.M, m0, wave, lane);
       sA.seg = s;
     };
-    // (B stage images of the fused epilogues: the per-DMA-wave row choices of Kernel::open_b — they concern LDS rows, not
-    //  the MFMA shape)
+    // B stage images of the fused epilogues: which rows of B DMA wave w fetches into LDS rows [32 w, 32 w + 32) (per-lane
+    // offsets as for wave 0: the bank swizzle only involves row bits below 32)
+    //   SwiGLU forward   rows n0 + 32 (w >> 1) .. of gate_proj (w even) / up_proj (w odd)
+    //   RoPE, D = 128    W rows of head n0 / 128 + (w >> 2), columns 64 (w & 1) + 32 ((w >> 1) & 1) ..: reader wave
+    //                    wc = w >> 1 then holds (c, c + 64) pairs.  D = 64: the plain order.
     const bool b_wave0 = EPI == EPI_SWIGLU_FWD || (EPI == EPI_ROPE && p.rope_d == 128);
     auto open_b = [&](int s) {
       int m0, n0;
@@ -1325,7 +1028,7 @@ struct Kernel16 {
       if constexpr (R < 4) ra.template read<(Q >> 1), (Q & 1) * 4 + R, R>(smem, sa * SLOT, a);
       else rb.template read<(Q >> 1), R - 4, R - 4>(smem, sb * SLOT, b);
     };
-    // (Measured and dropped, round 5: B fragments read first and retired by a counted `lgkmcnt(4)` while the four younger A
+    // (Measured and dropped: B fragments read first and retired by a counted `lgkmcnt(4)` while the four younger A
     //  reads stay in flight — 0.7 % SLOWER than A first + lgkmcnt(0), profiles/r05s_*.)
     // One quarter: 16 MFMAs of A part PART (fragments ca) against the half's B fragments cb; fragment r of the NEXT quarter
     // NQ (4 A fragments, and with RB its half's 4 B fragments) is read behind MFMA 2 r; DMA pieces of positions
@@ -1338,19 +1041,16 @@ struct Kernel16 {
         constexpr int m = decltype(MC)::value, i = m >> 2, j = m & 3;
         acc[PART * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cb.v[j], ca.v[i], acc[PART * 4 + i][j], 0, 0, 0);
         TN_PIN();
-        // fragment reads behind the FIRST MFMAs of the quarter (TN_G16_RSTEP = MFMAs per read: 1 = reads 0..7 behind
-        // MFMAs 0..7, so the last one is 8+ MFMAs old when the quarter's fragments are retired)
-        if constexpr ((m % TN_G16_RSTEP) == 0 && m / TN_G16_RSTEP < 8) {
-          constexpr int r = m / TN_G16_RSTEP;
-          if constexpr (r < 4 || RB) {
-            read_frag(NQC, std::integral_constant<int, r>{}, nsa, nsb, na, nb);
-            TN_PIN();
-          }
+        // fragment reads behind the FIRST MFMAs of the quarter (reads 0..7 behind MFMAs 0..7, so the last one is 8+ MFMAs
+        // old when the quarter's fragments are retired)
+        if constexpr (m < 4 || (m < 8 && RB)) {
+          read_frag(NQC, std::integral_constant<int, m>{}, nsa, nsb, na, nb);
+          TN_PIN();
         }
         if constexpr ((m & 1) == 0) {
           constexpr int r = m >> 1;
-          constexpr int pb = P0 < 0 ? -1 : piece_at<PLACE, false>(P0 + r);
-          constexpr int pa = P0 < 0 ? -1 : piece_at<PLACE, true>(P0 + r);
+          constexpr int pb = P0 < 0 ? -1 : piece_at<false>(P0 + r);
+          constexpr int pa = P0 < 0 ? -1 : piece_at<true>(P0 + r);
           if constexpr (pb >= 0) {
             piece_b(dst_b, pb);
             if constexpr (pb == 3) adv_b();
@@ -1383,7 +1083,7 @@ struct Kernel16 {
     auto early_pieces = [&](int dst_b, int dst_a) {
       auto one = [&](auto MC) {
         constexpr int m = decltype(MC)::value;
-        constexpr int pb = piece_at<PLACE, false>(m), pa = piece_at<PLACE, true>(m);
+        constexpr int pb = piece_at<false>(m), pa = piece_at<true>(m);
         if constexpr (pb >= 0) {
           piece_b(dst_b, pb);
           if constexpr (pb == 3) adv_b();
@@ -1416,10 +1116,7 @@ struct Kernel16 {
     for (int q = 0; q < 4; ++q) piece_a(2, q);
     adv_a();
     early_pieces(3, 4);
-    constexpr int kEarly = (Place<PLACE>::B[0] < 8) + (Place<PLACE>::B[1] < 8) + (Place<PLACE>::B[2] < 8) +
-                           (Place<PLACE>::B[3] < 8) + (Place<PLACE>::A[0] < 8) + (Place<PLACE>::A[1] < 8) +
-                           (Place<PLACE>::A[2] < 8) + (Place<PLACE>::A[3] < 8);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + kEarly) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + early_piece_count()) : "memory");
     __builtin_amdgcn_s_barrier();
     int sa = 0, sb = 1;
     int pa = 4, pb = 3;
@@ -1513,11 +1210,19 @@ struct Kernel16 {
     return park + row * 128 + (((bj * 2 + (g4 >> 1)) ^ (row & 7)) << 4) + (g4 & 1) * 8;
   }
 
-  // SwiGLU forward (see Kernel::epilogue_swiglu_fwd): blocks bj = 0, 1 of a lane are gate, bj = 2, 3 up of the SAME columns
-  // wn0 + 16 bj + 4 g4 ..; three park trips: gate | up of 64 rows each, then act of all 128 rows.
+  // ---- fused SwiGLU epilogues ------------------------------------------------------------------------------------------
+  // Arithmetic = tn::swiglu_fwd_kernel / swiglu_bwd_kernel (csrc/norm_act.hip) on the bf16-ROUNDED products, as the
+  // separate passes saw them: silu(gate) rounded to bf16 before the product (what the eager path materialises), so the
+  // fused and the unfused MLP agree bit for bit.
+  // Forward: blocks bj = 0, 1 of a lane are gate, bj = 2, 3 up of the SAME columns wn0 + 16 bj + 4 g4 ..  Three trips through
+  // the wave's park:
+  //   1, 2  rows half * 64 ..: columns 0-31 = gate, 32-63 = up  -> 64-byte row segments of C (gate) and C2 (up)
+  //   3     act of ALL 128 rows: columns 0-31 = rows 0-63, columns 32-63 = rows 64-127 -> 64-byte row segments of C3
   static __device__ __forceinline__ void epilogue16_swiglu_fwd(const Params& p, Acc16& acc, char* park, int wm0, int wn0,
                                                                int lane) {
     const int l15 = lane & 15, g4 = lane >> 4;
+    // (the per-lane choice between the two outputs as integer arithmetic on pointers held in registers: written as
+    //  `c < 4 ? p.C : p.C2` hipcc selects between the two kernel-argument ADDRESSES and re-loads the pointer per store)
     const uintptr_t c_gate = (uintptr_t)p.C, c_up = (uintptr_t)p.C2;
     bf16_t* const gu_base = reinterpret_cast<bf16_t*>(c_gate + ((lane & 4) ? c_up - c_gate : (uintptr_t)0));
 #pragma unroll
@@ -1564,7 +1269,9 @@ struct Kernel16 {
     }
   }
 
-  // SwiGLU backward (see Kernel::epilogue_swiglu_bwd): gate / up rows in through the park, d(gate) / d(up) out through it
+  // Backward.  acc = d(act) of the wave's 128 x 64 tile.  Per 64-row half: the gate and up rows come in as full 128-byte
+  // lines (16 bytes per lane), go through the park into the accumulator layout, d(gate) / d(up) are formed in registers and
+  // leave through the park like any other tile.
   static __device__ __forceinline__ void epilogue16_swiglu_bwd(const Params& p, Acc16& acc, char* park, int wm0, int wn0,
                                                                int lane) {
     const int l15 = lane & 15, g4 = lane >> 4;
@@ -1635,8 +1342,10 @@ struct Kernel16 {
     }
   }
 
-  // RoPE (see Kernel::epilogue_rope): blocks bj = 0, 1 hold columns col_a + 16 bj + 4 g4 .., blocks bj = 2, 3 the partners
-  // half a head further (col_a + D / 2 + ..); c0 = index of col_a's pair inside the head
+  // RoPE: blocks bj = 0, 1 hold columns col_a + 16 bj + 4 g4 .., blocks bj = 2, 3 the partners half a head further
+  // (col_a + D / 2 + ..): both members of every rotary pair in one lane; c0 = index of col_a's pair inside the head (table
+  // column).  Every table / bias element of a 64-row half is requested up front (ONE wait per half) — issued one (row block,
+  // column quad) at a time the epilogue paid a memory round trip per quad.
   static __device__ __forceinline__ void epilogue16_rope(const Params& p, Acc16& acc, char* park, int wm0, int col_a, int c0,
                                                          int lane) {
     const int l15 = lane & 15, g4 = lane >> 4;
@@ -1801,10 +1510,10 @@ struct Kernel16 {
   }
 };
 
-template <bool AK, bool BK, int PLACE, int EPI = EPI_PLAIN>
+template <bool AK, bool BK, int EPI = EPI_PLAIN>
 __global__ __launch_bounds__(NT, 2) void gemm16_kernel(const Params p) {
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
-  Kernel16<AK, BK, PLACE, EPI>::run(p, smem);
+  Kernel16<AK, BK, EPI>::run(p, smem);
 }
 
 // ws[S][ntiles][256 x 256] fp32 partial sums -> C = bf16(sum_s ws[s] (+ bias) (+ C)) on the tiles [tile0, tile0 + ntiles);
@@ -1870,128 +1579,53 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   out.store(dst);
 }
 
-// kernel-development switch: TN_GEMM_VARIANT = 100 * PLACE + 10 * ASYM + ILV (scripts/gemm_sweep.py sweeps it)
-#ifndef TN_GEMM_DEFAULT_VARIANT
-#define TN_GEMM_DEFAULT_VARIANT 601
-#endif
-
-// The half-stage ring (Kernel32) and the four-wave / AGPR-accumulator geometry (Kernel4) are measured variants, not product:
-// scripts/variants/gemm_kernel32_kernel4.inc, compiled in only by variant builds.
-#if defined(TN_GEMM_ALL_VARIANTS) || TN_GEMM_DEFAULT_VARIANT >= 1000
-#define TN_GEMM_HAVE_VARIANT_KERNELS 1
-#include "../../scripts/variants/gemm_kernel32_kernel4.inc"
-#endif
-
-
+// Which kernel a product runs on, by its shape alone (first match; -1 = no kernel for this combination, the entry points
+// answer TN_EINVAL):
+//   1. bias gradient wanted (weight-gradient mode only): Kernel EPI_BIASG — split-K + reduce, fp32 output, or bf16 output
+//   2. split-K (no transposed copy): Kernel SPLITK + splitk_reduce_kernel
+//   3. fp32 output (weight-gradient mode only): Kernel OUT_F32
+//   4. row-stored A without a transposed copy (forward and input-gradient products): Kernel16
+//   5. everything else (weight-gradient mode; any product with a transposed copy): Kernel
+// Weight-gradient mode = both operands contraction-major, no transposed copy.
 template <bool AK, bool BK, bool HAS_CT>
-static int launch_variant(int variant, dim3 grid, hipStream_t st, Params p) {
-  const int stages64 = p.stages;
-  p.stages = 2 * stages64;                     // (the half-stage ring counts 32-deep stages; reset below for the others)
-#define TN_V(PL, AS, IL)                                                                             \
-  case 100 * PL + 10 * AS + IL:                                                                      \
-    p.stages = stages64;                                                                             \
-    hipLaunchKernelGGL((gemm_kernel<AK, BK, PL, AS, IL, HAS_CT>), grid, dim3(NT), 0, st, p);         \
-    return 0;
-  constexpr int DPL = (TN_GEMM_DEFAULT_VARIANT % 1000) / 100, DAS = (TN_GEMM_DEFAULT_VARIANT / 10) % 10,
-                DIL = TN_GEMM_DEFAULT_VARIANT % 10;
-#define TN_V32(PL)                                                                                   \
-  case 1000 + PL:                                                                                    \
-    hipLaunchKernelGGL((gemm32_kernel<AK, BK, PL, HAS_CT>), grid, dim3(NT), 0, st, p);               \
-    return 0;
-#define TN_V4(DN)                                                                                    \
-  case 2000 + DN:                                                                                    \
-    p.stages = stages64;                                                                             \
-    hipLaunchKernelGGL((gemm4_kernel<AK, BK, DN, HAS_CT>), grid, dim3(256), 0, st, p);               \
-    return 0;
-#ifdef TN_GEMM_ALL_VARIANTS
-  if constexpr (!HAS_CT) {
-    switch (variant) {
-      TN_V4(1) TN_V4(2) TN_V4(3)
-      TN_V32(0) TN_V32(1) TN_V32(2) TN_V32(3)
-      TN_V(0, 0, 0) TN_V(0, 0, 1)
-      TN_V(1, 0, 0) TN_V(1, 0, 1) TN_V(1, 1, 0) TN_V(1, 1, 1)
-      TN_V(3, 0, 1) TN_V(3, 1, 1)
-      TN_V(4, 0, 1) TN_V(4, 1, 1)
-      TN_V(5, 0, 1) TN_V(5, 1, 1)
-      TN_V(6, 0, 1) TN_V(6, 1, 1)
-      default:
-        return -1;
-    }
-  }
-#endif
-  (void)variant;
-#if TN_GEMM_DEFAULT_VARIANT >= 2000
-  p.stages = stages64;
-  hipLaunchKernelGGL((gemm4_kernel<AK, BK, TN_GEMM_DEFAULT_VARIANT - 2000, HAS_CT>), grid, dim3(256), 0, st, p);
-#elif TN_GEMM_DEFAULT_VARIANT >= 1000
-  hipLaunchKernelGGL((gemm32_kernel<AK, BK, TN_GEMM_DEFAULT_VARIANT - 1000, HAS_CT>), grid, dim3(NT), 0, st, p);
-#else
-  {
-    p.stages = stages64;
-    if (p.bias_out != nullptr) {                   // weight gradient + bias gradient (EPI_BIASG)
-      if constexpr (AK && BK && !HAS_CT) {
-        if (p.splitk > 1) {
-          hipLaunchKernelGGL((gemm_kernel<true, true, DPL, DAS, DIL, false, true, false, EPI_BIASG>), grid, dim3(NT), 0, st, p);
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)p.ntiles * 32u), dim3(256), 0, st, p.ws, p.splitk, p.M,
-                             p.N, p.nbm, p.nbn, p.tile0, p.ntiles, p.C, p.ldc, p.bias, p.accumulate, p.c_f32,
-                             (const float*)p.bias_ws, p.bias_out);
-        } else if (p.c_f32) {
-          hipLaunchKernelGGL((gemm_kernel<true, true, DPL, DAS, DIL, false, false, true, EPI_BIASG>), grid, dim3(NT), 0, st, p);
-        } else {
-          hipLaunchKernelGGL((gemm_kernel<true, true, DPL, DAS, DIL, false, false, false, EPI_BIASG>), grid, dim3(NT), 0, st, p);
-        }
+static int launch(dim3 grid, hipStream_t st, const Params& p) {
+  constexpr bool WGRAD = AK && BK && !HAS_CT;
+  auto reduce = [&](const float* bias_ws, bf16_t* bias_out) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)p.ntiles * 32u), dim3(256), 0, st, p.ws, p.splitk, p.M, p.N,
+                       p.nbm, p.nbn, p.tile0, p.ntiles, p.C, p.ldc, p.bias, p.accumulate, p.c_f32, bias_ws, bias_out);
+  };
+  if (p.bias_out != nullptr) {
+    if constexpr (WGRAD) {
+      if (p.splitk > 1) {
+        hipLaunchKernelGGL((gemm_kernel<true, true, false, true, false, EPI_BIASG>), grid, dim3(NT), 0, st, p);
+        reduce(p.bias_ws, p.bias_out);
+      } else if (p.c_f32) {
+        hipLaunchKernelGGL((gemm_kernel<true, true, false, false, true, EPI_BIASG>), grid, dim3(NT), 0, st, p);
       } else {
-        return -1;
-      }
-    } else if (p.splitk > 1) {
-      if constexpr (!HAS_CT) {
-        hipLaunchKernelGGL((gemm_kernel<AK, BK, DPL, DAS, DIL, false, true>), grid, dim3(NT), 0, st, p);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)p.ntiles * 32u), dim3(256), 0, st, p.ws, p.splitk, p.M,
-                           p.N, p.nbm, p.nbn, p.tile0, p.ntiles, p.C, p.ldc, p.bias, p.accumulate, p.c_f32,
-                           (const float*)nullptr, (bf16_t*)nullptr);
-      } else {
-        return -1;
-      }
-    } else if (p.c_f32) {
-      if constexpr (AK && BK && !HAS_CT) {         // (weight-gradient mode only: the one caller)
-        hipLaunchKernelGGL((gemm_kernel<true, true, DPL, DAS, DIL, false, false, true>), grid, dim3(NT), 0, st, p);
-      } else {
-        return -1;
+        hipLaunchKernelGGL((gemm_kernel<true, true, false, false, false, EPI_BIASG>), grid, dim3(NT), 0, st, p);
       }
     } else {
-      // row-stored A (forward / input-gradient products): the 16x16x32 kernel (TN_GEMM_M16=0: the 32x32x16 one)
-      static const bool m16 = [] { const char* e = getenv("TN_GEMM_M16"); return !(e && e[0] == '0'); }();
-      if constexpr (!HAS_CT && !AK) {
-        if (m16) {
-#ifdef TN_G16_SWEEP   // kernel development: DMA placement table of Kernel16 from the environment (scripts/r05_g16_sweep.sh)
-          const char* e16 = getenv("TN_G16_PLACE");
-          switch (e16 ? atoi(e16) : DPL) {
-            case 1: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 1>), grid, dim3(NT), 0, st, p); return 0;
-            case 2: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 2>), grid, dim3(NT), 0, st, p); return 0;
-            case 3: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 3>), grid, dim3(NT), 0, st, p); return 0;
-            case 4: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 4>), grid, dim3(NT), 0, st, p); return 0;
-            case 5: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 5>), grid, dim3(NT), 0, st, p); return 0;
-            case 0: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 0>), grid, dim3(NT), 0, st, p); return 0;
-            case 7: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 7>), grid, dim3(NT), 0, st, p); return 0;
-            case 8: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 8>), grid, dim3(NT), 0, st, p); return 0;
-            case 9: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 9>), grid, dim3(NT), 0, st, p); return 0;
-            case 10: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 10>), grid, dim3(NT), 0, st, p); return 0;
-            case 11: hipLaunchKernelGGL((gemm16_kernel<AK, BK, 11>), grid, dim3(NT), 0, st, p); return 0;
-            default: break;
-          }
-#endif
-          hipLaunchKernelGGL((gemm16_kernel<AK, BK, DPL>), grid, dim3(NT), 0, st, p);
-          return 0;
-        }
-      }
-      hipLaunchKernelGGL((gemm_kernel<AK, BK, DPL, DAS, DIL, HAS_CT>), grid, dim3(NT), 0, st, p);
+      return -1;
     }
+  } else if (p.splitk > 1) {
+    if constexpr (!HAS_CT) {
+      hipLaunchKernelGGL((gemm_kernel<AK, BK, false, true>), grid, dim3(NT), 0, st, p);
+      reduce(nullptr, nullptr);
+    } else {
+      return -1;
+    }
+  } else if (p.c_f32) {
+    if constexpr (WGRAD) {
+      hipLaunchKernelGGL((gemm_kernel<true, true, false, false, true>), grid, dim3(NT), 0, st, p);
+    } else {
+      return -1;
+    }
+  } else if constexpr (!AK && !HAS_CT) {
+    hipLaunchKernelGGL((gemm16_kernel<AK, BK>), grid, dim3(NT), 0, st, p);
+  } else {
+    hipLaunchKernelGGL((gemm_kernel<AK, BK, HAS_CT>), grid, dim3(NT), 0, st, p);
   }
-#endif
   return 0;
-#undef TN_V
-#undef TN_V32
-#undef TN_V4
 }
 
 }  // namespace gemm
@@ -2005,6 +1639,30 @@ extern "C" {
 static int g_persistent = 1;
 void tn_gemm_set_persistent(int on) { g_persistent = on ? 1 : 0; }
 int tn_gemm_get_persistent(void) { return g_persistent; }
+
+namespace {
+
+int num_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n >= 8 ? n / 8 * 8 : 8;
+  }();
+  return ncu;
+}
+
+bool persistent_now() {
+  const char* pe = getenv("TN_GEMM_PERSIST");        // (the environment wins: kernel-development A/B)
+  return pe ? atoi(pe) != 0 : g_persistent != 0;
+}
+
+void clear_params(tn::gemm::Params& p) {
+  p = tn::gemm::Params{};
+  p.splitk = 1;
+  p.nseg = 1;
+}
+
+}  // namespace
 
 // General entry: C[M,N] = sum_s opA_s · opB_s^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M].
 //   a_kmaj / b_kmaj: 0 = operand stored [rows, K] (contraction-contiguous), 1 = stored [K, rows] (contraction-major).
@@ -2022,14 +1680,11 @@ static int gemm_launch(const void* const* A, const void* const* B, const long lo
                             (ldadd % 8) || ldadd < N || ((uintptr_t)addend & 15)))
     return TN_EINVAL;
   if (bias_grad != nullptr && (!(a_kmaj && b_kmaj) || nseg != 1 || Ct != nullptr || bias != nullptr || tail_only ||
-                               ((uintptr_t)bias_grad & 1) || TN_GEMM_DEFAULT_VARIANT >= 1000 ||
-                               getenv("TN_GEMM_VARIANT") != nullptr))
+                               ((uintptr_t)bias_grad & 1)))
     return TN_EINVAL;
   if (M <= 0 || N <= 0 || nseg < 1 || nseg > MAXSEG || (N % 8) != 0) return TN_EINVAL;
   if ((ldc % 8) || ldc < N || ((uintptr_t)C & 15)) return TN_EINVAL;
-  if (c_f32 && (!(a_kmaj && b_kmaj) || nseg != 1 || Ct != nullptr || bias != nullptr || tail_only ||
-                TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr))
-    return TN_EINVAL;
+  if (c_f32 && (!(a_kmaj && b_kmaj) || nseg != 1 || Ct != nullptr || bias != nullptr || tail_only)) return TN_EINVAL;
   if (a_kmaj && (M % 8)) return TN_EINVAL;
   Params p;
   p = Params{};
@@ -2082,17 +1737,11 @@ static int gemm_launch(const void* const* A, const void* const* B, const long lo
   p.tile0 = 0;
   p.ntiles = p.nbm * p.nbn;
   p.c_f32 = c_f32;
-  // persistent: one workgroup per CU walks its tiles (TN_GEMM_PERSIST=0: one workgroup per tile, kernel-development A/B)
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n >= 8 ? n / 8 * 8 : 8;
-  }();
+  const int ncu = num_cus();
   int main_tiles = 0;                                // tail split: tiles [0, main_tiles) run unsplit first
   if (splitk > 1) {
     // one segment, no transposed copy; a contraction-contiguous operand cannot be cut inside a stage or read behind K
-    if (nseg != 1 || Ct != nullptr || TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr)
-      return TN_EINVAL;
+    if (nseg != 1 || Ct != nullptr) return TN_EINVAL;
     if (!(a_kmaj && b_kmaj) && (p.stages % splitk) != 0) return TN_EINVAL;
     if (tail_only) {
       main_tiles = p.ntiles / ncu * ncu;
@@ -2108,15 +1757,12 @@ static int gemm_launch(const void* const* A, const void* const* B, const long lo
     p.bias_ws = bias_grad ? (float*)workspace + slabs : nullptr;     // [splitk][nbm * 256] partial column sums
   }
   p.bias_out = (tn::bf16_t*)bias_grad;
-  const char* pe = getenv("TN_GEMM_PERSIST");        // (the environment wins: kernel-development A/B)
-  const bool persist = pe ? atoi(pe) != 0 : g_persistent != 0;
+  // persistent: one workgroup per CU walks its tiles; else one workgroup per tile
+  const bool persist = persistent_now();
   hipStream_t st = (hipStream_t)stream;
-  const char* e = getenv("TN_GEMM_VARIANT");     // kernel-development A/B switch (read per call: the sweep changes it)
-  const int variant = e ? atoi(e) : TN_GEMM_DEFAULT_VARIANT;
   int rc = 0;
-#define TN_MODE(AKM, BKM, GRID, PRM)                                                       \
-  rc |= (Ct != nullptr) ? launch_variant<AKM, BKM, true>(variant, GRID, st, PRM)           \
-                        : launch_variant<AKM, BKM, false>(variant, GRID, st, PRM)
+#define TN_MODE(AKM, BKM, GRID, PRM) \
+  rc |= (Ct != nullptr) ? launch<AKM, BKM, true>(GRID, st, PRM) : launch<AKM, BKM, false>(GRID, st, PRM)
 #define TN_LAUNCH(GRID, PRM)                                                               \
   if (!a_kmaj && !b_kmaj) TN_MODE(false, false, GRID, PRM);                                \
   else if (!a_kmaj && b_kmaj) TN_MODE(false, true, GRID, PRM);                             \
@@ -2184,41 +1830,6 @@ int tn_gemm_bf16_wgrad_f32(const void* A, const void* B, long long lda, long lon
                      splitk > 1 ? splitk : 1, 0, workspace, workspace_bytes, stream, 1);
 }
 
-namespace {
-
-// 16x16x32 MFMAs (Kernel16) for the products whose A operand is row-stored — forward and input-gradient products — where
-// they are 5-7 % / 2-3 % faster; the weight-gradient mode (both operands through transpose reads) gains nothing and stays on
-// Kernel.  TN_GEMM_M16=0: every product on the 32x32x16 kernel (A/B runs).
-bool use_m16() {
-  static const bool on = [] { const char* e = getenv("TN_GEMM_M16"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-constexpr int kDPL = (TN_GEMM_DEFAULT_VARIANT % 1000) / 100, kDAS = (TN_GEMM_DEFAULT_VARIANT / 10) % 10,
-              kDIL = TN_GEMM_DEFAULT_VARIANT % 10;
-
-int num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n >= 8 ? n / 8 * 8 : 8;
-  }();
-  return ncu;
-}
-
-bool persistent_now() {
-  const char* pe = getenv("TN_GEMM_PERSIST");
-  return pe ? atoi(pe) != 0 : g_persistent != 0;
-}
-
-void clear_params(tn::gemm::Params& p) {
-  p = tn::gemm::Params{};
-  p.splitk = 1;
-  p.nseg = 1;
-}
-
-}  // namespace
-
 // Several independent products of ONE operand mode in one persistent launch (`ngrp` = 1..3; product g:
 // C_g[M_g, N_g] (+)= opA_g · opB_g^T, one segment each, no bias).  What it is for: the MLP's three weight gradients are 688
 // output tiles each = 2.69 rounds on 256 CUs, i.e. three launches idle a third of the chip in their last rounds; as one
@@ -2248,7 +1859,6 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
   using namespace tn::gemm;
   if (ngrp < 1 || ngrp > MAXSEG) return TN_EINVAL;
   if (!(a_kmaj && b_kmaj)) return TN_EINVAL;               // (weight-gradient mode: the one caller)
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr) return TN_EINVAL;
   Params p;
   clear_params(p);
   int total = 0, min_stages = 0x7fffffff;
@@ -2299,9 +1909,9 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
   {
     const dim3 grid(persist && main_tiles > ncu ? ncu : main_tiles);
     if (c_f32)
-      hipLaunchKernelGGL((gemm_kernel<true, true, kDPL, kDAS, kDIL, false, false, true, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((gemm_kernel<true, true, false, false, true, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
     else
-      hipLaunchKernelGGL((gemm_kernel<true, true, kDPL, kDAS, kDIL, false, false, false, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((gemm_kernel<true, true, false, false, false, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
   }
   if (S > 1) {
     float* ws = (float*)workspace;
@@ -2329,7 +1939,7 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
       q.c_f32 = c_f32;
       const int units = q.ntiles * S;
       const dim3 grid(persist && units > ncu ? ncu : units);
-      hipLaunchKernelGGL((gemm_kernel<true, true, kDPL, kDAS, kDIL, false, true>), grid, dim3(NT), 0, st, q);
+      hipLaunchKernelGGL((gemm_kernel<true, true, false, true>), grid, dim3(NT), 0, st, q);
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)q.ntiles * 32u), dim3(256), 0, st, q.ws, q.splitk, q.M, q.N,
                          q.nbm, q.nbn, q.tile0, q.ntiles, q.C, q.ldc, (const tn::bf16_t*)nullptr, q.accumulate, q.c_f32,
                          (const float*)nullptr, (tn::bf16_t*)nullptr);
@@ -2350,7 +1960,6 @@ int tn_gemm_bf16_swiglu_fwd(const void* x, const void* wg, const void* wu, void*
   if (ldx < K || ldw < K) return TN_EINVAL;        // (row pitches of the row-stored operands: at least the contraction)
   if (((uintptr_t)x | (uintptr_t)wg | (uintptr_t)wu | (uintptr_t)gate | (uintptr_t)up | (uintptr_t)act) & 15) return TN_EINVAL;
   if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr) return TN_EINVAL;
   Params p;
   clear_params(p);
   p.seg[0].A = p.seg[1].A = (const tn::bf16_t*)x;
@@ -2372,11 +1981,7 @@ int tn_gemm_bf16_swiglu_fwd(const void* x, const void* wg, const void* wu, void*
   p.ntiles = p.nbm * p.nbn;
   const int ncu = num_cus();
   const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  if (use_m16())
-    hipLaunchKernelGGL((gemm16_kernel<false, false, kDPL, EPI_SWIGLU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL((gemm_kernel<false, false, kDPL, kDAS, kDIL, false, false, false, EPI_SWIGLU_FWD>), grid, dim3(NT), 0,
-                       (hipStream_t)stream, p);
+  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_SWIGLU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
@@ -2393,7 +1998,6 @@ int tn_gemm_bf16_swiglu_bwd(const void* dy, const void* wd, const void* gate, co
     return TN_EINVAL;
   if ((long long)288 * lddy * 2 >= 0x7fffffffLL || ldw < I || ((long long)(H - 1) * ldw + I) * 2 >= 0x7fffffffLL)
     return TN_EINVAL;
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr) return TN_EINVAL;
   Params p;
   clear_params(p);
   p.seg[0].A = (const tn::bf16_t*)dy;
@@ -2415,11 +2019,7 @@ int tn_gemm_bf16_swiglu_bwd(const void* dy, const void* wd, const void* gate, co
   p.ntiles = p.nbm * p.nbn;
   const int ncu = num_cus();
   const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  if (use_m16())
-    hipLaunchKernelGGL((gemm16_kernel<false, true, kDPL, EPI_SWIGLU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL((gemm_kernel<false, true, kDPL, kDAS, kDIL, false, false, false, EPI_SWIGLU_BWD>), grid, dim3(NT), 0,
-                       (hipStream_t)stream, p);
+  hipLaunchKernelGGL((gemm16_kernel<false, true, EPI_SWIGLU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
@@ -2449,7 +2049,6 @@ int tn_gemm_bf16_rope(const void* x, const void* w, const void* bias, const void
   if (((uintptr_t)cos_t | (uintptr_t)sin_t | (uintptr_t)bias) & 7) return TN_EINVAL;
   if (cos_t == nullptr || sin_t == nullptr) return TN_EINVAL;
   if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr) return TN_EINVAL;
   Params p;
   clear_params(p);
   p.seg[0].A = (const tn::bf16_t*)x;
@@ -2472,11 +2071,7 @@ int tn_gemm_bf16_rope(const void* x, const void* w, const void* bias, const void
   p.ntiles = p.nbm * p.nbn;
   const int ncu = num_cus();
   const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  if (use_m16())
-    hipLaunchKernelGGL((gemm16_kernel<false, false, kDPL, EPI_ROPE>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL((gemm_kernel<false, false, kDPL, kDAS, kDIL, false, false, false, EPI_ROPE>), grid, dim3(NT), 0,
-                       (hipStream_t)stream, p);
+  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_ROPE>), grid, dim3(NT), 0, (hipStream_t)stream, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
@@ -2492,7 +2087,6 @@ int tn_gemm_bf16_gelu_fwd(const void* x, const void* w, const void* bias, void* 
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)pre | (uintptr_t)act) & 15) return TN_EINVAL;
   if (((uintptr_t)bias & 7) || pre == act) return TN_EINVAL;
   if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr || !use_m16()) return TN_EINVAL;
   Params p;
   clear_params(p);
   p.seg[0].A = (const tn::bf16_t*)x;
@@ -2513,7 +2107,7 @@ int tn_gemm_bf16_gelu_fwd(const void* x, const void* w, const void* bias, void* 
   p.ntiles = p.nbm * p.nbn;
   const int ncu = num_cus();
   const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, false, kDPL, EPI_GELU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_GELU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
@@ -2529,7 +2123,6 @@ int tn_gemm_bf16_gelu_bwd(const void* dy, const void* w2, const void* pre, void*
   if (((uintptr_t)dy | (uintptr_t)w2 | (uintptr_t)pre | (uintptr_t)dpre) & 15) return TN_EINVAL;
   if ((long long)288 * lddy * 2 >= 0x7fffffffLL || ldw < I || ((long long)(H - 1) * ldw + I) * 2 >= 0x7fffffffLL)
     return TN_EINVAL;
-  if (TN_GEMM_DEFAULT_VARIANT >= 1000 || getenv("TN_GEMM_VARIANT") != nullptr || !use_m16()) return TN_EINVAL;
   Params p;
   clear_params(p);
   p.seg[0].A = (const tn::bf16_t*)dy;
@@ -2549,13 +2142,13 @@ int tn_gemm_bf16_gelu_bwd(const void* dy, const void* w2, const void* pre, void*
   p.ntiles = p.nbm * p.nbn;
   const int ncu = num_cus();
   const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, true, kDPL, EPI_GELU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((gemm16_kernel<false, true, EPI_GELU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
-// C[M,N] = A[M,K] · B[N,K]^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M]: the round-2 entry point,
-// kept as the single-segment, both-operands-contraction-contiguous case of tn_gemm_bf16.
+// C[M,N] = A[M,K] · B[N,K]^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M]: the single-segment,
+// both-operands-contraction-contiguous case of tn_gemm_bf16.
 int tn_gemm_bf16_tn(const void* A, const void* B, void* C, void* Ct, const void* bias, int M, int N, int K,
                     long long lda, long long ldb, long long ldc, long long ldct, int accumulate, void* stream) {
   return tn_gemm_bf16(&A, &B, &lda, &ldb, &K, 1, 0, 0, C, Ct, bias, M, N, ldc, ldct, accumulate, stream);

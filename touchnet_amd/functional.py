@@ -705,8 +705,7 @@ def rope_epilogue_ok(M: int, N: int, K: int, head_dim: int) -> bool:
     """shapes tn_gemm_bf16_rope takes (and the hand-written kernel is the configured GEMM for)"""
     return (ROPE_EPILOGUE and _own(M, N, (K,)) and K % 64 == 0
             and (not SPLIT_K or split_k(M, N, K, False, False) == 1)     # (a split-K product sums in another order)
-            and ((head_dim == 128 and N % 256 == 0) or (head_dim == 64 and N % 64 == 0))
-            and not os.environ.get("TN_GEMM_VARIANT"))
+            and ((head_dim == 128 and N % 256 == 0) or (head_dim == 64 and N % 64 == 0)))
 
 
 ROPE_EPILOGUE = os.environ.get("TN_ROPE_EPILOGUE", "1") != "0"          # (A/B switch)
@@ -729,7 +728,7 @@ def split_k(M: int, N: int, K: int, a_kmaj: bool, b_kmaj: bool) -> int:
     number of 64-deep stages has to divide evenly."""
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     stages = (K + 63) // 64
-    if tiles * 2 > _NUM_CU or stages < 16 or os.environ.get("TN_GEMM_VARIANT"):
+    if tiles * 2 > _NUM_CU or stages < 16:
         return 1
     s = min(_NUM_CU // tiles, stages // 8)
     if not (a_kmaj and b_kmaj):
@@ -793,7 +792,7 @@ def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None
         # (a product that would be cut along its contraction — few output tiles, the last layer on the labelled rows — keeps
         #  its split-K form and gets the addition behind it: the epilogue variant is for whole-tile products)
         if (RESIDUAL_EPILOGUE and _own(M, N, (K,)) and _bf16_rows(a, b, addend) and (bias is None or bias.dtype == torch.bfloat16)
-                and K % 64 == 0 and not os.environ.get("TN_GEMM_VARIANT")
+                and K % 64 == 0
                 and (not SPLIT_K or split_k(M, N, K, False, False) == 1)):
             return gemm([(a, b)], bias=bias, addend=addend)
         return _mm_tn(a, b, bias) + addend           # (same bits: the product is rounded before the addition either way)
@@ -1093,7 +1092,7 @@ class _LinearGroup(torch.autograd.Function):
                 for i, (d, nw) in enumerate(zip(dys, need_w)):
                     # the bias gradient rides on the weight-gradient launch (column sums of the dY fragments it reads anyway)
                     bg = (torch.empty(Ns[i], dtype=x.dtype, device=x.device)
-                          if (nw and need_b[i] and BIAS_IN_WGRAD and not os.environ.get("TN_GEMM_VARIANT")) else None)
+                          if (nw and need_b[i] and BIAS_IN_WGRAD) else None)
                     if nw and _beside((d, x2c), lambda: _sink_wgrad(ws[i], d, x2c, bg), written=(bg,)):
                         sunk.add(i)
                         dbs[i] = bg
@@ -1184,8 +1183,7 @@ class _SwiGLUMLP(torch.autograd.Function):
         x2 = _c(x.reshape(-1, K))
         M = x2.shape[0]
         own = _own(M, I, (K,)) and _own(M, K, (I,)) and _own(I, K, (M,), True, True) and _own(K, I, (M,), True, True)
-        fused = (own and MLP_EPILOGUE and K % 64 == 0 and _bf16_rows(x2, wg, wu, wd) and wg.stride(0) == wu.stride(0)
-                 and not os.environ.get("TN_GEMM_VARIANT"))
+        fused = own and MLP_EPILOGUE and K % 64 == 0 and _bf16_rows(x2, wg, wu, wd) and wg.stride(0) == wu.stride(0)
         if fused:
             gate, up, act = gemm_swiglu_fwd(x2, wg, wu)       # SwiGLU in the epilogue of ONE gate + up launch
             kept = act
@@ -1221,7 +1219,7 @@ class _SwiGLUMLP(torch.autograd.Function):
         dy2 = _c(dy).reshape(M, H)
         nx, ng, nu, nd = ctx.needs_input_grad[:4]
         if ctx.own and LINEAR_GEMM == "own":
-            grouped = GROUPED_WGRAD and ng and nu and nd and not os.environ.get("TN_GEMM_VARIANT")
+            grouped = GROUPED_WGRAD and ng and nu and nd
             if not grouped:
                 dwd = None if (not nd or _beside((dy2, kept), lambda: _sink_wgrad(wd, dy2, kept))) \
                     else _beside((dy2, kept), lambda: gemm([(dy2, kept)], True, True))                   # dY^T act  [H, I]
@@ -1380,8 +1378,7 @@ def gelu_mlp(x, w1, b1, w2, b2):
     I, H = w1.shape[0], w2.shape[0]
     ok = (GELU_EPILOGUE and x.is_cuda and LINEAR_GEMM == "own" and x.dtype == torch.bfloat16 and K % 64 == 0 and I % 64 == 0
           and _own(M, I, (K,)) and _own(M, H, (I,)) and _own(M, I, (H,), False, True) and _own(M, K, (I,), False, True)
-          and _bf16_rows(w1, w2) and all(b is None or b.dtype == torch.bfloat16 for b in (b1, b2))
-          and not os.environ.get("TN_GEMM_VARIANT") and os.environ.get("TN_GEMM_M16", "1") != "0")
+          and _bf16_rows(w1, w2) and all(b is None or b.dtype == torch.bfloat16 for b in (b1, b2)))
     if ok:
         return _GeluMLP.apply(x, w1, b1, w2, b2)
     h = linear_group(x, [(w1, b1)], wgrad="nt", dgrad_tn=False)[0]
