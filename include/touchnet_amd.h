@@ -395,6 +395,51 @@ int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len,
                    int do_sample, float temperature, int top_k, float top_p, unsigned long long seed, const int* eos_ids,
                    int n_eos, int pad, int dtype, void* stream);
 
+/* ---- Beam search on a KV cache shared between beams — the search mode of HF generate() that
+ *      touchnet/models/touch_audio/inference_touch_audio.py:177-192 switches off by hand (num_beams=1) and
+ *      touchnet/models/qwen2_audio/inference_qwen2_audio.py takes from the checkpoint's generation_config.json;
+ *      transformers/generation/utils.py `_beam_search` (_get_top_k_continuations, _get_running_beams_for_next_iteration,
+ *      _update_finished_beams, _check_early_stop_heuristic).  R = B * K rows, utterance b owns rows b K .. b K + K - 1.
+ * attn_decode_beam: tn_attn_decode on R rows, plus src int32 [R, S_max]: key / value s < cache_len[r] of row r is read at
+ *      cache[src[r, s], s] — keys and values stay where they were written, beams share their ancestors' rows.  The new
+ *      key / value go to cache[r, cache_len[r]] (src is not consulted for that slot).  An entry outside [0, R) among the
+ *      consulted ones: row r's output is NaN, nothing is read out of bounds.  Key splits, workspace
+ *      (tn_attn_decode_workspace_bytes with B = R) and limits as for attn_decode; with a table that names a dense cache
+ *      the result equals attn_decode's on that cache bit for bit.  Precondition: no consulted entry names a slot that is
+ *      written in the same call, i.e. never src[r, s] == r' with s == cache_len[r'] and s < cache_len[r] (that slot is
+ *      being stored by another workgroup: the read would race).  Rows that share one cache_len, as the beams of an
+ *      utterance do, and a table that stays inside the utterance — what beam_step maintains — cannot violate it.
+ *      -22 as for attn_decode, and for a NULL or misaligned src. */
+int tn_attn_decode_beam(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                        const int* cache_len, const int* src, void* o, void* workspace, int R, int Nh, int Nkv, int D,
+                        int S_max, float scale, void* stream);
+/* beam_step: one step of `_beam_search` for every utterance that is not done.  logits [B * K_in, V] (`dtype`), K_in = 1
+ *      right after the prefill (row b K live) or K; hist / fin_ids / src int32 [R, S_hist]; hist_len / cache_len / fin_len /
+ *      fin_flag / out_ids / out_parent int32 [R]; run_score / fin_score fp32 [R] (an empty finished slot scores -1e9);
+ *      gen / unsat / done int32 [B]; n_unfinished int32 [1]; workspace >= tn_beam_step_workspace_bytes(B, K) bytes.
+ *      keep = max(2, 1 + n_eos) K.  acc = processors(log_softmax(fp32 logits)) + run_score[row]: repetition penalty
+ *      (lp < 0 ? lp * penalty : lp / penalty, each id of the row's history once) and -inf on ids completing an
+ *      `ngram`-gram (0 = off), both applied to the log-probabilities.  The top `keep` candidates of the utterance, ties to
+ *      the lower row * V + id; hit = id in eos_ids or gen + 1 >= n_new.  The first K that did not hit become the running
+ *      beams: run_score, out_ids, out_parent (absolute row); hist and src rows are permuted by parent, the id appended,
+ *      src[row, cache_len] = parent row, hist_len and cache_len advance.  Hits among the first K candidates enter the
+ *      finished set (fin_ids = the whole sequence, prompt included, fin_len its length) at acc / (gen + 1) ^ length_penalty;
+ *      the best K are kept, descending.  unsat &= run_score[0] / L ^ length_penalty > worst finished score (L = n_new for
+ *      early_stopping 2 = "never" with length_penalty > 0, else gen + 1); the utterance is done when !unsat, when the set
+ *      is full under early_stopping 1 = True (0 = False), or when every candidate hit; then done[b] = 1, n_unfinished -= 1
+ *      and later calls leave all its state untouched.  An utterance whose rows have no room for the appended id
+ *      (hist_len[b K] outside [1, S_hist) or cache_len[b K] outside [0, S_hist)) is skipped whole: nothing of it changes,
+ *      it does not advance and n_unfinished does not drop — the caller grows hist / fin_ids / src before the step, as
+ *      it grows the caches.  No host synchronisation.  -22 before any launch for NULL or
+ *      misaligned pointers, K outside [2, 8], K_in not 1 or K, n_eos outside [0, 3], V outside [64, 262144], penalty <= 0,
+ *      ngram < 0, n_new < 1, early_stopping outside [0, 2]. */
+long long tn_beam_step_workspace_bytes(int B, int K);
+int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score, int* fin_ids,
+                 int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done, int* n_unfinished,
+                 int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V, int S_hist, float penalty,
+                 int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty, int early_stopping, int dtype,
+                 void* stream);
+
 /* ---- Kimi-Audio's speech tokenizer (GLM-4-voice WhisperVQEncoder, touchnet/models/kimi_audio/modeling_kimi_audio.py:140-319,
  *      run by MoonshotKimiaForCausalLM.prepare_audio_input_embs under no_grad, :957-963).  Forward only: it is frozen.
  * attn_block_causal_fwd: the layers' self-attention under get_block_causal_attention_mask (:226-242, applied :293-301):

@@ -4,10 +4,16 @@ generate() (sdpa, same knobs, same weights).  Prints one JSON object per measure
 
     python scripts/decode_bench.py [--skip-hf] [--layers 16] [--batch 12] [--new 256]
     python scripts/decode_bench.py --qwen2-audio-7b [--batch 12]
+    python scripts/decode_bench.py --num-beams 4 [--batch 12]
 
 --qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
 per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
 (decode_logits + tn_sample_step, top_k 50 / top_p 0.9, caches of ~300 tokens per row).
+
+--num-beams K: beam search at LlamaForASR-1B and Qwen2-Audio-7B widths (B utterances, K beams, prompts of 300 ids, random
+weights, eos unreachable): tn_beam_step per call (µs) and its share of the decode step (decode_logits through the table +
+tn_beam_step), and per layer tn_attn_decode_beam against the path it replaces — index_select of both caches by the beams'
+parents (HF's reorder_cache) followed by tn_attn_decode on the dense result.
 
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
@@ -212,6 +218,69 @@ def bench_qwen2_audio_7b(B, steps=32, iters=200):
     return rows
 
 
+def bench_beams(K, B, steps=24, iters=100):
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    widths = (("llama_asr_1b", dict(model_type="llama", hidden_size=2048, intermediate_size=8192, num_attention_heads=32,
+                                    num_key_value_heads=8, head_dim=64, num_hidden_layers=16, vocab_size=128256,
+                                    rope_theta=500000.0, tie_word_embeddings=True, rms_norm_eps=1e-5), [-1], 1.5, 2),
+              ("qwen2_audio_7b", dict(model_type="qwen2", hidden_size=4096, intermediate_size=11008,
+                                      num_attention_heads=32, num_key_value_heads=32, head_dim=128, num_hidden_layers=32,
+                                      vocab_size=156032, rope_theta=10000.0, rms_norm_eps=1e-5,
+                                      tie_word_embeddings=False), [-1, -2], 1.1, 0))
+    rows = []
+    for name, text, eos, penalty, ngram in widths:
+        text.update(initializer_range=0.02, eos_token_id=1, pad_token_id=0)
+        cfg = DecoderConfig.from_dict(text)
+        torch.manual_seed(0)
+        with torch.device(DEV):
+            lm = PackedCausalLM(cfg)
+        lm.post_init()
+        lm = lm.to(torch.bfloat16).eval()
+        P, L, Nh, Nkv, D = 300, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        prompts = G.Prompts([torch.randint(2, 100000, (P,)) for _ in range(B)])
+        n_new = steps + iters + 8
+        st = G.BeamState.allocate(L, B, K, P + n_new, Nkv, D, DEV)
+        kw = dict(penalty=penalty, ngram=ngram, eos=eos, n_new=n_new, length_penalty=1.0, early_stopping=False)
+        with torch.no_grad():
+            F.beam_step(G._prefill(lm, None, prompts, st, DEV, row_stride=K), st, **kw)
+
+            def step():
+                F.beam_step(G.decode_logits(lm, st, table=st.src), st, **kw)
+            step()
+            ms = _events_time(step, steps - 2) / 1e3
+            # attention of one layer at this state: through the table, against reorder-copy + dense attention
+            R = B * K
+            q = torch.randn(R, Nh, D, device=DEV, dtype=torch.bfloat16)
+            kn = torch.randn(R, Nkv, D, device=DEV, dtype=torch.bfloat16)
+            kc, vc, cl, src = st.k[0], st.v[0], st.cache_len, st.src
+            parent = st.out_parent.to(torch.int64)
+            F.attn_decode_beam(q, kn, kn, kc, vc, cl, src)
+            us_table = _events_time(lambda: F.attn_decode_beam(q, kn, kn, kc, vc, cl, src), iters)
+
+            # HF's reorder_cache copies the cache at its current length: the live rows plus the slot of the new token
+            live = int(cl.max()) + 1
+
+            def reorder_then_dense():
+                F.attn_decode(q, kn, kn, kc[:, :live].index_select(0, parent), vc[:, :live].index_select(0, parent), cl)
+            reorder_then_dense()
+            us_copy = _events_time(reorder_then_dense, iters)
+            kd, vd = kc[:, :live].contiguous(), vc[:, :live].contiguous()
+            us_dense = _events_time(lambda: F.attn_decode(q, kn, kn, kd, vd, cl), iters)
+            logits = G.decode_logits(lm, st, table=st.src)
+            us_step = _events_time(lambda: F.beam_step(logits, st, **kw), iters)
+        rows.append(dict(width=name, B=B, K=K, V=cfg.vocab_size, cache_rows=int(st.cache_len[0]), S_max=st.capacity,
+                         ms_per_decode_step=round(ms, 3), beam_step_us=round(us_step, 2),
+                         beam_step_share=round(us_step / (ms * 1e3), 4), attn_decode_beam_us_per_layer=round(us_table, 2),
+                         reorder_copy_plus_attn_decode_us_per_layer=round(us_copy, 2), reorder_copied_rows=live,
+                         attn_decode_dense_alone_us_per_layer=round(us_dense, 2),
+                         utterances_still_running=int(st.n_unfinished.item())))
+        del lm, st, kc, vc, kd, vd
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -220,12 +289,17 @@ def main():
     ap.add_argument("--batch", type=int, default=12)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--qwen2-audio-7b", action="store_true")
+    ap.add_argument("--num-beams", type=int, default=0, help="K > 1: the beam-search measurements")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.num_beams > 1:
+        for r in bench_beams(a.num_beams, a.batch):
+            print(json.dumps(r), flush=True)
+        return
     if a.qwen2_audio_7b:
         for r in bench_qwen2_audio_7b(a.batch):
             print(json.dumps(r), flush=True)

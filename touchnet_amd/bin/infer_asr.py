@@ -115,6 +115,9 @@ def main(argv=None):
     ap.add_argument("--max_new_tokens", type=int, default=256)
     ap.add_argument("--repetition_penalty", type=float, default=1.5)
     ap.add_argument("--no_repeat_ngram_size", type=int, default=2)
+    ap.add_argument("--num_beams", type=int, default=1, help="> 1: beam search")
+    ap.add_argument("--length_penalty", type=float, default=1.0)
+    ap.add_argument("--early_stopping", default="false", choices=["true", "false", "never"])
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     args = ap.parse_args(argv)
@@ -131,7 +134,10 @@ def main(argv=None):
         items = [json.loads(line) for line in f if line.strip()]
     items = items[args.shard_index::args.num_shards]
     cfg = GenerationConfig(max_new_tokens=args.max_new_tokens, repetition_penalty=args.repetition_penalty,
-                           no_repeat_ngram_size=args.no_repeat_ngram_size)
+                           no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
+                           length_penalty=args.length_penalty,
+                           early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"))
+    cfg.check_beams()
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f"part_{args.shard_index + 1}_of_{args.num_shards}")
     with open(out_path, "w") as writer:

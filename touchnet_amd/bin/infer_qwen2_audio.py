@@ -82,6 +82,9 @@ def main(argv=None):
     ap.add_argument("--max_length", type=int, default=70000)
     ap.add_argument("--max_new_tokens", type=int, default=None, help="overrides the budget (default: HF's rule)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--num_beams", type=int, default=None, help="overrides the checkpoint's generation config")
+    ap.add_argument("--length_penalty", type=float, default=None)
+    ap.add_argument("--early_stopping", default=None, choices=["true", "false", "never"])
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     args = ap.parse_args(argv)
@@ -92,6 +95,12 @@ def main(argv=None):
     model = load_model(args.model_path, device)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path)
     over = dict(max_length=args.max_length, seed=args.seed)
+    if args.num_beams is not None:
+        over["num_beams"] = args.num_beams
+    if args.length_penalty is not None:
+        over["length_penalty"] = args.length_penalty
+    if args.early_stopping is not None:
+        over["early_stopping"] = {"true": True, "false": False}.get(args.early_stopping, "never")
     gen_file = os.path.join(args.model_path, "generation_config.json")
     cfg = GenerationConfig.from_hf(gen_file if os.path.exists(gen_file) else {}, **over)
     if args.max_new_tokens is not None:

@@ -20,6 +20,8 @@
 // workspace and a second launch combines them.  Split boundaries depend only on (B, Nkv, S_max) and cache_len: results are
 // bit-reproducible.  The slot cache_len[b] is read by nobody: the key at index cache_len[b] is taken from k_new / v_new,
 // and only the workgroup whose split contains that index writes the slot.
+#include <type_traits>
+
 #include "common.h"
 
 namespace tn {
@@ -65,11 +67,24 @@ __device__ __forceinline__ float group_sum(float v) {
 
 // Partial results: ws_o [B, Nkv, nsplit, G, D] fp32 (normalised by l), ws_lse [B, Nkv, nsplit, G] fp32 (m + log2 l, -inf =
 // empty split).  With nsplit == 1 the normalised output goes straight to o.
-template <int D, int G>
+//
+// BEAM (tn_attn_decode_beam): key / value s < cache_len[b] of row b is read at cache[src[b, s], s] — beams of one utterance
+// share the rows of their common ancestors, nothing is copied when beams are reordered.  The new key / value still go to
+// cache[b, cache_len[b]].  A table entry outside [0, B) is replaced by b (nothing is read out of bounds) and poisons the
+// row's output with NaN.  Everything else, the order of every floating-point operation included, is the dense kernel's.
+// Precondition: no consulted entry names the slot another row stores in this launch (src[b, s] == r' with s ==
+// cache_len[r'], s < cache_len[b]): that read would race with the store.  Rows that share a cache_len cannot do it.
+struct NoTable {};                        // the dense kernel's `src`: an empty argument, so its code is what it was
+struct Table {
+  const int* __restrict__ p;
+};
+
+template <int D, int G, bool BEAM = false>
 __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_new, const bf16_t* __restrict__ v_new,
     bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache, const int* __restrict__ cache_len, bf16_t* __restrict__ o,
-    float* __restrict__ ws_o, float* __restrict__ ws_lse, int Nkv, int S_max, int nsplit, float scale_log2) {
+    float* __restrict__ ws_o, float* __restrict__ ws_lse, int Nkv, int S_max, int nsplit, float scale_log2,
+    std::conditional_t<BEAM, Table, NoTable> src) {
   constexpr int LPK = D / 8;              // lanes per key row
   constexpr int KPW = 64 / LPK;           // keys per wave per iteration
   constexpr int KPI = KPW * kWaves;       // keys per workgroup per iteration
@@ -119,6 +134,13 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[h][e] *= scale_log2;
   }
+  [[maybe_unused]] int R = 0;
+  [[maybe_unused]] const int* srow = nullptr;
+  [[maybe_unused]] bool bad = false;
+  if constexpr (BEAM) {
+    R = gridDim.z;
+    srow = src.p + (size_t)b * S_max;
+  }
   float m[G], l[G], acc[G][8];
 #pragma unroll
   for (int h = 0; h < G; ++h) {
@@ -136,8 +158,23 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
       const int j = base + u * KPI + wave * KPW + kg;
       jj[u] = j;
       const int js = j < k1 ? j : k0;                                       // (in-bounds filler, never used)
-      const bf16_t* kp = js == len ? kn : kc + (size_t)js * row_stride;
-      const bf16_t* vp = js == len ? vn : vc + (size_t)js * row_stride;
+      const bf16_t *kp, *vp;
+      if constexpr (BEAM) {
+        int r = b;
+        if (js != len) {
+          r = srow[js];
+          if (r < 0 || r >= R) {
+            bad = true;
+            r = b;
+          }
+        }
+        const size_t off = ((size_t)r * S_max + js) * row_stride + (size_t)kvh * D + part * 8;
+        kp = js == len ? kn : k_cache + off;
+        vp = js == len ? vn : v_cache + off;
+      } else {
+        kp = js == len ? kn : kc + (size_t)js * row_stride;
+        vp = js == len ? vn : vc + (size_t)js * row_stride;
+      }
       kr[u] = *reinterpret_cast<const uint4*>(kp);
       vr[u] = *reinterpret_cast<const uint4*>(vp);
     }
@@ -199,7 +236,20 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
       }
     }
   }
-  __syncthreads();
+  if constexpr (BEAM) {
+    bad = __syncthreads_or(bad) != 0;
+    if (bad) {
+      if (nsplit == 1) {
+        for (int i = tid; i < G * D; i += kThreads)
+          o[((size_t)b * Nh + kvh * G + i / D) * D + i % D] = 0x7fc0;    // bf16 quiet NaN
+      } else if (tid < G) {
+        ws_lse[ws_row + tid] = __builtin_nanf("");
+      }
+      return;
+    }
+  } else {
+    __syncthreads();
+  }
   for (int i = tid; i < G * D; i += kThreads) {
     const int h = i / D, d = i % D;
     float mx = -INFINITY;
@@ -255,14 +305,19 @@ __global__ void __launch_bounds__(kThreads) attn_decode_combine_kernel(const flo
 
 template <int D, int G>
 static int launch(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
-                  void* o, void* workspace, int B, int Nkv, int S_max, float scale, hipStream_t st) {
+                  const int* src, void* o, void* workspace, int B, int Nkv, int S_max, float scale, hipStream_t st) {
   const int nsplit = num_splits(B, Nkv, S_max);
   float* ws_o = (float*)workspace;
   float* ws_lse = ws_o ? ws_o + (size_t)B * Nkv * nsplit * G * D : nullptr;
   const float sl2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL((attn_decode_split_kernel<D, G>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st, (const bf16_t*)q,
-                     (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache, cache_len, (bf16_t*)o,
-                     ws_o, ws_lse, Nkv, S_max, nsplit, sl2);
+  if (src)
+    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, true>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
+                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache,
+                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, Table{src});
+  else
+    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, false>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
+                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache,
+                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, NoTable{});
   TN_LAUNCH_CHECK();
   if (nsplit > 1) {
     hipLaunchKernelGGL((attn_decode_combine_kernel<D, G>), dim3(Nkv, B), dim3(kThreads), 0, st, (const float*)ws_o,
@@ -274,9 +329,10 @@ static int launch(const void* q, const void* k_new, const void* v_new, void* k_c
 
 template <int D>
 static int dispatch_g(int G, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
-                      const int* cache_len, void* o, void* ws, int B, int Nkv, int S_max, float scale, hipStream_t st) {
+                      const int* cache_len, const int* src, void* o, void* ws, int B, int Nkv, int S_max, float scale,
+                      hipStream_t st) {
 #define TN_DECODE_G(g) \
-  case g: return launch<D, g>(q, k_new, v_new, k_cache, v_cache, cache_len, o, ws, B, Nkv, S_max, scale, st);
+  case g: return launch<D, g>(q, k_new, v_new, k_cache, v_cache, cache_len, src, o, ws, B, Nkv, S_max, scale, st);
   switch (G) {
     TN_DECODE_G(1) TN_DECODE_G(2) TN_DECODE_G(3) TN_DECODE_G(4) TN_DECODE_G(5) TN_DECODE_G(6) TN_DECODE_G(7)
     TN_DECODE_G(8) TN_DECODE_G(9) TN_DECODE_G(10) TN_DECODE_G(11) TN_DECODE_G(12) TN_DECODE_G(13) TN_DECODE_G(14)
@@ -300,18 +356,35 @@ long long tn_attn_decode_workspace_bytes(int B, int Nh, int Nkv, int D, int S_ma
   return (long long)B * Nh * ns * (D + 1) * 4;
 }
 
-int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
-                   void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream) {
+static int decode_entry(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                        const int* cache_len, const int* src, bool beam, void* o, void* workspace, int B, int Nh, int Nkv,
+                        int D, int S_max, float scale, void* stream) {
   using namespace tn::decode;
   if (B <= 0 || Nh <= 0 || Nkv <= 0 || S_max <= 0 || (D != 64 && D != 128) || Nh % Nkv || Nh / Nkv > 16) return TN_EINVAL;
   if (!al16(q) || !al16(k_new) || !al16(v_new) || !al16(k_cache) || !al16(v_cache) || !al16(o) || cache_len == nullptr ||
       ((uintptr_t)cache_len & 3))
     return TN_EINVAL;
+  if (beam && (src == nullptr || ((uintptr_t)src & 3))) return TN_EINVAL;
   if (num_splits(B, Nkv, S_max) > 1 && !al16(workspace)) return TN_EINVAL;
   const int G = Nh / Nkv;
   hipStream_t st = (hipStream_t)stream;
-  return D == 64 ? dispatch_g<64>(G, q, k_new, v_new, k_cache, v_cache, cache_len, o, workspace, B, Nkv, S_max, scale, st)
-                 : dispatch_g<128>(G, q, k_new, v_new, k_cache, v_cache, cache_len, o, workspace, B, Nkv, S_max, scale, st);
+  return D == 64
+             ? dispatch_g<64>(G, q, k_new, v_new, k_cache, v_cache, cache_len, src, o, workspace, B, Nkv, S_max, scale, st)
+             : dispatch_g<128>(G, q, k_new, v_new, k_cache, v_cache, cache_len, src, o, workspace, B, Nkv, S_max, scale, st);
+}
+
+int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
+                   void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream) {
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, cache_len, nullptr, false, o, workspace, B, Nh, Nkv, D, S_max,
+                      scale, stream);
+}
+
+// as tn_attn_decode on R = B_utt * K rows, reading the cached keys / values through src int32 [R, S_max]
+int tn_attn_decode_beam(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                        const int* cache_len, const int* src, void* o, void* workspace, int R, int Nh, int Nkv, int D,
+                        int S_max, float scale, void* stream) {
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, cache_len, src, true, o, workspace, R, Nh, Nkv, D, S_max, scale,
+                      stream);
 }
 
 }  // extern "C"

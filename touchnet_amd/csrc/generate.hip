@@ -10,14 +10,14 @@
 //
 // One workgroup per batch row.  The seen-token set is a bitmap of V bits in LDS (16 KB at V = 128256), the banned set a
 // second one, filled by a scan of the history against its last n - 1 ids.  The row of logits is read once.
-#include "common.h"
+#include "history_sets.h"
 
 namespace tn {
 namespace greedy {
 
 constexpr int kThreads = 1024;
-constexpr int kMaxVocab = 262144;
-constexpr int kWords = kMaxVocab / 32;
+using histsets::kMaxVocab;
+using histsets::kWords;
 
 template <typename T>
 __device__ __forceinline__ float ld(const T* p);
@@ -40,34 +40,9 @@ __global__ void __launch_bounds__(kThreads) greedy_step_kernel(const T* __restri
   __shared__ float red_v[kThreads / 64];
   __shared__ int red_i[kThreads / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int words = (V + 31) / 32;
   const int len = min(max(hist_len[b], 0), S_hist);      // (a length past the row is never read past it)
   const int* h = hist + (size_t)b * S_hist;
-  const bool use_pen = penalty != 1.f;
-  for (int w = tid; w < words; w += kThreads) {
-    seen[w] = 0u;
-    banned[w] = 0u;
-  }
-  __syncthreads();
-  if (use_pen) {
-    for (int i = tid; i < len; i += kThreads) {
-      const int t = h[i];
-      if (t >= 0 && t < V) atomicOr(&seen[t >> 5], 1u << (t & 31));
-    }
-  }
-  if (ngram > 0 && len + 1 >= ngram) {
-    // n-grams h[i .. i+n-1] (i + n - 1 < len) whose first n - 1 ids equal the last n - 1 ids of the history
-    const int pre = len - (ngram - 1);
-    for (int i = tid; i + ngram - 1 < len; i += kThreads) {
-      bool match = true;
-      for (int j = 0; j < ngram - 1 && match; ++j) match = h[i + j] == h[pre + j];
-      if (match) {
-        const int t = h[i + ngram - 1];
-        if (t >= 0 && t < V) atomicOr(&banned[t >> 5], 1u << (t & 31));
-      }
-    }
-  }
-  __syncthreads();
+  histsets::fill(seen, banned, h, len, V, penalty != 1.f, ngram, tid, kThreads);
 
   const T* row = logits + (size_t)b * V;
   float bv = -INFINITY;

@@ -1546,6 +1546,35 @@ def sample_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penal
                    bool(do_sample), float(temperature), int(top_k), float(top_p), int(seed), eos, int(pad))
 
 
+# ------------------------------------------------------------------------------------ beam search (generation.py)
+def attn_decode_beam(q, k_new, v_new, k_cache, v_cache, cache_len, src, scale: Optional[float] = None):
+    """`attn_decode` for R = B * K beam rows whose caches are shared through an ancestry table: key / value s of row r is
+    read at cache[src[r, s], s] (src int32 [R, S_max]) for s < cache_len[r]; k_new / v_new are stored at
+    cache[r, cache_len[r]].  Nothing is copied when beams are reordered; `beam_step` maintains the table."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return L.attn_decode_beam_(q, k_new, v_new, k_cache, v_cache, cache_len, src, float(scale))
+
+
+EARLY_STOPPING_CODE = {False: 0, True: 1, "never": 2}
+
+
+def beam_step(logits, state, penalty: float = 1.0, ngram: int = 0, eos=(), n_new: int = 1, length_penalty: float = 1.0,
+              early_stopping=False) -> None:
+    """One step of HF's beam search (`_beam_search` of transformers) on the device: log_softmax, repetition penalty and
+    n-gram ban on the log-probabilities, the top continuations of every utterance, running beams, finished set, early-stop
+    heuristic, and the reordering of history and ancestry table by parent.  `state`: an object with the tensors of
+    `generation.BeamState` (num_beams, hist, hist_len, cache_len, src, run_score, fin_*, gen, unsat, done, n_unfinished,
+    out_ids, out_parent).  logits [B, V] on the first step (one live row per utterance), [B * num_beams, V] afterwards."""
+    if early_stopping not in (True, False, "never"):
+        raise ValueError(f"early_stopping must be True, False or 'never' (got {early_stopping!r})")
+    eos = [int(e) for e in ([eos] if isinstance(eos, int) else eos)]
+    s = state
+    L.beam_step_(logits, s.hist, s.hist_len, s.cache_len, s.src, s.run_score, s.fin_ids, s.fin_len, s.fin_score,
+                 s.fin_flag, s.gen, s.unsat, s.done, s.n_unfinished, s.out_ids, s.out_parent, int(s.num_beams),
+                 float(penalty), int(ngram), eos, int(n_new), float(length_penalty), EARLY_STOPPING_CODE[early_stopping])
+
+
 # ------------------------------------------------------------------------------------ Kimi-Audio speech tokenizer (frozen)
 @dataclass
 class BlockCausalMask:

@@ -32,7 +32,7 @@ from . import functional as F
 
 
 # generation_config.json keys this path does not implement, with the value that leaves them inert (HF's defaults)
-_UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "typical_p": 1.0, "min_p": None,
+_UNSUPPORTED = {"num_beam_groups": 1, "penalty_alpha": None, "typical_p": 1.0, "min_p": None,
                 "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "top_h": None, "bad_words_ids": None, "force_words_ids": None,
                 "sequence_bias": None, "constraints": None, "min_length": 0, "min_new_tokens": None,
                 "suppress_tokens": None, "begin_suppress_tokens": None, "forced_bos_token_id": None,
@@ -41,6 +41,9 @@ _UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "ty
                 "renormalize_logits": False, "num_return_sequences": 1, "assistant_model": None,
                 "prompt_lookup_num_tokens": None, "max_time": None, "stop_strings": None, "dola_layers": None,
                 "diversity_penalty": 0.0}
+
+
+MAX_BEAMS, MAX_BEAM_EOS = 8, 3             # tn_beam_step's limits
 
 
 @dataclass
@@ -61,6 +64,9 @@ class GenerationConfig:
     seed: int = 0                            # Philox key of the draws (with the row key and the step)
     max_length: Optional[int] = None         # prompt + new tokens, used when max_new_tokens is None
     cache_chunk: int = 1024                  # new-token rows of the first KV-cache allocation (it doubles on demand)
+    num_beams: int = 1                       # > 1: beam search (tn_beam_step), without do_sample
+    length_penalty: float = 1.0              # finished hypotheses score sum(log p) / length ** length_penalty
+    early_stopping: Union[bool, str] = False  # True, False or "never" (HF's three heuristics)
 
     @classmethod
     def from_hf(cls, path_or_dict, **overrides) -> "GenerationConfig":
@@ -84,7 +90,7 @@ class GenerationConfig:
             v = overrides.get(k, d.get(k, inert))
             if v not in (inert, None, [], {}):
                 raise ValueError(f"generation config: {k} = {v!r} is not supported by this decoder "
-                                 f"(greedy or sampled search, one sequence per prompt)")
+                                 f"(greedy, sampled or beam search, one sequence per prompt)")
         num = lambda k, default: overrides[k] if k in overrides else d.get(k, default)
         cfg = cls(max_new_tokens=d.get("max_new_tokens"), repetition_penalty=float(num("repetition_penalty", 1.0)),
                   no_repeat_ngram_size=int(num("no_repeat_ngram_size", 0)), eos_token_id=num("eos_token_id", None),
@@ -92,7 +98,8 @@ class GenerationConfig:
                   do_sample=bool(num("do_sample", False)), temperature=float(num("temperature", 1.0)),
                   top_k=int(num("top_k", 50) or 0), top_p=float(num("top_p", 1.0)), seed=int(num("seed", 0)),
                   max_length=int(num("max_length", 20)), check_every=int(num("check_every", 16)),
-                  cache_chunk=int(num("cache_chunk", 1024)))
+                  cache_chunk=int(num("cache_chunk", 1024)), num_beams=int(num("num_beams", 1) or 1),
+                  length_penalty=float(num("length_penalty", 1.0)), early_stopping=num("early_stopping", False))
         if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
             cfg.max_new_tokens = overrides["max_new_tokens"]
         if cfg.do_sample:
@@ -104,7 +111,27 @@ class GenerationConfig:
                 raise ValueError(f"generation config: top_k {cfg.top_k} must be >= 0")
         else:
             cfg.temperature, cfg.top_k, cfg.top_p = 1.0, 0, 1.0        # the warpers are inert without do_sample
+        cfg.check_beams()
         return cfg
+
+    def check_beams(self, eos: Optional[Sequence[int]] = None) -> None:
+        """What beam search accepts (tn_beam_step's limits); `eos`: the resolved eos ids (default: this config's)."""
+        if self.early_stopping not in (True, False, "never"):
+            raise ValueError(f"generation config: early_stopping = {self.early_stopping!r} must be True, False or 'never'")
+        if self.num_beams < 1:
+            raise ValueError(f"generation config: num_beams = {self.num_beams} must be >= 1")
+        if self.num_beams == 1:
+            return
+        if self.do_sample:
+            raise ValueError(f"generation config: num_beams = {self.num_beams} with do_sample is not supported by this "
+                             "decoder (beam search is deterministic here; beam sampling is not implemented)")
+        if self.num_beams > MAX_BEAMS:
+            raise ValueError(f"generation config: num_beams = {self.num_beams} exceeds {MAX_BEAMS}")
+        if eos is None:
+            e = self.eos_token_id
+            eos = [] if e is None else (list(e) if isinstance(e, (list, tuple)) else [e])
+        if len(eos) > MAX_BEAM_EOS:
+            raise ValueError(f"generation config: beam search takes at most {MAX_BEAM_EOS} eos ids (got {len(eos)})")
 
     def new_tokens(self, longest_prompt: int) -> int:
         """The token budget of a batch: max_new_tokens, else max_length minus the longest prompt (HF's rule)."""
@@ -162,6 +189,82 @@ class KVCache:
         self.k = [bigger(t) for t in self.k]
         self.v = [bigger(t) for t in self.v]
         self.hist = bigger(self.hist)
+
+
+@dataclass
+class BeamState:
+    """Beam search over R = B * K rows (utterance b owns rows b K .. b K + K - 1).  k / v [R, S_max, Nkv, D] per layer: a
+    key / value stays in the row that wrote it, and src int32 [R, S_max] names, per row and position, the row to read
+    (tn_attn_decode_beam).  hist / hist_len / cache_len as in KVCache, per row.  run_score fp32 [R]: the running beams'
+    sums of log-probabilities.  The finished set, K slots per utterance, best first: fin_ids int32 [R, S_max] (the whole
+    sequence, prompt included), fin_len, fin_flag int32 [R], fin_score fp32 [R] (-1e9 = empty).  Per utterance (int32 [B]):
+    gen (tokens generated), unsat (HF's early-stop heuristic still unsatisfied), done; n_unfinished int32 [1].  out_ids /
+    out_parent int32 [R]: the last step's ids and parent rows."""
+    num_beams: int
+    k: List[torch.Tensor]
+    v: List[torch.Tensor]
+    cache_len: torch.Tensor
+    hist: torch.Tensor
+    hist_len: torch.Tensor
+    src: torch.Tensor
+    run_score: torch.Tensor
+    fin_ids: torch.Tensor
+    fin_len: torch.Tensor
+    fin_score: torch.Tensor
+    fin_flag: torch.Tensor
+    gen: torch.Tensor
+    unsat: torch.Tensor
+    done: torch.Tensor
+    n_unfinished: torch.Tensor
+    out_ids: torch.Tensor
+    out_parent: torch.Tensor
+
+    @classmethod
+    def allocate(cls, num_layers: int, B: int, K: int, S_max: int, Nkv: int, D: int, device,
+                 dtype=torch.bfloat16) -> "BeamState":
+        R = B * K
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=device)
+        first = torch.arange(R, dtype=torch.int32, device=device) // K * K          # the row the prompt is stored in
+        return cls(num_beams=K, k=[torch.empty(R, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
+                   v=[torch.empty(R, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
+                   cache_len=z(R), hist=z(R, S_max), hist_len=z(R), src=first[:, None].repeat(1, S_max),
+                   run_score=torch.zeros(R, dtype=torch.float32, device=device), fin_ids=z(R, S_max), fin_len=z(R),
+                   fin_score=torch.full((R,), -1.0e9, dtype=torch.float32, device=device), fin_flag=z(R), gen=z(B),
+                   unsat=torch.ones(B, dtype=torch.int32, device=device), done=z(B),
+                   n_unfinished=torch.full((1,), B, dtype=torch.int32, device=device), out_ids=z(R), out_parent=z(R))
+
+    @property
+    def finished(self) -> torch.Tensor:
+        return self.done
+
+    @property
+    def capacity(self) -> int:
+        return self.hist.shape[1]
+
+    def grow(self, S_new: int) -> None:
+        """Reallocate caches, history, finished ids and table with S_new >= S_max columns, keeping their contents."""
+        S = self.capacity
+        if S_new <= S:
+            return
+        def bigger(t):
+            n = t.new_empty(t.shape[0], S_new, *t.shape[2:]) if t.dim() > 2 else t.new_zeros(t.shape[0], S_new)
+            n[:, :S].copy_(t)
+            return n
+        self.k = [bigger(t) for t in self.k]
+        self.v = [bigger(t) for t in self.v]
+        self.hist, self.fin_ids, self.src = bigger(self.hist), bigger(self.fin_ids), bigger(self.src)
+
+    def best(self, prompt_lens: Sequence[int], pad: int):
+        """-> (ids int64 [B, N] of every utterance's best finished hypothesis behind its prompt, `pad` after its end;
+        scores fp32 [B])."""
+        K = self.num_beams
+        lens = torch.tensor(list(prompt_lens), dtype=torch.int64, device=self.hist.device)
+        n = self.fin_len[::K].to(torch.int64) - lens
+        N = max(int(n.max()), 0)
+        idx = lens[:, None] + torch.arange(N, device=lens.device)[None]
+        ids = self.fin_ids[::K].gather(1, idx.clamp(max=self.capacity - 1)).to(torch.int64)
+        ids = torch.where(torch.arange(N, device=lens.device)[None] < n[:, None], ids, torch.full_like(ids, pad))
+        return ids, self.fin_score[::K].clone()
 
 
 def _parts(model):
@@ -223,11 +326,11 @@ _MAX_EOS = 8                                 # eos ids tn_sample_step takes
 EmbedFn = Callable[[torch.Tensor, List[int], int], torch.Tensor]
 
 
-def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device, embed: Optional[EmbedFn] = None):
+def _prefill(lm, proj_w, prompts: Prompts, cache, device, embed: Optional[EmbedFn] = None, row_stride: int = 1):
     """Packed forward over all prompts (one row, one document each) -> logits [B, V] of every prompt's last position;
     keys / values of every layer scattered into the caches.  `embed` builds the packed embeddings for a model of its own
     (Qwen2-Audio: the audio tower's rows at the AUDIO positions); by default embed(ids), plus projector(features) for
-    TouchAudio."""
+    TouchAudio.  Prompt b goes to cache row b * row_stride (beam search: the first row of the utterance's K)."""
     lens = [int(t.numel()) for t in prompts.input_ids]
     B, T = len(lens), sum(lens)
     Tp = (T + 255) // 256 * 256
@@ -245,7 +348,7 @@ def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device, embed: Option
         o += n
     last = torch.tensor([sum(lens[:b + 1]) - 1 for b in range(B)], dtype=torch.int64)
     S_max = cache.k[0].shape[1]
-    dst = torch.cat([torch.arange(n) + b * S_max for b, n in enumerate(lens)])
+    dst = torch.cat([torch.arange(n) + b * row_stride * S_max for b, n in enumerate(lens)])
     ids, pos, doc, last, src, dst = (x.to(device, non_blocking=True) for x in (ids, pos, doc, last, torch.cat(src), dst))
     if embed is not None:
         emb = embed(ids, lens, Tp)                                                         # [Tp, H]
@@ -258,16 +361,16 @@ def _prefill(lm, proj_w, prompts: Prompts, cache: KVCache, device, embed: Option
         kc.view(-1, Nkv, D).index_copy_(0, dst, k[0].index_select(0, src))
         vc.view(-1, Nkv, D).index_copy_(0, dst, v[0].index_select(0, src))
     lens_d = torch.tensor(lens, dtype=torch.int32, device=device)
-    cache.hist.view(-1).index_copy_(0, torch.cat([torch.arange(n, device=device) + b * cache.hist.shape[1]
+    cache.hist.view(-1).index_copy_(0, torch.cat([torch.arange(n, device=device) + b * row_stride * cache.hist.shape[1]
                                                   for b, n in enumerate(lens)]), ids.index_select(0, src).to(torch.int32))
-    cache.hist_len.copy_(lens_d)
-    cache.cache_len.copy_(lens_d - 1)        # the greedy step counts the prompt's last row (see the module docstring)
+    cache.hist_len[::row_stride].copy_(lens_d)
+    cache.cache_len[::row_stride].copy_(lens_d - 1)   # the step kernels count the prompt's last row (module docstring)
     cache.finished.zero_()
     cache.n_unfinished.fill_(B)
     return lm.lm_head(h[0])                                                                # [B, V]
 
 
-def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len):
+def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len, table=None):
     attn = layer.self_attn
     B = delta.shape[0]
     if residual is None:
@@ -278,22 +381,27 @@ def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len):
     q, k, v = F.linear_group(x, [(attn.q_proj.weight, attn.q_proj.bias), (attn.k_proj.weight, attn.k_proj.bias),
                                  (attn.v_proj.weight, attn.v_proj.bias)], rope=(cos, sin, attn.head_dim, (0, 1)))
     D = attn.head_dim
-    o = F.attn_decode(q.view(B, attn.num_heads, D), k.view(B, attn.num_kv_heads, D), v.view(B, attn.num_kv_heads, D),
-                      kc, vc, cache_len, attn.scaling)
+    if table is None:
+        o = F.attn_decode(q.view(B, attn.num_heads, D), k.view(B, attn.num_kv_heads, D), v.view(B, attn.num_kv_heads, D),
+                          kc, vc, cache_len, attn.scaling)
+    else:
+        o = F.attn_decode_beam(q.view(B, attn.num_heads, D), k.view(B, attn.num_kv_heads, D),
+                               v.view(B, attn.num_kv_heads, D), kc, vc, cache_len, table, attn.scaling)
     a = F.linear_group(o.view(B, attn.num_heads * D), [(attn.o_proj.weight, None)])[0]
     x, residual = layer.post_attention_layernorm(a, residual)
     return layer.mlp(x), residual
 
 
-def decode_logits(lm, cache: KVCache) -> torch.Tensor:
+def decode_logits(lm, cache, table: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step of every row: the newest token of the history at position cache_len -> logits [B, V]
-    (its key / value are appended to the caches; cache_len itself is advanced by the greedy step)."""
+    (its key / value are appended to the caches; cache_len itself is advanced by the greedy step).  `table` int32
+    [B, S_max]: the rows are beams that read their cached keys / values through it (BeamState.src)."""
     tok = cache.hist.gather(1, (cache.hist_len.to(torch.int64) - 1)[:, None])[:, 0]
     x = lm.model.embed_tokens(tok.to(torch.int64))                                          # [B, H]
     cos, sin = lm.model.rotary_emb(cache.cache_len.to(torch.int64), x.dtype)
     delta, residual = x, None
     for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):
-        delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len)
+        delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table)
     h, _ = lm.model.norm(delta, residual)
     return lm.lm_head(h)
 
@@ -301,13 +409,16 @@ def decode_logits(lm, cache: KVCache) -> torch.Tensor:
 @torch.no_grad()
 def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, return_cache: bool = False,
              row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None):
-    """Greedy or sampled generation for a batch of prompts -> int64 [B, N] generated ids (the prompt excluded), `pad`
-    after a row's eos — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM,
+    """Greedy, sampled or beam-search generation for a batch of prompts -> int64 [B, N] generated ids (the prompt
+    excluded), `pad` after a row's eos — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM,
     Qwen2AudioPackedForConditionalGeneration (with its `embed` builder) or PackedCausalLM, bf16, on the device.
 
     Without do_sample and with at most one eos id every step is tn_greedy_step (repetition penalty, n-gram ban, argmax);
     otherwise tn_sample_step (penalty, temperature, top-k, top-p, draw).  `row_keys` int64 [B] (default arange(B)) key
-    the draws with cfg.seed and the step: a row draws the same tokens whatever batch it is decoded in."""
+    the draws with cfg.seed and the step: a row draws the same tokens whatever batch it is decoded in.
+
+    With cfg.num_beams > 1 (and no do_sample): HF's beam search, tn_beam_step per token; the result is every utterance's
+    best finished hypothesis, and `return_cache` hands out the BeamState that holds the scores."""
     cfg = cfg or GenerationConfig()
     lm, proj_w = _parts(model)
     _check_model(model, lm)
@@ -324,6 +435,8 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     if n_new <= 0:
         return torch.empty(B, 0, dtype=torch.int64, device=device)
     penalty, ngram = float(cfg.repetition_penalty), int(cfg.no_repeat_ngram_size)
+    if int(cfg.num_beams) != 1:
+        return _beam_search(lm, proj_w, prompts, cfg, eos, pad, lens, n_new, device, embed, return_cache)
     greedy = not cfg.do_sample and len(eos) <= 1
     if not greedy:
         if ngram > 0:
@@ -367,6 +480,30 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         first = torch.where(is_eos.any(1), is_eos.to(torch.int8).argmax(1), torch.full_like(out[:, 0], steps - 1))
         out = out[:, :int(first.max()) + 1]
     return (out, cache) if return_cache else out
+
+
+def _beam_search(lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos, pad, lens, n_new, device, embed, return_cache):
+    """generate() with num_beams > 1: HF's beam search, one tn_beam_step per token.  The prompts are prefilled once, into
+    the first row of every utterance; the K beams of an utterance read them, and every later key, through the table."""
+    cfg.check_beams(eos)
+    K, c = int(cfg.num_beams), lm.config
+    chunk = max(1, int(cfg.cache_chunk))
+    st = BeamState.allocate(len(lm.model.layers), len(lens), K, max(lens) + min(n_new, chunk), c.num_key_value_heads,
+                            c.head_dim, device)
+    S_full = max(lens) + n_new
+    kw = dict(penalty=float(cfg.repetition_penalty), ngram=int(cfg.no_repeat_ngram_size), eos=eos, n_new=n_new,
+              length_penalty=float(cfg.length_penalty), early_stopping=cfg.early_stopping)
+    F.beam_step(_prefill(lm, proj_w, prompts, st, device, embed, row_stride=K), st, **kw)     # one live row per utterance
+    steps = 1
+    while steps < n_new:
+        if steps % max(1, int(cfg.check_every)) == 0 and int(st.n_unfinished.item()) == 0:
+            break
+        if max(lens) + steps >= st.capacity:
+            st.grow(min(S_full, 2 * st.capacity))
+        F.beam_step(decode_logits(lm, st, table=st.src), st, **kw)
+        steps += 1
+    out, _ = st.best(lens, pad)
+    return (out, st) if return_cache else out
 
 
 def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[int]]:

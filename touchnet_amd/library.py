@@ -983,6 +983,89 @@ def _(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, unifor
     return None
 
 
+# ===================================================================================================== beam search
+@custom_op(f"{NS}::attn_decode_beam_", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def attn_decode_beam_(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, cache_len: Tensor,
+                      src: Tensor, scale: float) -> Tensor:
+    """attn_decode_ on R = B * K beam rows that share their ancestors' cache rows (tn_attn_decode_beam): key / value s of
+    row r is read at cache[src[r, s], s], src int32 [R, S_max]; k_new / v_new are stored at cache[r, cache_len[r]]."""
+    _no_grad_inputs("attn_decode_beam_", q, k_new, v_new, k_cache, v_cache)
+    B, Nh, D = q.shape
+    S_max, Nkv = k_cache.shape[1], k_cache.shape[2]
+    if (q.dtype != torch.bfloat16 or k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16
+            or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16 or cache_len.dtype != torch.int32
+            or src.dtype != torch.int32 or tuple(k_new.shape) != (B, Nkv, D) or tuple(v_new.shape) != (B, Nkv, D)
+            or tuple(k_cache.shape) != (B, S_max, Nkv, D) or tuple(v_cache.shape) != (B, S_max, Nkv, D)
+            or tuple(cache_len.shape) != (B,) or tuple(src.shape) != (B, S_max) or not k_cache.is_contiguous()
+            or not v_cache.is_contiguous() or not src.is_contiguous()):
+        raise _C.KernelError("attn_decode_beam_: bf16 q [R, Nh, D], k_new / v_new [R, Nkv, D], contiguous caches "
+                             "[R, S_max, Nkv, D], int32 cache_len [R], contiguous int32 src [R, S_max]")
+    q, k_new, v_new, cache_len = _c(q), _c(k_new), _c(v_new), _c(cache_len)
+    o = torch.empty_like(q)
+    nbytes = int(_lib().tn_attn_decode_workspace_bytes(B, Nh, Nkv, D, S_max))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    _C.check(_lib().tn_attn_decode_beam(_p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(cache_len), _p(src),
+                                        _p(o), _p(ws), B, Nh, Nkv, D, S_max, float(scale), _cur()), "tn_attn_decode_beam")
+    return o
+
+
+@attn_decode_beam_.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, cache_len, src, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+BEAM_MAX_K, BEAM_MAX_EOS = 8, 3
+_BEAM_STATE = ("hist", "hist_len", "cache_len", "src", "run_score", "fin_ids", "fin_len", "fin_score", "fin_flag", "gen",
+               "unsat", "done", "n_unfinished", "out_ids", "out_parent")
+
+
+@custom_op(f"{NS}::beam_step_", mutates_args=_BEAM_STATE, device_types="cuda")
+def beam_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, src: Tensor, run_score: Tensor,
+               fin_ids: Tensor, fin_len: Tensor, fin_score: Tensor, fin_flag: Tensor, gen: Tensor, unsat: Tensor,
+               done: Tensor, n_unfinished: Tensor, out_ids: Tensor, out_parent: Tensor, num_beams: int, penalty: float,
+               ngram: int, eos: List[int], n_new: int, length_penalty: float, early_stopping: int) -> None:
+    """One step of HF's beam search (tn_beam_step) on R = B * num_beams rows: logits [B, V] (right after the prefill: one
+    live row per utterance) or [R, V], fp32 / bf16; hist / fin_ids / src int32 [R, S_hist]; hist_len / cache_len / fin_len /
+    fin_flag / out_ids / out_parent int32 [R]; run_score / fin_score fp32 [R]; gen / unsat / done int32 [B]; n_unfinished
+    int32 [1] — all advanced on the device.  early_stopping: 0 False, 1 True, 2 "never"."""
+    _no_grad_inputs("beam_step_", logits)
+    K = int(num_beams)
+    if not 2 <= K <= BEAM_MAX_K:
+        raise _C.KernelError(f"beam_step_: num_beams must be in [2, {BEAM_MAX_K}]")
+    if len(eos) > BEAM_MAX_EOS:
+        raise _C.KernelError(f"beam_step_: at most {BEAM_MAX_EOS} eos ids")
+    if hist.dim() != 2 or hist.shape[0] % K or logits.dim() != 2:
+        raise _C.KernelError("beam_step_: hist [B * num_beams, S_hist], logits [B or B * num_beams, V]")
+    R, S_hist = hist.shape
+    B, V = R // K, logits.shape[1]
+    if logits.shape[0] not in (B, R):
+        raise _C.KernelError("beam_step_: logits must have B (first step) or B * num_beams rows")
+    for name, t, dt, shape in (("hist", hist, torch.int32, (R, S_hist)), ("fin_ids", fin_ids, torch.int32, (R, S_hist)),
+                               ("src", src, torch.int32, (R, S_hist)), ("hist_len", hist_len, torch.int32, (R,)),
+                               ("cache_len", cache_len, torch.int32, (R,)), ("fin_len", fin_len, torch.int32, (R,)),
+                               ("fin_flag", fin_flag, torch.int32, (R,)), ("out_ids", out_ids, torch.int32, (R,)),
+                               ("out_parent", out_parent, torch.int32, (R,)), ("run_score", run_score, torch.float32, (R,)),
+                               ("fin_score", fin_score, torch.float32, (R,)), ("gen", gen, torch.int32, (B,)),
+                               ("unsat", unsat, torch.int32, (B,)), ("done", done, torch.int32, (B,)),
+                               ("n_unfinished", n_unfinished, torch.int32, (1,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _C.KernelError(f"beam_step_: {name} must be a contiguous {dt} tensor of shape {list(shape)}")
+    logits = _c(logits)
+    eos_arr = (ctypes.c_int * max(1, len(eos)))(*[int(e) for e in eos])
+    ws = torch.empty(int(_lib().tn_beam_step_workspace_bytes(B, K)) // 4, dtype=torch.float32, device=logits.device)
+    _C.check(_lib().tn_beam_step(_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(src), _p(run_score), _p(fin_ids),
+                                 _p(fin_len), _p(fin_score), _p(fin_flag), _p(gen), _p(unsat), _p(done), _p(n_unfinished),
+                                 _p(out_ids), _p(out_parent), _p(ws), B, K, logits.shape[0] // B, V, S_hist, float(penalty),
+                                 int(ngram), eos_arr, len(eos), int(n_new), float(length_penalty), int(early_stopping),
+                                 _C.dcode(logits), _cur()), "tn_beam_step")
+
+
+@beam_step_.register_fake
+def _(logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat, done,
+      n_unfinished, out_ids, out_parent, num_beams, penalty, ngram, eos, n_new, length_penalty, early_stopping):
+    return None
+
+
 # ===================================================================================================== speech tokenizer (frozen)
 @custom_op(f"{NS}::attn_block_causal_fwd", mutates_args=(), device_types="cuda")
 def attn_block_causal_fwd(q: Tensor, k: Tensor, v: Tensor, seg_start: Tensor, key_end: Tensor, block: int,
@@ -1035,4 +1118,5 @@ OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_f
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
-       "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest")
+       "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
+       "beam_step_")

@@ -43,12 +43,13 @@ def _special_ids(model, cfg: GenerationConfig):
 
 
 def transcribe(model, feats: List[torch.Tensor], cfg: Optional[GenerationConfig] = None) -> List[List[int]]:
-    """Greedy transcripts of a batch of utterances -> per utterance the generated ids (the prompt excluded), cut in front
-    of the first eos."""
+    """Greedy (or, with cfg.num_beams > 1, beam-search) transcripts of a batch of utterances -> per utterance the
+    generated ids (the prompt excluded), cut in front of the first eos."""
     cfg = cfg or GenerationConfig()
     pad, bos, eos = _special_ids(model, cfg)
     gcfg = GenerationConfig(max_new_tokens=cfg.max_new_tokens, repetition_penalty=cfg.repetition_penalty,
                             no_repeat_ngram_size=cfg.no_repeat_ngram_size, eos_token_id=eos, pad_token_id=pad,
-                            bos_token_id=bos, check_every=cfg.check_every)
+                            bos_token_id=bos, check_every=cfg.check_every, num_beams=cfg.num_beams,
+                            length_penalty=cfg.length_penalty, early_stopping=cfg.early_stopping)
     out = generate(model, build_prompts(feats, pad, bos), gcfg)
     return trim_at_eos(out, eos)
