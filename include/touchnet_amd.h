@@ -394,6 +394,29 @@ int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len,
                    const long long* row_key, const float* uniforms, int* n_kept, int B, int V, int S_hist, float penalty,
                    int do_sample, float temperature, int top_k, float top_p, unsigned long long seed, const int* eos_ids,
                    int n_eos, int pad, int dtype, void* stream);
+/* kimi_text_step: one text-stream step of Kimi-Audio's decoding loop — KimiASampler.sample_text_logits and the per-row
+ *      bookkeeping of MoonshotKimiaForCausalLM._generate_loop (touchnet/models/kimi_audio/modeling_kimi_audio.py:797-844
+ *      and :1153-1214) — in one launch, without the loop's per-row `.item()` synchronisations.
+ *      logits [B, V] (`dtype`), V <= 262144; hist / hist_len / cache_len / finished / n_unfinished as for greedy_step;
+ *      prompt_len int32 [B]; embed bf16 [V, H], x_next bf16 [B, H], H % 8 == 0, both 16-byte aligned.
+ *      Per row: with penalty > 1 and hist_len[b] - prompt_len[b] > window, every id of the last `window` (1..64) entries
+ *      of the history, once: l < 0 ? l * penalty : l / penalty, rounded to the logits' dtype.  temperature <= 1e-6: argmax,
+ *      lowest id on ties (the argmax of the reference's log_softmax wherever that has no tie of its own).  Otherwise, with
+ *      1 <= top_k <= 64: the top_k largest in descending order (ties to the lower id), fp32 weights exp((l - max) /
+ *      temperature) (the reference's exp((l - lse) / temperature) up to a factor common to all candidates), the first
+ *      candidate whose running weight exceeds u * total; u from uniforms[b] (fp32 [B]) or from Philox4x32-10 keyed by
+ *      `seed` with counter (hist_len[b], row_key[b]) as in sample_step (row_key int64 [B], NULL: the row index).
+ *      A finished row emits `blank`.  Then the bookkeeping of greedy_step with `eos`, and
+ *      x_next[b] = bf16(float(embed[token]) + float(embed[audio_token])) — the next step's input row, bit-equal to
+ *      torch's bf16 add.  A row with no room in hist (hist_len[b] >= S_hist) does not advance, as in greedy_step; its
+ *      x_next is still written.  No host synchronisation.
+ *      -22 before any launch for NULL or misaligned pointers, V, S_hist, window or top_k out of range, penalty <= 0,
+ *      H not a multiple of 8, blank or audio_token outside [0, V), and temperature > 1e-6 with top_k == 0 (the
+ *      full-vocabulary multinomial: out of scope). */
+int tn_kimi_text_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* finished, int* n_unfinished,
+                      const int* prompt_len, const void* embed, void* x_next, const long long* row_key,
+                      const float* uniforms, int B, int V, int S_hist, int H, float penalty, int window, float temperature,
+                      int top_k, unsigned long long seed, int eos, int blank, int audio_token, int dtype, void* stream);
 
 /* ---- Beam search on a KV cache shared between beams — the search mode of HF generate() that
  *      touchnet/models/touch_audio/inference_touch_audio.py:177-192 switches off by hand (num_beams=1) and

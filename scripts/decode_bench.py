@@ -5,6 +5,7 @@ generate() (sdpa, same knobs, same weights).  Prints one JSON object per measure
     python scripts/decode_bench.py [--skip-hf] [--layers 16] [--batch 12] [--new 256]
     python scripts/decode_bench.py --qwen2-audio-7b [--batch 12]
     python scripts/decode_bench.py --num-beams 4 [--batch 12]
+    python scripts/decode_bench.py --kimi-audio-7b [--batch 12]
 
 --qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
 per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
@@ -14,6 +15,12 @@ per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 
 weights, eos unreachable): tn_beam_step per call (µs) and its share of the decode step (decode_logits through the table +
 tn_beam_step), and per layer tn_attn_decode_beam against the path it replaces — index_select of both caches by the beams'
 parents (HF's reorder_cache) followed by tn_attn_decode on the dense result.
+
+--kimi-audio-7b: the decoder of Kimi-Audio-7B (28 layers, 28 / 4 heads, D 128, H 3584, V 168 448, random bf16 weights, prompts
+of 300 rows, eos unreachable): tn_kimi_text_step per call (µs) in greedy and top-k 5 mode on bf16 logits [B, 168 448] with
+tn_sample_step's greedy mode beside it at the same shape, prefill ms, and ms per decode step (decode_logits on the row the
+step kernel wrote + tn_kimi_text_step) against the same step with the row built by torch (history gather, two embedding
+lookups, add) — the launches the fused write removes.
 
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
@@ -218,6 +225,85 @@ def bench_qwen2_audio_7b(B, steps=32, iters=200):
     return rows
 
 
+def bench_kimi_audio_7b(B, steps=32, iters=200):
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.kimi_audio import KimiAudioConfig, KimiAudioPackedForCausalLM
+    from touchnet_amd.models.kimi_audio.inference_kimi_audio import _TextDecoder
+    V, H, P, W = 168448, 3584, 300, 16
+    blank, eos = 151666, -1                                              # eos unreachable
+    g = torch.Generator(device=DEV).manual_seed(0)
+    cfg = KimiAudioConfig(vocab_size=V, hidden_size=H, intermediate_size=18944, num_hidden_layers=28, num_attention_heads=28,
+                          num_key_value_heads=4, head_dim=128, rms_norm_eps=1e-6, rope_theta=1e6, initializer_range=0.02)
+    torch.manual_seed(0)
+    torch.set_default_dtype(torch.bfloat16)
+    try:
+        with torch.device(DEV):
+            m = KimiAudioPackedForCausalLM(cfg)
+        m.post_init()
+    finally:
+        torch.set_default_dtype(torch.float32)
+    m = m.eval()
+    lm = _TextDecoder(m)
+    E = m.model.embed_tokens.weight.detach()
+    logits = (torch.randn(B, V, device=DEV, generator=g) * 3).to(torch.bfloat16)
+    hist = torch.randint(0, V, (B, 512), device=DEV, generator=g, dtype=torch.int32)
+    z = lambda: torch.zeros(B, dtype=torch.int32, device=DEV)
+    fin, nu, keys = z(), torch.ones(1, dtype=torch.int32, device=DEV), torch.arange(B, device=DEV)
+    pl = torch.full((B,), 200, dtype=torch.int32, device=DEV)            # 100 generated: the penalty window is in force
+    x = torch.empty(B, H, dtype=torch.bfloat16, device=DEV)
+    rows = []
+    with torch.no_grad():
+        for name, T, k in (("greedy", 0.0, 5), ("top_k 5", 0.8, 5), ("top_k 64", 0.8, 64)):
+            hl, cl = torch.full((B,), 300, dtype=torch.int32, device=DEV), z()
+
+            def call():
+                hl.fill_(300)
+                F.kimi_text_step(logits, hist, hl, cl, fin, nu, pl, E, x, 1.1, W, T, k, 1, eos, blank, row_key=keys)
+            call()
+            rows.append(dict(kernel="tn_kimi_text_step", mode=name, B=B, V=V, H=H, us=round(_events_time(call, iters), 2)))
+        hl, cl = torch.full((B,), 300, dtype=torch.int32, device=DEV), z()
+
+        def call_sample():
+            hl.fill_(300)
+            F.sample_step(logits, hist, hl, cl, fin, nu, 1.1, False, 1.0, 0, 1.0, 1, [], blank, row_key=keys)
+        call_sample()
+        rows.append(dict(kernel="tn_sample_step", mode="greedy", B=B, V=V, us=round(_events_time(call_sample, iters), 2)))
+        rows.append(dict(kernel="fill_ of hist_len alone (inside every figure above)", B=B,
+                         us=round(_events_time(lambda: hl.fill_(300), iters), 2)))
+        prompts = G.Prompts([torch.randint(0, 150000, (P,)) for _ in range(B)])
+        pre = []
+        for _ in range(3):
+            cache = G.KVCache.allocate(28, B, P + 6 * steps + 8, 4, 128, DEV)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            first = G._prefill(lm, None, prompts, cache, DEV, lambda ids, lens, Tp: E[ids] + E[blank][None])
+            torch.cuda.synchronize()
+            pre.append(time.perf_counter() - t0)
+        pl = torch.full((B,), P, dtype=torch.int32, device=DEV)
+        kstep = lambda lg: F.kimi_text_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished,
+                                            cache.n_unfinished, pl, E, x, 1.1, W, 0.0, 5, 1, eos, blank, row_key=keys)
+        kstep(first)
+
+        def fused():
+            kstep(G.decode_logits(lm, cache, inputs_embeds=x))
+
+        def by_torch():
+            tok = cache.hist.gather(1, (cache.hist_len.to(torch.int64) - 1)[:, None])[:, 0].to(torch.int64)
+            kstep(G.decode_logits(lm, cache, inputs_embeds=E[tok] + E[blank][None]))
+        fused()
+        by_torch()
+        ab = [(_events_time(fused, steps - 2) / 1e3, _events_time(by_torch, steps - 2) / 1e3) for _ in range(3)]   # A B A B A B
+        ms_fused, ms_torch = min(a for a, _ in ab), min(b for _, b in ab)
+    greedy = next(r["us"] for r in rows if r.get("kernel") == "tn_kimi_text_step" and r["mode"] == "greedy")
+    k5 = next(r["us"] for r in rows if r.get("mode") == "top_k 5")
+    rows.append(dict(e2e="kimi_audio_7b_decode", B=B, prompt_rows=P, prefill_ms=round(min(pre) * 1e3, 2),
+                     ms_per_step_x_next=round(ms_fused, 3), ms_per_step_gather_add_by_torch=round(ms_torch, 3),
+                     ab_runs_ms=[[round(a, 3), round(b, 3)] for a, b in ab],
+                     step_share_greedy=round(greedy / (ms_fused * 1e3), 4), step_share_top_k5=round(k5 / (ms_fused * 1e3), 4)))
+    return rows
+
+
 def bench_beams(K, B, steps=24, iters=100):
     import touchnet_amd.functional as F
     from touchnet_amd import generation as G
@@ -290,6 +376,7 @@ def main():
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--qwen2-audio-7b", action="store_true")
     ap.add_argument("--num-beams", type=int, default=0, help="K > 1: the beam-search measurements")
+    ap.add_argument("--kimi-audio-7b", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
@@ -298,6 +385,10 @@ def main():
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
     if a.num_beams > 1:
         for r in bench_beams(a.num_beams, a.batch):
+            print(json.dumps(r), flush=True)
+        return
+    if a.kimi_audio_7b:
+        for r in bench_kimi_audio_7b(a.batch):
             print(json.dumps(r), flush=True)
         return
     if a.qwen2_audio_7b:

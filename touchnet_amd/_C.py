@@ -93,6 +93,7 @@ PROTOTYPES = {
     "tn_greedy_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp],
     "tn_sample_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _i, _f, _ull, _vp, _i, _i, _i,
                        _vp],
+    "tn_kimi_text_step": [_vp] * 11 + [_i, _i, _i, _i, _f, _i, _f, _i, _ull, _i, _i, _i, _i, _vp],
     "tn_attn_decode_beam": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "tn_beam_step_workspace_bytes": [_i, _i],
     "tn_beam_step": [_vp] * 17 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _f, _i, _i, _vp],

@@ -1546,6 +1546,19 @@ def sample_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penal
                    bool(do_sample), float(temperature), int(top_k), float(top_p), int(seed), eos, int(pad))
 
 
+def kimi_text_step(logits, hist, hist_len, cache_len, finished, n_unfinished, prompt_len, embed, x_next,
+                   penalty: float = 1.1, window: int = 16, temperature: float = 0.0, top_k: int = 5, seed: int = 0,
+                   eos: int = -1, blank: int = 0, audio_token: Optional[int] = None, row_key=None, uniforms=None) -> None:
+    """One text-stream step of Kimi-Audio's `_generate_loop` on logits [B, V]: repetition penalty over the last `window`
+    generated ids (only once more than `window` were generated, rounded in the logits' dtype), argmax — or, with
+    temperature > 1e-6, a draw among the `top_k` largest — appended to the device history; a finished row emits `blank`;
+    rows that emitted `eos` are marked finished.  x_next bf16 [B, H] receives embed[token] + embed[audio_token], the next
+    step's input (`audio_token` defaults to `blank`: the audio stream of a text-only generation)."""
+    L.kimi_text_step_(logits, hist, hist_len, cache_len, finished, n_unfinished, prompt_len, embed, x_next, row_key,
+                      uniforms, float(penalty), int(window), float(temperature), int(top_k), int(seed), int(eos), int(blank),
+                      int(blank if audio_token is None else audio_token))
+
+
 # ------------------------------------------------------------------------------------ beam search (generation.py)
 def attn_decode_beam(q, k_new, v_new, k_cache, v_cache, cache_len, src, scale: Optional[float] = None):
     """`attn_decode` for R = B * K beam rows whose caches are shared through an ancestry table: key / value s of row r is

@@ -142,6 +142,56 @@ class GenerationConfig:
         return int(self.max_length) - int(longest_prompt)
 
 
+KIMI_MAX_WINDOW, KIMI_MAX_TOP_K = 64, 64     # tn_kimi_text_step's limits
+
+
+@dataclass
+class KimiGenerationConfig:
+    """The arguments of MoonshotKimiaForCausalLM.generate() (touchnet/models/kimi_audio/modeling_kimi_audio.py:1084-1101)
+    with its defaults, and the ids KimiASampler hard-codes.  The text stream is all that generate() returns: it never asks
+    `_generate_loop` for audio output, so the audio-stream token of every step is the blank.  The four audio_* knobs and
+    kimia_text_audiodelaytokens are therefore accepted and ignored here (models/kimi_audio/inference_kimi_audio.py)."""
+    text_temperature: float = 0.0            # <= 1e-6: argmax
+    text_top_k: int = 5                      # candidates of a draw (inert at temperature <= 1e-6)
+    text_repetition_penalty: float = 1.1     # > 1: on, over the last `window` generated tokens once more than that exist
+    text_repetition_window_size: int = 16
+    audio_temperature: float = 0.8           # ignored (see above)
+    audio_top_k: int = 10                    # ignored
+    audio_repetition_penalty: float = 1.0    # ignored
+    audio_repetition_window_size: int = 64   # ignored
+    kimia_text_audiodelaytokens: int = 6     # ignored
+    max_new_tokens: int = 2048               # the inference script's value; -1: 7500 - the longest prompt (generate()'s rule)
+    kimia_text_blank: int = 151666           # <|im_kimia_text_blank|>
+    kimia_text_eos: int = 151667             # <|im_kimia_text_eos|>
+    cache_chunk: int = 1024                  # new-token rows of the first KV-cache allocation (it doubles on demand)
+    check_every: int = 16                    # steps between two host reads of the unfinished count
+    seed: int = 0                            # Philox key of the draws (with the row key and the step)
+
+    def __post_init__(self):
+        self.check()
+
+    def check(self) -> None:
+        """Refuses what tn_kimi_text_step refuses."""
+        if not self.text_repetition_penalty > 0.0:
+            raise ValueError(f"Kimi generation config: text_repetition_penalty {self.text_repetition_penalty} must be > 0")
+        if not 1 <= int(self.text_repetition_window_size) <= KIMI_MAX_WINDOW:
+            raise ValueError(f"Kimi generation config: text_repetition_window_size {self.text_repetition_window_size} "
+                             f"must be in [1, {KIMI_MAX_WINDOW}]")
+        if not 0 <= int(self.text_top_k) <= KIMI_MAX_TOP_K:
+            raise ValueError(f"Kimi generation config: text_top_k {self.text_top_k} must be in [0, {KIMI_MAX_TOP_K}]")
+        if self.text_temperature > 1e-6 and int(self.text_top_k) == 0:
+            raise ValueError("Kimi generation config: text_temperature > 1e-6 with text_top_k = 0 (a draw over the whole "
+                             "vocabulary) is not supported by this decoder")
+        if not 0 <= int(self.seed) < 2 ** 64:
+            raise ValueError("Kimi generation config: seed must fit in 64 unsigned bits")
+        if int(self.max_new_tokens) < -1:
+            raise ValueError(f"Kimi generation config: max_new_tokens {self.max_new_tokens} must be >= -1")
+
+    def new_tokens(self, longest_prompt: int) -> int:
+        n = int(self.max_new_tokens)
+        return 7500 - int(longest_prompt) if n == -1 else n
+
+
 @dataclass
 class Prompts:
     """One prompt per utterance: token ids int64 [n_b] and, for TouchAudio, feature rows [n_b, F] (projected and added to
@@ -392,12 +442,18 @@ def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len, table=Non
     return layer.mlp(x), residual
 
 
-def decode_logits(lm, cache, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
+                  inputs_embeds: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step of every row: the newest token of the history at position cache_len -> logits [B, V]
     (its key / value are appended to the caches; cache_len itself is advanced by the greedy step).  `table` int32
-    [B, S_max]: the rows are beams that read their cached keys / values through it (BeamState.src)."""
-    tok = cache.hist.gather(1, (cache.hist_len.to(torch.int64) - 1)[:, None])[:, 0]
-    x = lm.model.embed_tokens(tok.to(torch.int64))                                          # [B, H]
+    [B, S_max]: the rows are beams that read their cached keys / values through it (BeamState.src).  `inputs_embeds`
+    [B, H]: the step's input rows where they are not embed(newest token) (Kimi-Audio: the sum of two embeddings, written
+    by tn_kimi_text_step); by default they are gathered from the history."""
+    if inputs_embeds is None:
+        tok = cache.hist.gather(1, (cache.hist_len.to(torch.int64) - 1)[:, None])[:, 0]
+        x = lm.model.embed_tokens(tok.to(torch.int64))                                      # [B, H]
+    else:
+        x = inputs_embeds
     cos, sin = lm.model.rotary_emb(cache.cache_len.to(torch.int64), x.dtype)
     delta, residual = x, None
     for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):

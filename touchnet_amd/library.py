@@ -983,6 +983,47 @@ def _(logits, hist, hist_len, cache_len, finished, n_unfinished, row_key, unifor
     return None
 
 
+KIMI_MAX_WINDOW, KIMI_MAX_TOP_K = 64, 64
+
+
+@custom_op(f"{NS}::kimi_text_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished", "x_next"),
+           device_types="cuda")
+def kimi_text_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor,
+                    n_unfinished: Tensor, prompt_len: Tensor, embed: Tensor, x_next: Tensor, row_key: Optional[Tensor],
+                    uniforms: Optional[Tensor], penalty: float, window: int, temperature: float, top_k: int, seed: int,
+                    eos: int, blank: int, audio_token: int) -> None:
+    """One text-stream step of Kimi-Audio's decoding loop (tn_kimi_text_step): logits [B, V] fp32 / bf16; hist int32
+    [B, S_hist], hist_len / cache_len / finished / prompt_len int32 [B], n_unfinished int32 [1]; embed bf16 [V, H]; x_next
+    bf16 [B, H] receives embed[token] + embed[audio_token].  row_key int64 [B] / uniforms fp32 [B] as for sample_step_."""
+    _no_grad_inputs("kimi_text_step_", logits, embed)
+    B, V = logits.shape
+    for t, shape in ((hist_len, (B,)), (cache_len, (B,)), (finished, (B,)), (prompt_len, (B,)), (n_unfinished, (1,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _C.KernelError("kimi_text_step_: int32 hist_len / cache_len / finished / prompt_len [B], n_unfinished [1]")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != B or not hist.is_contiguous():
+        raise _C.KernelError("kimi_text_step_: int32 contiguous hist [B, S_hist]")
+    if (embed.dtype != torch.bfloat16 or embed.dim() != 2 or embed.shape[0] != V or not embed.is_contiguous()
+            or x_next.dtype != torch.bfloat16 or tuple(x_next.shape) != (B, embed.shape[1]) or not x_next.is_contiguous()):
+        raise _C.KernelError("kimi_text_step_: contiguous bf16 embed [V, H] and x_next [B, H]")
+    for name, t, dt in (("row_key", row_key, torch.int64), ("uniforms", uniforms, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (B,) or not t.is_contiguous()):
+            raise _C.KernelError(f"kimi_text_step_: {name} must be a contiguous {dt} [B] tensor")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise _C.KernelError("kimi_text_step_: seed must fit in 64 unsigned bits")
+    logits = _c(logits)
+    _C.check(_lib().tn_kimi_text_step(_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(finished), _p(n_unfinished),
+                                      _p(prompt_len), _p(embed), _p(x_next), _p(row_key), _p(uniforms), B, V,
+                                      hist.shape[1], embed.shape[1], float(penalty), int(window), float(temperature),
+                                      int(top_k), int(seed), int(eos), int(blank), int(audio_token), _C.dcode(logits),
+                                      _cur()), "tn_kimi_text_step")
+
+
+@kimi_text_step_.register_fake
+def _(logits, hist, hist_len, cache_len, finished, n_unfinished, prompt_len, embed, x_next, row_key, uniforms, penalty,
+      window, temperature, top_k, seed, eos, blank, audio_token):
+    return None
+
+
 # ===================================================================================================== beam search
 @custom_op(f"{NS}::attn_decode_beam_", mutates_args=("k_cache", "v_cache"), device_types="cuda")
 def attn_decode_beam_(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, cache_len: Tensor,
@@ -1119,4 +1160,4 @@ OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_f
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
-       "beam_step_")
+       "beam_step_", "kimi_text_step_")

@@ -109,7 +109,12 @@ class KimiDecoderModel(nn.Module):
         if config.use_whisper_feature:                                   # `:392-394`
             self.vq_adaptor = VQAdaptor(config)
 
-    def forward(self, inputs_embeds, position_ids=None, attention_mask=None, with_mimo: bool = False):
+    def forward(self, inputs_embeds, position_ids=None, attention_mask=None, with_mimo: bool = False, keep_rows=None,
+                kv_out=None):
+        """`keep_rows` (int64 [R], flat indices into B*T) / `kv_out` (a list): the inference prefill's arguments of
+        DecoderModel.forward, handed to the same DecoderLayer in the same way — behind the last layer's attention core only
+        the kept rows are computed (h is [1, R, H]), and every layer appends its rotated keys and its values.  Decoding
+        discards the mimo branch (the reference computes `mimo_output` and drops it), so neither goes with `with_mimo`."""
         B, T, _ = inputs_embeds.shape
         if position_ids is None:
             position_ids = torch.arange(T, device=inputs_embeds.device).expand(B, T)
@@ -120,10 +125,20 @@ class KimiDecoderModel(nn.Module):
         elif isinstance(mask, torch.Tensor):
             mask = ops().build_packed_mask(mask)
         sp = getattr(self, "_tn_sp", None)                  # sequence parallelism (models/tensor_parallel.py)
+        if keep_rows is not None or kv_out is not None:
+            if with_mimo:
+                raise RuntimeError("keep_rows / kv_out are not available with the mimo branch (with_mimo)")
+            if sp is not None:
+                raise RuntimeError("keep_rows / kv_out are not available under sequence parallelism")
+        kw = {} if kv_out is None else {"kv_out": kv_out}
         delta, residual = (inputs_embeds if sp is None else sp.scatter(inputs_embeds)), None
         tap = None
+        last = len(self.layers) - 1
         for idx, layer in enumerate(self.layers):
-            delta, residual = layer(delta, residual, cos, sin, mask)
+            if keep_rows is not None and idx == last:
+                delta, residual = layer(delta, residual, cos, sin, mask, keep_rows, **kw)
+            else:
+                delta, residual = layer(delta, residual, cos, sin, mask, **kw)
             if with_mimo and idx == self.config.kimia_mimo_transformer_from_layer_index:
                 tap = residual + delta               # the hidden state after this layer (`:506-507`)
         h, _ = self.norm(delta, residual)
