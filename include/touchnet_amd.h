@@ -118,7 +118,16 @@ int tn_attn_bwd_bidir(const void* q, const void* k, const void* v, const void* o
  * [B, Nh, rows_per_batch]: segment i = local rows [row0_i, row0_i+rows_i) holding GLOBAL positions
  * [off_i, off_i+rows_i) (head/tail load balancing = 2 segments per rank); `segs` = host int[6]
  * {row0_a, rows_a, off_a, row0_b, rows_b, off_b}.  k/v/doc/meta are global ([B, T, ...], all-gathered by the
- * caller); dk/dv come back as this rank's partial sums over [B, T, Nkv, D] for the caller to reduce-scatter. */
+ * caller); dk/dv come back as this rank's partial sums over [B, T, Nkv, D] for the caller to reduce-scatter.
+ * The segment contract, checked on the host by all three *_seg* entry points (TN_EINVAL, nothing is launched):
+ *   - nseg is 1 or 2, host_segs is not null, rows_per_batch > 0; every segment has rows > 0, row0 >= 0, off >= 0,
+ *     off + rows <= T and row0 + rows <= rows_per_batch;
+ *   - row0 and off are multiples of 128, and so is rows of every segment but the last, which may have any length (a
+ *     contiguous split's last shard, a ragged T);
+ *   - two segments overlap neither in their local rows nor in their global positions.  They need not be equal, adjacent
+ *     or in ascending order, and one segment {0, T, 0} with rows_per_batch = T is the plain tn_attn_fwd / tn_attn_bwd.
+ * Local rows that no segment covers are neither read nor written (o, lse2, delta and dq keep what they held).  dk / dv
+ * are written for all T rows: rows that no local query may see come back as zeros. */
 int tn_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                     const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, int nseg,
                     const int* host_segs, int rows_per_batch, void* stream);

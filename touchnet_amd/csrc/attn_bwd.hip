@@ -99,7 +99,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   const bool bidir = qv.bidir != 0;
   // ---- round trip A: the stored list of query tiles, the id statistics of this wave's rows, this lane's id, and the
   // wave's K / V rows — issued together
-  const bool plain = R6 && qv.nseg == 1 && qv.off[0] == 0 && qv.row0[0] == 0 && !bidir;   // (the stored lists are causal)
+  // (the stored lists are causal and name every query tile of the row: only a launch whose one segment IS the whole row
+  // may follow them — a shorter shard at offset 0 would be walked past its local [B, rpb] buffers)
+  const bool plain = R6 && qv.nseg == 1 && qv.off[0] == 0 && qv.row0[0] == 0 && qv.rows[0] == T && qv.rpb == T && !bidir;
   i32x4_t ql_head = {kListPre + 1, 0, 0, 0}, ql_mine = {0, 0, 0, 0};
   if (plain) {
     const i32x4_t* ql = reinterpret_cast<const i32x4_t*>(meta.qlist) + ((size_t)b * meta.nq128 + kt) * (1 + kListPre);
@@ -511,8 +513,6 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
                            void* stream, const void* rope_cos = nullptr, const void* rope_sin = nullptr) {
   if (B <= 0 || T <= 0 || Nh <= 0 || Nkv <= 0 || Nh % Nkv) return TN_EINVAL;
   if (D != 64 && D != 128) return TN_EINVAL;
-  for (int s = 0; s < qv.nseg; ++s)
-    if (qv.off[s] % 128 || qv.row0[s] % 128 || (s + 1 < qv.nseg && qv.rows[s] % 128)) return TN_EINVAL;
   const AttnMeta m = make_attn_meta(meta, B, T);
   hipStream_t st = (hipStream_t)stream;
   const float sl2 = scale * 1.4426950408889634f;
@@ -584,9 +584,8 @@ int tn_attn_bwd_seg(const void* q, const void* k, const void* v, const void* o, 
                     const float* lse2, float* delta, void* dq, void* dk, void* dv, const int* doc, const int* meta,
                     int B, int T, int Nh, int Nkv, int D, float scale, int nseg, const int* segs, int rows_per_batch,
                     void* stream) {
-  if (nseg < 1 || nseg > 2) return TN_EINVAL;
-  const QView qv = {nseg, {segs[0], nseg > 1 ? segs[3] : 0}, {segs[1], nseg > 1 ? segs[4] : 0},
-                    {segs[2], nseg > 1 ? segs[5] : 0}, rows_per_batch, 0, ~0ull};
+  QView qv;
+  if (seg_view(nseg, segs, rows_per_batch, T, &qv) != TN_OK) return TN_EINVAL;
   return attn_bwd_launch(q, k, v, o, dout, lse2, delta, dq, dk, dv, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }
 

@@ -194,7 +194,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
 
   // ---- round trip A: the stored list of query tiles, the id statistics of the four waves' rows, this lane's id, and the
   // wave's K / V rows — issued together
-  const bool plain = qv.nseg == 1 && qv.off[0] == 0 && qv.row0[0] == 0;     // (this pass is causal)
+  // (this pass is causal.  The stored list names every query tile of the row: only a launch whose one segment IS the whole
+  // row may follow it — a shorter shard at offset 0 would be walked past its local [B, rpb] buffers)
+  const bool plain = qv.nseg == 1 && qv.off[0] == 0 && qv.row0[0] == 0 && qv.rows[0] == T && qv.rpb == T;
   i32x4_t ql_head = {kListPre + 1, 0, 0, 0}, ql_mine = {0, 0, 0, 0};
   if (plain) {
     const i32x4_t* ql = reinterpret_cast<const i32x4_t*>(meta.qlist) + ((size_t)b * meta.nq128 + kt) * (1 + kListPre);

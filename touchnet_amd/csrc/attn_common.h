@@ -97,7 +97,8 @@ __host__ inline AttnMeta make_attn_meta(const int* meta, int B, int T) {
 // positions [off, off + rows) of the packed row (K / V / doc ids / metadata are always global, [B, T, ...]).
 // Plain attention: one segment {0, T, 0}, rpb = T.  Context parallel with head/tail load balancing
 // (touchnet/utils/distributed.py:292-315 -> torch's round-robin CP sharding): two segments per rank.
-// Segment offsets and all but the last segment's length must be multiples of 128.
+// Segment offsets and all but the last segment's length must be multiples of 128; seg_view() below holds the whole
+// contract of what the kernels can serve.
 struct QView {
   int nseg;
   int row0[2], rows[2], off[2];
@@ -124,6 +125,34 @@ struct QView {
     left = rows[s] - lt * bm;
   }
 };
+
+// The QView of a tn_attn_*_seg* call, or TN_EINVAL for a description the kernels cannot serve (the contract stated in
+// include/touchnet_amd.h) — checked on the host, before any launch: the kernels index the local buffers with
+// row0 + (rows of the segment) and K / V / the ids with off + (rows of the segment) and trust both.  `segs` = host
+// int[3 * nseg] {row0, rows, off} per segment.  The segments may come in any order of their global positions.
+__host__ inline int seg_view(int nseg, const int* segs, int rows_per_batch, int T, QView* out) {
+  if (nseg < 1 || nseg > 2 || segs == nullptr || rows_per_batch <= 0 || T <= 0) return TN_EINVAL;
+  QView qv = {nseg, {0, 0}, {0, 0}, {0, 0}, rows_per_batch, 0, ~0ull, 0};
+  for (int s = 0; s < nseg; ++s) {
+    const int row0 = segs[3 * s], rows = segs[3 * s + 1], off = segs[3 * s + 2];
+    if (rows <= 0 || off < 0 || row0 < 0) return TN_EINVAL;
+    if ((long long)off + rows > T || (long long)row0 + rows > rows_per_batch) return TN_EINVAL;
+    // a 128-row tile of the kernels never straddles two segments, and its global position is a multiple of 128 (the
+    // stored tile lists and the per-32-row statistics are indexed by it)
+    if (off % 128 || row0 % 128 || (s + 1 < nseg && rows % 128)) return TN_EINVAL;
+    qv.row0[s] = row0;
+    qv.rows[s] = rows;
+    qv.off[s] = off;
+  }
+  if (nseg == 2) {
+    // disjoint local rows (two tiles would write the same O / dQ rows) and disjoint global positions (a query would be
+    // counted twice in dK / dV)
+    if (qv.row0[0] < qv.row0[1] + qv.rows[1] && qv.row0[1] < qv.row0[0] + qv.rows[0]) return TN_EINVAL;
+    if (qv.off[0] < qv.off[1] + qv.rows[1] && qv.off[1] < qv.off[0] + qv.rows[0]) return TN_EINVAL;
+  }
+  *out = qv;
+  return TN_OK;
+}
 
 // Workgroup -> (head, tile) mapping shared by the attention kernels.  Launch grids are (heads, tiles, batch):
 //  * blockIdx.x = head slot.  Workgroups go to XCDs round-robin by linear id (MI355X_MICROARCH.md "Workgroup

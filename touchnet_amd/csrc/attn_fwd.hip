@@ -226,8 +226,6 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
                            const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, QView qv,
                            void* stream) {
   if (B <= 0 || T <= 0 || Nh <= 0 || Nkv <= 0 || Nh % Nkv || (D != 64 && D != 128)) return TN_EINVAL;
-  for (int s = 0; s < qv.nseg; ++s)
-    if (qv.off[s] % 128 || qv.row0[s] % 128 || (s + 1 < qv.nseg && qv.rows[s] % 128)) return TN_EINVAL;
   const int nt = (T + kTile - 1) / kTile;
   const AttnMeta m = make_attn_meta(meta, B, T);
   const float sl2 = scale * 1.4426950408889634f;
@@ -251,13 +249,13 @@ int tn_attn_fwd_bidir(const void* q, const void* k, const void* v, void* o, floa
 }
 
 // Sequence-sharded query side (context parallel): q / o are [B, rows_per_batch, Nh, D], lse2 [B, Nh, rows_per_batch];
-// segs = host int[6] {row0_a, rows_a, off_a, row0_b, rows_b, off_b}; k / v / doc / meta stay global ([B, T, ...]).
+// segs = host int[3 * nseg] {row0_a, rows_a, off_a, row0_b, rows_b, off_b}; k / v / doc / meta stay global ([B, T, ...]).
+// What a segment list may hold: attn_common.h seg_view (refused with TN_EINVAL before any launch otherwise).
 int tn_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                     const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, int nseg, const int* segs,
                     int rows_per_batch, void* stream) {
-  if (nseg < 1 || nseg > 2) return TN_EINVAL;
-  const QView qv = {nseg, {segs[0], nseg > 1 ? segs[3] : 0}, {segs[1], nseg > 1 ? segs[4] : 0},
-                    {segs[2], nseg > 1 ? segs[5] : 0}, rows_per_batch, 0, ~0ull};
+  QView qv;
+  if (seg_view(nseg, segs, rows_per_batch, T, &qv) != TN_OK) return TN_EINVAL;
   return attn_fwd_launch(q, k, v, o, lse2, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }
 
@@ -267,9 +265,11 @@ int tn_attn_fwd_seg(const void* q, const void* k, const void* v, void* o, float*
 int tn_attn_fwd_seg_chunks(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                            const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, int nseg, const int* segs,
                            int rows_per_batch, int chunk_len, unsigned long long chunk_mask, void* stream) {
-  if (nseg < 1 || nseg > 2 || chunk_len <= 0 || chunk_len % kTile || (T + chunk_len - 1) / chunk_len > 64) return TN_EINVAL;
-  const QView qv = {nseg, {segs[0], nseg > 1 ? segs[3] : 0}, {segs[1], nseg > 1 ? segs[4] : 0},
-                    {segs[2], nseg > 1 ? segs[5] : 0}, rows_per_batch, chunk_len / kTile, chunk_mask};
+  QView qv;
+  if (seg_view(nseg, segs, rows_per_batch, T, &qv) != TN_OK) return TN_EINVAL;
+  if (chunk_len <= 0 || chunk_len % kTile || (T + chunk_len - 1) / chunk_len > 64) return TN_EINVAL;
+  qv.kv_tpc = chunk_len / kTile;
+  qv.kv_mask = chunk_mask;
   return attn_fwd_launch(q, k, v, o, lse2, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }
 
