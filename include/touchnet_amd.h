@@ -30,7 +30,9 @@ const char* tn_version(void);   /* "touchnet_amd <ver> gfx950" */
  *      transformers/models/llama/modeling_llama.py:62-67 and the residual adds at :306-324,
  *      swapped in the way liger does at touchnet/models/llama/__init__.py:11-15.
  * fwd:  h = x (+ res_in);  res_out = h (if res_in);  y = w * T(h * rsqrt(mean(h^2) + eps));  rstd[rows] fp32
- * bwd:  dh = rmsnorm'(dy) (+ dres);  dw[H]     workspace: tn_norm_bwd_workspace_floats(rows, H) floats */
+ * bwd:  dh = rmsnorm'(dy) (+ dres);  dw[H]     workspace: tn_norm_bwd_workspace_floats(rows, H) floats
+ * -22 (before any launch) unless rows > 0, H > 0, H a multiple of the 16-byte vector (8 bf16 / 4 fp32), H <= 8192 (bf16) /
+ * 4096 (fp32), dtype 0 (fp32) or 1 (bf16); the same contract holds for the LayerNorm entries. */
 int tn_norm_bwd_workspace_floats(int rows, int H);
 int tn_rmsnorm_fwd(const void* x, const void* res_in, const void* w, void* y, void* res_out, float* rstd,
                    int rows, int H, float eps, int dtype, void* stream);
@@ -45,12 +47,14 @@ int tn_layernorm_bwd(const void* dy, const void* h, const void* w, const float* 
                      const void* dres, void* dh, void* dw, void* db, float* workspace, int rows, int H, int dtype,
                      void* stream);
 
-/* ---- SwiGLU / GELU — transformers/models/llama/modeling_llama.py:174-176; encoder fc1 activation */
+/* ---- SwiGLU / GELU — transformers/models/llama/modeling_llama.py:174-176; encoder fc1 activation
+ *      -22 (before any launch) unless n >= 0, n a multiple of the 16-byte vector (8 bf16 / 4 fp32), dtype 0 or 1. */
 int tn_swiglu_fwd(const void* gate, const void* up, void* out, long long n, int dtype, void* stream);
 int tn_swiglu_bwd(const void* dout, const void* gate, const void* up, void* dgate, void* dup, long long n,
                   int dtype, void* stream);
 /* bf16 variants that ALSO write the transposed tensors the MLP's weight-gradient GEMMs consume (rows, cols multiples
- * of 8): out_t [cols, rows] = out^T;  dgu_t [2*cols, rows] = [dgate^T ; dup^T].  Same arithmetic as the two above. */
+ * of 8): out_t [cols, rows] = out^T;  dgu_t [2*cols, rows] = [dgate^T ; dup^T].  Same arithmetic as the two above.
+ * -22 (before any launch) unless rows > 0, cols > 0 and both are multiples of 8. */
 int tn_swiglu_fwd_t(const void* gate, const void* up, void* out, void* out_t, int rows, int cols, void* stream);
 int tn_swiglu_bwd_t(const void* dout, const void* gate, const void* up, void* dgate, void* dup, void* dgu_t, int rows,
                     int cols, void* stream);
@@ -61,7 +65,8 @@ int tn_gelu_bwd(const void* dout, const void* x, void* dx, long long n, int dtyp
  *      position_ids restarting per sentence (touchnet/models/llama/processing_llama.py:96-97).
  * table: cos/sin [n, half] in `dtype` = cos/sin(position_ids[n] * inv_freq[half]) * attention_scaling
  * apply: q [n, hq, D] -> q_out, k [n, hk, D] -> k_out (may alias; half-split rotate_half convention);
- *        backward = 1 applies the transpose rotation to gradients */
+ *        backward = 1 applies the transpose rotation to gradients
+ * -22 (before any launch) unless n > 0, half > 0 (table); n > 0, hq > 0, hk >= 0, D > 0 and even (apply); dtype 0 or 1. */
 int tn_rope_table(const long long* position_ids, const float* inv_freq, void* cos_t, void* sin_t, int n, int half,
                   float attention_scaling, int dtype, void* stream);
 int tn_rope_apply(const void* q, const void* k, void* q_out, void* k_out, const void* cos_t, const void* sin_t,
@@ -181,11 +186,13 @@ int tn_resample_polyphase(const float* x, float* y, const float* tab, long long 
  * step 1: tn_sumsq accumulates sum(g^2) of one (flat) tensor into norm_sq[0] (fp32, zeroed by the caller);
  *         deterministic two-stage reduction through `scratch` (tn_sumsq_scratch_floats() floats)
  * step 2: tn_adamw_step updates p/m/v (fp32) from g, scaling g by min(1, max_norm/(sqrt(norm_sq)+1e-6));
- *         if norm_sq is NaN/Inf nothing is written (the reference skips the step, train.py:467-473) */
+ *         if norm_sq is NaN/Inf nothing is written (the reference skips the step, train.py:467-473)
+ * -22 (before any launch) unless n > 0 and the (gradient) dtype is 0 (fp32) or 1 (bf16); tn_sumsq ADDS to norm_sq[0]. */
 int tn_sumsq_scratch_floats(void);
 int tn_sumsq(const void* g, float* scratch, float* norm_sq, long long n, int dtype, void* stream);
 /* multi-tensor step 1 (one launch for all gradient tensors of one dtype): device tables ptrs[t], sizes[t]
- * (elements), first_chunk[t] = sum_{u<t} ceil(sizes[u] / tn_sumsq_multi_chunk()); partial: nchunks floats */
+ * (elements), first_chunk[t] = sum_{u<t} ceil(sizes[u] / tn_sumsq_multi_chunk()); partial: nchunks floats.
+ * ADDS to norm_sq[0].  -22 (before any launch) unless ntensors > 0, 0 < nchunks < 2^31, dtype 0 or 1. */
 long long tn_sumsq_multi_chunk(void);
 int tn_sumsq_multi(const void* const* ptrs, const long long* sizes, const long long* first_chunk, int ntensors,
                    long long nchunks, float* partial, float* norm_sq, int dtype, void* stream);
@@ -197,7 +204,9 @@ int tn_adamw_step(float* p, float* m, float* v, const void* g, void* p_shadow_bf
  * per tensor would dominate).  tn_adamw_prepare turns norm_sq into the device-side step state (8 floats owned by the
  * caller, zeroed once): step count — advanced only when the norm is finite, like torch's AdamW on a skipped step —
  * bias corrections, clip coefficient, skip flag; no host round trip.  Tables as in tn_sumsq_multi with
- * first_chunk over tn_adamw_multi_chunk(); shadows[t] may be NULL. */
+ * first_chunk over tn_adamw_multi_chunk(); shadows[t] may be NULL.
+ * -22 (before any launch) unless state != NULL (all three entries), ntensors > 0, 0 < nchunks < 2^31, g_dtype 0 or 1,
+ * max_workgroups >= 0.  norm_sq may be NULL in tn_adamw_prepare: no clip, no skip, the step advances. */
 long long tn_adamw_multi_chunk(void);
 int tn_adamw_prepare(const float* norm_sq, float* state, float beta1, float beta2, float max_norm, void* stream);
 int tn_adamw_multi(void* const* ps, void* const* ms, void* const* vs, const void* const* gs, void* const* shadows,
@@ -224,7 +233,8 @@ int tn_transpose_bf16(const void* src, void* dst, int rows, int cols, long long 
 /* ---- bias gradient of a linear layer: out[c] = sum_r x[r*ld + c], x bf16 [rows, cols] (cols, ld multiples of 8),
  *      out bf16 [cols]; fp32 accumulation, deterministic two-stage reduction through ws
  *      (tn_colsum_workspace_floats(rows, cols) floats).  Replaces the `grad_output.sum(0)` of
- *      torch.nn.functional.linear's backward for the biased projections (Qwen2 q/k/v, the audio tower). */
+ *      torch.nn.functional.linear's backward for the biased projections (Qwen2 q/k/v, the audio tower).
+ *      -22 (before any launch) unless rows > 0, cols > 0, cols % 8 == 0, ld % 8 == 0, ld >= cols, x 16-byte aligned. */
 long long tn_colsum_workspace_floats(int rows, int cols);
 int tn_colsum_bf16(const void* x, void* out, float* ws, int rows, int cols, long long ld, void* stream);
 

@@ -707,7 +707,7 @@ template <typename T>
 static int rmsnorm_fwd_t(const void* x, const void* res_in, const void* w, void* y, void* res_out, float* rstd,
                          int rows, int H, float eps, hipStream_t st) {
   constexpr int N = Vec16<T>::N;
-  if (H % N || rows <= 0) return TN_EINVAL;
+  if (rows <= 0 || H <= 0 || H % N) return TN_EINVAL;
   const int mv = pick_maxv(H, N);
   dim3 grid((rows + kRowWaves - 1) / kRowWaves), block(256);
   TN_DISPATCH_MAXV(mv, hipLaunchKernelGGL((rmsnorm_fwd_kernel<T, MAXV>), grid, block, 0, st, (const T*)x,
@@ -727,7 +727,7 @@ template <typename T>
 static int rmsnorm_bwd_t(const void* dy, const void* h, const void* w, const float* rstd, const void* dres, void* dh,
                          void* dw, float* ws, int rows, int H, hipStream_t st) {
   constexpr int N = Vec16<T>::N;
-  if (H % N || rows <= 0) return TN_EINVAL;
+  if (rows <= 0 || H <= 0 || H % N) return TN_EINVAL;
   const int mv = pick_maxv_block(H, N);
   const int nb = norm_bwd_blocks(rows);
   TN_DISPATCH_MAXV(mv, hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, MAXV>), dim3(nb), dim3(256), 0, st, (const T*)dy,
@@ -742,7 +742,7 @@ template <typename T>
 static int layernorm_fwd_t(const void* x, const void* res_in, const void* w, const void* b, void* y, void* res_out,
                            float* mean, float* rstd, int rows, int H, float eps, hipStream_t st) {
   constexpr int N = Vec16<T>::N;
-  if (H % N || rows <= 0) return TN_EINVAL;
+  if (rows <= 0 || H <= 0 || H % N) return TN_EINVAL;
   const int mv = pick_maxv(H, N);
   dim3 grid((rows + kRowWaves - 1) / kRowWaves), block(256);
   TN_DISPATCH_MAXV(mv, hipLaunchKernelGGL((layernorm_fwd_kernel<T, MAXV>), grid, block, 0, st, (const T*)x,
@@ -757,7 +757,7 @@ static int layernorm_bwd_t(const void* dy, const void* h, const void* w, const f
                            const void* dres, void* dh, void* dw, void* db, float* ws, int rows, int H,
                            hipStream_t st) {
   constexpr int N = Vec16<T>::N;
-  if (H % N || rows <= 0) return TN_EINVAL;
+  if (rows <= 0 || H <= 0 || H % N) return TN_EINVAL;
   const int mv = pick_maxv_block(H, N);
   const int nb = norm_bwd_blocks(rows);
   float* ws_b = ws + (size_t)nb * H;
@@ -816,7 +816,7 @@ int tn_layernorm_bwd(const void* dy, const void* h, const void* w, const float* 
 int tn_swiglu_fwd(const void* gate, const void* up, void* out, long long n, int dtype, void* stream) {
   TN_DTYPE_SWITCH(dtype, {
     constexpr int N = Vec16<T>::N;
-    if (n % N) return TN_EINVAL;
+    if (n < 0 || n % N) return TN_EINVAL;
     const size_t nvec = (size_t)n / N;
     hipLaunchKernelGGL((swiglu_fwd_kernel<T>), dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream,
                        (const T*)gate, (const T*)up, (T*)out, nvec);
@@ -829,7 +829,7 @@ int tn_swiglu_bwd(const void* dout, const void* gate, const void* up, void* dgat
                   void* stream) {
   TN_DTYPE_SWITCH(dtype, {
     constexpr int N = Vec16<T>::N;
-    if (n % N) return TN_EINVAL;
+    if (n < 0 || n % N) return TN_EINVAL;
     const size_t nvec = (size_t)n / N;
     hipLaunchKernelGGL((swiglu_bwd_kernel<T>), dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream,
                        (const T*)dout, (const T*)gate, (const T*)up, (T*)dgate, (T*)dup, nvec);
@@ -861,7 +861,7 @@ int tn_swiglu_bwd_t(const void* dout, const void* gate, const void* up, void* dg
 int tn_gelu_fwd(const void* x, void* out, long long n, int dtype, void* stream) {
   TN_DTYPE_SWITCH(dtype, {
     constexpr int N = Vec16<T>::N;
-    if (n % N) return TN_EINVAL;
+    if (n < 0 || n % N) return TN_EINVAL;
     const size_t nvec = (size_t)n / N;
     hipLaunchKernelGGL((gelu_fwd_kernel<T>), dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
                        (T*)out, nvec);
@@ -873,7 +873,7 @@ int tn_gelu_fwd(const void* x, void* out, long long n, int dtype, void* stream) 
 int tn_gelu_bwd(const void* dout, const void* x, void* dx, long long n, int dtype, void* stream) {
   TN_DTYPE_SWITCH(dtype, {
     constexpr int N = Vec16<T>::N;
-    if (n % N) return TN_EINVAL;
+    if (n < 0 || n % N) return TN_EINVAL;
     const size_t nvec = (size_t)n / N;
     hipLaunchKernelGGL((gelu_bwd_kernel<T>), dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream,
                        (const T*)dout, (const T*)x, (T*)dx, nvec);
@@ -884,6 +884,7 @@ int tn_gelu_bwd(const void* dout, const void* x, void* dx, long long n, int dtyp
 
 int tn_rope_table(const long long* position_ids, const float* inv_freq, void* cos_t, void* sin_t, int n, int half,
                   float attention_scaling, int dtype, void* stream) {
+  if (n <= 0 || half <= 0) return TN_EINVAL;
   TN_DTYPE_SWITCH(dtype, {
     const size_t total = (size_t)n * half;
     hipLaunchKernelGGL((rope_table_kernel<T>), dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
@@ -895,7 +896,7 @@ int tn_rope_table(const long long* position_ids, const float* inv_freq, void* co
 
 int tn_rope_apply(const void* q, const void* k, void* q_out, void* k_out, const void* cos_t, const void* sin_t, int n,
                   int hq, int hk, int D, int backward, int dtype, void* stream) {
-  if (D % 2) return TN_EINVAL;
+  if (n <= 0 || hq <= 0 || hk < 0 || D <= 0 || D % 2) return TN_EINVAL;
   const float sign = backward ? -1.f : 1.f;
   TN_DTYPE_SWITCH(dtype, {
     constexpr int N = Vec16<T>::N;

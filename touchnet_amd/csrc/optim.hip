@@ -181,6 +181,21 @@ __global__ void adamw_prepare_kernel(const float* __restrict__ norm_sq, float* _
   state[4] = bad ? 1.f : 0.f;
 }
 
+// One element of the multi-tensor update — ONE definition, every product / sum and every fused multiply-add written out and
+// contraction off inside, for the 16-byte path and for the scalar path (tensors off a 16-byte boundary, tails): left to the
+// compiler, the bf16-gradient instantiation contracted the moments differently in its two loops (m as fma(b1, m, (1 - b1) g)
+// in the scalar one), so the last bit of m and v depended on where the allocator had put a tensor.  The forms below are the ones
+// the 16-byte path had in both instantiations.
+__device__ __forceinline__ void adamw_element(float& p, float& m, float& v, float g, float clip, float decay, float step,
+                                              float rs_bc2, float b1, float b2, float omb1, float omb2, float eps) {
+#pragma clang fp contract(off)
+  const float gj = g * clip;
+  m = __builtin_fmaf(omb1, gj, b1 * m);
+  v = __builtin_fmaf(gj, omb2 * gj, b2 * v);
+  const float upd = (step * m) / __builtin_fmaf(sqrtf(v), rs_bc2, eps);
+  p = __builtin_fmaf(decay, p, -upd);
+}
+
 template <typename G>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restrict__ ps, float* const* __restrict__ ms,
                                                           float* const* __restrict__ vs,
@@ -209,6 +224,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restri
   const long long end = min(beg + kAdamChunk, sizes[lo]);
   const float clip = state[3];
   const float step = lr / state[1], rs_bc2 = rsqrtf(state[2]), decay = 1.f - lr * wd;
+  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
   const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) |
                          reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(g) |
                          reinterpret_cast<uintptr_t>(shadow)) & 15) == 0;
@@ -226,13 +242,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restri
       float* mp = &mv.x;
       float* vp = &vv.x;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gj = gf[j] * clip;
-        pp[j] *= decay;
-        mp[j] = b1 * mp[j] + (1.f - b1) * gj;
-        vp[j] = b2 * vp[j] + (1.f - b2) * gj * gj;
-        pp[j] -= step * mp[j] / (sqrtf(vp[j]) * rs_bc2 + eps);
-      }
+      for (int j = 0; j < 4; ++j)
+        adamw_element(pp[j], mp[j], vp[j], gf[j], clip, decay, step, rs_bc2, b1, b2, omb1, omb2, eps);
       reinterpret_cast<float4*>(p)[base4 + i] = pv;
       reinterpret_cast<float4*>(m)[base4 + i] = mv;
       reinterpret_cast<float4*>(v)[base4 + i] = vv;
@@ -241,11 +252,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restri
     done = beg + n4 * 4;
   }
   for (long long i = done + threadIdx.x; i < end; i += 256) {
-    const float gi = Elem<G>::ld(g + i) * clip;
-    float pi = p[i] * decay;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * rs_bc2 + eps);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_element(pi, mi, vi, Elem<G>::ld(g + i), clip, decay, step, rs_bc2, b1, b2, omb1, omb2, eps);
     p[i] = pi;
     m[i] = mi;
     v[i] = vi;
