@@ -38,7 +38,9 @@ __device__ __forceinline__ void stat_push(RowStat& st, float x, int idx) {
   if (x > st.m) {
     st.s = st.s * exp2f((st.m - x) * kLog2e) + 1.f;
     st.m = x;
-  } else {
+  } else if (x != -INFINITY) {
+    // (x = -inf adds exactly 0 to a finite max's sum; while the max is still -inf, (-inf) - (-inf) would be NaN.
+    //  A NaN logit still takes this branch and poisons the row.)
     st.s += exp2f((x - st.m) * kLog2e);
   }
 }
@@ -50,7 +52,9 @@ __device__ __forceinline__ void stat_merge(RowStat& a, const RowStat& b) {
   }
   const float m = fmaxf(a.m, b.m);
   if (m == -INFINITY) return;
-  a.s = a.s * exp2f((a.m - m) * kLog2e) + b.s * exp2f((b.m - m) * kLog2e);
+  // (the contraction is written out: left to the compiler, WHICH product is fused follows the surrounding code, and the
+  //  last bit of lse with it)
+  a.s = fmaf(b.s, exp2f((b.m - m) * kLog2e), a.s * exp2f((a.m - m) * kLog2e));
   a.m = m;
 }
 

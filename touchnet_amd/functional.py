@@ -293,7 +293,9 @@ class _FusedLinearCE(torch.autograd.Function):
     (the liger fused-linear-CE idea, touchnet/bin/train.py:443-445 — but keeping the reference's
     per-sentence normalisation, which liger's mean-over-tokens drops, SURVEY.md §2.3 K10').
     Gradients w.r.t. hidden and weight are produced in the forward pass and scaled by the upstream
-    gradient in backward."""
+    gradient in backward.
+    Roundings: the logits and the dlogits of a chunk are stored in bf16; d(hidden) and d(weight) are fp32 sums rounded to
+    bf16 once (d(weight) over ALL chunks: fp32 buffer, one rounding); the upstream gradient is cast to bf16 in backward."""
 
     @staticmethod
     def forward(ctx, hidden, weight, labels, sentence_lens, num_sentence, ignore_index, chunk, compact=False, tp=None):
@@ -383,13 +385,23 @@ class _FusedLinearCE(torch.autograd.Function):
             else:
                 torch.mm(logits, weight, out=dh[s:e])
             own_w = (logits.is_cuda and _own(V, H, (e - s,), True, True) and _bf16_rows(logits, hc))
-            if dw is None:
+            if n <= chunk:                                                    # one chunk: one product, one rounding
                 dw = gemm([(logits, hc)], True, True) if own_w else torch.mm(logits.t(), hc)     # dW = dlogits^T @ h
-            elif own_w:
-                gemm([(logits, hc)], True, True, out=dw, accumulate=True)     # accumulate inside the GEMM epilogue
+            elif logits.dtype != torch.bfloat16:                              # (fp32 operands: nothing to gain)
+                dw = torch.mm(logits.t(), hc) if dw is None else dw.addmm_(logits.t(), hc)
             else:
-                dw.addmm_(logits.t(), hc)
+                # several chunks: the sum over the chunks is kept in fp32 and rounded to bf16 ONCE behind the loop (a bf16
+                # buffer would round the partial sum once per chunk).  Costs V x H x 4 bytes while the loop runs and one
+                # cast pass; the step's usual shape (labelled rows <= chunk) does not come here.
+                if dw is None:
+                    dw = torch.zeros(V, H, dtype=torch.float32, device=h2.device)
+                if own_w:
+                    gemm([(logits, hc)], True, True, out=dw, accumulate=True)     # accumulate inside the GEMM epilogue
+                else:
+                    dw.addmm_(logits.t().float(), hc.float())
             del logits
+        if dw.dtype != h2.dtype:
+            dw = dw.to(h2.dtype)
         nll = torch.cat([a for a, _ in parts]) if len(parts) > 1 else parts[0][0]
         hit = torch.cat([b for _, b in parts]) if len(parts) > 1 else parts[0][1]
         out = L.ce_reduce(nll, hit, lab, sl, ns, int(ignore_index))
