@@ -295,8 +295,8 @@ int tn_gemm_bf16_addend(const void* A, const void* B, long long lda, long long l
  *      audio tower's 1280 x 1280 weight gradients contract 30000 frames: 25 tiles for 256 CUs).  tail_only = 1: the whole
  *      rounds of tiles run unsplit and only the last partial round is split (the MLP weight gradients are 688 tiles = 2
  *      rounds + 176: cut in 4 the remainder costs 0.75 of a round instead of 1).  fp32 partial sums travel through
- *      `workspace` (whole-tile slabs: >= splitk * split_tiles * 262144 bytes, 16-byte aligned); a second kernel adds them
- *      (+ bias, + C when accumulate).  -22 additionally when an operand is contraction-contiguous and
+ *      `workspace` (>= tn_gemm_splitk_workspace_bytes(M, N, splitk, 0, tail_only) bytes, 16-byte aligned); a second kernel
+ *      adds them (+ bias, + C when accumulate).  -22 additionally when an operand is contraction-contiguous and
  *      ceil(K / 64) % splitk != 0, or tail_only without a whole round / without a remainder. */
 int tn_gemm_bf16_splitk(const void* A, const void* B, long long lda, long long ldb, int K, int a_kmaj, int b_kmaj,
                         void* C, const void* bias, int M, int N, long long ldc, int accumulate, int splitk, int tail_only,
@@ -305,7 +305,8 @@ int tn_gemm_bf16_splitk(const void* A, const void* B, long long lda, long long l
  *      MixedPrecisionPolicy(reduce_dtype=float32), touchnet/models/helper_func.py:165) and wants dW written straight into its
  *      reduce-scatter input instead of cast-copied there: C[M,N] (float, ldc in floats) = (+= when accumulate)
  *      A[K,M]^T . B[K,N], both operands contraction-major as stored (dY [tokens, M], x [tokens, N]).  splitk <= 1: one
- *      launch; >= 2: split-K through `workspace` (>= splitk * tiles * 262144 bytes).  Same -22 rules as tn_gemm_bf16. */
+ *      launch; >= 2: split-K through `workspace` (tn_gemm_splitk_workspace_bytes(M, N, splitk, 0, 0)).  Same -22 rules as
+ *      tn_gemm_bf16. */
 int tn_gemm_bf16_wgrad_f32(const void* A, const void* B, long long lda, long long ldb, int K, float* C, int M, int N,
                            long long ldc, int accumulate, int splitk, void* workspace, long long workspace_bytes,
                            void* stream);
@@ -314,11 +315,17 @@ int tn_gemm_bf16_wgrad_f32(const void* A, const void* B, long long lda, long lon
  *      C[M, N] (bf16; float with ldc in floats when c_f32; += when accumulate) = A[K, M]^T . B[K, N], bias_grad[M] (bf16)
  *      = column sums of A (A = dY [tokens, M], B = x [tokens, N] as stored).  The sums are taken from the dY fragments
  *      the matrix pipe reads anyway: the separate column-sum pass (tn_colsum_bf16, one more trip of dY through HBM) is
- *      not needed.  splitk >= 2: split-K, `workspace` >= (splitk * tiles * 65536 + splitk * ceil(M / 256) * 256) * 4 bytes.
+ *      not needed.  splitk >= 2: split-K through `workspace` (tn_gemm_splitk_workspace_bytes(M, N, splitk, 1, 0)).
  *      -22 as for tn_gemm_bf16 with both operands contraction-major; bias_grad must not be NULL. */
 int tn_gemm_bf16_wgrad_bias(const void* A, const void* B, long long lda, long long ldb, int K, void* C, void* bias_grad,
                             int M, int N, long long ldc, int accumulate, int c_f32, int splitk, void* workspace,
                             long long workspace_bytes, void* stream);
+/*      The split-K workspace of tn_gemm_bf16_splitk, tn_gemm_bf16_wgrad_f32 and tn_gemm_bf16_wgrad_bias, stated here
+ *      ONCE — in floats: splitk x split_tiles x 256 x 256 partial-sum slabs of whole tiles (split_tiles = every 256 x 256
+ *      output tile, or with tail_only the tiles of the last partial round, tiles mod CUs), then — with a bias gradient —
+ *      splitk x ceil(M / 256) x 256 partial column sums.  Returns its size in bytes: 0 for splitk <= 1 (no workspace
+ *      needed), -1 where the launch itself answers -22 (M or N <= 0; tail_only without a whole round / a remainder). */
+long long tn_gemm_splitk_workspace_bytes(int M, int N, int splitk, int with_bias_grad, int tail_only);
 /*      Several INDEPENDENT products of one operand mode as one persistent launch (ngrp = 1..3, weight-gradient mode
  *      a_kmaj = b_kmaj = 1 only): C_g[M_g, N_g] (+= when accumulate) A_g[K_g, M_g]^T . B_g[K_g, N_g], bf16 outputs (ldc in
  *      elements) or, c_f32 = 1, float outputs (ldc in floats).  The three weight gradients of transformers' LlamaMLP

@@ -116,6 +116,55 @@ def test_round5_gemm_entry_points_refuse_malformed_arguments_before_any_launch()
     assert grouped(ngrp=0) == EINVAL
     assert grouped(ngrp=1000) == EINVAL
     assert grouped(a_kmaj=0) == EINVAL
+    arr_ll[0] = I - 8                                    # lda < M: the contraction-major A's rows would overlap
+    assert grouped() == EINVAL
+    arr_ll[0] = I
+    # GELU forward / backward (the audio tower: 1280 -> 5120 -> 1280): a depth that is no multiple of 64, a pitch shorter than
+    # the row, a misaligned base, one buffer for both outputs
+    D, Fd = 1280, 5120
+    ok = dict(x=p, pre=p, act=p + 4096, M=M, N=Fd, K=D, ldx=D, ldw=D, ldc=Fd)
+    def gelu_fwd(**kw):
+        a = {**ok, **kw}
+        return lib.tn_gemm_bf16_gelu_fwd(a["x"], p, p, a["pre"], a["act"], a["M"], a["N"], a["K"], a["ldx"], a["ldw"], a["ldc"], None)
+    assert gelu_fwd(K=D + 32) == EINVAL
+    assert gelu_fwd(ldx=D - 64) == EINVAL and gelu_fwd(ldw=D - 64) == EINVAL and gelu_fwd(ldc=Fd - 8) == EINVAL
+    assert gelu_fwd(x=odd) == EINVAL and gelu_fwd(act=odd) == EINVAL
+    assert gelu_fwd(act=p) == EINVAL                                                  # pre == act
+    ok = dict(dy=p, M=M, I=Fd, H=D, lddy=D, ldw=Fd, ld=Fd)
+    def gelu_bwd(**kw):
+        a = {**ok, **kw}
+        return lib.tn_gemm_bf16_gelu_bwd(a["dy"], p, p, p, a["M"], a["I"], a["H"], a["lddy"], a["ldw"], a["ld"], None)
+    assert gelu_bwd(H=D + 32) == EINVAL
+    assert gelu_bwd(lddy=D - 64) == EINVAL and gelu_bwd(ldw=Fd - 8) == EINVAL and gelu_bwd(ld=Fd - 8) == EINVAL
+    assert gelu_bwd(dy=odd) == EINVAL
+    # the general entry: N not a multiple of 8, A contraction-major beside a row-stored B, a pitch that is no multiple of 8
+    one = lambda t, v: (t * 1)(v)
+    def general(N=H, a_kmaj=0, b_kmaj=0, lda=H):
+        return lib.tn_gemm_bf16(one(C.c_void_p, p), one(C.c_void_p, p), one(C.c_longlong, lda), one(C.c_longlong, H),
+                                one(C.c_int, H), 1, a_kmaj, b_kmaj, p, None, None, M, N, N, 0, 0, None)
+    assert general(N=H + 4) == EINVAL
+    assert general(a_kmaj=1, b_kmaj=0) == EINVAL
+    assert general(lda=H + 4) == EINVAL
+    # the residual addend may not be the output
+    assert lib.tn_gemm_bf16_addend(p, p, H, H, H, 0, 0, p, None, p, H, M, H, H, None) == EINVAL
+    # split-K: fewer than two parts, 64 stages of a row-stored operand cut in 3, a workspace one byte short of
+    # tn_gemm_splitk_workspace_bytes
+    need = lib.tn_gemm_splitk_workspace_bytes(M, H, 4, 0, 0)
+    def splitk(parts=4, ws_bytes=need):
+        return lib.tn_gemm_bf16_splitk(p, p, H, H, H, 0, 0, p, None, M, H, H, 0, parts, 0, p, ws_bytes, None)
+    assert splitk(parts=1) == EINVAL
+    assert splitk(parts=3, ws_bytes=need) == EINVAL
+    assert splitk(ws_bytes=need - 1) == EINVAL
+    # ... whose layout is the header's: parts x tiles x 256 x 256 floats of slabs (+ parts x ceil(M / 256) x 256 floats of
+    # partial column sums with a bias gradient); tail_only: the tiles of the last partial round (256 CUs: an MI355X, and what
+    # the library assumes where no device is visible)
+    assert need == 4 * (1 * 16) * 65536 * 4
+    assert lib.tn_gemm_splitk_workspace_bytes(1280, 520, 4, 0, 0) == 4 * (5 * 3) * 65536 * 4
+    assert lib.tn_gemm_splitk_workspace_bytes(1280, 520, 4, 1, 0) == (4 * (5 * 3) * 65536 + 4 * 5 * 256) * 4
+    assert lib.tn_gemm_splitk_workspace_bytes(1280, 520, 1, 1, 0) == 0
+    assert lib.tn_gemm_splitk_workspace_bytes(11008, 4096, 4, 0, 1) == 4 * (43 * 16 % 256) * 65536 * 4      # 688 = 2 rounds + 176
+    assert lib.tn_gemm_splitk_workspace_bytes(4096, 4096, 4, 0, 1) == -1       # 256 tiles: a whole round, no remainder
+    assert lib.tn_gemm_splitk_workspace_bytes(1280, 520, 4, 0, 1) == -1        # 15 tiles: no whole round
 
 
 def test_attn_bwd_rope_refuses_missing_or_misaligned_tables_before_any_launch():

@@ -1250,10 +1250,11 @@ def test_gemm_split_k_matches_fp64_reference(mode, M, N, K, monkeypatch):
             return F.gemm([(a, b)], ak, bk, bias=bias, out=out, accumulate=accumulate)
         from touchnet_amd import _C
         out = torch.empty(M, N, dtype=torch.bfloat16, device=DEV) if out is None else out
-        ws = torch.empty(parts * (tiles % 256) * 65536, dtype=torch.float32, device=DEV)
+        need = _C.lib().tn_gemm_splitk_workspace_bytes(M, N, parts, 0, 1)
+        ws = torch.empty(need // 4, dtype=torch.float32, device=DEV)
         ptr = lambda t: None if t is None else t.data_ptr()
         _C.check(_C.lib().tn_gemm_bf16_splitk(ptr(a), ptr(b), a.stride(0), b.stride(0), K, int(ak), int(bk), ptr(out), ptr(bias),
-                                              M, N, out.stride(0), int(accumulate), parts, 1, ptr(ws), ws.numel() * 4,
+                                              M, N, out.stride(0), int(accumulate), parts, 1, ptr(ws), need,
                                               torch.cuda.current_stream().cuda_stream), "tn_gemm_bf16_splitk")
         return out
 
@@ -1272,21 +1273,48 @@ def test_gemm_split_k_matches_fp64_reference(mode, M, N, K, monkeypatch):
     assert torch.equal(product(), got)                      # deterministic
 
 
-@pytest.mark.parametrize("mode,M,N,K", [("fwd", 4360, 4104, 128), ("dgrad", 1000, 776, 1088), ("wgrad", 1280, 1280, 30000),
-                                        ("wgrad", 1280, 520, 3000)])
+@pytest.mark.parametrize("mode,M,N,K", [
+    ("fwd", 4360, 4104, 128), ("dgrad", 1000, 776, 1088), ("wgrad", 1280, 1280, 30000), ("wgrad", 1280, 520, 3000),
+    # the fused products and the grouped launch size their grids themselves.  18 x 16 = 288 tiles: more than the CUs, no
+    # multiple of them, a ragged last row of tiles; contraction 128 (the grid does not depend on the depth)
+    ("swiglu_fwd", 4360, 2048, 128),  # (an output tile is 128 gate + 128 up columns)
+    ("swiglu_bwd", 4360, 4096, 128), ("rope", 4360, 4096, 128), ("gelu_fwd", 4360, 4096, 128), ("gelu_bwd", 4360, 4096, 128),
+    ("grouped", 2560, 2560, 1024),    # three products: 300 tiles = one round + 44, which run split-K in 2 parts
+])
 def test_gemm_one_workgroup_per_tile_launch(mode, M, N, K, monkeypatch):
     """TN_GEMM_PERSIST=0 (what the Trainer selects when collectives run beside the compute): grid = tiles (x split-K parts),
-    every workgroup handles exactly one unit — same results as the persistent launch, bit for bit."""
+    every workgroup handles exactly one unit — same results as the persistent launch, bit for bit, from every entry point."""
     F = _f()
     g = torch.Generator().manual_seed(M + N + K)
     r = lambda *sh: (torch.rand(*sh, generator=g) * 2 - 1).to(torch.bfloat16).to(DEV)
-    a, b = (r(M, K), r(N, K)) if mode == "fwd" else (r(M, K), r(K, N)) if mode == "dgrad" else (r(K, M), r(K, N))
-    ak, bk = mode == "wgrad", mode != "fwd"
+    if mode == "swiglu_fwd":
+        x, wg, wu = r(M, K), r(N, K), r(N, K)
+        run = lambda: F.gemm_swiglu_fwd(x, wg, wu)
+    elif mode == "swiglu_bwd":
+        dy, wd, gate, up = r(M, K), r(K, N), r(M, N), r(M, N)
+        run = lambda: F.gemm_swiglu_bwd(dy, wd, gate, up)
+    elif mode == "rope":
+        x, w, bias, cos, sin = r(M, K), r(N, K), r(N), r(M, 64), r(M, 64)
+        run = lambda: (F.gemm_rope(x, w, bias, cos, sin, 128),)
+    elif mode == "gelu_fwd":
+        x, w, bias = r(M, K), r(N, K), r(N)
+        run = lambda: F.gemm_gelu_fwd(x, w, bias)
+    elif mode == "gelu_bwd":
+        dy, w2, pre = r(M, K), r(K, N), r(M, N)
+        run = lambda: (F.gemm_gelu_bwd(dy, w2, pre),)
+    elif mode == "grouped":
+        pairs = [(r(K, M), r(K, N)) for _ in range(3)]
+        run = lambda: F.gemm_grouped_wgrad(pairs)
+    else:
+        a, b = (r(M, K), r(N, K)) if mode == "fwd" else (r(M, K), r(K, N)) if mode == "dgrad" else (r(K, M), r(K, N))
+        run = lambda: (F.gemm([(a, b)], mode == "wgrad", mode != "fwd"),)
     monkeypatch.delenv("TN_GEMM_PERSIST", raising=False)
-    persistent = F.gemm([(a, b)], ak, bk)
+    persistent = run()
     monkeypatch.setenv("TN_GEMM_PERSIST", "0")
-    per_tile = F.gemm([(a, b)], ak, bk)
-    assert torch.equal(persistent, per_tile)
+    per_tile = run()
+    assert len(persistent) == len(per_tile)
+    for whole, one in zip(persistent, per_tile):
+        assert torch.equal(whole, one)
 
 
 @pytest.mark.parametrize("M,N,K", [(4096, 4104, 2048), (1280, 1280, 30000), (520, 264, 2500)])

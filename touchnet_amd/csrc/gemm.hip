@@ -1631,16 +1631,20 @@ static int launch(dim3 grid, hipStream_t st, const Params& p) {
 }  // namespace gemm
 }  // namespace tn
 
-extern "C" {
+// ---- host side: ONE owner per rule — the grid (grid_for), the argument checks (row_operand_ok, kmaj_operand_ok, out_ok),
+// the split-K workspace layout (tn_gemm_splitk_workspace_bytes), the grouped launch's remainder split (grouped_split), the
+// general launcher (gemm_launch) and the fused-epilogue launcher (launch_fused); the C entry points follow them --------------
+using namespace tn::gemm;
+using tn::bf16_t;
+
+extern "C" long long tn_gemm_splitk_workspace_bytes(int M, int N, int splitk, int with_bias_grad, int tail_only);
+
+namespace {
 
 // One workgroup per CU walking a fixed tile list (1, default) or one workgroup per tile (0).  A host that runs collectives
 // beside the compute (RCCL kernels hold CUs) selects 0 — touchnet_amd/bin/train.py — instead of changing the process
 // environment; TN_GEMM_PERSIST in the environment still overrides it.
-static int g_persistent = 1;
-void tn_gemm_set_persistent(int on) { g_persistent = on ? 1 : 0; }
-int tn_gemm_get_persistent(void) { return g_persistent; }
-
-namespace {
+int g_persistent = 1;
 
 int num_cus() {
   static const int ncu = [] {
@@ -1656,144 +1660,221 @@ bool persistent_now() {
   return pe ? atoi(pe) != 0 : g_persistent != 0;
 }
 
-void clear_params(tn::gemm::Params& p) {
-  p = tn::gemm::Params{};
+// THE grid rule — persistent: one workgroup per CU walks its units (tiles x split-K parts); else one workgroup per unit
+dim3 grid_for(int units) {
+  const int ncu = num_cus();
+  return dim3(persistent_now() && units > ncu ? ncu : units);
+}
+
+void clear_params(Params& p) {
+  p = Params{};
   p.splitk = 1;
   p.nseg = 1;
 }
 
-}  // namespace
+void set_seg(Seg& s, const void* A, const void* B, long long lda, long long ldb, int K) {
+  s.A = (const bf16_t*)A;
+  s.B = (const bf16_t*)B;
+  s.lda = lda;
+  s.ldb = ldb;
+  s.K = K;
+  s.pad_ = 0;
+}
 
-// General entry: C[M,N] = sum_s opA_s · opB_s^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M].
-//   a_kmaj / b_kmaj: 0 = operand stored [rows, K] (contraction-contiguous), 1 = stored [K, rows] (contraction-major).
-//   A, B, lda, ldb, K: arrays of nseg (1..3) entries.
-// Requirements (else -22): every K % 64 == 0 (any K when both operands are contraction-major), N % 8 == 0, ld % 8 == 0, 16-byte aligned bases; KMAJ operands span
-// < 2 GB ((K-1) * ld + rows) * 2 bytes); with Ct: M % 8 == 0, ldct % 8 == 0.
-static int gemm_launch(const void* const* A, const void* const* B, const long long* lda, const long long* ldb,
-                       const int* K, int nseg, int a_kmaj, int b_kmaj, void* C, void* Ct, const void* bias, int M, int N,
-                       long long ldc, long long ldct, int accumulate, int splitk, int tail_only, void* workspace,
-                       long long workspace_bytes, void* stream, int c_f32 = 0, void* bias_grad = nullptr,
-                       const void* addend = nullptr, long long ldadd = 0) {
-  using namespace tn::gemm;
+// ---- THE argument checks: every entry point below refuses (-22) what these refuse, before anything is launched ----------
+template <typename... P>
+bool aligned(uintptr_t mask, P... ps) {
+  return ((... | (uintptr_t)ps) & mask) == 0;
+}
+
+// per-tile DMA offsets are 32-bit: what one buffer descriptor spans stays below 2 GB
+constexpr long long DMA_SPAN = 0x7fffffffLL;
+
+// Row-stored operand X[rows, K] (pitch ld): whole 64-deep stages (behind K a stage would read the row's own next columns),
+// 16-byte base, pitch % 8, the 288 rows a tile's descriptor spans below 2 GB.  min_ld is the entries' one difference: the
+// fused ones pass K; the general entry passes 1, because it also takes OVERLAPPING rows (ld < K) — the im2col view of a
+// k = 3 convolution over a channels-last sequence, row r = 3 C elements from r * stride * C on.
+bool row_operand_ok(const void* X, long long ld, int K, long long min_ld) {
+  return K > 0 && (K % 64) == 0 && aligned(15, X) && (ld % 8) == 0 && ld >= min_ld && 288 * ld * 2 < DMA_SPAN;
+}
+
+// Contraction-major operand X[K, rows] (pitch ld): any depth K (beside a row-stored operand, that one's check holds K to
+// whole stages; two contraction-major descriptors both zero-fill the rows k >= K), 16-byte base, pitch % 8, the whole
+// operand below 2 GB.  min_ld: `rows` for A and for the fused entries' B; 1 where the general and the grouped entry have
+// always taken a B with overlapping rows.
+bool kmaj_operand_ok(const void* X, long long ld, int K, int rows, long long min_ld) {
+  return K > 0 && aligned(15, X) && (ld % 8) == 0 && ld >= min_ld && ((long long)(K - 1) * ld + rows) * 2 < DMA_SPAN;
+}
+
+// Output (or same-shape epilogue input) of `cols` columns: 16-byte base, pitch >= cols.  ld_mult: 8 elements everywhere
+// (fp32 outputs of the general entry included) except the grouped launch's fp32 outputs, which need 4 floats = 16 bytes.
+bool out_ok(const void* C, long long ld, int cols, int ld_mult) { return aligned(15, C) && (ld % ld_mult) == 0 && ld >= cols; }
+
+// ---- split-K workspaces: fp32 slabs of whole tiles, [parts][tiles][256 x 256] ---------------------------------------------
+long long slab_floats(int parts, long long tiles) { return parts * tiles * BM * BN; }
+
+// The grouped launch's remainder split: r = tiles of the last partial round; returns the parts it is cut into (1 = it runs
+// as whole tiles: no whole round before it, more than half a round of it, or fewer than 16 stages somewhere)
+int grouped_split(long long total, int min_stages, int& r) {
+  const int ncu = num_cus();
+  r = (int)(total % ncu);
+  if (total <= ncu || r == 0 || r * 2 > ncu || min_stages < 16) return 1;
+  return min(ncu / r, min_stages / 8);
+}
+
+// One call of the general launcher; an entry point sets the fields it means and leaves the rest.
+struct GemmCall {
+  // C[M,N] = sum_s opA_s · opB_s^T: arrays of nseg (1..3) entries; a_kmaj / b_kmaj: 0 = operand stored [rows, K]
+  // (contraction-contiguous), 1 = stored [K, rows] (contraction-major)
+  const void* const* A;
+  const void* const* B;
+  const long long* lda;
+  const long long* ldb;
+  const int* K;
+  int nseg, a_kmaj, b_kmaj;
+  void* C;
+  long long ldc;
+  int M, N;
+  void* stream;
+  const void* bias = nullptr;      // + bias[N]
+  int accumulate = 0;              // + C
+  void* Ct = nullptr;              // transposed copy [N, M], pitch ldct
+  long long ldct = 0;
+  int splitk = 1, tail_only = 0;   // split-K through `workspace` (tn_gemm_splitk_workspace_bytes)
+  void* workspace = nullptr;
+  long long workspace_bytes = 0;
+  int c_f32 = 0;                   // C is float (weight-gradient mode)
+  void* bias_grad = nullptr;       // bf16 [M] column sums of A (weight-gradient mode)
+  const void* addend = nullptr;    // + addend[M, N], pitch ldadd
+  long long ldadd = 0;
+};
+
+int launch_mode(bool a_kmaj, bool b_kmaj, bool ct, dim3 grid, hipStream_t st, const Params& p) {
+  if (!a_kmaj && !b_kmaj) return ct ? launch<false, false, true>(grid, st, p) : launch<false, false, false>(grid, st, p);
+  if (!a_kmaj) return ct ? launch<false, true, true>(grid, st, p) : launch<false, true, false>(grid, st, p);
+  return ct ? launch<true, true, true>(grid, st, p) : launch<true, true, false>(grid, st, p);
+}
+
+// Requirements (else -22): the operand checks above per segment, N % 8 == 0, a_kmaj: M % 8 == 0; with Ct: M % 8 == 0,
+// ldct % 8 == 0, no accumulate.
+int gemm_launch(const GemmCall& c) {
+  const int M = c.M, N = c.N;
+  const bool wgrad_mode = c.a_kmaj && c.b_kmaj && c.nseg == 1 && c.Ct == nullptr && c.bias == nullptr;
+  if (c.a_kmaj && !c.b_kmaj) return TN_EINVAL;       // (A contraction-major with B contraction-contiguous: no caller)
   // (the addend rides on the plain epilogue of an unsplit, single-output product)
-  if (addend != nullptr && (accumulate || splitk > 1 || tail_only || Ct != nullptr || c_f32 || bias_grad != nullptr ||
-                            (ldadd % 8) || ldadd < N || ((uintptr_t)addend & 15)))
+  if (c.addend != nullptr && (c.accumulate || c.splitk > 1 || c.tail_only || c.Ct != nullptr || c.c_f32 ||
+                              c.bias_grad != nullptr || !out_ok(c.addend, c.ldadd, N, 8)))
     return TN_EINVAL;
-  if (bias_grad != nullptr && (!(a_kmaj && b_kmaj) || nseg != 1 || Ct != nullptr || bias != nullptr || tail_only ||
-                               ((uintptr_t)bias_grad & 1)))
-    return TN_EINVAL;
-  if (M <= 0 || N <= 0 || nseg < 1 || nseg > MAXSEG || (N % 8) != 0) return TN_EINVAL;
-  if ((ldc % 8) || ldc < N || ((uintptr_t)C & 15)) return TN_EINVAL;
-  if (c_f32 && (!(a_kmaj && b_kmaj) || nseg != 1 || Ct != nullptr || bias != nullptr || tail_only)) return TN_EINVAL;
-  if (a_kmaj && (M % 8)) return TN_EINVAL;
+  if ((c.bias_grad != nullptr || c.c_f32) && (!wgrad_mode || c.tail_only)) return TN_EINVAL;
+  if (!aligned(1, c.bias_grad)) return TN_EINVAL;
+  if (M <= 0 || N <= 0 || c.nseg < 1 || c.nseg > MAXSEG || (N % 8) != 0 || (c.a_kmaj && (M % 8))) return TN_EINVAL;
+  if (!out_ok(c.C, c.ldc, N, 8)) return TN_EINVAL;
+  if (c.Ct != nullptr && ((M % 8) || c.accumulate || !out_ok(c.Ct, c.ldct, M, 8))) return TN_EINVAL;
   Params p;
-  p = Params{};
-  p.stages = 0;
-  for (int s = 0; s < nseg; ++s) {
-    const int k = K[s];
-    // (two contraction-major operands: rows k >= K are zero-filled by both descriptors, so any depth works; a
-    //  contraction-contiguous operand would read its own next columns there)
-    if (k <= 0 || ((k % 64) != 0 && !(a_kmaj && b_kmaj)) || (lda[s] % 8) || (ldb[s] % 8)) return TN_EINVAL;
-    if (((uintptr_t)A[s] | (uintptr_t)B[s]) & 15) return TN_EINVAL;
-    if (a_kmaj) {
-      if (lda[s] < M || ((long long)(k - 1) * lda[s] + M) * 2 >= 0x7fffffffLL) return TN_EINVAL;
-    } else {
-      // per-tile DMA offsets are 32-bit: 288 rows of the operand must stay below 2 GB.  (lda < K is allowed: OVERLAPPING rows,
-      // the im2col view of a k = 3 convolution over a channels-last sequence — row r = 3 C elements from r * stride * C on)
-      if (lda[s] <= 0 || (long long)288 * lda[s] * 2 >= 0x7fffffffLL) return TN_EINVAL;
-    }
-    if (b_kmaj) {
-      if (ldb[s] <= 0 || ((long long)(k - 1) * ldb[s] + N) * 2 >= 0x7fffffffLL) return TN_EINVAL;   // (ldb < N: overlapping rows)
-    } else {
-      if (ldb[s] <= 0 || (long long)288 * ldb[s] * 2 >= 0x7fffffffLL) return TN_EINVAL;
-    }
-    p.seg[s].A = (const tn::bf16_t*)A[s];
-    p.seg[s].B = (const tn::bf16_t*)B[s];
-    p.seg[s].lda = lda[s];
-    p.seg[s].ldb = ldb[s];
-    p.seg[s].K = k;
-    p.seg[s].pad_ = 0;
+  clear_params(p);
+  for (int s = 0; s < c.nseg; ++s) {
+    const int k = c.K[s];
+    if (!(c.a_kmaj ? kmaj_operand_ok(c.A[s], c.lda[s], k, M, M) : row_operand_ok(c.A[s], c.lda[s], k, 1))) return TN_EINVAL;
+    if (!(c.b_kmaj ? kmaj_operand_ok(c.B[s], c.ldb[s], k, N, 1) : row_operand_ok(c.B[s], c.ldb[s], k, 1))) return TN_EINVAL;
+    set_seg(p.seg[s], c.A[s], c.B[s], c.lda[s], c.ldb[s], k);
     p.stages += (k + 63) / 64;
   }
-  for (int s = nseg; s < MAXSEG; ++s) p.seg[s] = p.seg[0];
-  if (Ct != nullptr && ((M % 8) || (ldct % 8) || ldct < M || ((uintptr_t)Ct & 15))) return TN_EINVAL;
-  if (Ct != nullptr && accumulate) return TN_EINVAL;
-  p.nseg = nseg;
+  for (int s = c.nseg; s < MAXSEG; ++s) p.seg[s] = p.seg[0];
+  p.nseg = c.nseg;
   p.M = M;
   p.N = N;
-  p.C = (tn::bf16_t*)C;
-  p.Ct = (tn::bf16_t*)Ct;
-  p.bias = (const tn::bf16_t*)bias;
-  p.ldc = ldc;
-  p.ldct = ldct;
-  p.accumulate = accumulate;
-  p.addend = (const tn::bf16_t*)addend;
-  p.ldadd = ldadd;
+  p.C = (bf16_t*)c.C;
+  p.Ct = (bf16_t*)c.Ct;
+  p.bias = (const bf16_t*)c.bias;
+  p.ldc = c.ldc;
+  p.ldct = c.ldct;
+  p.accumulate = c.accumulate;
+  p.addend = (const bf16_t*)c.addend;
+  p.ldadd = c.ldadd;
   p.nbm = (M + BM - 1) / BM;
   p.nbn = (N + BN - 1) / BN;
-  p.splitk = 1;
-  p.kchunk = 0;
-  p.ws = nullptr;
-  p.tile0 = 0;
   p.ntiles = p.nbm * p.nbn;
-  p.c_f32 = c_f32;
+  p.c_f32 = c.c_f32;
+  p.bias_out = (bf16_t*)c.bias_grad;
   const int ncu = num_cus();
   int main_tiles = 0;                                // tail split: tiles [0, main_tiles) run unsplit first
-  if (splitk > 1) {
+  if (c.splitk > 1) {
     // one segment, no transposed copy; a contraction-contiguous operand cannot be cut inside a stage or read behind K
-    if (nseg != 1 || Ct != nullptr) return TN_EINVAL;
-    if (!(a_kmaj && b_kmaj) && (p.stages % splitk) != 0) return TN_EINVAL;
-    if (tail_only) {
-      main_tiles = p.ntiles / ncu * ncu;
-      if (main_tiles <= 0 || main_tiles >= p.ntiles) return TN_EINVAL;
-    }
-    const long long slabs = (long long)splitk * (p.ntiles - main_tiles) * BM * BN;      // floats
-    if (workspace == nullptr || ((uintptr_t)workspace & 15) ||
-        workspace_bytes < (slabs + (bias_grad ? (long long)splitk * p.nbm * BM : 0)) * (long long)sizeof(float))
-      return TN_EINVAL;
-    p.splitk = splitk;
-    p.kchunk = (p.stages + splitk - 1) / splitk;
-    p.ws = (float*)workspace;
-    p.bias_ws = bias_grad ? (float*)workspace + slabs : nullptr;     // [splitk][nbm * 256] partial column sums
+    if (c.nseg != 1 || c.Ct != nullptr) return TN_EINVAL;
+    if (!(c.a_kmaj && c.b_kmaj) && (p.stages % c.splitk) != 0) return TN_EINVAL;
+    const long long need = tn_gemm_splitk_workspace_bytes(M, N, c.splitk, c.bias_grad != nullptr, c.tail_only);
+    if (need < 0 || c.workspace == nullptr || !aligned(15, c.workspace) || c.workspace_bytes < need) return TN_EINVAL;
+    if (c.tail_only) main_tiles = p.ntiles / ncu * ncu;
+    p.splitk = c.splitk;
+    p.kchunk = (p.stages + c.splitk - 1) / c.splitk;
+    p.ws = (float*)c.workspace;
+    if (c.bias_grad != nullptr) p.bias_ws = p.ws + slab_floats(c.splitk, p.ntiles);   // [splitk][nbm * 256] behind the slabs
   }
-  p.bias_out = (tn::bf16_t*)bias_grad;
-  // persistent: one workgroup per CU walks its tiles; else one workgroup per tile
-  const bool persist = persistent_now();
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
   int rc = 0;
-#define TN_MODE(AKM, BKM, GRID, PRM) \
-  rc |= (Ct != nullptr) ? launch<AKM, BKM, true>(GRID, st, PRM) : launch<AKM, BKM, false>(GRID, st, PRM)
-#define TN_LAUNCH(GRID, PRM)                                                               \
-  if (!a_kmaj && !b_kmaj) TN_MODE(false, false, GRID, PRM);                                \
-  else if (!a_kmaj && b_kmaj) TN_MODE(false, true, GRID, PRM);                             \
-  else if (a_kmaj && b_kmaj) TN_MODE(true, true, GRID, PRM);                               \
-  else return TN_EINVAL /* (A contraction-major with B contraction-contiguous: no caller) */
-  if (main_tiles > 0) {                          // whole rounds first, unsplit ...
+  if (main_tiles > 0) {                              // whole rounds first, unsplit, one workgroup per CU ...
     Params pm = p;
     pm.splitk = 1;
     pm.ntiles = main_tiles;
-    const dim3 gm(ncu);
-    TN_LAUNCH(gm, pm);
-    p.tile0 = main_tiles;                        // ... then the last partial round, split
+    rc |= launch_mode(c.a_kmaj, c.b_kmaj, c.Ct != nullptr, dim3(ncu), st, pm);
+    p.tile0 = main_tiles;                            // ... then the last partial round, split
     p.ntiles -= main_tiles;
   }
-  {
-    const int units = p.ntiles * p.splitk;
-    const dim3 grid(persist && units > ncu ? ncu : units);
-    TN_LAUNCH(grid, p);
-  }
-#undef TN_LAUNCH
-#undef TN_MODE
+  rc |= launch_mode(c.a_kmaj, c.b_kmaj, c.Ct != nullptr, grid_for(p.ntiles * p.splitk), st, p);
   if (rc != 0) return TN_EINVAL;
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
+// THE launcher of the fused-epilogue products (Kernel16, row-stored A, one accumulator, whole tiles): the entry has checked
+// its arguments and set the segments it uses (seg[0]; SwiGLU forward also seg[1]), the outputs and the epilogue's extra
+// inputs.  col_tile: output columns per tile — 256, or 128 where a tile is 128 gate + 128 up columns.
+template <int EPI, bool B_KMAJ>
+int launch_fused(Params& p, int M, int N, long long ldc, int col_tile, void* stream) {
+  for (int s = 1; s < MAXSEG; ++s)
+    if (p.seg[s].K == 0) p.seg[s] = p.seg[0];
+  p.stages = p.seg[0].K / 64;
+  p.M = M;
+  p.N = N;
+  p.ldc = ldc;
+  p.nbm = (M + BM - 1) / BM;
+  p.nbn = (N + col_tile - 1) / col_tile;
+  p.ntiles = p.nbm * p.nbn;
+  hipLaunchKernelGGL((gemm16_kernel<false, B_KMAJ, EPI>), grid_for(p.ntiles), dim3(NT), 0, (hipStream_t)stream, p);
+  TN_LAUNCH_CHECK();
+  return TN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tn_gemm_set_persistent(int on) { g_persistent = on ? 1 : 0; }
+int tn_gemm_get_persistent(void) { return g_persistent; }
+
+long long tn_gemm_splitk_workspace_bytes(int M, int N, int splitk, int with_bias_grad, int tail_only) {
+  if (splitk <= 1) return 0;
+  if (M <= 0 || N <= 0) return -1;
+  const long long nbm = (M + BM - 1) / BM;
+  long long tiles = nbm * ((N + BN - 1) / BN);
+  if (tail_only) {                                   // whole rounds run unsplit: only the last partial round is split
+    const int ncu = num_cus();
+    if (tiles < ncu || tiles % ncu == 0) return -1;
+    tiles %= ncu;
+  }
+  return (slab_floats(splitk, tiles) + (with_bias_grad ? splitk * nbm * BM : 0)) * (long long)sizeof(float);
+}
+
+// General entry: C[M,N] = sum_s opA_s · opB_s^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M].
 int tn_gemm_bf16(const void* const* A, const void* const* B, const long long* lda, const long long* ldb, const int* K,
                  int nseg, int a_kmaj, int b_kmaj, void* C, void* Ct, const void* bias, int M, int N, long long ldc,
                  long long ldct, int accumulate, void* stream) {
-  return gemm_launch(A, B, lda, ldb, K, nseg, a_kmaj, b_kmaj, C, Ct, bias, M, N, ldc, ldct, accumulate, 1, 0, nullptr, 0,
-                     stream);
+  GemmCall c{A, B, lda, ldb, K, nseg, a_kmaj, b_kmaj, C, ldc, M, N, stream};
+  c.bias = bias;
+  c.accumulate = accumulate;
+  c.Ct = Ct;
+  c.ldct = ldct;
+  return gemm_launch(c);
 }
 
 // C = A B^T (+ bias) + addend: the residual stream added in the producing GEMM's epilogue (addend [M, N] bf16, pitch ldadd;
@@ -1803,60 +1884,86 @@ int tn_gemm_bf16(const void* const* A, const void* const* B, const long long* ld
 int tn_gemm_bf16_addend(const void* A, const void* B, long long lda, long long ldb, int K, int a_kmaj, int b_kmaj, void* C,
                         const void* bias, const void* addend, long long ldadd, int M, int N, long long ldc, void* stream) {
   if (addend == nullptr || addend == C) return TN_EINVAL;
-  return gemm_launch(&A, &B, &lda, &ldb, &K, 1, a_kmaj, b_kmaj, C, nullptr, bias, M, N, ldc, 0, 0, 1, 0, nullptr, 0, stream,
-                     0, nullptr, addend, ldadd);
+  GemmCall c{&A, &B, &lda, &ldb, &K, 1, a_kmaj, b_kmaj, C, ldc, M, N, stream};
+  c.bias = bias;
+  c.addend = addend;
+  c.ldadd = ldadd;
+  return gemm_launch(c);
 }
 
 // The same product with the contraction cut into `splitk` parts that run as independent units; fp32 partial sums go through
-// `workspace` (whole 256 x 256 tile slabs: >= splitk * tiles_split * 262144 bytes, 16-byte aligned) and a second kernel
-// adds them up (+ bias, + C).  tail_only = 0: every tile is split (outputs of few tiles with a deep contraction);
-// tail_only = 1: the whole rounds of tiles (floor(tiles / CUs) * CUs) run unsplit, only the last partial round is split
-// (tiles_split = tiles mod CUs; -22 when there is no whole round or no remainder).  One segment, no transposed copy; with a
-// contraction-contiguous operand the number of 64-deep stages must be a multiple of splitk (else -22).
+// `workspace` (tn_gemm_splitk_workspace_bytes, 16-byte aligned) and a second kernel adds them up (+ bias, + C).
+// tail_only = 0: every tile is split (outputs of few tiles with a deep contraction); tail_only = 1: the whole rounds of
+// tiles (floor(tiles / CUs) * CUs) run unsplit, only the last partial round is split (-22 when there is no whole round or
+// no remainder).  One segment, no transposed copy; with a contraction-contiguous operand the number of 64-deep stages must
+// be a multiple of splitk (else -22).
 int tn_gemm_bf16_splitk(const void* A, const void* B, long long lda, long long ldb, int K, int a_kmaj, int b_kmaj,
                         void* C, const void* bias, int M, int N, long long ldc, int accumulate, int splitk, int tail_only,
                         void* workspace, long long workspace_bytes, void* stream) {
   if (splitk < 2) return TN_EINVAL;
-  return gemm_launch(&A, &B, &lda, &ldb, &K, 1, a_kmaj, b_kmaj, C, nullptr, bias, M, N, ldc, 0, accumulate, splitk,
-                     tail_only, workspace, workspace_bytes, stream);
+  GemmCall c{&A, &B, &lda, &ldb, &K, 1, a_kmaj, b_kmaj, C, ldc, M, N, stream};
+  c.bias = bias;
+  c.accumulate = accumulate;
+  c.splitk = splitk;
+  c.tail_only = tail_only;
+  c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes;
+  return gemm_launch(c);
 }
 
-// Weight gradient with fp32 output: C[M,N] (float, ldc in floats) = (+=) A[K,M]^T · B[K,N], both operands contraction-major
-// (dW = dY^T x read as stored).  splitk <= 1: plain; >= 2: split-K through `workspace` as in tn_gemm_bf16_splitk.
+// Weight gradient AND (bias_grad != NULL) bias gradient of a linear layer y = x W^T + b in one launch: C[M, N] (bf16, or
+// float with ldc in floats when c_f32; += when accumulate) = A[K, M]^T . B[K, N] and bias_grad[M] (bf16) = column sums of
+// A — A = dY [tokens, M], B = x [tokens, N] as stored, both contraction-major.  The sums come from the A fragments the matrix
+// pipe reads anyway (EPI_BIASG above): no separate pass over dY.  splitk <= 1: plain; >= 2: split-K through `workspace`
+// (tn_gemm_splitk_workspace_bytes).
+static int wgrad(const void* A, const void* B, long long lda, long long ldb, int K, void* C, void* bias_grad, int M, int N,
+                 long long ldc, int accumulate, int c_f32, int splitk, void* workspace, long long workspace_bytes,
+                 void* stream) {
+  GemmCall c{&A, &B, &lda, &ldb, &K, 1, 1, 1, C, ldc, M, N, stream};
+  c.accumulate = accumulate;
+  c.c_f32 = c_f32;
+  c.bias_grad = bias_grad;
+  c.splitk = splitk > 1 ? splitk : 1;
+  c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes;
+  return gemm_launch(c);
+}
+
 int tn_gemm_bf16_wgrad_f32(const void* A, const void* B, long long lda, long long ldb, int K, float* C, int M, int N,
                            long long ldc, int accumulate, int splitk, void* workspace, long long workspace_bytes,
                            void* stream) {
-  return gemm_launch(&A, &B, &lda, &ldb, &K, 1, 1, 1, C, nullptr, nullptr, M, N, ldc, 0, accumulate,
-                     splitk > 1 ? splitk : 1, 0, workspace, workspace_bytes, stream, 1);
+  return wgrad(A, B, lda, ldb, K, C, nullptr, M, N, ldc, accumulate, 1, splitk, workspace, workspace_bytes, stream);
+}
+
+int tn_gemm_bf16_wgrad_bias(const void* A, const void* B, long long lda, long long ldb, int K, void* C, void* bias_grad,
+                            int M, int N, long long ldc, int accumulate, int c_f32, int splitk, void* workspace,
+                            long long workspace_bytes, void* stream) {
+  if (bias_grad == nullptr) return TN_EINVAL;
+  return wgrad(A, B, lda, ldb, K, C, bias_grad, M, N, ldc, accumulate, c_f32, splitk, workspace, workspace_bytes, stream);
 }
 
 // Several independent products of ONE operand mode in one persistent launch (`ngrp` = 1..3; product g:
 // C_g[M_g, N_g] (+)= opA_g · opB_g^T, one segment each, no bias).  What it is for: the MLP's three weight gradients are 688
 // output tiles each = 2.69 rounds on 256 CUs, i.e. three launches idle a third of the chip in their last rounds; as one
-// tile list they are 2064 tiles = 8 whole rounds + 16.  That remainder (tiles mod CUs, when it is at most half the CUs and
-// the contraction is >= 16 stages deep) runs split-K — `workspace` >= tn_gemm_grouped_workspace_bytes(...) — so it costs
-// a fraction of a round instead of a whole one.  c_f32: fp32 outputs (ldc in floats; both operands contraction-major).
+// tile list they are 2064 tiles = 8 whole rounds + 16.  That remainder (grouped_split) runs split-K — `workspace` >=
+// tn_gemm_grouped_workspace_bytes(...) — so it costs a fraction of a round instead of a whole one.  c_f32: fp32 outputs
+// (ldc in floats; both operands contraction-major).
 long long tn_gemm_grouped_workspace_bytes(const int* M, const int* N, const int* K, int ngrp) {
-  using namespace tn::gemm;
   if (ngrp < 1 || ngrp > MAXSEG) return -1;
   long long tiles = 0;
-  int min_stages = 0x7fffffff;
+  int min_stages = 0x7fffffff, r;
   for (int g = 0; g < ngrp; ++g) {
     tiles += (long long)((M[g] + BM - 1) / BM) * ((N[g] + BN - 1) / BN);
     min_stages = min(min_stages, (K[g] + 63) / 64);
   }
-  const int ncu = num_cus();
-  const int r = (int)(tiles % ncu);
-  if (tiles <= ncu || r == 0 || r * 2 > ncu || min_stages < 16) return 0;
-  const int S = min(ncu / r, min_stages / 8);
-  return S > 1 ? (long long)S * r * BM * BN * (long long)sizeof(float) : 0;
+  const int S = grouped_split(tiles, min_stages, r);
+  return S > 1 ? slab_floats(S, r) * (long long)sizeof(float) : 0;
 }
 
 int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long long* lda, const long long* ldb,
                          const int* K, void* const* C, const long long* ldc, const int* M, const int* N, int ngrp,
                          int a_kmaj, int b_kmaj, int accumulate, int c_f32, void* workspace, long long workspace_bytes,
                          void* stream) {
-  using namespace tn::gemm;
   if (ngrp < 1 || ngrp > MAXSEG) return TN_EINVAL;
   if (!(a_kmaj && b_kmaj)) return TN_EINVAL;               // (weight-gradient mode: the one caller)
   Params p;
@@ -1864,18 +1971,11 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
   int total = 0, min_stages = 0x7fffffff;
   for (int g = 0; g < ngrp; ++g) {
     const int k = K[g], m = M[g], n = N[g];
-    if (m <= 0 || n <= 0 || k <= 0 || (n % 8) || (m % 8) || (lda[g] % 8) || (ldb[g] % 8) || (ldc[g] % (c_f32 ? 4 : 8)))
+    if (m <= 0 || n <= 0 || (m % 8) || (n % 8) || !kmaj_operand_ok(A[g], lda[g], k, m, m) ||
+        !kmaj_operand_ok(B[g], ldb[g], k, n, 1) || !out_ok(C[g], ldc[g], n, c_f32 ? 4 : 8))
       return TN_EINVAL;
-    if (lda[g] < m || ldb[g] <= 0 || ldc[g] < n) return TN_EINVAL;
-    if (((uintptr_t)A[g] | (uintptr_t)B[g] | (uintptr_t)C[g]) & 15) return TN_EINVAL;
-    if (((long long)(k - 1) * lda[g] + m) * 2 >= 0x7fffffffLL || ((long long)(k - 1) * ldb[g] + n) * 2 >= 0x7fffffffLL)
-      return TN_EINVAL;
-    p.seg[g].A = (const tn::bf16_t*)A[g];
-    p.seg[g].B = (const tn::bf16_t*)B[g];
-    p.seg[g].lda = lda[g];
-    p.seg[g].ldb = ldb[g];
-    p.seg[g].K = k;
-    p.grp[g].C = (tn::bf16_t*)C[g];
+    set_seg(p.seg[g], A[g], B[g], lda[g], ldb[g], k);
+    p.grp[g].C = (bf16_t*)C[g];
     p.grp[g].ldc = ldc[g];
     p.grp[g].M = m;
     p.grp[g].N = n;
@@ -1894,25 +1994,18 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
   p.ngrp = ngrp;
   p.accumulate = accumulate;
   p.c_f32 = c_f32;
-  const int ncu = num_cus();
-  const bool persist = persistent_now();
   hipStream_t st = (hipStream_t)stream;
-  // the remainder of the tile list, split-K
-  int r = total % ncu, S = 1;
-  if (total > ncu && r > 0 && r * 2 <= ncu && min_stages >= 16) S = min(ncu / r, min_stages / 8);
-  if (S > 1 && (workspace == nullptr || ((uintptr_t)workspace & 15) ||
-                workspace_bytes < (long long)S * r * BM * BN * (long long)sizeof(float)))
+  int r, S = grouped_split(total, min_stages, r);
+  if (S > 1 && (workspace == nullptr || !aligned(15, workspace) ||
+                workspace_bytes < slab_floats(S, r) * (long long)sizeof(float)))
     S = 1;                                                  // (no workspace: the remainder runs as whole tiles)
   const int main_tiles = S > 1 ? total - r : total;
   p.tile0 = 0;
   p.ntiles = main_tiles;
-  {
-    const dim3 grid(persist && main_tiles > ncu ? ncu : main_tiles);
-    if (c_f32)
-      hipLaunchKernelGGL((gemm_kernel<true, true, false, false, true, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<true, true, false, false, false, EPI_GROUPED>), grid, dim3(NT), 0, st, p);
-  }
+  if (c_f32)
+    hipLaunchKernelGGL((gemm_kernel<true, true, false, false, true, EPI_GROUPED>), grid_for(main_tiles), dim3(NT), 0, st, p);
+  else
+    hipLaunchKernelGGL((gemm_kernel<true, true, false, false, false, EPI_GROUPED>), grid_for(main_tiles), dim3(NT), 0, st, p);
   if (S > 1) {
     float* ws = (float*)workspace;
     for (int g = 0; g < ngrp; ++g) {
@@ -1937,13 +2030,11 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
       q.tile0 = lo - p.grp[g].start;
       q.ntiles = hi - lo;
       q.c_f32 = c_f32;
-      const int units = q.ntiles * S;
-      const dim3 grid(persist && units > ncu ? ncu : units);
-      hipLaunchKernelGGL((gemm_kernel<true, true, false, true>), grid, dim3(NT), 0, st, q);
+      hipLaunchKernelGGL((gemm_kernel<true, true, false, true>), grid_for(q.ntiles * S), dim3(NT), 0, st, q);
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)q.ntiles * 32u), dim3(256), 0, st, q.ws, q.splitk, q.M, q.N,
-                         q.nbm, q.nbn, q.tile0, q.ntiles, q.C, q.ldc, (const tn::bf16_t*)nullptr, q.accumulate, q.c_f32,
-                         (const float*)nullptr, (tn::bf16_t*)nullptr);
-      ws += (long long)S * q.ntiles * BM * BN;
+                         q.nbm, q.nbn, q.tile0, q.ntiles, q.C, q.ldc, (const bf16_t*)nullptr, q.accumulate, q.c_f32,
+                         (const float*)nullptr, (bf16_t*)nullptr);
+      ws += slab_floats(S, q.ntiles);
     }
   }
   TN_LAUNCH_CHECK();
@@ -1955,35 +2046,17 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
 // bf16 with row pitch ldc; x [M, K] (pitch ldx), Wg / Wu [I, K] (pitch ldw).  -22 unless K % 64 == 0, I % 8 == 0, pitches % 8.
 int tn_gemm_bf16_swiglu_fwd(const void* x, const void* wg, const void* wu, void* gate, void* up, void* act, int M, int I,
                             int K, long long ldx, long long ldw, long long ldc, void* stream) {
-  using namespace tn::gemm;
-  if (M <= 0 || I <= 0 || K <= 0 || (K % 64) || (I % 8) || (ldx % 8) || (ldw % 8) || (ldc % 8) || ldc < I) return TN_EINVAL;
-  if (ldx < K || ldw < K) return TN_EINVAL;        // (row pitches of the row-stored operands: at least the contraction)
-  if (((uintptr_t)x | (uintptr_t)wg | (uintptr_t)wu | (uintptr_t)gate | (uintptr_t)up | (uintptr_t)act) & 15) return TN_EINVAL;
-  if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
+  if (M <= 0 || I <= 0 || (I % 8) || !row_operand_ok(x, ldx, K, K) || !row_operand_ok(wg, ldw, K, K) ||
+      !row_operand_ok(wu, ldw, K, K) || !out_ok(gate, ldc, I, 8) || !aligned(15, up, act))
+    return TN_EINVAL;
   Params p;
   clear_params(p);
-  p.seg[0].A = p.seg[1].A = (const tn::bf16_t*)x;
-  p.seg[0].B = (const tn::bf16_t*)wg;
-  p.seg[1].B = (const tn::bf16_t*)wu;
-  p.seg[0].lda = p.seg[1].lda = ldx;
-  p.seg[0].ldb = p.seg[1].ldb = ldw;
-  p.seg[0].K = p.seg[1].K = K;
-  p.seg[2] = p.seg[0];
-  p.stages = K / 64;
-  p.M = M;
-  p.N = I;
-  p.C = (tn::bf16_t*)gate;
-  p.C2 = (tn::bf16_t*)up;
-  p.C3 = (tn::bf16_t*)act;
-  p.ldc = ldc;
-  p.nbm = (M + BM - 1) / BM;
-  p.nbn = (I + 127) / 128;
-  p.ntiles = p.nbm * p.nbn;
-  const int ncu = num_cus();
-  const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_SWIGLU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
+  set_seg(p.seg[0], x, wg, ldx, ldw, K);
+  set_seg(p.seg[1], x, wu, ldx, ldw, K);
+  p.C = (bf16_t*)gate;
+  p.C2 = (bf16_t*)up;
+  p.C3 = (bf16_t*)act;
+  return launch_fused<EPI_SWIGLU_FWD, false>(p, M, I, ldc, 128, stream);
 }
 
 // Its backward counterpart: d(act) = dY W_down (dY [M, H] pitch lddy, W_down [H, I] read contraction-major, pitch ldw) is
@@ -1991,49 +2064,18 @@ int tn_gemm_bf16_swiglu_fwd(const void* x, const void* wg, const void* wu, void*
 // -22 unless H % 64 == 0, I % 8 == 0, pitches % 8.
 int tn_gemm_bf16_swiglu_bwd(const void* dy, const void* wd, const void* gate, const void* up, void* dgate, void* dup,
                             int M, int I, int H, long long lddy, long long ldw, long long ld, void* stream) {
-  using namespace tn::gemm;
-  if (M <= 0 || I <= 0 || H <= 0 || (H % 64) || (I % 8) || (lddy % 8) || (ldw % 8) || (ld % 8) || ld < I) return TN_EINVAL;
-  if (lddy < H) return TN_EINVAL;                  // (dY is row-stored: its pitch is at least the contraction)
-  if (((uintptr_t)dy | (uintptr_t)wd | (uintptr_t)gate | (uintptr_t)up | (uintptr_t)dgate | (uintptr_t)dup) & 15)
-    return TN_EINVAL;
-  if ((long long)288 * lddy * 2 >= 0x7fffffffLL || ldw < I || ((long long)(H - 1) * ldw + I) * 2 >= 0x7fffffffLL)
+  if (M <= 0 || I <= 0 || (I % 8) || !row_operand_ok(dy, lddy, H, H) || !kmaj_operand_ok(wd, ldw, H, I, I) ||
+      !out_ok(dgate, ld, I, 8) || !aligned(15, dup, gate, up))
     return TN_EINVAL;
   Params p;
   clear_params(p);
-  p.seg[0].A = (const tn::bf16_t*)dy;
-  p.seg[0].B = (const tn::bf16_t*)wd;
-  p.seg[0].lda = lddy;
-  p.seg[0].ldb = ldw;
-  p.seg[0].K = H;
-  p.seg[1] = p.seg[2] = p.seg[0];
-  p.stages = H / 64;
-  p.M = M;
-  p.N = I;
-  p.C = (tn::bf16_t*)dgate;
-  p.C2 = (tn::bf16_t*)dup;
-  p.E1 = (const tn::bf16_t*)gate;
-  p.E2 = (const tn::bf16_t*)up;
-  p.ldc = p.lde = ld;
-  p.nbm = (M + BM - 1) / BM;
-  p.nbn = (I + BN - 1) / BN;
-  p.ntiles = p.nbm * p.nbn;
-  const int ncu = num_cus();
-  const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, true, EPI_SWIGLU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
-}
-
-// Weight gradient AND bias gradient of a linear layer y = x W^T + b in one launch: C[M, N] (bf16, or float when c_f32;
-// += when accumulate) = A[K, M]^T . B[K, N] and bias_grad[M] (bf16) = column sums of A — A = dY [tokens, M], B = x [tokens, N]
-// as stored.  The sums come from the A fragments the matrix pipe reads anyway (EPI_BIASG above): no separate pass over dY.
-// splitk >= 2: split-K through `workspace` (>= (splitk * tiles * 65536 + splitk * ceil(M / 256) * 256) * 4 bytes).
-int tn_gemm_bf16_wgrad_bias(const void* A, const void* B, long long lda, long long ldb, int K, void* C, void* bias_grad,
-                            int M, int N, long long ldc, int accumulate, int c_f32, int splitk, void* workspace,
-                            long long workspace_bytes, void* stream) {
-  if (bias_grad == nullptr) return TN_EINVAL;
-  return gemm_launch(&A, &B, &lda, &ldb, &K, 1, 1, 1, C, nullptr, nullptr, M, N, ldc, 0, accumulate,
-                     splitk > 1 ? splitk : 1, 0, workspace, workspace_bytes, stream, c_f32, bias_grad);
+  set_seg(p.seg[0], dy, wd, lddy, ldw, H);
+  p.C = (bf16_t*)dgate;
+  p.C2 = (bf16_t*)dup;
+  p.E1 = (const bf16_t*)gate;
+  p.E2 = (const bf16_t*)up;
+  p.lde = ld;
+  return launch_fused<EPI_SWIGLU_BWD, true>(p, M, I, ld, BN, stream);
 }
 
 // A q / k projection with the rotary embedding in the epilogue: out[M, N] = rope(x W^T + bias), N = heads x head_dim
@@ -2041,39 +2083,20 @@ int tn_gemm_bf16_wgrad_bias(const void* A, const void* B, long long lda, long lo
 // output row (tn_rope_table).  -22 unless K % 64 == 0 and the pitches are multiples of 8.
 int tn_gemm_bf16_rope(const void* x, const void* w, const void* bias, const void* cos_t, const void* sin_t, void* out, int M,
                       int N, int K, long long ldx, long long ldw, long long ldc, int head_dim, void* stream) {
-  using namespace tn::gemm;
-  if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || (ldx % 8) || (ldw % 8) || (ldc % 8) || ldc < N) return TN_EINVAL;
-  if (ldx < K || ldw < K) return TN_EINVAL;        // (row pitches of the row-stored operands: at least the contraction)
+  if (M <= 0 || N <= 0 || !row_operand_ok(x, ldx, K, K) || !row_operand_ok(w, ldw, K, K) || !out_ok(out, ldc, N, 8))
+    return TN_EINVAL;
   if (!((head_dim == 128 && N % 256 == 0) || (head_dim == 64 && N % 64 == 0))) return TN_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)out) & 15) return TN_EINVAL;
-  if (((uintptr_t)cos_t | (uintptr_t)sin_t | (uintptr_t)bias) & 7) return TN_EINVAL;
-  if (cos_t == nullptr || sin_t == nullptr) return TN_EINVAL;
-  if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
+  // (the epilogue reads the tables and the bias in 8-byte pieces)
+  if (cos_t == nullptr || sin_t == nullptr || !aligned(7, cos_t, sin_t, bias)) return TN_EINVAL;
   Params p;
   clear_params(p);
-  p.seg[0].A = (const tn::bf16_t*)x;
-  p.seg[0].B = (const tn::bf16_t*)w;
-  p.seg[0].lda = ldx;
-  p.seg[0].ldb = ldw;
-  p.seg[0].K = K;
-  p.seg[1] = p.seg[2] = p.seg[0];
-  p.stages = K / 64;
-  p.M = M;
-  p.N = N;
-  p.C = (tn::bf16_t*)out;
-  p.bias = (const tn::bf16_t*)bias;
-  p.ldc = ldc;
-  p.rope_cos = (const tn::bf16_t*)cos_t;
-  p.rope_sin = (const tn::bf16_t*)sin_t;
+  set_seg(p.seg[0], x, w, ldx, ldw, K);
+  p.C = (bf16_t*)out;
+  p.bias = (const bf16_t*)bias;
+  p.rope_cos = (const bf16_t*)cos_t;
+  p.rope_sin = (const bf16_t*)sin_t;
   p.rope_d = head_dim;
-  p.nbm = (M + BM - 1) / BM;
-  p.nbn = (N + BN - 1) / BN;
-  p.ntiles = p.nbm * p.nbn;
-  const int ncu = num_cus();
-  const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_ROPE>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
+  return launch_fused<EPI_ROPE, false>(p, M, N, ldc, BN, stream);
 }
 
 // The audio tower's MLP, first half: pre[M, N] = x[M, K] W[N, K]^T + bias AND act = gelu(pre) from one launch (exact-erf
@@ -2081,35 +2104,17 @@ int tn_gemm_bf16_rope(const void* x, const void* w, const void* bias, const void
 // >= the rows they span, 16-byte aligned bases.
 int tn_gemm_bf16_gelu_fwd(const void* x, const void* w, const void* bias, void* pre, void* act, int M, int N, int K,
                           long long ldx, long long ldw, long long ldc, void* stream) {
-  using namespace tn::gemm;
-  if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || (N % 8) || (ldx % 8) || (ldw % 8) || (ldc % 8) || ldc < N) return TN_EINVAL;
-  if (ldx < K || ldw < K) return TN_EINVAL;
-  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)pre | (uintptr_t)act) & 15) return TN_EINVAL;
-  if (((uintptr_t)bias & 7) || pre == act) return TN_EINVAL;
-  if ((long long)288 * ldx * 2 >= 0x7fffffffLL || (long long)288 * ldw * 2 >= 0x7fffffffLL) return TN_EINVAL;
+  if (M <= 0 || N <= 0 || (N % 8) || !row_operand_ok(x, ldx, K, K) || !row_operand_ok(w, ldw, K, K) ||
+      !out_ok(pre, ldc, N, 8) || !aligned(15, act) || !aligned(7, bias))
+    return TN_EINVAL;
+  if (pre == act) return TN_EINVAL;                  // (this entry alone has two outputs of one meaning to mix up)
   Params p;
   clear_params(p);
-  p.seg[0].A = (const tn::bf16_t*)x;
-  p.seg[0].B = (const tn::bf16_t*)w;
-  p.seg[0].lda = ldx;
-  p.seg[0].ldb = ldw;
-  p.seg[0].K = K;
-  p.seg[1] = p.seg[2] = p.seg[0];
-  p.stages = K / 64;
-  p.M = M;
-  p.N = N;
-  p.C = (tn::bf16_t*)pre;
-  p.C2 = (tn::bf16_t*)act;
-  p.bias = (const tn::bf16_t*)bias;
-  p.ldc = ldc;
-  p.nbm = (M + BM - 1) / BM;
-  p.nbn = (N + BN - 1) / BN;
-  p.ntiles = p.nbm * p.nbn;
-  const int ncu = num_cus();
-  const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, false, EPI_GELU_FWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
+  set_seg(p.seg[0], x, w, ldx, ldw, K);
+  p.C = (bf16_t*)pre;
+  p.C2 = (bf16_t*)act;
+  p.bias = (const bf16_t*)bias;
+  return launch_fused<EPI_GELU_FWD, false>(p, M, N, ldc, BN, stream);
 }
 
 // ... and the backward of its second half: d(pre)[M, I] = (dY[M, H] W2[H, I]) o gelu'(pre) — the product d(act) is formed in
@@ -2117,34 +2122,16 @@ int tn_gemm_bf16_gelu_fwd(const void* x, const void* w, const void* bias, void* 
 // I % 8 == 0, pitches % 8.
 int tn_gemm_bf16_gelu_bwd(const void* dy, const void* w2, const void* pre, void* dpre, int M, int I, int H, long long lddy,
                           long long ldw, long long ld, void* stream) {
-  using namespace tn::gemm;
-  if (M <= 0 || I <= 0 || H <= 0 || (H % 64) || (I % 8) || (lddy % 8) || (ldw % 8) || (ld % 8) || ld < I) return TN_EINVAL;
-  if (lddy < H) return TN_EINVAL;
-  if (((uintptr_t)dy | (uintptr_t)w2 | (uintptr_t)pre | (uintptr_t)dpre) & 15) return TN_EINVAL;
-  if ((long long)288 * lddy * 2 >= 0x7fffffffLL || ldw < I || ((long long)(H - 1) * ldw + I) * 2 >= 0x7fffffffLL)
+  if (M <= 0 || I <= 0 || (I % 8) || !row_operand_ok(dy, lddy, H, H) || !kmaj_operand_ok(w2, ldw, H, I, I) ||
+      !out_ok(dpre, ld, I, 8) || !aligned(15, pre))
     return TN_EINVAL;
   Params p;
   clear_params(p);
-  p.seg[0].A = (const tn::bf16_t*)dy;
-  p.seg[0].B = (const tn::bf16_t*)w2;
-  p.seg[0].lda = lddy;
-  p.seg[0].ldb = ldw;
-  p.seg[0].K = H;
-  p.seg[1] = p.seg[2] = p.seg[0];
-  p.stages = H / 64;
-  p.M = M;
-  p.N = I;
-  p.C = (tn::bf16_t*)dpre;
-  p.E1 = (const tn::bf16_t*)pre;
-  p.ldc = p.lde = ld;
-  p.nbm = (M + BM - 1) / BM;
-  p.nbn = (I + BN - 1) / BN;
-  p.ntiles = p.nbm * p.nbn;
-  const int ncu = num_cus();
-  const dim3 grid(persistent_now() && p.ntiles > ncu ? ncu : p.ntiles);
-  hipLaunchKernelGGL((gemm16_kernel<false, true, EPI_GELU_BWD>), grid, dim3(NT), 0, (hipStream_t)stream, p);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
+  set_seg(p.seg[0], dy, w2, lddy, ldw, H);
+  p.C = (bf16_t*)dpre;
+  p.E1 = (const bf16_t*)pre;
+  p.lde = ld;
+  return launch_fused<EPI_GELU_BWD, true>(p, M, I, ld, BN, stream);
 }
 
 // C[M,N] = A[M,K] · B[N,K]^T (+ bias) (+ C if accumulate); optional transposed copy Ct[N,M]: the single-segment,

@@ -10,6 +10,7 @@ TrainSpec loss / acc functions (hook 3).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -520,76 +521,76 @@ def gemm(segs, a_kmaj: bool = False, b_kmaj: bool = False, bias: Optional[torch.
         if accumulate:
             raise _C.KernelError("gemm: accumulate needs `out`")
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a0.device)
-    if out.dtype == torch.float32:
+    n = len(segs)
+    f32 = out.dtype == torch.float32
+    wgrad_mode = a_kmaj and b_kmaj and n == 1 and bias is None and out_t is None
+    if f32:
         # weight gradient straight into an fp32 buffer (the data-parallel engine's reduce-scatter input)
-        if not (a_kmaj and b_kmaj and len(segs) == 1 and bias is None and out_t is None):
+        if not wgrad_mode:
             raise _C.KernelError("gemm: fp32 output exists for the single-segment weight-gradient mode only")
         if out.stride(1) != 1 or tuple(out.shape) != (M, N) or not a0.is_cuda:
             raise _C.KernelError("gemm: bad fp32 `out`")
-        split = split_k(M, N, Ks[0], True, True) if SPLIT_K else 1
-        ws = None
-        if split > 1:
-            ws = torch.empty(split * (((M + 255) // 256) * ((N + 255) // 256) * 65536 + (M + 255) // 256 * 256),
-                             dtype=torch.float32, device=a0.device)
-        if bias_grad is not None:
-            _check_bias_grad(bias_grad, M, a0)
-            _C.check(_C.lib().tn_gemm_bf16_wgrad_bias(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], _p(out), _p(bias_grad),
-                                                      M, N, out.stride(0), int(accumulate), 1, split, _p(ws),
-                                                      ws.numel() * 4 if ws is not None else 0, _cur()),
-                     "tn_gemm_bf16_wgrad_bias")
+    else:
+        if out.stride(1) != 1 or tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16:
+            raise _C.KernelError("gemm: bad `out`")
+        if bias is not None:
+            bias = _c(bias).to(torch.bfloat16)
+        if not a0.is_cuda:
+            raise _C.KernelError("touchnet_amd kernels need device (HIP) tensors; got a CPU tensor")
+        if addend is not None:
+            if (n != 1 or accumulate or out_t is not None or bias_grad is not None or addend.dtype != torch.bfloat16
+                    or tuple(addend.shape) != (M, N) or addend.stride(1) != 1 or addend.data_ptr() == out.data_ptr()):
+                raise _C.KernelError("gemm: addend needs one segment, a bf16 [M, N] matrix with contiguous rows that is not `out`")
+            _C.check(_C.lib().tn_gemm_bf16_addend(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], int(a_kmaj), int(b_kmaj),
+                                                  _p(out), _p(bias), _p(addend), addend.stride(0), M, N, out.stride(0), _cur()),
+                     "tn_gemm_bf16_addend")
             return out
-        _C.check(_C.lib().tn_gemm_bf16_wgrad_f32(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], _p(out), M, N,
-                                                 out.stride(0), int(accumulate), split, _p(ws),
-                                                 ws.numel() * 4 if ws is not None else 0, _cur()), "tn_gemm_bf16_wgrad_f32")
-        return out
-    if out.stride(1) != 1 or tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16:
-        raise _C.KernelError("gemm: bad `out`")
-    if bias is not None:
-        bias = _c(bias).to(torch.bfloat16)
-    n = len(segs)
-    if not a0.is_cuda:
-        raise _C.KernelError("touchnet_amd kernels need device (HIP) tensors; got a CPU tensor")
-    if addend is not None:
-        if (n != 1 or accumulate or out_t is not None or bias_grad is not None or addend.dtype != torch.bfloat16
-                or tuple(addend.shape) != (M, N) or addend.stride(1) != 1 or addend.data_ptr() == out.data_ptr()):
-            raise _C.KernelError("gemm: addend needs one segment, a bf16 [M, N] matrix with contiguous rows that is not `out`")
-        _C.check(_C.lib().tn_gemm_bf16_addend(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], int(a_kmaj), int(b_kmaj),
-                                              _p(out), _p(bias), _p(addend), addend.stride(0), M, N, out.stride(0), _cur()),
-                 "tn_gemm_bf16_addend")
-        return out
-    split = 1
-    if bias_grad is not None:
-        if not (a_kmaj and b_kmaj and n == 1 and bias is None and out_t is None):
+    lib = _C.lib()
+    if f32 or bias_grad is not None:
+        # the weight gradient's own entry points: fp32 or bf16 output, with or without the bias gradient
+        if not wgrad_mode:
             raise _C.KernelError("gemm: bias_grad exists for the single-segment weight-gradient mode only")
-        _check_bias_grad(bias_grad, M, a0)
         split = split_k(M, N, Ks[0], True, True) if SPLIT_K else 1
-        ws = None
-        if split > 1:
-            ws = torch.empty(split * (((M + 255) // 256) * ((N + 255) // 256) * 65536 + (M + 255) // 256 * 256),
-                             dtype=torch.float32, device=a0.device)
-        _C.check(_C.lib().tn_gemm_bf16_wgrad_bias(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], _p(out), _p(bias_grad), M,
-                                                  N, out.stride(0), int(accumulate), 0, split, _p(ws),
-                                                  ws.numel() * 4 if ws is not None else 0, _cur()), "tn_gemm_bf16_wgrad_bias")
+        ws, ws_bytes = _splitk_workspace(M, N, split, bias_grad is not None, a0.device)
+        if bias_grad is None:
+            _C.check(lib.tn_gemm_bf16_wgrad_f32(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], _p(out), M, N, out.stride(0),
+                                                int(accumulate), split, _p(ws), ws_bytes, _cur()), "tn_gemm_bf16_wgrad_f32")
+        else:
+            _check_bias_grad(bias_grad, M, a0)
+            _C.check(lib.tn_gemm_bf16_wgrad_bias(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], _p(out), _p(bias_grad), M, N,
+                                                 out.stride(0), int(accumulate), int(f32), split, _p(ws), ws_bytes, _cur()),
+                     "tn_gemm_bf16_wgrad_bias")
         return out
-    if n == 1 and out_t is None and SPLIT_K:
-        split = split_k(M, N, Ks[0], a_kmaj, b_kmaj)
+    split = split_k(M, N, Ks[0], a_kmaj, b_kmaj) if n == 1 and out_t is None and SPLIT_K else 1
     if split > 1:
-        tiles = ((M + 255) // 256) * ((N + 255) // 256)
-        ws = torch.empty(split * tiles * 65536, dtype=torch.float32, device=a0.device)
-        _C.check(_C.lib().tn_gemm_bf16_splitk(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], int(a_kmaj), int(b_kmaj),
-                                              _p(out), _p(bias), M, N, out.stride(0), int(accumulate), split, 0,
-                                              _p(ws), ws.numel() * 4, _cur()), "tn_gemm_bf16_splitk")
+        ws, ws_bytes = _splitk_workspace(M, N, split, False, a0.device)
+        _C.check(lib.tn_gemm_bf16_splitk(_p(a0), _p(b0), a0.stride(0), b0.stride(0), Ks[0], int(a_kmaj), int(b_kmaj), _p(out),
+                                         _p(bias), M, N, out.stride(0), int(accumulate), split, 0, _p(ws), ws_bytes, _cur()),
+                 "tn_gemm_bf16_splitk")
         return out
-    import ctypes as C
-    Ap = (C.c_void_p * n)(*[a.data_ptr() for a, _ in segs])
-    Bp = (C.c_void_p * n)(*[b.data_ptr() for _, b in segs])
-    la = (C.c_longlong * n)(*[a.stride(0) for a, _ in segs])
-    lb = (C.c_longlong * n)(*[b.stride(0) for _, b in segs])
-    Kc = (C.c_int * n)(*Ks)
-    _C.check(_C.lib().tn_gemm_bf16(Ap, Bp, la, lb, Kc, n, int(a_kmaj), int(b_kmaj), _p(out), _p(out_t), _p(bias), M, N,
-                                   out.stride(0), out_t.stride(0) if out_t is not None else 0, int(accumulate),
-                                   _cur()), "tn_gemm_bf16")
+    _C.check(lib.tn_gemm_bf16(*_operand_arrays(segs), _carr(ctypes.c_int, Ks), n, int(a_kmaj), int(b_kmaj), _p(out), _p(out_t),
+                              _p(bias), M, N, out.stride(0), out_t.stride(0) if out_t is not None else 0, int(accumulate),
+                              _cur()), "tn_gemm_bf16")
     return out
+
+
+def _splitk_workspace(M, N, split, with_bias_grad, device):
+    """``(workspace, its size in bytes)`` of a product cut into ``split`` parts — ``(None, 0)`` when it is not split; the
+    library owns the layout (tn_gemm_splitk_workspace_bytes)."""
+    if split <= 1:
+        return None, 0
+    need = int(_C.lib().tn_gemm_splitk_workspace_bytes(M, N, split, int(with_bias_grad), 0))
+    return torch.empty(need // 4, dtype=torch.float32, device=device), need
+
+
+def _carr(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+def _operand_arrays(pairs):
+    """The ctypes arrays ``A, B, lda, ldb`` of tn_gemm_bf16 / tn_gemm_bf16_grouped: base addresses and row pitches."""
+    return (_carr(ctypes.c_void_p, [a.data_ptr() for a, _ in pairs]), _carr(ctypes.c_void_p, [b.data_ptr() for _, b in pairs]),
+            _carr(ctypes.c_longlong, [a.stride(0) for a, _ in pairs]), _carr(ctypes.c_longlong, [b.stride(0) for _, b in pairs]))
 
 
 def _check_bias_grad(bias_grad, M, like):
@@ -604,7 +605,6 @@ def gemm_grouped_wgrad(pairs, outs=None, accumulate: bool = False):
     (tn_gemm_bf16_grouped): the tile lists of the products are concatenated, so that only the remainder of the WHOLE list
     — not of every product — is left for a partial last round, and that remainder runs split-K.  ``outs``: bf16 or fp32
     [M_g, N_g] matrices (all of one dtype) to write (or, ``accumulate``, to add to); default new bf16 tensors."""
-    import ctypes as C
     n = len(pairs)
     if not 1 <= n <= 3:
         raise _C.KernelError("gemm_grouped_wgrad: 1..3 products")
@@ -621,19 +621,15 @@ def gemm_grouped_wgrad(pairs, outs=None, accumulate: bool = False):
         if (o.dtype != outs[0].dtype or o.dtype not in (torch.float32, torch.bfloat16) or o.stride(1) != 1
                 or tuple(o.shape) != (a.shape[1], b.shape[1])):
             raise _C.KernelError("gemm_grouped_wgrad: bad `outs`")
-    Ms = (C.c_int * n)(*[a.shape[1] for a, _ in pairs])
-    Ns = (C.c_int * n)(*[b.shape[1] for _, b in pairs])
-    Ks = (C.c_int * n)(*[a.shape[0] for a, _ in pairs])
+    Ms = _carr(ctypes.c_int, [a.shape[1] for a, _ in pairs])
+    Ns = _carr(ctypes.c_int, [b.shape[1] for _, b in pairs])
+    Ks = _carr(ctypes.c_int, [a.shape[0] for a, _ in pairs])
     need = int(_C.lib().tn_gemm_grouped_workspace_bytes(Ms, Ns, Ks, n))
     ws = torch.empty(need // 4, dtype=torch.float32, device=outs[0].device) if need > 0 else None
-    Ap = (C.c_void_p * n)(*[a.data_ptr() for a, _ in pairs])
-    Bp = (C.c_void_p * n)(*[b.data_ptr() for _, b in pairs])
-    Cp = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-    la = (C.c_longlong * n)(*[a.stride(0) for a, _ in pairs])
-    lb = (C.c_longlong * n)(*[b.stride(0) for _, b in pairs])
-    lc = (C.c_longlong * n)(*[o.stride(0) for o in outs])
-    _C.check(_C.lib().tn_gemm_bf16_grouped(Ap, Bp, la, lb, Ks, Cp, lc, Ms, Ns, n, 1, 1, int(accumulate), int(f32), _p(ws),
-                                           need, _cur()), "tn_gemm_bf16_grouped")
+    Ap, Bp, la, lb = _operand_arrays(pairs)
+    _C.check(_C.lib().tn_gemm_bf16_grouped(Ap, Bp, la, lb, Ks, _carr(ctypes.c_void_p, [o.data_ptr() for o in outs]),
+                                           _carr(ctypes.c_longlong, [o.stride(0) for o in outs]), Ms, Ns, n, 1, 1,
+                                           int(accumulate), int(f32), _p(ws), need, _cur()), "tn_gemm_bf16_grouped")
     return list(outs)
 
 
