@@ -180,6 +180,18 @@ int tn_feat_augment(const float* x, float* y, int T, int F, int out_rows, const 
  * float; built by the host side, touchnet_amd/functional.py::speed_perturb).  Not bit-comparable with libsox. */
 int tn_resample_polyphase(const float* x, float* y, const float* tab, long long n_in, long long n_out, int p, int q,
                           int ntap, void* stream);
+/* Sample-rate conversion, touchnet/data/functions.py:83-96 (`torchaudio.transforms.Resample(orig, new)`, torchaudio's
+ * defaults: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99): x [n_in] -> y [n_out] fp32.  With o = orig / gcd,
+ * n = new_ / gcd, output m sits at input position m o / n (integer part i, phase r = (m o) mod n) and
+ * y[m] = sum_j tab[r][j] x[i - ntap / 2 + 1 + j], x = 0 outside [0, n_in); tab: device float [n][ntap], torchaudio's
+ * kernel in float32 without its zero columns (touchnet_amd/functional.py::sinc_resample_table).  x is fp32, or int16 PCM
+ * read as v * 2^-15 when x_is_pcm16 (exact: the same bits as converting first).  One launch, no allocation, no
+ * synchronisation; all index arithmetic is 64-bit.
+ * -22 (before any launch) for a null pointer, y == x, n_in < 1, n_out outside [1, ceil(n_in new_ / orig)], orig < 1,
+ * new_ < 1, ntap < 2, odd or above 12286 (a workgroup stages the samples of its outputs, ntap of them for one, in
+ * 48 KiB of LDS). */
+int tn_resample_sinc(const void* x, int x_is_pcm16, float* y, const float* tab, long long n_in, long long n_out,
+                     int orig, int new_, int ntap, void* stream);
 
 /* ---- fused AdamW on fp32 master weights with bf16 shadow write-back and device-side
  *      skip-on-nonfinite — touchnet/utils/optimizer.py:157-172 + touchnet/bin/train.py:458-474.

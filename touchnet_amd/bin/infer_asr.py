@@ -7,7 +7,8 @@ touchnet/models/touch_audio/inference_touch_audio.py (same inputs, same output l
 CKPT_DIR holds HF-format `*.safetensors` (the parameter names of TouchAudioForCausalLM are Hugging Face's) and a model
 config (`config.json` in the directory, else `../../model_config.json` as the reference reads it); the data config comes
 from `--data_config` or `CKPT_DIR/../../data_config.json` (fbank, 80 bins, stacking to the projector width when absent).
-`data.list`: one JSON object per line with at least "key" and "wav" (16-bit PCM wav).  Output:
+`data.list`: one JSON object per line with at least "key" and "wav" (16-bit PCM wav of any sample rate; other rates
+than 16 kHz are resampled on the device, see read_wav).  Output:
 OUT/part_{i+1}_of_{n}, one JSON line per utterance: {"label": the input line, "predict_ids": [...], "predict": text} —
 "predict" only when CKPT_DIR has a tokenizer.  One GPU per process; `--shard_index / --num_shards` split the list
 without collectives.
@@ -26,6 +27,7 @@ import torch
 
 from touchnet_amd.data import functions as stages
 from touchnet_amd.generation import GenerationConfig
+from touchnet_amd.models.backend import ops
 from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
 from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
 
@@ -82,15 +84,22 @@ def data_config(args, model) -> types.SimpleNamespace:
 
 
 def read_wav(path: str) -> torch.Tensor:
-    """16-bit PCM wav -> int16 [1, N] (first channel)."""
+    """16-bit PCM wav (first channel) -> the 16 kHz waveform [1, N]: the int16 samples themselves, on the host, for a
+    16 kHz file; a file of any other rate is resampled on the device (functional.resample: torchaudio's windowed-sinc
+    formula) and comes back as fp32 [1, ceil(N 16000 / rate)] there.  The reference's scripts resample with
+    `ffmpeg -ar 16000`, a different algorithm: the same band-limited signal, not the same samples, and no parity with it
+    is claimed."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: 16-bit PCM only")
         ch, rate = w.getnchannels(), w.getframerate()
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, ch)[:, 0].copy()
+    pcm = torch.from_numpy(pcm)
     if rate != 16000:
-        raise ValueError(f"{path}: {rate} Hz; the device frontend is 16 kHz only")
-    return torch.from_numpy(pcm)[None]
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{path}: {rate} Hz is resampled on the MI355X (there is no CPU path)")
+        return ops().resample(pcm.to(torch.device("cuda", torch.cuda.current_device())), rate, 16000)[None]
+    return pcm[None]
 
 
 def features(wavs, dcfg) -> list:

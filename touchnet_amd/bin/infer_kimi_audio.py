@@ -10,7 +10,8 @@ touchnet_amd.models.kimi_audio.inference_kimi_audio.generate_kimi with the defau
 CKPT_DIR is an HF checkpoint directory: config.json (the keys of Kimi-Audio-7B.json, with `speech_encoder_config` and
 `speech_tokenizer_config`), *.safetensors under MoonshotKimiaForCausalLM's parameter names (`model.*`, `lm_head.*`,
 `mimo_output.*`, `speech_encoder.*`, `speech_tokenizer.*`) and the tokenizer files (loaded locally with AutoTokenizer,
-trust_remote_code as in the reference).  `data.list`: one JSON object per line with at least "wav" (16-bit PCM, 16 kHz).
+trust_remote_code as in the reference).  `data.list`: one JSON object per line with at least "wav" (16-bit PCM; a rate
+other than 16 kHz is resampled on the device, infer_asr.read_wav).
 Output: OUT/part_{i+1}_of_{n}, one JSON line per utterance, {"label": the input line, "predict": text}.  The draws of a
 sampled run are keyed by the utterance's line number in the data list, so it decodes the same whatever its batch or shard.
 """

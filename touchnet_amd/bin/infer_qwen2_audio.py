@@ -10,7 +10,8 @@ CKPT_DIR is an HF checkpoint directory: config.json, generation_config.json, *.s
 (loaded locally with AutoTokenizer).  Parameter names: Qwen2AudioForConditionalGeneration's of transformers 4.51
 (`audio_tower.*`, `multi_modal_projector.*`, `language_model.model.*`, `language_model.lm_head.*`) or of transformers 5
 (`model.audio_tower.*`, `model.multi_modal_projector.*`, `model.language_model.*`, `lm_head.*`).
-`data.list`: one JSON object per line with at least "wav" (16-bit PCM, 16 kHz).  As in the reference, a batch whose longest
+`data.list`: one JSON object per line with at least "wav" (16-bit PCM; a rate
+other than 16 kHz is resampled on the device, infer_asr.read_wav).  As in the reference, a batch whose longest
 prompt exceeds --max_length is skipped; the budget is max_length minus the longest prompt unless the generation config
 sets max_new_tokens.  Output: OUT/part_{i+1}_of_{n}, one JSON line per utterance, {"label": the input line, "predict":
 text}.  The draws of an utterance are keyed by its line number in the data list, so it decodes the same whatever its

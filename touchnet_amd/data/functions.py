@@ -2,6 +2,7 @@
 `f(data_iter, config) -> iterator` as touchnet/data/functions.py, so they compose with the reference's
 MidLevelTouchDatapipe(source, f, *args) (touchnet/data/datapipe.py:183-213) unchanged.
 
+    audio_resample                      functions.py:83-96
     audio_compute_fbank                 functions.py:117-134
     audio_compute_log_mel_spectrogram   functions.py:159-190
     audiofeat_spec_aug / _sub / _trim   functions.py:193-255   (draws on the host, applied in one device pass)
@@ -18,10 +19,14 @@ import torch
 from touchnet_amd.models.backend import ops
 
 
-def _dev_wave(sample):
-    w = sample["waveform"]
+def _on_device(w):
     if not w.is_cuda and torch.cuda.is_available():      # (without a GPU the HIP ops below refuse the tensor loudly)
         w = w.to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+    return w
+
+
+def _dev_wave(sample):
+    w = _on_device(sample["waveform"])
     if w.dtype == torch.int16:
         w = ops().pcm16_to_float(w)
     return w.reshape(-1)
@@ -131,13 +136,16 @@ def audiofeat_augment(data, config):
 
 
 def audio_resample(data, config):
-    """functions.py:83-96.  Every reference recipe stores and trains on 16 kHz audio (`--audio_resample_rate 16000`), where
-    the stage is the identity; another rate would need torchaudio's windowed-sinc resampler, which has no kernel here."""
+    """functions.py:83-96: a sample whose `sample_rate` is not `config.audio_resample_rate` is resampled ON THE DEVICE by
+    torchaudio's own formula (functional.resample: `torchaudio.transforms.Resample(orig, new)` at its defaults, fp32 or
+    int16 PCM in, fp32 out) and carries the new rate; a sample already at that rate passes through untouched, its
+    waveform left where it is."""
     for sample in data:
         rate = getattr(config, "audio_resample_rate", 16000)
         if "sample_rate" in sample and sample["sample_rate"] != rate:
-            raise NotImplementedError(f"audio_resample {sample['sample_rate']} -> {rate}: "
-                                      f"resample when the dataset is written (the device frontend is 16 kHz only)")
+            w = ops().resample(_on_device(sample["waveform"]).reshape(-1), sample["sample_rate"], rate)
+            sample["waveform"] = w.reshape(1, -1)
+            sample["sample_rate"] = rate
         yield sample
 
 

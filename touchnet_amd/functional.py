@@ -1511,6 +1511,70 @@ def speed_perturb(wave: torch.Tensor, speed: float) -> torch.Tensor:
     return L.resample_polyphase(_c(wave).float(), tab, p_, q_, max(n_out, 1))
 
 
+RESAMPLE_WIDTH = 6          # torchaudio's lowpass_filter_width: zero crossings of the sinc on each side
+RESAMPLE_ROLLOFF = 0.99     # torchaudio's rolloff: cutoff as a fraction of the narrower Nyquist band
+RESAMPLE_MAX_RATIO = 64     # o / n within [1 / 64, 64] ...
+RESAMPLE_MAX_TABLE = 2 ** 22   # ... and at most this many table entries (16 MiB of float32)
+_RESAMPLE_TABLES = {}
+
+
+def _resample_geometry(orig: int, new: int):
+    """(o, n, base, width, half): the rates in lowest terms, torchaudio's base_freq and padding width, and half the
+    number of columns of its kernel that are not zero"""
+    orig, new = int(orig), int(new)
+    if orig < 1 or new < 1:
+        raise ValueError(f"resample: sample rates {orig} -> {new} Hz must be positive")
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    base = min(o, n) * RESAMPLE_ROLLOFF
+    return o, n, base, int(math.ceil(RESAMPLE_WIDTH * o / base)), int(math.floor(RESAMPLE_WIDTH * o / base)) + 1
+
+
+def sinc_resample_table(orig: int, new: int):
+    """(o, n, ntap, table [n, ntap] float64) of `torchaudio.transforms.Resample(orig, new)` at torchaudio's defaults
+    (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), o / n = orig / new in lowest terms.  torchaudio's kernel is
+        K[j][k] = sinc(t) cos(t pi / 12)^2 base / o,  t = clamp((-j / n + (k - width) / o) base, -6, 6),
+        base = 0.99 min(o, n), width = ceil(6 o / base), j < n, k < 2 width + o,
+    applied to the waveform padded by (width, width + o) at stride o.  Row r of the table is phase j = r o^-1 mod n of K
+    — the phase of every output m with (m o) mod n = r — cut to the ntap = 2 floor(6 o / base) + 2 columns around input
+    floor(m o / n) in the layout of tn_resample_polyphase; each entry is K's expression evaluated in K's order at its
+    (j, k), and the columns left out are exactly 0 once rounded to float32 (|t| clamps to 6 there, where the window is
+    cos(pi / 2)^2 ~ 4e-33)."""
+    import numpy as np
+    o, n, base, width, half = _resample_geometry(orig, new)
+    ntap = 2 * half
+    r = np.arange(n, dtype=np.int64)
+    j = (r * pow(o, -1, n)) % n if n > 1 else r                               # (j o) mod n = r
+    k = (width + (j * o) // n - half + 1)[:, None] + np.arange(ntap, dtype=np.int64)[None, :]
+    t = (-j.astype(np.float64)[:, None] / n + (k - width).astype(np.float64) / o) * base
+    t = np.clip(t, -float(RESAMPLE_WIDTH), float(RESAMPLE_WIDTH))
+    w = np.cos(t * math.pi / RESAMPLE_WIDTH / 2) ** 2
+    t = t * math.pi
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tab = np.where(t == 0, 1.0, np.sin(t) / t) * w * (base / o)
+    tab[(k < 0) | (k >= 2 * width + o)] = 0.0                                 # (outside K: the padding's zeros)
+    return o, n, ntap, tab
+
+
+def resample(wave: torch.Tensor, orig: int, new: int) -> torch.Tensor:
+    """1-D fp32 or int16 PCM waveform [N] on the device at `orig` Hz -> fp32 [ceil(N new / orig)] at `new` Hz
+    (touchnet/data/functions.py:83-96: torchaudio.transforms.Resample(orig, new); int16 is read as v / 32768)."""
+    o, n, _, _, half = _resample_geometry(orig, new)
+    if o == n:
+        return wave
+    if o > RESAMPLE_MAX_RATIO * n or n > RESAMPLE_MAX_RATIO * o or n * 2 * half > RESAMPLE_MAX_TABLE:
+        raise ValueError(f"resample: {orig} -> {new} Hz needs a ratio within [1/{RESAMPLE_MAX_RATIO}, "
+                         f"{RESAMPLE_MAX_RATIO}] and a filter table of at most {RESAMPLE_MAX_TABLE} entries "
+                         f"(this one: {n} phases x {2 * half} taps)")
+    if not wave.is_cuda or wave.dim() != 1 or wave.numel() == 0 or wave.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError("resample: expects a non-empty 1-D fp32 or int16 device waveform")
+    key = (o, n, wave.device)
+    if key not in _RESAMPLE_TABLES:
+        _RESAMPLE_TABLES[key] = torch.from_numpy(sinc_resample_table(o, n)[3]).to(torch.float32).to(wave.device).contiguous()
+    n_out = -((-wave.numel() * n) // o)
+    return L.resample_sinc(_c(wave), _RESAMPLE_TABLES[key], o, n, n_out)
+
+
 def feat_augment(feat: torch.Tensor, t_masks=(), f_masks=(), subs=(), out_rows: Optional[int] = None) -> torch.Tensor:
     """fp32 [T, F] -> fp32 [out_rows, F]: zero stripes (spec_aug), row substitutions from earlier rows (spec_sub) and the
     tail trim (spec_trim) of touchnet/data/functions.py:193-255 in one pass; the draws come from the caller."""

@@ -833,6 +833,14 @@ def resample_polyphase(wave: Tensor, tab: Tensor, p: int, q: int, n_out: int) ->
     return out
 
 
+def resample_sinc(wave: Tensor, tab: Tensor, orig: int, new: int, n_out: int) -> Tensor:
+    """tn_resample_sinc on a 1-D fp32 or int16 device waveform"""
+    out = torch.empty(n_out, dtype=torch.float32, device=wave.device)
+    _C.check(_lib().tn_resample_sinc(_p(wave), int(wave.dtype == torch.int16), _p(out), _p(tab), wave.numel(), int(n_out),
+                                     int(orig), int(new), int(tab.shape[1]), _cur()), "tn_resample_sinc")
+    return out
+
+
 def feat_augment(feat: Tensor, t_masks, f_masks, subs, out_rows: int) -> Tensor:
     """tn_feat_augment: the draws travel as kernel arguments (host int arrays), so this is a plain function, not a
     registered op (no tensor carries them)."""
