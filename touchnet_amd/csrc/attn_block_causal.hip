@@ -193,7 +193,7 @@ extern "C" int tn_attn_block_causal_fwd(const void* q, const void* k, const void
   dim3 grid((T + tn::kBcRows - 1) / tn::kBcRows, Nh, B), blk(256);
   hipLaunchKernelGGL(tn::attn_block_causal_fwd_kernel, grid, blk, 0, (hipStream_t)stream, (const tn::bf16_t*)q,
                      (const tn::bf16_t*)k, (const tn::bf16_t*)v, (tn::bf16_t*)o, seg_start, key_end, T, Nh, block,
-                     scale * 1.4426950408889634f);
+                     scale * tn::kLog2e);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }

@@ -34,13 +34,6 @@ namespace tn {
 // barriers either 206 us, no MFMA/softmax 134 us).  The per-tile document-id statistics come from an LDS window
 // filled once per workgroup instead of dependent scalar loads per tile.
 // ------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 struct QStage {      // one stage of the stream; every field is wave-uniform (SGPRs)
   int valid;
   int qsb;           // global position of the stage's first query row
@@ -76,9 +69,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   // registers for the same two waves per SIMD; its row loads and stores are half as many) and keeps the direct form.
   using KTile = PTile<32, D>;
   constexpr int KIMGB = KTile::SIZE * 2;
-  constexpr int OSTR = 2 * D + 16;
   constexpr bool R6 = D == 128;
-  constexpr int RING0 = NST * STAGEB, RING1 = 4 * 2 * 32 * OSTR, RING2 = 4 * 2 * KIMGB;
+  constexpr int RING0 = NST * STAGEB, RING1 = 4 * 2 * WholeRows<D>::BYTES, RING2 = 4 * 2 * KIMGB;
   constexpr int RINGX = RING0 > RING1 ? (RING0 > RING2 ? RING0 : RING2) : (RING1 > RING2 ? RING1 : RING2);
   constexpr int RING = D == 128 ? RINGX : RING0;
   __shared__ __attribute__((aligned(1024))) char smem[RING + (LCAP + NST) * 32 + 16 + kListPre * 16];
@@ -264,6 +256,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
 
   // ---- LDS-DMA sources: descriptors over this batch row's slices, lane part of the offsets
   const size_t qrow_elems = (size_t)Nh * D;
+  // (BatchRows' arithmetic written out, here and for K / V above: through the struct hipcc groups the byte count's product
+  // differently and this kernel's assembly changes)
   const uint32_t q_bytes = (uint32_t)min((size_t)qv.rpb * qrow_elems * 2, (size_t)0x7fffffff);
   const __amdgpu_buffer_rsrc_t rq =
       __builtin_amdgcn_make_buffer_rsrc((void*)(Q + (size_t)b * qv.rpb * qrow_elems), 0, q_bytes, 0x00020000);
@@ -452,9 +446,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
       }
     }
   } else {
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
-    char* obv = smem + wave * (2 * 32 * OSTR);
-    char* obk = obv + 32 * OSTR;
+    using WR = WholeRows<D>;
+    char* obv = smem + wave * (2 * WR::BYTES);
+    char* obk = obv + WR::BYTES;
 #pragma unroll
     for (int db = 0; db < DBLK; ++db) {
 #pragma unroll
@@ -462,24 +456,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
         if (DO_DV) {
           const u32x2_t o = {pack2bf(dvacc[db][4 * r4 + 0], dvacc[db][4 * r4 + 1]),
                              pack2bf(dvacc[db][4 * r4 + 2], dvacc[db][4 * r4 + 3])};
-          *reinterpret_cast<u32x2_t*>(obv + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o;
+          *WR::put(obv, l31, hi, db, r4) = o;
         }
         if (DO_DK) {
           const u32x2_t o = {pack2bf(dkacc[db][4 * r4 + 0] * scale, dkacc[db][4 * r4 + 1] * scale),
                              pack2bf(dkacc[db][4 * r4 + 2] * scale, dkacc[db][4 * r4 + 3] * scale)};
-          *reinterpret_cast<u32x2_t*>(obk + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o;
+          *WR::put(obk, l31, hi, db, r4) = o;
         }
       }
     }
-    constexpr int CPR = D / 8, RPI = 64 / CPR;           // 16-byte chunks per row, rows per store instruction
+    constexpr int CPR = WR::CPR, RPI = WR::RPI;
     const int cc = lane % CPR, r0 = lane / CPR;
     const size_t off = (((size_t)b * T + wk0) * Nkv + hk) * D + cc * 8;
 #pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
+    for (int i = 0; i < WR::NI; ++i) {
       const int row = i * RPI + r0;
       u32x4_t v4 = {0, 0, 0, 0}, k4 = {0, 0, 0, 0};
-      if (DO_DV) v4 = *reinterpret_cast<const u32x4_t*>(obv + row * OSTR + cc * 16);
-      if (DO_DK) k4 = *reinterpret_cast<const u32x4_t*>(obk + row * OSTR + cc * 16);
+      if (DO_DV) v4 = *WR::get(obv, row, cc);
+      if (DO_DK) k4 = *WR::get(obk, row, cc);
       if (wk0 + row < T) {
         if (DO_DV) *reinterpret_cast<u32x4_t*>(dV + off + (size_t)row * Nkv * D) = v4;
         if (DO_DK) *reinterpret_cast<u32x4_t*>(dK + off + (size_t)row * Nkv * D) = k4;
@@ -511,11 +505,10 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
                            const float* lse2, float* delta, void* dq, void* dk, void* dv, const int* doc,
                            const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, QView qv,
                            void* stream, const void* rope_cos = nullptr, const void* rope_sin = nullptr) {
-  if (B <= 0 || T <= 0 || Nh <= 0 || Nkv <= 0 || Nh % Nkv) return TN_EINVAL;
-  if (D != 64 && D != 128) return TN_EINVAL;
+  if (!attn_shape_ok(B, T, Nh, Nkv, D)) return TN_EINVAL;
   const AttnMeta m = make_attn_meta(meta, B, T);
   hipStream_t st = (hipStream_t)stream;
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   dim3 gk(Nkv, (T + 127) / 128, B), block(256);
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v, *dO = (const bf16_t*)dout;
   // rope_cos / rope_sin (tn_attn_bwd_rope): dq / dk are wanted as gradients of the UN-rotated q / k.  The causal D = 128
@@ -549,7 +542,7 @@ static int attn_bwd_launch(const void* q, const void* k, const void* v, const vo
 int tn_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse2,
                 float* delta, void* dq, void* dk, void* dv, const int* doc, const int* meta, int B, int T, int Nh,
                 int Nkv, int D, float scale, void* stream) {
-  const QView qv = {1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull};
+  const QView qv = QView::whole(T);
   return attn_bwd_launch(q, k, v, o, dout, lse2, delta, dq, dk, dv, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }
 
@@ -562,7 +555,7 @@ int tn_attn_bwd_rope(const void* q, const void* k, const void* v, const void* o,
                      float* delta, void* dq, void* dk, void* dv, const int* doc, const int* meta, int B, int T, int Nh,
                      int Nkv, int D, float scale, const void* cos_t, const void* sin_t, void* stream) {
   if (cos_t == nullptr || sin_t == nullptr || (((uintptr_t)cos_t | (uintptr_t)sin_t) & 15)) return TN_EINVAL;
-  const QView qv = {1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull};
+  const QView qv = QView::whole(T);
   return attn_bwd_launch(q, k, v, o, dout, lse2, delta, dq, dk, dv, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream, cos_t,
                          sin_t);
 }
@@ -571,7 +564,7 @@ int tn_attn_bwd_rope(const void* q, const void* k, const void* v, const void* o,
 int tn_attn_bwd_bidir(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse2,
                       float* delta, void* dq, void* dk, void* dv, const int* doc, const int* meta, int B, int T, int Nh,
                       int Nkv, int D, float scale, void* stream) {
-  QView qv = {1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull};
+  QView qv = QView::whole(T);
   qv.bidir = 1;
   return attn_bwd_launch(q, k, v, o, dout, lse2, delta, dq, dk, dv, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }

@@ -26,25 +26,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
     const bf16_t* __restrict__ rsin) {
   // O != null: this kernel ALSO forms delta = rowsum(dO o O) of its 128 query rows and writes it to `Delta` for the
   // dK / dV pass, which is launched BEHIND it.  O == null: `Delta` is read.
-  using namespace fstream;
-  constexpr int BM = 128, BN = 64, NST = 2;
-  constexpr int KSTEPS = D / 16, DBLK = D / 32;
-  using Tile = PTile<BN, D>;
+  using G = StreamGeom<D>;
+  using Tile = typename G::Tile;
   using QTile = PTile<32, D>;                   // a wave's private 32-row image of Q / dO
-  constexpr int IMGB = Tile::SIZE * 2;          // bytes of one panel image
+  constexpr int BM = G::BM, BN = G::BN, NST = G::NST, KSTEPS = G::KSTEPS, DBLK = G::DBLK, IMGB = G::IMGB;
+  constexpr int STAGEB = G::STAGEB, CAP = G::CAP;
   constexpr int QIMGB = QTile::SIZE * 2;
-  constexpr int NPC = Tile::NP * (BN / 16);     // 1-KiB DMA pieces per image: 16 rows of one panel each
-  constexpr int PPW = NPC / 4;                  // pieces per wave and image
-  constexpr int OSTR = 2 * D + 16;              // row stride (bytes) of the dQ staging image
-  constexpr int STAGE_KV = 2 * IMGB + 4 * 256;  // {K image | V image | doc ids[64] per wave}
-  constexpr int STAGEB = STAGE_KV > BM * OSTR ? STAGE_KV : BM * OSTR;
-  constexpr int CAP = 192;                      // tile-list chunk
   static_assert(4 * 2 * QIMGB <= NST * STAGEB, "the waves' private Q / dO images live in the ring area");
-  // ONE LDS variable (attn_bwd.hip explains why two would serialise the DMA ring)
-  __shared__ __attribute__((aligned(1024))) char smem[NST * STAGEB + (CAP + 4) * 16 + 16];
-  i32x4_t* tlist = reinterpret_cast<i32x4_t*>(smem + NST * STAGEB);
-  int* wcount = reinterpret_cast<int*>(smem + NST * STAGEB + (CAP + 4) * 16);
+  __shared__ __attribute__((aligned(1024))) char smem[G::SMEM];
+  i32x4_t* tlist = reinterpret_cast<i32x4_t*>(smem + G::LIST);
+  int* wcount = reinterpret_cast<int*>(smem + G::WCOUNT);
 
+  // (what follows down to the chunk loop's predicates mirrors attn_fwd_stream.hip line by line: see the note there)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
@@ -59,7 +52,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
   const bool qvalid = (32 * wave + l31 < qleft) && (qrow < T);
 
   // ---- round trip A: tile list, id statistics, the lane's own id / LSE / delta inputs, the wave's Q and dO rows
-  const bool pre_ok = !bidir;                               // (the stored lists are causal)
+  // (the stored lists are causal.  The forward also asks for kv_tpc == 0: no backward entry point sets a key-chunk
+  // restriction, so there is nothing to ask here — attn_stream.h TileLister)
+  const bool pre_ok = !bidir;
   i32x4_t kl_head = {kListPre + 1, 0, 0, 0}, kl_first = {0, 0, 0, 0}, kl_mine = {0, 0, 0, 0};
   if (pre_ok) {
     const i32x4_t* kl = reinterpret_cast<const i32x4_t*>(meta.klist) +
@@ -85,22 +80,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
   }
 
   const size_t qrow_elems = (size_t)Nh * D;
-  const uint32_t q_bytes = (uint32_t)min((size_t)qv.rpb * qrow_elems * 2, (size_t)0x7fffffff);
-  const __amdgpu_buffer_rsrc_t rq =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(Q + (size_t)b * qv.rpb * qrow_elems), 0, q_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(dO + (size_t)b * qv.rpb * qrow_elems), 0, q_bytes, 0x00020000);
+  const BatchRows qrows(b, qv.rpb, qrow_elems);
+  const __amdgpu_buffer_rsrc_t rq = qrows.rsrc(Q), rdo = qrows.rsrc(dO);
   const size_t krow_elems = (size_t)Nkv * D;
-  const uint32_t k_bytes = (uint32_t)min((size_t)T * krow_elems * 2, (size_t)0x7fffffff);
-  const __amdgpu_buffer_rsrc_t rk =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(K + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(V + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
+  const BatchRows kvrows(b, T, krow_elems);
+  const __amdgpu_buffer_rsrc_t rk = kvrows.rsrc(K), rv = kvrows.rsrc(V);
   const __amdgpu_buffer_rsrc_t rdoc =
       __builtin_amdgcn_make_buffer_rsrc((void*)(doc + (size_t)b * T), 0, (uint32_t)T * 4, 0x00020000);
   const int rr = lane >> 2;
   const int lane_chunk = 8 * ((lane & 3) ^ ((rr >> 2) & 3));
-  constexpr uint32_t OOB = 0x80000000u;
+  constexpr uint32_t OOB = KVStage<D>::OOB;
   char* qpriv = smem + wave * (2 * QIMGB);      // {Q image | dO image} of this wave's 32 rows
   {
     const int wrows = min(qleft - 32 * wave, T - wq0);      // valid rows of this wave (<= 0: none)
@@ -135,52 +124,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
   }
   const int qcap = bidir ? 0x7fffffff : qrow;               // `kv <= qcap`: the causal term of the predicate
 
-  auto build_list = [&](int lo, int hi_t) {
-    const int j = lo + tid;
-    int mn = 0, mx = 0, mp = 0;
-    bool ok = false;
-    if (j <= hi_t) {
-      mn = m_min[j];
-      mx = m_max[j];
-      mp = m_minpos[j];
-      ok = tile_may_interact(bminpos, bmax, mp, mx);
-    }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = wcount[w];
-      before += w < wave ? c : 0;
-      total += c;
-    }
-    if (ok) tlist[before + __popcll(bal & ((1ull << lane) - 1ull))] = i32x4_t{j, mn, mx, mp};
-    const int n = __builtin_amdgcn_readfirstlane(total);
-    if (tid < 4) tlist[n + tid] = i32x4_t{j_hi + 1, 0, 0, 0};
-    __syncthreads();
-    return n;
-  };
+  const TileLister<EveryKeyChunk> build_list = {tid, m_min, m_max, m_minpos, bminpos, bmax,
+                                                {}, lane, wcount, wave, tlist, j_hi};
 
   const uint32_t voff = (uint32_t)(((size_t)rr * krow_elems + lane_chunk) * 2);
-  auto issue = [&](int j, int slot) {
-    char* st = smem + slot * STAGEB;
-    const int k0 = j * BN;
-    const int left = min(T - k0, BN);
-    const uint32_t base = (uint32_t)(((size_t)k0 * Nkv + hk) * D * 2);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int pc = wave + 4 * i, panel = pc % Tile::NP, rh = pc / Tile::NP;
-      const uint32_t vo = (16 * rh + rr < left) ? voff : OOB;
-      const uint32_t so = base + (uint32_t)((16 * rh * krow_elems + 32 * panel) * 2);
-      char* dst = st + panel * (Tile::PSTRIDE * 2) + rh * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)dst, 16, vo, so, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(dst + IMGB), 16, vo, so, 0, 0);
-    }
-    const uint32_t va = lane < left ? (uint32_t)lane * 4 : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rdoc, (lds_ptr_t)(st + 2 * IMGB + 256 * wave), 4, va, (uint32_t)k0 * 4, 0,
-                                             0);
-  };
+  const KVStage<D> issue = {smem, T, Nkv, hk, wave, lane, rr, krow_elems, voff, rk, rv, rdoc};
 
   // ---- the wave's Q / dO rows have landed (its own DMA: no barrier) -> MFMA B operands in registers
   wait_vmcnt<0>();
@@ -276,9 +224,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
       if (active) {
         const bool need_mask = uniform(!(kmin == kmax && kmax == wminpos && wminpos == wmax && !w_has_zero &&
                                          (bidir || k0 + BN - 1 <= wq0)));
-#define TN_K_RETIRE(buf, keep)                                                                                        \
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(kf[buf][0]), "+v"(kf[buf][1]), "+v"(kf[buf][2]), "+v"(kf[buf][3])       \
-               : "n"(keep))
         auto block = [&](auto BLK, bool act) {
           constexpr int blk = decltype(BLK)::value;
           if (!act) return;                                   // this 32-row KV block is above the diagonal
@@ -402,7 +347,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
         };
         block(I0{}, act0);
         block(I1{}, act1);
-#undef TN_K_RETIRE
       }
       e_cur = e_nxt;
       e_nxt = scalarize(e_nn);
@@ -413,7 +357,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
 
   // ---- epilogue: the dQ rows leave through the free ring slot as whole rows (attn_fwd_stream.hip)
   {
-    constexpr int CPR = D / 8, RPI = 64 / CPR, NI = 32 / RPI;
+    using WR = WholeRows<D>;
+    constexpr int CPR = WR::CPR, RPI = WR::RPI, NI = WR::NI;
     const int cc = lane % CPR, r0 = lane / CPR;
     // rcos / rsin (tn_attn_bwd_rope, D = 128): the rows leave as the gradient of the UN-rotated q.  The table entries of
     // this lane's eight chunks are asked for first, all at once, and arrive while the accumulators are staged (fetched
@@ -428,24 +373,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_stream_kernel(
         s4[i] = *reinterpret_cast<const u32x4_t*>(rsin + to);
       }
     }
-    char* ob = smem + cur * STAGEB + wave * (32 * OSTR);
+    char* ob = smem + cur * STAGEB + wave * WR::BYTES;
 #pragma unroll
     for (int db = 0; db < DBLK; ++db)
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         u32x2_t o2 = {pack2bf(dqacc[db][4 * r4 + 0] * scale, dqacc[db][4 * r4 + 1] * scale),
                       pack2bf(dqacc[db][4 * r4 + 2] * scale, dqacc[db][4 * r4 + 3] * scale)};
-        *reinterpret_cast<u32x2_t*>(ob + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o2;
+        *WR::put(ob, l31, hi, db, r4) = o2;
       }
     bf16_t* op = dQ + (((size_t)b * qv.rpb + lq0 + 32 * wave) * Nh + h) * D + cc * 8;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int row = i * RPI + r0;
-      u32x4_t v4 = *reinterpret_cast<const u32x4_t*>(ob + row * OSTR + cc * 16);
+      u32x4_t v4 = *WR::get(ob, row, cc);
       if (rot) {
         // tn_rope_apply(backward)'s arithmetic on the staged bf16 values, the other half of the row from the same image:
         // the bits the row kernel would produce
-        const u32x4_t p4 = *reinterpret_cast<const u32x4_t*>(ob + row * OSTR + (cc ^ (CPR / 2)) * 16);
+        const u32x4_t p4 = *WR::get(ob, row, cc ^ (CPR / 2));
         v4 = rope_grad_chunk(v4, p4, c4[i], s4[i], cc >= CPR / 2);
       }
       if (32 * wave + row < qleft && wq0 + row < T) *reinterpret_cast<u32x4_t*>(op + (size_t)row * Nh * D) = v4;

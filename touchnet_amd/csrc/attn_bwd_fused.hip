@@ -29,30 +29,11 @@
 // behind >= 8 further MFMAs or an explicit s_nop pad tied to the result; packed P / dS operands are written >= one gap
 // before the MFMA that reads them and the first MFMA of a group opens with s_nop 1; transpose reads are asm loads
 // retired by one lgkmcnt(0) statement naming every destination.
-#include <utility>
-
 #include "attn_common.h"
 
 namespace tn {
 
 namespace fusedkv {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 #define TN_FKV_BLOCKS(M)                                                                                              \
   if constexpr (BLK == 0) { M("a0","a1","a2","a3","a4","a5","a6","a7","a8","a9","a10","a11","a12","a13","a14","a15"); } \
@@ -111,20 +92,6 @@ __device__ __forceinline__ void mfma_acc(f32x16_t& d, u32x4_t a, bf16x8_t b) {
 // >= 13 wait states between the last MFMA of a chain and the first VALU read of its result
 __device__ __forceinline__ void mfma_result_pad(f32x16_t& d) { asm volatile("s_nop 7\n\ts_nop 4" : "+v"(d)); }
 
-template <int OFF>
-__device__ __forceinline__ u32x2_t ds_tr16(uint32_t addr) {
-  u32x2_t r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-
-template <class V, int OFF>
-__device__ __forceinline__ V ds_b128(uint32_t addr) {
-  V r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-
 // LDS operations issued in gap g of group 2 of a trip with a current AND a next stage (see the table in the kernel)
 constexpr int g2_ops(int g, bool mask) { return g < 4 ? 4 : g < 6 ? 3 + (mask ? 1 : 0) : 1 + (mask ? 1 : 0); }
 // ... and how many of the trip's LDS operations are younger than Q row operand s when S MFMA s is issued
@@ -175,8 +142,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
   // ONE LDS variable (attn_bwd.hip explains why two would serialise the DMA ring)
   using KTile = PTile<32, D>;                   // a wave's private 32-row image of K / V (prologue)
   constexpr int KIMGB = KTile::SIZE * 2;
-  constexpr int OSTR = 2 * D + 16;              // row stride (bytes) of the dV / dK staging images (epilogue)
-  static_assert(4 * 2 * KIMGB <= NST * STAGEB && 4 * 2 * 32 * OSTR <= NST * STAGEB, "private images live in the ring area");
+  static_assert(4 * 2 * KIMGB <= NST * STAGEB && 4 * 2 * WholeRows<D>::BYTES <= NST * STAGEB, "private images live in the ring area");
   __shared__ __attribute__((aligned(1024))) char smem[NST * STAGEB + (LCAP + NST + 1) * 16 + 16 + kListPre * 16];
   i32x4_t* slist = reinterpret_cast<i32x4_t*>(smem + NST * STAGEB);     // stage list, one QStage per entry
   int* wcount = reinterpret_cast<int*>(smem + NST * STAGEB + (LCAP + NST + 1) * 16);
@@ -212,6 +178,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
   const int dkdoc = kvalid ? doc[(size_t)b * T + kvrow] : 0;
   {
     const size_t krow_elems = (size_t)Nkv * D;
+    // (BatchRows' arithmetic written out, here and for Q / dO below: through the struct hipcc groups the byte count's product
+    // differently and this kernel's assembly changes)
     const uint32_t k_bytes = (uint32_t)min((size_t)T * krow_elems * 2, (size_t)0x7fffffff);
     const __amdgpu_buffer_rsrc_t rk =
         __builtin_amdgcn_make_buffer_rsrc((void*)(K + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
@@ -434,8 +402,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
         th[i][0] = ds_tr16<off>(ta0);
         th[i][1] = ds_tr16<off + 512>(ta1);
       });
-      de4[0] = ds_b128<f32x4_t, 2 * IMGB + 256>(axc);
-      de4[1] = ds_b128<f32x4_t, 2 * IMGB + 256 + 32>(axc);
+      de4[0] = ds_b128<2 * IMGB + 256, f32x4_t>(axc);
+      de4[1] = ds_b128<2 * IMGB + 256 + 32, f32x4_t>(axc);
     }
     // my pieces of stage n have landed (stage n + 1 may stay in flight) ...
     wait_vmcnt<IPS>();
@@ -480,11 +448,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
       if constexpr (CUR) {
         acc_mfma<db, i == 0>(tf[i], Pc[sp]);
         ds_elem(std::integral_constant<int, i>{});
-        if constexpr (i == 2 || i == 3) de4[i] = ds_b128<f32x4_t, 2 * IMGB + 256 + 32 * i>(axc);
+        if constexpr (i == 2 || i == 3) de4[i] = ds_b128<2 * IMGB + 256 + 32 * i, f32x4_t>(axc);
       }
       if constexpr (NEXT && i >= 4) {
         constexpr int s = i - 4;
-        rq_[s] = ds_b128<u32x4_t, 2 * ((s >> 1) * Tile::PSTRIDE)>((s & 1) ? rn1 : rn0);
+        rq_[s] = ds_b128<2 * ((s >> 1) * Tile::PSTRIDE)>((s & 1) ? rn1 : rn0);
       }
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -500,7 +468,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
           asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(de4[2]), "+v"(de4[3]) : "n"(k));
         if constexpr (s == 0) mfma_first<k>(S, rq_[0], kreg[0]);
         else mfma_acc<k>(S, rq_[s], kreg[s]);
-        if constexpr (s < 4) rq_[s + 4] = ds_b128<u32x4_t, 2 * (((s + 4) >> 1) * Tile::PSTRIDE)>((s & 1) ? rn1 : rn0);
+        if constexpr (s < 4) rq_[s + 4] = ds_b128<2 * (((s + 4) >> 1) * Tile::PSTRIDE)>((s & 1) ? rn1 : rn0);
       }
       if constexpr (CUR) {
         ds_elem(std::integral_constant<int, 8 + s>{});
@@ -514,8 +482,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
         }
       }
       if constexpr (NEXT && s >= 4) {
-        le4[s - 4] = ds_b128<f32x4_t, 2 * IMGB + 32 * (s - 4)>(axn);
-        if constexpr (MASK) qd4[s - 4] = ds_b128<i32x4_t, 2 * IMGB + 512 + 32 * (s - 4)>(axn);
+        le4[s - 4] = ds_b128<2 * IMGB + 32 * (s - 4), f32x4_t>(axn);
+        if constexpr (MASK) qd4[s - 4] = ds_b128<2 * IMGB + 512 + 32 * (s - 4), i32x4_t>(axn);
       }
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -552,7 +520,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
       if constexpr (NEXT) {
         if constexpr (i == 0 && CUR) asm volatile("s_nop 4" : "+v"(S));   // S chain -> first VALU read: >= 13 states
         p_elem(std::integral_constant<int, i>{});
-        rdo_[i] = ds_b128<u32x4_t, 2 * (Tile::SIZE + (i >> 1) * Tile::PSTRIDE)>((i & 1) ? rn1 : rn0);
+        rdo_[i] = ds_b128<2 * (Tile::SIZE + (i >> 1) * Tile::PSTRIDE)>((i & 1) ? rn1 : rn0);
       }
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -660,7 +628,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
   // (8-byte runs of the accumulator layout) into private images and reads them back as whole rows — 16-byte stores, four
   // rows per instruction, instead of 8 bytes per lane at a row stride (attn_fwd_stream.hip)
   {
-    constexpr int CPR = D / 8, RPI = 64 / CPR, NI = 32 / RPI;      // 16-byte chunks per row, rows per store instruction
+    using WR = WholeRows<D>;
+    constexpr int CPR = WR::CPR, RPI = WR::RPI, NI = WR::NI;
     const int cc = lane % CPR, r0 = lane / CPR;
     // rcos / rsin (tn_attn_bwd_rope): dK leaves as the gradient of the UN-rotated k; table entries asked for up front
     // (attn_bwd_dq_stream.hip's epilogue)
@@ -674,8 +643,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
         s4[i] = *reinterpret_cast<const u32x4_t*>(rsin + to);
       }
     }
-    char* obv = smem + wave * (2 * 32 * OSTR);
-    char* obk = obv + 32 * OSTR;
+    char* obv = smem + wave * (2 * WR::BYTES);
+    char* obk = obv + WR::BYTES;
     static_for<DBLK>([&](auto DB) {
       constexpr int db = decltype(DB)::value;
       static_for<4>([&](auto R4) {
@@ -683,20 +652,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv_fused_kernel(
         u32x2_t o;
         o.x = pack2bf(acc_read<16 * db + 4 * r4 + 0>(), acc_read<16 * db + 4 * r4 + 1>());
         o.y = pack2bf(acc_read<16 * db + 4 * r4 + 2>(), acc_read<16 * db + 4 * r4 + 3>());
-        *reinterpret_cast<u32x2_t*>(obv + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o;
+        *WR::put(obv, l31, hi, db, r4) = o;
         o.x = pack2bf(acc_read<64 + 16 * db + 4 * r4 + 0>() * scale, acc_read<64 + 16 * db + 4 * r4 + 1>() * scale);
         o.y = pack2bf(acc_read<64 + 16 * db + 4 * r4 + 2>() * scale, acc_read<64 + 16 * db + 4 * r4 + 3>() * scale);
-        *reinterpret_cast<u32x2_t*>(obk + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o;
+        *WR::put(obk, l31, hi, db, r4) = o;
       });
     });
     const size_t off = (((size_t)b * T + wk0) * Nkv + hk) * D + cc * 8;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int row = i * RPI + r0;
-      const u32x4_t v4 = *reinterpret_cast<const u32x4_t*>(obv + row * OSTR + cc * 16);
-      u32x4_t k4 = *reinterpret_cast<const u32x4_t*>(obk + row * OSTR + cc * 16);
+      const u32x4_t v4 = *WR::get(obv, row, cc);
+      u32x4_t k4 = *WR::get(obk, row, cc);
       if (rot) {
-        const u32x4_t p4 = *reinterpret_cast<const u32x4_t*>(obk + row * OSTR + (cc ^ (CPR / 2)) * 16);
+        const u32x4_t p4 = *WR::get(obk, row, cc ^ (CPR / 2));
         k4 = rope_grad_chunk(k4, p4, c4[i], s4[i], cc >= CPR / 2);
       }
       if (wk0 + row < T) {

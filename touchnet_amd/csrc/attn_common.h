@@ -14,6 +14,7 @@
 //     i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
 #pragma once
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
@@ -22,6 +23,9 @@ namespace tn {
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // LDS reads in kernels that fill LDS by LDS-DMA (buffer_load ... lds) must go through these ext_vector_type pointers,
 // NOT through HIP's uint4 / int4 / float4 structs: hipcc's waitcnt insertion puts an `s_waitcnt vmcnt(0)` in front of
 // any LDS access that carries no alias metadata while an LDS-DMA is pending (it cannot tell the slots of a ring apart),
@@ -47,6 +51,37 @@ __device__ __forceinline__ bf16x8_t as_bf16x8(uint2 lo, uint2 hi) {
 }
 // row index inside a 32x32 MFMA result tile held by register r of a lane with hi = lane >> 5
 __device__ __forceinline__ int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// ---- Inline-asm pieces of the kernels that count their own waits: hipcc serialises compiler-visible reads of an LDS-DMA
+// ring (above) and pairs every MFMA of a chain with its own read, so those kernels issue LDS reads as asm statements and
+// retire them with hand-counted s_waitcnt statements that name the registers they release.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ u32x2_t ds_tr16(uint32_t addr) {
+  u32x2_t r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+  return r;
+}
+// (V: any 16-byte vector — the fused dK / dV pass reads float and int rows straight into the type it computes with)
+template <int OFF, class V = u32x4_t>
+__device__ __forceinline__ V ds_b128(uint32_t addr) {
+  V r;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+  return r;
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression (asm
+// immediates, register-array indices)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
 
 constexpr int kTile = 64;  // granularity of the document-range metadata
 
@@ -113,6 +148,8 @@ struct QView {
   // touchnet/models/kimi_audio/modeling_kimi_audio.py:933-960): the key range of a query tile then runs to the LAST
   // tile that shares a document with it and the predicate loses its `kv <= q` term
   int bidir;
+  // plain attention: the one segment is the whole row, every key chunk, causal
+  __host__ static QView whole(int T) { return QView{1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull, 0}; }
   __device__ __forceinline__ bool kv_tile_on(int j) const { return kv_tpc == 0 || ((kv_mask >> (j / kv_tpc)) & 1ull); }
   __host__ __device__ int tiles(int s, int bm) const { return s < nseg ? (rows[s] + bm - 1) / bm : 0; }
   // tile `idx` of size bm over all segments -> local first row, global first position, rows left in segment
@@ -125,6 +162,11 @@ struct QView {
     left = rows[s] - lt * bm;
   }
 };
+
+// What every attention entry point asks of its shape: whole GQA groups, a head size the kernels are built for.
+__host__ inline bool attn_shape_ok(int B, int T, int Nh, int Nkv, int D) {
+  return B > 0 && T > 0 && Nh > 0 && Nkv > 0 && Nh % Nkv == 0 && (D == 64 || D == 128);
+}
 
 // The QView of a tn_attn_*_seg* call, or TN_EINVAL for a description the kernels cannot serve (the contract stated in
 // include/touchnet_amd.h) — checked on the host, before any launch: the kernels index the local buffers with
@@ -183,8 +225,23 @@ __device__ __forceinline__ int4 scalarize(int4 e) {
                    __builtin_amdgcn_readfirstlane(e.z), __builtin_amdgcn_readfirstlane(e.w));
 }
 
-// max over the two 32-lane halves of a wave without an LDS round trip (ds_bpermute queues behind other waves'
-// operand reads): v_permlane32_swap exchanges a's upper half with b's lower half.
+// v_permlane32_swap: {a with its upper half replaced by b's lower half, b with its lower half replaced by a's upper half}
+__device__ __forceinline__ u32x2_t swap32(uint32_t a, uint32_t b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+  return u32x2_t{r[0], r[1]};
+}
+// sum / max over the two 32-lane halves of a wave without an LDS round trip (ds_bpermute queues behind other waves'
+// operand reads)
+__device__ __forceinline__ float half_sum(float x) {
+  const u32x2_t r = swap32(__float_as_uint(x), __float_as_uint(x));
+  return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+__device__ __forceinline__ float half_max(float x) {
+  const u32x2_t r = swap32(__float_as_uint(x), __float_as_uint(x));
+  return fmaxf(__uint_as_float(r.x), __uint_as_float(r.y));
+}
+// half_max as inline asm, for attn_fwd_pp.hip alone: with the builtin its assembly changes (the pads around the swap go and
+// the registers of the tile loop are renumbered), so the kernel keeps the form it was measured with.
 __device__ __forceinline__ float half_swap_max(float x) {
   float a = x, b = x;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
@@ -286,6 +343,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const bf16_t* base, 
   return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
                                            __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
+// Batch row b of a [B][rows][row_elems] bf16 tensor (K / V: rows = T, row_elems = Nkv D; Q / dO: rows = rpb, row_elems =
+// Nh D) as an LDS-DMA source: rsrc(X) = the descriptor over X's slice.  An offset at or past the slice's bytes (capped at
+// 2^31 - 1) reads zeros and touches no memory.  (Constructor arguments by reference: taken by value hipcc groups the byte
+// count's product differently and the stream kernels' assembly changes.  In the two dK / dV kernels this form does so too:
+// attn_bwd.hip and attn_bwd_fused.hip write the same arithmetic out.)
+struct BatchRows {
+  int b, rows;
+  size_t row_elems;
+  uint32_t bytes;
+  __device__ __forceinline__ BatchRows(const int& b_, const int& rows_, const size_t& row_elems_)
+      : b(b_), rows(rows_), row_elems(row_elems_),
+        bytes((uint32_t)min((size_t)rows_ * row_elems_ * 2, (size_t)0x7fffffff)) {}
+  __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const bf16_t* base) const {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (size_t)b * rows * row_elems), 0, bytes, 0x00020000);
+  }
+};
 __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
   const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
   return make_uint4(v.x, v.y, v.z, v.w);
@@ -315,5 +388,27 @@ __device__ __forceinline__ u32x4_t rope_grad_chunk(u32x4_t own, u32x4_t other, u
   }
   return out;
 }
+
+// ---- Whole-row store: how a wave's 32 x D accumulator block (MFMA result layout: lane = row l31, 8-byte runs of columns)
+// leaves as whole rows.  The wave writes the block into a private staging image (32 rows at stride OSTR: conflict-free
+// 8-byte stores) and reads it back as 16-byte chunks — 16-byte stores, RPI rows per instruction, instead of 8 bytes per
+// lane at a row stride (store-issue bound: MI355X_MICROARCH.md "attention epilogue store tail").  The layout has this one
+// definition; the two loops around it stay in each kernel's epilogue: as a shared function, whatever way its arguments
+// are handed over, hipcc pairs the staging stores and schedules the scaling differently, and the assembly changes.
+template <int D>
+struct WholeRows {
+  static constexpr int OSTR = 2 * D + 16;              // row stride (bytes) of the staging image
+  static constexpr int BYTES = 32 * OSTR;              // ... and its size
+  static constexpr int CPR = D / 8, RPI = 64 / CPR;    // 16-byte chunks per row, rows per store instruction
+  static constexpr int NI = 32 / RPI;                  // store instructions per block
+  // where registers 4 r4 .. 4 r4 + 3 of accumulator block db (an 8-byte run of row l31) go in the image at ob
+  static __device__ __forceinline__ u32x2_t* put(char* ob, int l31, int hi, int db, int r4) {
+    return reinterpret_cast<u32x2_t*>(ob + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2);
+  }
+  // ... and of 16-byte chunk cc of row `row`: lane L takes chunk L % CPR of row i RPI + L / CPR in store instruction i
+  static __device__ __forceinline__ const u32x4_t* get(const char* ob, int row, int cc) {
+    return reinterpret_cast<const u32x4_t*>(ob + row * OSTR + cc * 16);
+  }
+};
 
 }  // namespace tn

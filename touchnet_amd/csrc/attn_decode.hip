@@ -309,7 +309,7 @@ static int launch(const void* q, const void* k_new, const void* v_new, void* k_c
   const int nsplit = num_splits(B, Nkv, S_max);
   float* ws_o = (float*)workspace;
   float* ws_lse = ws_o ? ws_o + (size_t)B * Nkv * nsplit * G * D : nullptr;
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   if (src)
     hipLaunchKernelGGL((attn_decode_split_kernel<D, G, true>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
                        (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache,

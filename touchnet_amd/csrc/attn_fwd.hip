@@ -225,10 +225,10 @@ int tn_attn_build_meta(const int* doc, int* meta, int B, int T, void* stream) {
 static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                            const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, QView qv,
                            void* stream) {
-  if (B <= 0 || T <= 0 || Nh <= 0 || Nkv <= 0 || Nh % Nkv || (D != 64 && D != 128)) return TN_EINVAL;
+  if (!attn_shape_ok(B, T, Nh, Nkv, D)) return TN_EINVAL;
   const int nt = (T + kTile - 1) / kTile;
   const AttnMeta m = make_attn_meta(meta, B, T);
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   hipStream_t st = (hipStream_t)stream;
   if (fwd_pingpong(T, D, nt, qv)) return tn_attn_fwd_pp_launch(q, k, v, o, lse2, doc, m, qv, B, T, Nh, Nkv, D, sl2, st);
   return tn_attn_fwd_stream_launch(q, k, v, o, lse2, doc, m, qv, B, T, Nh, Nkv, D, sl2, st);
@@ -236,14 +236,14 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
 
 int tn_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc, const int* meta,
                 int B, int T, int Nh, int Nkv, int D, float scale, void* stream) {
-  const QView qv = {1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull};
+  const QView qv = QView::whole(T);
   return attn_fwd_launch(q, k, v, o, lse2, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }
 
 // Bidirectional inside a document (no causal term): the Whisper speech encoder of Kimi-Audio.
 int tn_attn_fwd_bidir(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                       const int* meta, int B, int T, int Nh, int Nkv, int D, float scale, void* stream) {
-  QView qv = {1, {0, 0}, {T, 0}, {0, 0}, T, 0, ~0ull};
+  QView qv = QView::whole(T);
   qv.bidir = 1;
   return attn_fwd_launch(q, k, v, o, lse2, doc, meta, B, T, Nh, Nkv, D, scale, qv, stream);
 }

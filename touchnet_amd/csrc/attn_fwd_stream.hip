@@ -38,23 +38,17 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
     float* __restrict__ LSE2, const int* __restrict__ doc, AttnMeta meta, QView qv, int T, int Nh, int Nkv,
     float scale_log2) {
-  using namespace fstream;
-  constexpr int BM = 128, BN = 64, NST = 2;
-  constexpr int KSTEPS = D / 16, DBLK = D / 32;
-  using Tile = PTile<BN, D>;
-  constexpr int IMGB = Tile::SIZE * 2;          // bytes of one panel image
-  constexpr int NPC = Tile::NP * (BN / 16);     // 1-KiB DMA pieces per image: 16 rows of one panel each
-  constexpr int PPW = NPC / 4;                  // pieces per wave and image
-  constexpr int IPS = 2 * PPW + 1;              // DMA instructions per wave and stage
-  constexpr int OSTR = 2 * D + 16;              // row stride (bytes) of the O staging image: conflict-free 8-byte stores
-  constexpr int STAGE_KV = 2 * IMGB + 4 * 256;  // {K image | V image | doc ids[64] per wave}
-  constexpr int STAGEB = STAGE_KV > BM * OSTR ? STAGE_KV : BM * OSTR;      // a slot also stages 128 O rows
-  constexpr int CAP = 192;                      // tile-list chunk
-  // ONE LDS variable (attn_bwd.hip explains why two would serialise the DMA ring)
-  __shared__ __attribute__((aligned(1024))) char smem[NST * STAGEB + (CAP + 4) * 16 + 16];
-  i32x4_t* tlist = reinterpret_cast<i32x4_t*>(smem + NST * STAGEB);
-  int* wcount = reinterpret_cast<int*>(smem + NST * STAGEB + (CAP + 4) * 16);
+  using G = StreamGeom<D>;
+  using Tile = typename G::Tile;
+  constexpr int BM = G::BM, BN = G::BN, KSTEPS = G::KSTEPS, DBLK = G::DBLK, IMGB = G::IMGB, PPW = G::PPW, IPS = G::IPS;
+  constexpr int STAGEB = G::STAGEB, CAP = G::CAP;
+  __shared__ __attribute__((aligned(1024))) char smem[G::SMEM];
+  i32x4_t* tlist = reinterpret_cast<i32x4_t*>(smem + G::LIST);
+  int* wcount = reinterpret_cast<int*>(smem + G::WCOUNT);
 
+  // (Workgroup coordinates, stored-list head, descriptors, tile range, list hand-off and the per-trip predicates are written
+  // out in both stream kernels: moved into attn_stream.h — as one struct or as functions, arguments by value or by
+  // reference — each of them changes the kernels' assembly; what could move without that is there.)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
 
   // ---- round trip A: list of KV tiles, id statistics of the wave's rows, the lane's own id — issued together, in front
   // of the Q rows' DMA
-  const bool pre_ok = !bidir && qv.kv_tpc == 0;          // (the stored lists are causal and cover every chunk)
+  const bool pre_ok = !bidir && qv.kv_tpc == 0;          // (the stored lists are causal and cover every key chunk)
   i32x4_t kl_head = {kListPre + 1, 0, 0, 0}, kl_first = {0, 0, 0, 0}, kl_mine = {0, 0, 0, 0};
   if (pre_ok) {
     const i32x4_t* kl = reinterpret_cast<const i32x4_t*>(meta.klist) +
@@ -85,21 +79,16 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
 
   // ---- LDS-DMA sources: descriptors over this batch row's Q / K / V / id slices, lane part of the offsets
   const size_t qrow_elems = (size_t)Nh * D;
-  const uint32_t q_bytes = (uint32_t)min((size_t)qv.rpb * qrow_elems * 2, (size_t)0x7fffffff);
-  const __amdgpu_buffer_rsrc_t rq =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(Q + (size_t)b * qv.rpb * qrow_elems), 0, q_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rq = BatchRows(b, qv.rpb, qrow_elems).rsrc(Q);
   const size_t krow_elems = (size_t)Nkv * D;
-  const uint32_t k_bytes = (uint32_t)min((size_t)T * krow_elems * 2, (size_t)0x7fffffff);
-  const __amdgpu_buffer_rsrc_t rk =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(K + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(V + (size_t)b * T * krow_elems), 0, k_bytes, 0x00020000);
+  const BatchRows kvrows(b, T, krow_elems);
+  const __amdgpu_buffer_rsrc_t rk = kvrows.rsrc(K), rv = kvrows.rsrc(V);
   const __amdgpu_buffer_rsrc_t rdoc =
       __builtin_amdgcn_make_buffer_rsrc((void*)(doc + (size_t)b * T), 0, (uint32_t)T * 4, 0x00020000);
   // lane L of a piece writes LDS chunk L = (row L >> 2, physical chunk L & 3) of a 16-row x 64-byte panel slab
   const int rr = lane >> 2;
   const int lane_chunk = 8 * ((lane & 3) ^ ((rr >> 2) & 3));
-  constexpr uint32_t OOB = 0x80000000u;       // >= num_records: the load returns 0 and touches no memory
+  constexpr uint32_t OOB = KVStage<D>::OOB;
   // The 128 Q rows as two 64-row panel images in slot 1 (free until the first trip hands it to a K / V tile): 64-byte
   // runs per row instead of 16 bytes per lane at a row stride.  Rows past the segment / the sequence are zero-filled by
   // the descriptor's bounds check.
@@ -140,53 +129,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
   }
   const int qcap = bidir ? 0x7fffffff : qrow;          // `kv <= qcap`: the causal term of the predicate
 
-  // tiles of [lo, hi] that may interact with this query tile -> list entries {tile, min id, max id, min positive id}
-  auto build_list = [&](int lo, int hi_t) {
-    const int j = lo + tid;
-    int mn = 0, mx = 0, mp = 0;
-    bool ok = false;
-    if (j <= hi_t) {
-      mn = m_min[j];
-      mx = m_max[j];
-      mp = m_minpos[j];
-      ok = tile_may_interact(bminpos, bmax, mp, mx) && qv.kv_tile_on(j);
-    }
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const int c = wcount[w];
-      before += w < wave ? c : 0;
-      total += c;
-    }
-    if (ok) tlist[before + __popcll(bal & ((1ull << lane) - 1ull))] = i32x4_t{j, mn, mx, mp};
-    const int n = __builtin_amdgcn_readfirstlane(total);
-    if (tid < 4) tlist[n + tid] = i32x4_t{j_hi + 1, 0, 0, 0};
-    __syncthreads();
-    return n;
-  };
+  const TileLister<const QView&> build_list = {tid, m_min, m_max, m_minpos, bminpos, bmax,
+                                               qv, lane, wcount, wave, tlist, j_hi};
 
   const uint32_t voff = (uint32_t)(((size_t)rr * krow_elems + lane_chunk) * 2);
-  auto issue = [&](int j, int slot) {           // always IPS instructions (the counted wait below relies on it)
-    char* st = smem + slot * STAGEB;
-    const int k0 = j * BN;
-    const int left = min(T - k0, BN);
-    const uint32_t base = (uint32_t)(((size_t)k0 * Nkv + hk) * D * 2);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int pc = wave + 4 * i, panel = pc % Tile::NP, rh = pc / Tile::NP;
-      const uint32_t vo = (16 * rh + rr < left) ? voff : OOB;
-      const uint32_t so = base + (uint32_t)((16 * rh * krow_elems + 32 * panel) * 2);
-      char* dst = st + panel * (Tile::PSTRIDE * 2) + rh * 1024;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)dst, 16, vo, so, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(dst + IMGB), 16, vo, so, 0, 0);
-    }
-    const uint32_t va = lane < left ? (uint32_t)lane * 4 : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rdoc, (lds_ptr_t)(st + 2 * IMGB + 256 * wave), 4, va, (uint32_t)k0 * 4, 0,
-                                             0);
-  };
+  const KVStage<D> issue = {smem, T, Nkv, hk, wave, lane, rr, krow_elems, voff, rk, rv, rdoc};
 
   const PRowReader<BN, D> krd(l31, hi);
   const PTrReader<BN, D> vrd(lane);
@@ -286,9 +233,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
             !(kmin == kmax && kmax == wminpos && wminpos == wmax && !w_has_zero && (bidir || k0 + BN - 1 <= wq0)));
         // ---- S^T[kv, q] = K[kv, :] . Q[q, :]   (two chains, one per 32-row block, interleaved)
         f32x16_t sacc[2];
-#define TN_K_RETIRE(buf, keep)                                                                                        \
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(kf[buf][0]), "+v"(kf[buf][1]), "+v"(kf[buf][2]), "+v"(kf[buf][3])       \
-               : "n"(keep))
         auto k_mfma = [&](auto GG, auto BUF) {
           constexpr int g = decltype(GG)::value, buf = decltype(BUF)::value;
           static_for<4>([&](auto F) {
@@ -318,7 +262,6 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
           TN_K_RETIRE(1, 0);
           k_mfma(I3{}, I1{});
         }
-#undef TN_K_RETIRE
         // ---- mask, online softmax (lane-local: this lane's query column); scores stay RAW in the accumulator,
         // the softmax scale rides in the exponent's fma: p = exp2(s * c - m), m tracked in the scaled domain
         if (need_mask) {
@@ -448,22 +391,23 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_stream_kernel(
   const float l_tot = half_sum(l_run);
   const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
   {
-    char* ob = smem + cur * STAGEB + wave * (32 * OSTR);
+    using WR = WholeRows<D>;
+    char* ob = smem + cur * STAGEB + wave * WR::BYTES;
 #pragma unroll
     for (int db = 0; db < DBLK; ++db)
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) {
         u32x2_t o2 = {pack2bf(oacc[db][4 * r4 + 0] * inv, oacc[db][4 * r4 + 1] * inv),
                       pack2bf(oacc[db][4 * r4 + 2] * inv, oacc[db][4 * r4 + 3] * inv)};
-        *reinterpret_cast<u32x2_t*>(ob + l31 * OSTR + (32 * db + 8 * r4 + 4 * hi) * 2) = o2;
+        *WR::put(ob, l31, hi, db, r4) = o2;
       }
-    constexpr int CPR = D / 8, RPI = 64 / CPR;           // 16-byte chunks per row, rows per store instruction
+    constexpr int CPR = WR::CPR, RPI = WR::RPI;
     const int cc = lane % CPR, r0 = lane / CPR;
     bf16_t* op = O + (((size_t)b * qv.rpb + lq0 + 32 * wave) * Nh + h) * D + cc * 8;
 #pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
+    for (int i = 0; i < WR::NI; ++i) {
       const int row = i * RPI + r0;
-      const u32x4_t v4 = *reinterpret_cast<const u32x4_t*>(ob + row * OSTR + cc * 16);
+      const u32x4_t v4 = *WR::get(ob, row, cc);
       if (32 * wave + row < qleft && wq0 + row < T) *reinterpret_cast<u32x4_t*>(op + (size_t)row * Nh * D) = v4;
     }
     if (qvalid && hi == 0) LSE2[((size_t)b * Nh + h) * qv.rpb + lrow] = l_tot > 0.f ? m_run + log2f(l_tot) : INFINITY;

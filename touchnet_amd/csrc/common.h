@@ -17,6 +17,8 @@ namespace tn {
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 
+constexpr float kLog2e = 1.4426950408889634f;   // log2(e): exp(x) = exp2(x * kLog2e)
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;   // MFMA A/B operand (4 VGPRs)
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;   // 32x32 MFMA accumulator
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;

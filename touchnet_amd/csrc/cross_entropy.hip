@@ -20,7 +20,6 @@
 
 namespace tn {
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
 struct RowStat {
