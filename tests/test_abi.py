@@ -183,3 +183,73 @@ def test_attn_bwd_rope_refuses_missing_or_misaligned_tables_before_any_launch():
     assert call(p + 2, p) == EINVAL and call(p, p + 8) == EINVAL          # 16-byte loads of the table rows
     assert call(p, p, D=96) == EINVAL
     assert call(p, p, Nh=6, Nkv=4) == EINVAL                              # query heads not a multiple of kv heads
+
+
+def test_row_kernel_entry_points_refuse_by_rule_before_any_launch():
+    """Every rule the host layer of csrc/norm_act.hip owns, by name, for every entry point it guards: one launcher checks the
+    two norm forwards, one the two backwards, one the four element-wise entries; the transposing SwiGLU, RoPE and column-sum
+    entries carry their own guards.  A refused call returns TN_EINVAL (-22) before any launch, so host addresses that are
+    never dereferenced will do.  (tests/test_row_kernels_cpu.py sweeps more values per rule; valid calls are the `-m gpu`
+    tests' business: tests/test_row_kernels_gpu.py.)  The workspace sizes are the header's layouts, restated here."""
+    import ctypes as C
+    from touchnet_amd import _C
+    lib = _C.lib()
+    EINVAL = -22
+    raw = (C.c_char * 8192)()
+    p = (C.addressof(raw) + 255) // 256 * 256
+    F32, BF16 = 0, 1
+    table = []                                            # (rule, entry point, return code)
+
+    def norms(rule, rows, H, dtype):
+        table.extend([(rule, "tn_rmsnorm_fwd", lib.tn_rmsnorm_fwd(p, p, p, p, p, p, rows, H, 1e-5, dtype, None)),
+                      (rule, "tn_rmsnorm_bwd", lib.tn_rmsnorm_bwd(p, p, p, p, p, p, p, p, rows, H, dtype, None)),
+                      (rule, "tn_layernorm_fwd", lib.tn_layernorm_fwd(p, p, p, p, p, p, p, p, rows, H, 1e-5, dtype, None)),
+                      (rule, "tn_layernorm_bwd", lib.tn_layernorm_bwd(p, p, p, p, p, p, p, p, p, p, rows, H, dtype, None))])
+
+    def elementwise(rule, n, dtype):
+        table.extend([(rule, "tn_swiglu_fwd", lib.tn_swiglu_fwd(p, p, p, n, dtype, None)),
+                      (rule, "tn_swiglu_bwd", lib.tn_swiglu_bwd(p, p, p, p, p, n, dtype, None)),
+                      (rule, "tn_gelu_fwd", lib.tn_gelu_fwd(p, p, n, dtype, None)),
+                      (rule, "tn_gelu_bwd", lib.tn_gelu_bwd(p, p, p, n, dtype, None))])
+
+    def transposing(rule, rows, cols):
+        table.extend([(rule, "tn_swiglu_fwd_t", lib.tn_swiglu_fwd_t(p, p, p, p, rows, cols, None)),
+                      (rule, "tn_swiglu_bwd_t", lib.tn_swiglu_bwd_t(p, p, p, p, p, p, rows, cols, None))])
+
+    for dtype, name, N, widest in ((F32, "fp32", 4, 4096), (BF16, "bf16", 8, 8192)):
+        norms(f"rows <= 0 ({name})", 0, 64, dtype)
+        norms(f"rows < 0 ({name})", -4, 64, dtype)
+        norms(f"H <= 0 ({name})", 4, 0, dtype)
+        norms(f"H < 0 ({name})", 4, -64, dtype)
+        norms(f"H % {N} ({name})", 4, 64 + N // 2, dtype)
+        norms(f"H one vector above the widest row ({name})", 4, widest + N, dtype)
+        elementwise(f"n < 0 ({name})", -N, dtype)
+        elementwise(f"n % {N} ({name})", 3 * N + N // 2, dtype)
+        for rule, (n, hq, hk, D) in {"odd D": (5, 4, 2, 63), "D <= 0": (5, 4, 2, 0), "hq <= 0": (5, 0, 2, 64),
+                                     "hk < 0": (5, 4, -1, 64), "n <= 0": (0, 4, 2, 64)}.items():
+            table.append((f"{rule} ({name})", "tn_rope_apply", lib.tn_rope_apply(p, p, p, p, p, p, n, hq, hk, D, 0, dtype, None)))
+        table.append((f"n <= 0 ({name})", "tn_rope_table", lib.tn_rope_table(p, p, p, p, 0, 32, 1.0, dtype, None)))
+        table.append((f"half <= 0 ({name})", "tn_rope_table", lib.tn_rope_table(p, p, p, p, 5, 0, 1.0, dtype, None)))
+    norms("an unknown dtype code", 4, 64, 2)
+    elementwise("an unknown dtype code", 64, 2)
+    table.append(("an unknown dtype code", "tn_rope_apply", lib.tn_rope_apply(p, p, p, p, p, p, 5, 4, 2, 64, 0, 2, None)))
+    table.append(("an unknown dtype code", "tn_rope_table", lib.tn_rope_table(p, p, p, p, 5, 32, 1.0, 2, None)))
+    transposing("rows % 8", 12, 64)
+    transposing("cols % 8", 64, 100)
+    transposing("rows <= 0", 0, 64)
+    transposing("cols <= 0", 64, 0)
+    for rule, (x, rows, cols, ld) in {"rows <= 0": (p, 0, 64, 64), "cols <= 0": (p, 4, 0, 64), "cols % 8": (p, 4, 60, 64),
+                                      "ld % 8": (p, 4, 64, 68), "ld < cols": (p, 4, 64, 56),
+                                      "x not 16-byte aligned": (p + 8, 4, 64, 64)}.items():
+        table.append((rule, "tn_colsum_bf16", lib.tn_colsum_bf16(x, p, p, rows, cols, ld, None)))
+    assert len(table) == 102
+    accepted = [(rule, entry, rc) for rule, entry, rc in table if rc != EINVAL]
+    assert not accepted, accepted
+
+    # norm backward: dw partials, then db partials, one row of H floats per workgroup, a workgroup per row up to 1024;
+    # column sum: one row of `cols` floats per slab, about 4096 workgroups of 256 columns, at most 1024 slabs of >= 16 rows
+    for rows in (1, 5, 1023, 1024, 1025, 2051, 30000):
+        for H in (8, 64, 520, 1280, 4096, 8192):
+            assert lib.tn_norm_bwd_workspace_floats(rows, H) == 2 * min(rows, 1024) * H, (rows, H)
+            slabs = max(1, min(-(-4096 // -(-H // 256)), 1024, max(rows // 16, 1)))
+            assert lib.tn_colsum_workspace_floats(rows, H) == slabs * H, (rows, H)

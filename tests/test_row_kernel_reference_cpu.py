@@ -244,7 +244,7 @@ def test_budget_at_the_edge_values_is_the_half_ulp_and_the_fp32_allowance(dtype)
 
 @pytest.mark.parametrize("H", [260, 520, 2052, 4104])
 def test_layernorm_budget_tells_the_two_pass_variance_from_the_one_pass_form(H):
-    """rows at 100 +- 1.3, float32 arithmetic on the CPU: the two-pass variance (what layernorm_fwd_kernel does) is inside
+    """rows at 100 +- 1.3, float32 arithmetic on the CPU: the two-pass variance (what norm_fwd_kernel does for LayerNorm) is inside
     the rstd budget, E[h^2] - mean^2 is not"""
     g = torch.Generator().manual_seed(H)
     h = 1.3 * torch.randn(33, H, generator=g) + 100.2

@@ -3,8 +3,8 @@ dispatch boundaries the product uses and at the edges of the number formats.
 
 Every comparison goes through row_kernel_reference.check: half an ulp of the kernel's dtype for the output rounding,
 the project's fp32 allowance (1e-5) of the UNcancelled terms, one flip of a restated interior rounding — no atol /
-rtol pair wide enough to hide a term.  Two one-line mutations these tests are built to see: dropping `- xh * dot` in
-rmsnorm_bwd_kernel moves dh by rstd |xhat| |dot|, |dot| about 1 / sqrt(H) = 0.011 .. 0.35 of the widths here, against a
+rtol pair wide enough to hide a term.  Two one-line mutations these tests are built to see: dropping `- xh * s2` in
+norm_bwd_kernel's RMSNorm form moves dh by rstd |xhat| |dot|, |dot| about 1 / sqrt(H) = 0.011 .. 0.35 of the widths here, against a
 bf16 budget of 2^-9 |dh| (a float32 emulation of the kernel with the term dropped is 1700 budgets off in bf16, 10^4 in
 fp32); the `v < nvec` guard of the last slot off by one at nvec = 65 (H = 520 bf16 / 260 fp32) either folds a vector of the
 next row into the statistics (rstd moves by 0.8 % against a budget of 1e-5) or leaves the row's last vector unwritten.

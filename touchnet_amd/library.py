@@ -38,17 +38,62 @@ def _empty0(like: Tensor) -> Tensor:
     return like.new_empty(0)
 
 
-# ===================================================================================================== RMSNorm
+# ===================================================================================================== norms
+# RMSNorm and LayerNorm are two ops each way that differ by one tensor (the bias in, the mean out, db back); the reshapes,
+# allocations, meta results and the autograd formula are stated once for both.
+def _norm_fwd_buffers(x: Tensor, residual: Optional[Tensor]):
+    """-> (x2, r2, y, h): x and the residual as [rows, H]; y and, with a residual, h = x + residual for the kernel to fill"""
+    H = x.shape[-1]
+    x2 = _c(x).view(-1, H)
+    r2 = _c(residual).view(-1, H) if residual is not None else None
+    return x2, r2, torch.empty_like(x2), (torch.empty_like(x2) if r2 is not None else None)
+
+
+def _norm_fwd_fake(x, residual, nstats):
+    e = lambda: torch.empty_like(x, memory_format=torch.contiguous_format)
+    rows = x.numel() // x.shape[-1]
+    return (e(), e() if residual is not None else x.new_empty(0),
+            *(x.new_empty(rows, dtype=torch.float32) for _ in range(nstats)))
+
+
+def _norm_bwd_buffers(dy: Tensor, h: Tensor, dres: Optional[Tensor]):
+    """-> (dy2, h2, dr2, dh, ws): the operands as [rows, H], dh for the kernel to fill, the partial sums' workspace"""
+    H = h.shape[-1]
+    h2 = _c(h).view(-1, H)
+    rows = h2.shape[0]
+    dy2 = _c(dy).view(rows, H)
+    dr2 = _c(dres).view(rows, H) if dres is not None else None
+    ws = torch.empty(_lib().tn_norm_bwd_workspace_floats(rows, H), dtype=torch.float32, device=h.device)
+    return dy2, h2, dr2, torch.empty_like(h2), ws
+
+
+def _norm_setup(ctx, inputs, output):
+    """inputs = (x, residual, weight, ...), output = (y, h, *statistics)"""
+    x, residual, weight = inputs[:3]
+    ctx.has_res = residual is not None
+    ctx.wdtype = weight.dtype
+    ctx.set_materialize_grads(False)     # (no zero tensors for the statistics outputs' gradients: 2-3 tiny fills per norm)
+    ctx.save_for_backward(output[1] if ctx.has_res else x, weight, *output[2:])
+
+
+def _norm_backward(bwd_op):
+    """the autograd formula over `bwd_op(dy, h, weight, *statistics, dres) -> (dh, *parameter gradients)`"""
+    def backward(ctx, dy, dh_new, *_dstats):
+        h, weight, *stats = ctx.saved_tensors
+        dres = dh_new if (ctx.has_res and dh_new is not None) else None
+        if dy is None:
+            dy = torch.zeros_like(h)
+        dh, *dparams = bwd_op(dy, h, weight, *stats, dres)
+        return (dh, dh if ctx.has_res else None, *[d.to(ctx.wdtype) for d in dparams], None)
+    return backward
+
+
 @custom_op(f"{NS}::rmsnorm_fwd", mutates_args=(), device_types="cuda")
 def rmsnorm_fwd(x: Tensor, residual: Optional[Tensor], weight: Tensor, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
     """-> (y, h, rstd): h = x + residual (EMPTY when residual is None: then h == x), y = w * T(h * rstd)."""
-    H = x.shape[-1]
-    x2 = _c(x).view(-1, H)
-    rows = x2.shape[0]
-    r2 = _c(residual).view(-1, H) if residual is not None else None
+    x2, r2, y, h = _norm_fwd_buffers(x, residual)
+    rows, H = x2.shape
     w = _c(weight).to(x.dtype)
-    y = torch.empty_like(x2)
-    h = torch.empty_like(x2) if r2 is not None else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     _C.check(_lib().tn_rmsnorm_fwd(_p(x2), _p(r2), _p(w), _p(y), _p(h), _p(rstd), rows, H, float(eps), _C.dcode(x2),
                                    _cur()), "tn_rmsnorm_fwd")
@@ -57,24 +102,16 @@ def rmsnorm_fwd(x: Tensor, residual: Optional[Tensor], weight: Tensor, eps: floa
 
 @rmsnorm_fwd.register_fake
 def _(x, residual, weight, eps):
-    rows = x.numel() // x.shape[-1]
-    return (torch.empty_like(x, memory_format=torch.contiguous_format),
-            torch.empty_like(x, memory_format=torch.contiguous_format) if residual is not None else x.new_empty(0),
-            x.new_empty(rows, dtype=torch.float32))
+    return _norm_fwd_fake(x, residual, 1)
 
 
 @custom_op(f"{NS}::rmsnorm_bwd", mutates_args=(), device_types="cuda")
 def rmsnorm_bwd(dy: Tensor, h: Tensor, weight: Tensor, rstd: Tensor, dres: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
     """-> (dh, dw): dh includes the incoming residual-stream gradient `dres`."""
-    H = h.shape[-1]
-    h2 = _c(h).view(-1, H)
-    rows = h2.shape[0]
-    dy2 = _c(dy).view(rows, H)
-    dr2 = _c(dres).view(rows, H) if dres is not None else None
+    dy2, h2, dr2, dh, ws = _norm_bwd_buffers(dy, h, dres)
+    rows, H = h2.shape
     w = _c(weight).to(h.dtype)
-    dh = torch.empty_like(h2)
     dw = torch.empty(H, dtype=h.dtype, device=h.device)
-    ws = torch.empty(_lib().tn_norm_bwd_workspace_floats(rows, H), dtype=torch.float32, device=h.device)
     _C.check(_lib().tn_rmsnorm_bwd(_p(dy2), _p(h2), _p(w), _p(rstd), _p(dr2), _p(dh), _p(dw), _p(ws), rows, H,
                                    _C.dcode(h2), _cur()), "tn_rmsnorm_bwd")
     return dh.view(h.shape), dw
@@ -85,39 +122,16 @@ def _(dy, h, weight, rstd, dres):
     return torch.empty_like(h, memory_format=torch.contiguous_format), h.new_empty(h.shape[-1])
 
 
-def _rmsnorm_setup(ctx, inputs, output):
-    x, residual, weight, eps = inputs
-    _, h, rstd = output
-    ctx.has_res = residual is not None
-    ctx.wdtype = weight.dtype
-    ctx.set_materialize_grads(False)     # (no zero tensors for the statistics outputs' gradients: 2-3 tiny fills per norm)
-    ctx.save_for_backward(h if ctx.has_res else x, weight, rstd)
+rmsnorm_fwd.register_autograd(_norm_backward(rmsnorm_bwd), setup_context=_norm_setup)
 
 
-def _rmsnorm_backward(ctx, dy, dh_new, _drstd):
-    h, weight, rstd = ctx.saved_tensors
-    dres = dh_new if (ctx.has_res and dh_new is not None) else None
-    if dy is None:
-        dy = torch.zeros_like(h)
-    dh, dw = rmsnorm_bwd(dy, h, weight, rstd, dres)
-    return dh, (dh if ctx.has_res else None), dw.to(ctx.wdtype), None
-
-
-rmsnorm_fwd.register_autograd(_rmsnorm_backward, setup_context=_rmsnorm_setup)
-
-
-# ===================================================================================================== LayerNorm
 @custom_op(f"{NS}::layernorm_fwd", mutates_args=(), device_types="cuda")
 def layernorm_fwd(x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: Tensor,
                   eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """-> (y, h, mean, rstd); h EMPTY when residual is None."""
-    H = x.shape[-1]
-    x2 = _c(x).view(-1, H)
-    rows = x2.shape[0]
-    r2 = _c(residual).view(-1, H) if residual is not None else None
+    x2, r2, y, h = _norm_fwd_buffers(x, residual)
+    rows, H = x2.shape
     w, b = _c(weight).to(x.dtype), _c(bias).to(x.dtype)
-    y = torch.empty_like(x2)
-    h = torch.empty_like(x2) if r2 is not None else None
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     _C.check(_lib().tn_layernorm_fwd(_p(x2), _p(r2), _p(w), _p(b), _p(y), _p(h), _p(mean), _p(rstd), rows, H,
@@ -127,25 +141,18 @@ def layernorm_fwd(x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: T
 
 @layernorm_fwd.register_fake
 def _(x, residual, weight, bias, eps):
-    rows = x.numel() // x.shape[-1]
-    e = lambda: torch.empty_like(x, memory_format=torch.contiguous_format)
-    return (e(), e() if residual is not None else x.new_empty(0), x.new_empty(rows, dtype=torch.float32),
-            x.new_empty(rows, dtype=torch.float32))
+    return _norm_fwd_fake(x, residual, 2)
 
 
 @custom_op(f"{NS}::layernorm_bwd", mutates_args=(), device_types="cuda")
 def layernorm_bwd(dy: Tensor, h: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor,
                   dres: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
-    H = h.shape[-1]
-    h2 = _c(h).view(-1, H)
-    rows = h2.shape[0]
-    dy2 = _c(dy).view(rows, H)
-    dr2 = _c(dres).view(rows, H) if dres is not None else None
+    """-> (dh, dw, db): dh includes the incoming residual-stream gradient `dres`."""
+    dy2, h2, dr2, dh, ws = _norm_bwd_buffers(dy, h, dres)
+    rows, H = h2.shape
     w = _c(weight).to(h.dtype)
-    dh = torch.empty_like(h2)
     dw = torch.empty(H, dtype=h.dtype, device=h.device)
     db = torch.empty_like(dw)
-    ws = torch.empty(_lib().tn_norm_bwd_workspace_floats(rows, H), dtype=torch.float32, device=h.device)
     _C.check(_lib().tn_layernorm_bwd(_p(dy2), _p(h2), _p(w), _p(mean), _p(rstd), _p(dr2), _p(dh), _p(dw), _p(db),
                                      _p(ws), rows, H, _C.dcode(h2), _cur()), "tn_layernorm_bwd")
     return dh.view(h.shape), dw, db
@@ -157,25 +164,7 @@ def _(dy, h, weight, mean, rstd, dres):
             h.new_empty(h.shape[-1]))
 
 
-def _layernorm_setup(ctx, inputs, output):
-    x, residual, weight, bias, eps = inputs
-    _, h, mean, rstd = output
-    ctx.has_res = residual is not None
-    ctx.wdtype = weight.dtype
-    ctx.set_materialize_grads(False)
-    ctx.save_for_backward(h if ctx.has_res else x, weight, mean, rstd)
-
-
-def _layernorm_backward(ctx, dy, dh_new, _dm, _dr):
-    h, weight, mean, rstd = ctx.saved_tensors
-    dres = dh_new if (ctx.has_res and dh_new is not None) else None
-    if dy is None:
-        dy = torch.zeros_like(h)
-    dh, dw, db = layernorm_bwd(dy, h, weight, mean, rstd, dres)
-    return dh, (dh if ctx.has_res else None), dw.to(ctx.wdtype), db.to(ctx.wdtype), None
-
-
-layernorm_fwd.register_autograd(_layernorm_backward, setup_context=_layernorm_setup)
+layernorm_fwd.register_autograd(_norm_backward(layernorm_bwd), setup_context=_norm_setup)
 
 
 # ===================================================================================================== activations
