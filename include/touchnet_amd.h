@@ -351,6 +351,22 @@ int tn_gemm_bf16_grouped(const void* const* A, const void* const* B, const long 
                          const int* K, void* const* C, const long long* ldc, const int* M, const int* N, int ngrp,
                          int a_kmaj, int b_kmaj, int accumulate, int c_f32, void* workspace, long long workspace_bytes,
                          void* stream);
+/*      The same for ANY number of weight gradients (n = 1..1024, both operands contraction-major), whole tiles only:
+ *      C_g[M_g, N_g] (+= when accumulate) A_g[K_g, M_g]^T . B_g[K_g, N_g] and, where bias_grad is not NULL and
+ *      bias_grad[g] is not NULL, bias_grad[g][M_g] (bf16) = column sums of A_g.  The linear layers of the Whisper-style
+ *      audio tower (q / k / v / out_proj, fc1, fc2 of transformers' Qwen2AudioEncoderLayer) are 300 output tiles per layer
+ *      = 1.17 rounds on 256 CUs; nothing reads a weight gradient before the gradient norm, so the products of many layers
+ *      run as ONE tile list (11 layers: 3300 tiles = 12.9 rounds).  Every output has the bits of the unsplit single-product
+ *      launch (tn_gemm_bf16_wgrad_bias / tn_gemm_bf16_wgrad_f32 with splitk <= 1).  The products' records reach the
+ *      device through `table` (device memory, >= tn_gemm_grouped_table_bytes(n) bytes, 16-byte aligned), written
+ *      stream-ordered by the call: the caller keeps it untouched until the launch has run.  Outputs of different products
+ *      may not overlap.  -22: n out of range (tn_gemm_grouped_table_bytes: -1), no / a misaligned / a short table, shapes
+ *      as for tn_gemm_bf16_grouped. */
+long long tn_gemm_grouped_table_bytes(int n);
+int tn_gemm_bf16_grouped_table(const void* const* A, const void* const* B, const long long* lda, const long long* ldb,
+                               const int* K, void* const* C, const long long* ldc, const int* M, const int* N,
+                               void* const* bias_grad, int n, int accumulate, int c_f32, void* table,
+                               long long table_bytes, void* stream);
 /*      The MLP's gate and up products with SwiGLU in the epilogue (LlamaMLP.forward: down(silu(gate(x)) * up(x));
  *      the reference swaps in liger's fused SwiGLU at touchnet/models/llama/__init__.py:11-15): one launch computes
  *      gate[M, I] = x Wg^T, up[M, I] = x Wu^T and act = silu(gate) * up (all bf16, row pitch ldc; gate and up are kept

@@ -82,6 +82,10 @@ PROTOTYPES = {
     "tn_gemm_grouped_workspace_bytes": [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i],
     "tn_gemm_bf16_grouped": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_i), C.POINTER(_vp),
                              C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _i, _vp, _ll, _vp],
+    "tn_gemm_grouped_table_bytes": [_i],
+    "tn_gemm_bf16_grouped_table": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_ll), C.POINTER(_i),
+                                   C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), C.POINTER(_vp), _i, _i, _i,
+                                   _vp, _ll, _vp],
     "tn_gemm_bf16_wgrad_bias": [_vp, _vp, _ll, _ll, _i, _vp, _vp, _i, _i, _ll, _i, _i, _i, _vp, _ll, _vp],
     "tn_gemm_bf16_rope": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp],
     "tn_gemm_bf16_gelu_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _vp],
@@ -104,7 +108,7 @@ PROTOTYPES = {
 }
 _RESTYPE = {"tn_gemm_set_persistent": None, "tn_version": C.c_char_p, "tn_sumsq_multi_chunk": C.c_longlong, "tn_adamw_multi_chunk": C.c_longlong,
             "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_splitk_workspace_bytes": C.c_longlong,
-            "tn_gemm_grouped_workspace_bytes": C.c_longlong,
+            "tn_gemm_grouped_workspace_bytes": C.c_longlong, "tn_gemm_grouped_table_bytes": C.c_longlong,
             "tn_attn_decode_workspace_bytes": C.c_longlong, "tn_beam_step_workspace_bytes": C.c_longlong,
             "tn_philox4x32_10": None}
 

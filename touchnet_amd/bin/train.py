@@ -207,6 +207,18 @@ class Trainer:
                     and not any(hasattr(p, "_local_tensor") for p in model.parameters())):
                 from touchnet_amd.utils.optimizer import pipeline_updates_under_forward
                 pipeline_updates_under_forward(model, self.optimizer)
+        # The audio tower's weight gradients wait in a queue and run as one launch over many layers (functional.DeferredWgrad:
+        # a layer's six products alone are 1.17 rounds of output tiles).  Only here, on the plain single-device path: sharding
+        # engines own their weight gradients, tensor / context parallelism change the operands, and a checkpointed layer
+        # runs its backward on recomputed tensors.
+        self.wgrad_queue = None
+        if (device.type == "cuda" and not sharded and not flat and tp == 1 and not ac and self.cp_group is None
+                and self.cp_emulate is None):
+            import touchnet_amd.functional as _F
+            layers = [ly for m in model.modules() if hasattr(m, "deferred_wgrad_layers") for ly in m.deferred_wgrad_layers()]
+            if layers and _F.DEFERRED_WGRAD:
+                self.wgrad_queue = _F.DeferredWgrad(layers)
+                self.wgrad_queue.enabled = False           # (switched on around train_step's backward)
         self.step = 0
         # the reference's "dp_cp" mesh (loss / metric all-reduces, train.py:485-494): every rank that holds other rows or
         # another part of the sequence
@@ -292,7 +304,17 @@ class Trainer:
         # Exactly the reference (train.py:456): backward on the loss normalised by the GLOBAL num_sentence;
         # FSDP2's reduce-scatter then AVERAGES over dp, i.e. gradients are 1/dp of the global-batch mean
         # gradient.  We keep that scale for parity (AdamW is invariant to it, the clip threshold is not).
-        loss.backward()
+        if self.wgrad_queue is not None:
+            # the tower's weight gradients are queued during THIS backward only (a caller that runs the model's backward by
+            # itself finds every gradient where autograd leaves it) and run before the gradient norm
+            self.wgrad_queue.enabled = True
+            try:
+                loss.backward()
+                self.wgrad_queue.flush()
+            finally:
+                self.wgrad_queue.enabled = False
+        else:
+            loss.backward()
         from touchnet_amd.models.backend import ops as _ops
         if hasattr(_ops(), "sync_wgrad_stream"):
             _ops().sync_wgrad_stream()                   # (weight-gradient GEMMs issued beside the input-gradient chain)

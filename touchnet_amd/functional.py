@@ -633,6 +633,48 @@ def gemm_grouped_wgrad(pairs, outs=None, accumulate: bool = False):
     return list(outs)
 
 
+GROUPED_TABLE_MAX = 1024          # products per tn_gemm_bf16_grouped_table launch
+
+
+def gemm_grouped_table_wgrad(pairs, outs=None, accumulate: bool = False, bias_grads=None):
+    """``out_g[M_g, N_g] (+)= a_g^T @ b_g`` for ANY number (1..1024) of independent pairs of bf16 device matrices stored
+    [K_g, M_g] / [K_g, N_g] as ONE persistent launch over the concatenation of their tile lists (tn_gemm_bf16_grouped_table):
+    whole tiles only, every output has the bits of the unsplit single-product launch.  ``outs``: bf16 or fp32 matrices (all
+    of one dtype; they may have a row pitch) to write or, ``accumulate``, to add to; default new bf16 tensors.
+    ``bias_grads``: per product None or a contiguous bf16 [M_g] vector that receives the column sums of ``a_g``."""
+    n = len(pairs)
+    if not 1 <= n <= GROUPED_TABLE_MAX:
+        raise _C.KernelError(f"gemm_grouped_table_wgrad: 1..{GROUPED_TABLE_MAX} products")
+    for a, b in pairs:
+        if (a.dim() != 2 or b.dim() != 2 or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.stride(1) != 1
+                or b.stride(1) != 1 or a.shape[0] != b.shape[0] or not a.is_cuda):
+            raise _C.KernelError("gemm_grouped_table_wgrad: pairs of 2-D bf16 device matrices [K, M] / [K, N] with contiguous rows")
+    if outs is None:
+        if accumulate:
+            raise _C.KernelError("gemm_grouped_table_wgrad: accumulate needs `outs`")
+        outs = [torch.empty(a.shape[1], b.shape[1], dtype=torch.bfloat16, device=a.device) for a, b in pairs]
+    for o, (a, b) in zip(outs, pairs):
+        if (o.dtype != outs[0].dtype or o.dtype not in (torch.float32, torch.bfloat16) or o.stride(1) != 1
+                or tuple(o.shape) != (a.shape[1], b.shape[1])):
+            raise _C.KernelError("gemm_grouped_table_wgrad: bad `outs`")
+    if bias_grads is None:
+        bias_grads = [None] * n
+    for bg, (a, _) in zip(bias_grads, pairs):
+        if bg is not None:
+            _check_bias_grad(bg, a.shape[1], a)
+    lib = _C.lib()
+    need = int(lib.tn_gemm_grouped_table_bytes(n))
+    table = torch.empty(need, dtype=torch.uint8, device=outs[0].device)       # (stream-ordered: free to go after the call)
+    Ap, Bp, la, lb = _operand_arrays(pairs)
+    _C.check(lib.tn_gemm_bf16_grouped_table(
+        Ap, Bp, la, lb, _carr(ctypes.c_int, [a.shape[0] for a, _ in pairs]),
+        _carr(ctypes.c_void_p, [o.data_ptr() for o in outs]), _carr(ctypes.c_longlong, [o.stride(0) for o in outs]),
+        _carr(ctypes.c_int, [a.shape[1] for a, _ in pairs]), _carr(ctypes.c_int, [b.shape[1] for _, b in pairs]),
+        _carr(ctypes.c_void_p, [bg.data_ptr() if bg is not None else None for bg in bias_grads]), n, int(accumulate),
+        int(outs[0].dtype == torch.float32), _p(table), need, _cur()), "tn_gemm_bf16_grouped_table")
+    return list(outs)
+
+
 def gemm_swiglu_fwd(x2: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor):
     """``(gate, up, act)`` with gate = x2 @ w_gate^T, up = x2 @ w_up^T, act = silu(gate) * up from ONE launch of the
     hand-written kernel whose epilogue applies the SwiGLU (tn_gemm_bf16_swiglu_fwd; bit-identical to the two products
@@ -937,6 +979,139 @@ def _sink_wgrad(w, dy, x2, bias_grad=None) -> bool:
     return True
 
 
+# Deferred weight gradients (the audio tower's linear layers).  Nothing reads a weight gradient before the gradient norm,
+# so a product dY^T x does not have to run where the backward forms dY.  Per tower layer the six products (q, k, v, out,
+# fc1, fc2 at 1280 / 5120 wide) are 4 x 25 + 2 x 100 = 300 output tiles of 256 x 256 — 1.17 rounds on 256 CUs, which no
+# per-layer launch fills: whole tiles pay two rounds for 1.17, so `split_k` cut the contraction (fp32 workspace, a reduce
+# kernel, 56 idle CUs at 100 tiles x 2).  A queue takes ``(weight, dY, x)`` instead, and ONE table-driven launch
+# (gemm_grouped_table_wgrad) runs the products of many layers as a single unsplit tile list.  It follows the gradient-sink
+# protocol below: autograd sees no gradient for a queued weight (nor for its bias), the queue writes ``.grad`` itself.
+#   flush threshold  11 layers = 3300 tiles = 12.89 rounds -> 13 rounds at 99.2 % occupancy; the 32 layers of the tower flush
+#                    as 11 + 11 + 10 (3000 tiles = 11.72 -> 12 rounds): 38 rounds in all, the same as ONE flush of 9600 tiles
+#                    (37.5 -> 38), at a third of the memory
+#   memory           a queued layer keeps its dY (691 MB at 30000 frames) and x (538 MB, saved activations that would have
+#                    been freed by then) alive: at most 11 x 1.23 GB = 13.5 GB, while the tower's backward runs — after the
+#                    decoder's activations are freed, so the step's peak (end of the decoder's forward) does not move
+# Kept on the per-layer path: weights a data-parallel engine's sink owns, the side stream (`enable_wgrad_stream`), operands
+# the kernel does not take, an existing ``.grad`` that is not a bf16 matrix; tensor / context parallelism and activation
+# checkpointing never install a queue (bin/train.py).  TN_DEFERRED_WGRAD=0: the per-layer path everywhere (A/B switch).
+DEFERRED_WGRAD = os.environ.get("TN_DEFERRED_WGRAD", "1") != "0"
+DEFERRED_WGRAD_FLUSH_LAYERS = 11
+WGRAD_QUEUES = {}        # id(weight) -> weakref to its queue (a dead queue's entries are ignored)
+
+
+class DeferredWgrad:
+    """The queue.  ``layers``: per layer a list of ``(weight, bias or None)`` parameters, the only ones it takes.  `push`
+    during the backward, `flush` behind it (and by itself once ``flush_layers`` layers are waiting and another one
+    arrives).  ``launch``: `gemm_grouped_table_wgrad`, replaceable (tests of the bookkeeping)."""
+
+    def __init__(self, layers, flush_layers: int = DEFERRED_WGRAD_FLUSH_LAYERS):
+        import weakref
+        if flush_layers < 1:
+            raise ValueError("DeferredWgrad: flush_layers >= 1")
+        self.flush_layers = flush_layers
+        self.launch = gemm_grouped_table_wgrad
+        self.enabled = True              # False: `push` takes nothing (an owner that flushes only behind its own backward)
+        self._owned = {}                 # id(weight) -> (weight, bias, layer)
+        self._items = []                 # (weight, dy, x2, bias or None, stream) in queue order
+        self._waiting = set()            # ids of the queued weights
+        self._layers = set()             # layers with a queued weight
+        self.flushes = 0
+        for li, layer in enumerate(layers):
+            for w, b in layer:
+                self._owned[id(w)] = (w, b, li)
+                WGRAD_QUEUES[id(w)] = weakref.ref(self)
+
+    def __len__(self):
+        return len(self._items)
+
+    def close(self):
+        """give the weights back to the per-layer path (the queue must be empty)"""
+        if self._items:
+            raise _C.KernelError("DeferredWgrad.close: the queue is not empty")
+        for k in self._owned:
+            ref = WGRAD_QUEUES.get(k)
+            if ref is not None and ref() is self:
+                del WGRAD_QUEUES[k]
+        self._owned = {}
+
+    def push(self, w, dy, x2, with_bias: bool) -> bool:
+        """Take ``dW = dy^T x2`` (and, ``with_bias``, the bias gradient ``dy.sum(0)``) of an owned weight.  False: not this
+        queue's business — the caller forms the gradient itself."""
+        own = self._owned.get(id(w))
+        if not self.enabled or own is None or own[0] is not w:
+            return False
+        _, bias, layer = own
+        if id(w) in self._waiting:
+            raise _C.KernelError("DeferredWgrad: a weight was queued twice without a flush in between "
+                                 "(two backward passes through one layer: flush between them)")
+        ok = (LINEAR_GEMM == "own" and w.dtype == torch.bfloat16 and w.dim() == 2
+              and all((t.is_cuda or t.is_meta) and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+                      and t.stride(0) % 8 == 0 and (t.is_meta or t.data_ptr() % 16 == 0) for t in (dy, x2))
+              and dy.shape[0] == x2.shape[0] and tuple(w.shape) == (dy.shape[1], x2.shape[1])
+              and gemm_supported(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True)
+              and (not with_bias or (bias is not None and bias.dtype == torch.bfloat16))
+              and (w.grad is None or (w.grad.dtype == torch.bfloat16 and w.grad.is_contiguous()
+                                      and (w.grad.is_meta or w.grad.data_ptr() % 16 == 0))))
+        if not ok:
+            return False
+        if layer not in self._layers and len(self._layers) >= self.flush_layers:
+            self.flush()
+        self._items.append((w, dy, x2, bias if with_bias else None, torch.cuda.current_stream() if dy.is_cuda else None))
+        self._waiting.add(id(w))
+        self._layers.add(layer)
+        return True
+
+    def flush(self) -> None:
+        """Run everything queued, in queue order, and write the ``.grad`` of the weights and biases (added to an existing
+        one).  One launch — two when some of the weights already have a gradient and others do not."""
+        items, self._items = self._items, []
+        self._waiting.clear()
+        self._layers.clear()
+        if not items:
+            return
+        self.flushes += 1
+        cur = torch.cuda.current_stream() if items[0][1].is_cuda else None
+        for w, dy, x2, _, st in items:
+            if st is not None and st != cur:       # formed on another stream than the one the products run on
+                cur.wait_stream(st)
+                dy.record_stream(cur)
+                x2.record_stream(cur)
+        parts = {acc: [it for it in items if (it[0].grad is not None) == acc] for acc in (False, True)}
+        for acc, part in parts.items():
+            for i in range(0, len(part), GROUPED_TABLE_MAX):
+                chunk = part[i:i + GROUPED_TABLE_MAX]
+                outs = [w.grad if acc else torch.empty(w.shape, dtype=torch.bfloat16, device=dy.device)
+                        for w, dy, _, _, _ in chunk]
+                bgs = [torch.empty(dy.shape[1], dtype=torch.bfloat16, device=dy.device) if b is not None else None
+                       for _, dy, _, b, _ in chunk]
+                self.launch([(dy, x2) for _, dy, x2, _, _ in chunk], outs=outs, accumulate=acc, bias_grads=bgs)
+                for (w, _, _, b, _), o, bg in zip(chunk, outs, bgs):
+                    if not acc:
+                        w.grad = o
+                    if b is not None:
+                        if b.grad is None:
+                            b.grad = bg
+                        else:
+                            b.grad.add_(bg)
+
+
+def _queue_wgrad(w, dy, x2, with_bias: bool) -> bool:
+    """Hand ``dW = dy^T x2`` to the deferred-weight-gradient queue that owns ``w``, if there is one and nothing else claims
+    the product (a data-parallel engine's sink, the side stream)."""
+    if not DEFERRED_WGRAD or WGRAD_STREAM is not None:
+        return False
+    ref = WGRAD_QUEUES.get(id(w))
+    q = ref() if ref is not None else None
+    if q is None:
+        return False
+    sref = GRAD_SINKS.get(id(w))
+    sink = sref() if sref is not None else None
+    if sink is not None and sink.owns(w):
+        return False
+    return q.push(w, dy, x2, with_bias)
+
+
 def _wgrad_group(items):
     """Weight gradients dY_i^T x_i of up to three layers ``items = [(w, dy, x2), ...]`` as ONE grouped launch
     (gemm_grouped_wgrad).  With a data-parallel engine's gradient sinks registered for ALL of them (one dtype, one
@@ -1098,6 +1273,11 @@ class _LinearGroup(torch.autograd.Function):
             if own:
                 x2c = _c(x2)
                 for i, (d, nw) in enumerate(zip(dys, need_w)):
+                    # a deferred-weight-gradient queue that owns the weight takes the product (and writes both gradients)
+                    if nw and _queue_wgrad(ws[i], d, x2c, bool(need_b[i] and BIAS_IN_WGRAD)):
+                        sunk.add(i)
+                        need_b[i] = need_b[i] and not BIAS_IN_WGRAD
+                        continue
                     # the bias gradient rides on the weight-gradient launch (column sums of the dY fragments it reads anyway)
                     bg = (torch.empty(Ns[i], dtype=x.dtype, device=x.device)
                           if (nw and need_b[i] and BIAS_IN_WGRAD) else None)
@@ -1360,6 +1540,8 @@ class _GeluMLP(torch.autograd.Function):
         dx = gemm([(dpre, _c(w1))], b_kmaj=True).view(ctx.xshape) if nx else None
 
         def wgrad(w, d, a, want_w, want_b):
+            if want_w and _queue_wgrad(w, d, a, bool(want_b and BIAS_IN_WGRAD)):     # (deferred: the queue writes .grad)
+                return None, (None if BIAS_IN_WGRAD else (column_sum(d) if want_b else None))
             bg = (torch.empty(d.shape[1], dtype=d.dtype, device=d.device)
                   if (want_w and want_b and BIAS_IN_WGRAD) else None)
             dw = None

@@ -140,6 +140,12 @@ class Qwen2AudioEncoder(nn.Module):
         self.layers = nn.ModuleList([EncoderLayer(cfg, causal) for _ in range(cfg.encoder_layers)])
         self.layer_norm = LayerNorm(cfg.d_model)
 
+    def deferred_wgrad_layers(self):
+        """Per encoder layer the ``(weight, bias or None)`` of its six linear layers: the weight gradients a trainer may
+        queue and run as one launch over many layers (functional.DeferredWgrad)."""
+        return [[(lin.weight, lin.bias) for lin in (l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj,
+                                                    l.self_attn.out_proj, l.fc1, l.fc2)] for l in self.layers]
+
     def positions(self, seq_len):
         """qwen2_audio/__init__.py:52-73: slice the table, or tile it for audio longer than 30 s."""
         pos = self.embed_positions.weight
