@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -460,6 +461,15 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
     return L.colsum_bf16(x)
 
 
+def _out_or_new(name, out, accumulate, M, N, device):
+    """The output of a GEMM entry point: ``out`` or, by default, a new bf16 [M, N] matrix — which nothing can be added to."""
+    if out is not None:
+        return out
+    if accumulate:
+        raise _C.KernelError(f"{name}: accumulate needs an output to add to")
+    return torch.empty(M, N, dtype=torch.bfloat16, device=device)
+
+
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
             accumulate: bool = False, out_t: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out = a @ b.T (+ bias) (+ out)`` with the hand-written MFMA kernel (csrc/gemm.hip): a [M, K], b [N, K] bf16
@@ -470,10 +480,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = Non
         raise _C.KernelError("gemm_tn: operands must be contraction-contiguous [M, K] / [N, K]")
     M, K = a.shape
     N = b.shape[0]
-    if out is None:
-        if accumulate:
-            raise _C.KernelError("gemm_tn: accumulate needs `out`")
-        out = torch.empty(M, N, dtype=a.dtype, device=a.device)
+    out = _out_or_new("gemm_tn", out, accumulate, M, N, a.device)
     if out.stride(1) != 1 or tuple(out.shape) != (M, N):
         raise _C.KernelError("gemm_tn: bad `out`")
     if bias is not None:
@@ -517,10 +524,7 @@ def gemm(segs, a_kmaj: bool = False, b_kmaj: bool = False, bias: Optional[torch.
         if Ka != Kb or Ma != M or Nb != N:
             raise _C.KernelError(f"gemm: segment shapes disagree: a {tuple(a.shape)} b {tuple(b.shape)}")
         Ks.append(Ka)
-    if out is None:
-        if accumulate:
-            raise _C.KernelError("gemm: accumulate needs `out`")
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=a0.device)
+    out = _out_or_new("gemm", out, accumulate, M, N, a0.device)
     n = len(segs)
     f32 = out.dtype == torch.float32
     wgrad_mode = a_kmaj and b_kmaj and n == 1 and bias is None and out_t is None
@@ -599,6 +603,22 @@ def _check_bias_grad(bias_grad, M, like):
         raise _C.KernelError("gemm: bias_grad must be a contiguous bf16 [M] device vector")
 
 
+def _check_grouped(name, pairs, outs, accumulate):
+    """The operand and output checks of `gemm_grouped_wgrad` and `gemm_grouped_table_wgrad` (``name``: the caller, for the
+    message); returns ``outs`` or, by default, new bf16 tensors."""
+    for a, b in pairs:
+        if (a.dim() != 2 or b.dim() != 2 or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.stride(1) != 1
+                or b.stride(1) != 1 or a.shape[0] != b.shape[0] or not a.is_cuda):
+            raise _C.KernelError(f"{name}: pairs of 2-D bf16 device matrices [K, M] / [K, N] with contiguous rows")
+    if outs is None:
+        outs = [_out_or_new(name, None, accumulate, a.shape[1], b.shape[1], a.device) for a, b in pairs]
+    for o, (a, b) in zip(outs, pairs):
+        if (o.dtype != outs[0].dtype or o.dtype not in (torch.float32, torch.bfloat16) or o.stride(1) != 1
+                or tuple(o.shape) != (a.shape[1], b.shape[1])):
+            raise _C.KernelError(f"{name}: bad `outs`")
+    return outs
+
+
 def gemm_grouped_wgrad(pairs, outs=None, accumulate: bool = False):
     """``out_g[M_g, N_g] (+)= a_g^T @ b_g`` for 1..3 independent pairs of bf16 device matrices stored [K_g, M_g] / [K_g, N_g]
     (contraction-major: the weight gradients dY^T x of linear layers) as ONE persistent launch of the hand-written kernel
@@ -608,19 +628,8 @@ def gemm_grouped_wgrad(pairs, outs=None, accumulate: bool = False):
     n = len(pairs)
     if not 1 <= n <= 3:
         raise _C.KernelError("gemm_grouped_wgrad: 1..3 products")
-    for a, b in pairs:
-        if (a.dim() != 2 or b.dim() != 2 or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.stride(1) != 1
-                or b.stride(1) != 1 or a.shape[0] != b.shape[0] or not a.is_cuda):
-            raise _C.KernelError("gemm_grouped_wgrad: pairs of 2-D bf16 device matrices [K, M] / [K, N] with contiguous rows")
-    if outs is None:
-        if accumulate:
-            raise _C.KernelError("gemm_grouped_wgrad: accumulate needs `outs`")
-        outs = [torch.empty(a.shape[1], b.shape[1], dtype=torch.bfloat16, device=a.device) for a, b in pairs]
+    outs = _check_grouped("gemm_grouped_wgrad", pairs, outs, accumulate)
     f32 = outs[0].dtype == torch.float32
-    for o, (a, b) in zip(outs, pairs):
-        if (o.dtype != outs[0].dtype or o.dtype not in (torch.float32, torch.bfloat16) or o.stride(1) != 1
-                or tuple(o.shape) != (a.shape[1], b.shape[1])):
-            raise _C.KernelError("gemm_grouped_wgrad: bad `outs`")
     Ms = _carr(ctypes.c_int, [a.shape[1] for a, _ in pairs])
     Ns = _carr(ctypes.c_int, [b.shape[1] for _, b in pairs])
     Ks = _carr(ctypes.c_int, [a.shape[0] for a, _ in pairs])
@@ -645,18 +654,7 @@ def gemm_grouped_table_wgrad(pairs, outs=None, accumulate: bool = False, bias_gr
     n = len(pairs)
     if not 1 <= n <= GROUPED_TABLE_MAX:
         raise _C.KernelError(f"gemm_grouped_table_wgrad: 1..{GROUPED_TABLE_MAX} products")
-    for a, b in pairs:
-        if (a.dim() != 2 or b.dim() != 2 or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or a.stride(1) != 1
-                or b.stride(1) != 1 or a.shape[0] != b.shape[0] or not a.is_cuda):
-            raise _C.KernelError("gemm_grouped_table_wgrad: pairs of 2-D bf16 device matrices [K, M] / [K, N] with contiguous rows")
-    if outs is None:
-        if accumulate:
-            raise _C.KernelError("gemm_grouped_table_wgrad: accumulate needs `outs`")
-        outs = [torch.empty(a.shape[1], b.shape[1], dtype=torch.bfloat16, device=a.device) for a, b in pairs]
-    for o, (a, b) in zip(outs, pairs):
-        if (o.dtype != outs[0].dtype or o.dtype not in (torch.float32, torch.bfloat16) or o.stride(1) != 1
-                or tuple(o.shape) != (a.shape[1], b.shape[1])):
-            raise _C.KernelError("gemm_grouped_table_wgrad: bad `outs`")
+    outs = _check_grouped("gemm_grouped_table_wgrad", pairs, outs, accumulate)
     if bias_grads is None:
         bias_grads = [None] * n
     for bg, (a, _) in zip(bias_grads, pairs):
@@ -827,9 +825,11 @@ def _own(M: int, N: int, Ks, a_kmaj: bool = False, b_kmaj: bool = False) -> bool
     return SPLIT_K and len(Ks) == 1 and tiles * split_k(M, N, Ks[0], a_kmaj, b_kmaj) >= _OWN_MIN_TILES
 
 
-def _bf16_rows(*ts) -> bool:
-    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0
-               and t.data_ptr() % 16 == 0 for t in ts)
+def _bf16_rows(*ts, meta_ok: bool = False) -> bool:
+    """Operands the hand-written kernel takes: bf16 device matrices with contiguous rows, 16-byte aligned.  ``meta_ok``:
+    meta tensors pass too (the bookkeeping of `DeferredWgrad` runs without a device)."""
+    return all((t.is_cuda or (meta_ok and t.is_meta)) and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
+               and t.stride(0) % 8 == 0 and (t.is_meta or t.data_ptr() % 16 == 0) for t in ts)
 
 
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -880,13 +880,9 @@ RESIDUAL_EPILOGUE = True
 BIAS_IN_WGRAD = os.environ.get("TN_BIAS_IN_WGRAD", "1") != "0"          # (A/B switch)
 
 
-def _wgrad(dy, x2, bias_grad=None) -> Optional[torch.Tensor]:
-    """dY^T x [N, K] on the hand-written kernel (both operands contraction-major: the contraction runs over tokens),
-    or None.  ``bias_grad`` [N] bf16: filled with dY.sum(0) by the same launch."""
-    M, N = dy.shape
-    if not (_own(N, x2.shape[1], (M,), True, True) and _bf16_rows(dy, x2)):
-        return None
-    return gemm([(dy, x2)], True, True, bias_grad=bias_grad)
+def _takes_wgrad(dy, x2) -> bool:
+    """The hand-written kernel takes dY^T x [N, K] (both operands contraction-major: the contraction runs over tokens)."""
+    return _own(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True) and _bf16_rows(dy, x2)
 
 
 # Weight-gradient GEMMs on a side stream.  Nothing in the backward consumes a weight gradient, so these products can
@@ -961,22 +957,21 @@ def _beside(inputs, fn, written=()):
 # Gradient sinks: a data-parallel engine (utils/zero_dp.py) registers, per weight (by id), an object with
 #   take(w) -> (view [N, K] in its reduce-scatter input — fp32 or bf16 —, accumulate?)   and   done(w)
 # and the weight-gradient GEMM of that weight writes straight into the view instead of returning a tensor that would have
-# to be cast-copied there (autograd then sees no gradient for the weight: the engine counts the arrival itself).
+# to be cast-copied there (autograd then sees no gradient for the weight: the engine counts the arrival itself).  Who asks
+# them: `_route_wgrad` (one product) and `_wgrad_group` (the MLP's three), through `_sink_of`.
 GRAD_SINKS = {}          # id(weight) -> weakref to the engine (a dead engine's entries are ignored)
 
 
-def _sink_wgrad(w, dy, x2, bias_grad=None) -> bool:
-    ref = GRAD_SINKS.get(id(w))
-    sink = ref() if ref is not None else None
-    if sink is None or not sink.owns(w):
-        return False
-    M, N = dy.shape
-    if not (_own(N, x2.shape[1], (M,), True, True) and _bf16_rows(dy, x2)):
-        return False
-    view, acc = sink.take(w)
-    gemm([(dy, x2)], True, True, out=view, accumulate=acc, bias_grad=bias_grad)
-    sink.done(w)
-    return True
+def _live(table, w):
+    """the live object `table` (GRAD_SINKS, WGRAD_QUEUES) holds for ``w``, or None"""
+    ref = table.get(id(w))
+    return ref() if ref is not None else None
+
+
+def _sink_of(w):
+    """the live gradient sink that owns ``w``, or None"""
+    sink = _live(GRAD_SINKS, w)
+    return sink if sink is not None and sink.owns(w) else None
 
 
 # Deferred weight gradients (the audio tower's linear layers).  Nothing reads a weight gradient before the gradient norm,
@@ -985,7 +980,7 @@ def _sink_wgrad(w, dy, x2, bias_grad=None) -> bool:
 # per-layer launch fills: whole tiles pay two rounds for 1.17, so `split_k` cut the contraction (fp32 workspace, a reduce
 # kernel, 56 idle CUs at 100 tiles x 2).  A queue takes ``(weight, dY, x)`` instead, and ONE table-driven launch
 # (gemm_grouped_table_wgrad) runs the products of many layers as a single unsplit tile list.  It follows the gradient-sink
-# protocol below: autograd sees no gradient for a queued weight (nor for its bias), the queue writes ``.grad`` itself.
+# protocol above: autograd sees no gradient for a queued weight (nor for its bias), the queue writes ``.grad`` itself.
 #   flush threshold  11 layers = 3300 tiles = 12.89 rounds -> 13 rounds at 99.2 % occupancy; the 32 layers of the tower flush
 #                    as 11 + 11 + 10 (3000 tiles = 11.72 -> 12 rounds): 38 rounds in all, the same as ONE flush of 9600 tiles
 #                    (37.5 -> 38), at a third of the memory
@@ -1000,13 +995,17 @@ DEFERRED_WGRAD_FLUSH_LAYERS = 11
 WGRAD_QUEUES = {}        # id(weight) -> weakref to its queue (a dead queue's entries are ignored)
 
 
+def _queue_of(w):
+    """the live queue registered for ``w``, or None (`DeferredWgrad.push` checks that the weight is still the one it owns)"""
+    return _live(WGRAD_QUEUES, w)
+
+
 class DeferredWgrad:
     """The queue.  ``layers``: per layer a list of ``(weight, bias or None)`` parameters, the only ones it takes.  `push`
     during the backward, `flush` behind it (and by itself once ``flush_layers`` layers are waiting and another one
     arrives).  ``launch``: `gemm_grouped_table_wgrad`, replaceable (tests of the bookkeeping)."""
 
     def __init__(self, layers, flush_layers: int = DEFERRED_WGRAD_FLUSH_LAYERS):
-        import weakref
         if flush_layers < 1:
             raise ValueError("DeferredWgrad: flush_layers >= 1")
         self.flush_layers = flush_layers
@@ -1045,9 +1044,7 @@ class DeferredWgrad:
         if id(w) in self._waiting:
             raise _C.KernelError("DeferredWgrad: a weight was queued twice without a flush in between "
                                  "(two backward passes through one layer: flush between them)")
-        ok = (LINEAR_GEMM == "own" and w.dtype == torch.bfloat16 and w.dim() == 2
-              and all((t.is_cuda or t.is_meta) and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
-                      and t.stride(0) % 8 == 0 and (t.is_meta or t.data_ptr() % 16 == 0) for t in (dy, x2))
+        ok = (LINEAR_GEMM == "own" and w.dtype == torch.bfloat16 and w.dim() == 2 and _bf16_rows(dy, x2, meta_ok=True)
               and dy.shape[0] == x2.shape[0] and tuple(w.shape) == (dy.shape[1], x2.shape[1])
               and gemm_supported(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True)
               and (not with_bias or (bias is not None and bias.dtype == torch.bfloat16))
@@ -1097,51 +1094,84 @@ class DeferredWgrad:
 
 
 def _queue_wgrad(w, dy, x2, with_bias: bool) -> bool:
-    """Hand ``dW = dy^T x2`` to the deferred-weight-gradient queue that owns ``w``, if there is one and nothing else claims
-    the product (a data-parallel engine's sink, the side stream)."""
+    """Step 1 of `_route_wgrad`: hand ``dW = dy^T x2`` to the deferred-weight-gradient queue that owns ``w``, if there is one
+    and nothing else claims the product (a data-parallel engine's sink, the side stream)."""
     if not DEFERRED_WGRAD or WGRAD_STREAM is not None:
         return False
-    ref = WGRAD_QUEUES.get(id(w))
-    q = ref() if ref is not None else None
-    if q is None:
-        return False
-    sref = GRAD_SINKS.get(id(w))
-    sink = sref() if sref is not None else None
-    if sink is not None and sink.owns(w):
-        return False
-    return q.push(w, dy, x2, with_bias)
+    q = _queue_of(w)
+    return q is not None and _sink_of(w) is None and q.push(w, dy, x2, with_bias)
+
+
+# WHERE A WEIGHT GRADIENT GOES.  `_route_wgrad` is the one owner of that decision for a single product dW = dY^T x of a
+# linear layer: `_LinearGroup`, `_GeluMLP` and `_SwiGLUMLP` (and the per-product fallback of `_wgrad_group`) ask it and
+# nothing else.  The rule, first match wins:
+#   1. queue       DEFERRED_WGRAD is on, no side stream is enabled, a live queue owns the weight, no live sink owns it, and
+#                  `DeferredWgrad.push` accepts the product (`_queue_wgrad`).  The queue is asked for the bias gradient exactly
+#                  when it is wanted and BIAS_IN_WGRAD is on; it writes ``.grad`` itself, autograd gets no gradient.
+#   2. sink        the kernel takes the product (`_takes_wgrad`) and a live sink owns the weight (`_sink_of`): the launch
+#                  writes the view the sink hands out (`take` ... `done`), autograd gets no gradient for the weight.
+#   3. own kernel  the kernel takes the product: the same launch returns a new bf16 tensor.
+#   4. not taken   the caller runs its library form.
+# In 2 and 3 a wanted bias gradient rides on the launch when BIAS_IN_WGRAD is on (column sums of the dY fragments it reads
+# anyway): a bf16 [N] vector allocated on the current stream, that `_beside` is told about as `written`.  Everywhere else
+# a wanted bias gradient is left to the caller's `column_sum(dy)` — `_bias_left` says when; the callers keep that pass where
+# it has always run in their launch order (`_LinearGroup`: behind all its weight gradients).
+def _route_wgrad(w, dy, x2, want_bias: bool = False):
+    """``(dw, db, taken)`` for ``dW = dy^T x2`` of the weight ``w``; see the rule above.  ``dw``: the new gradient, None where
+    a queue or a sink received it or nothing took it; ``db``: the bias gradient that rode on the launch, else None."""
+    ride = bool(want_bias and BIAS_IN_WGRAD)
+    if _queue_wgrad(w, dy, x2, ride):
+        return None, None, True
+    if not _takes_wgrad(dy, x2):
+        return None, None, False
+    sink = _sink_of(w)
+    db = torch.empty(dy.shape[1], dtype=torch.bfloat16, device=dy.device) if ride else None
+
+    def launch():
+        if sink is None:
+            return gemm([(dy, x2)], True, True, bias_grad=db)
+        view, acc = sink.take(w)
+        gemm([(dy, x2)], True, True, out=view, accumulate=acc, bias_grad=db)
+        sink.done(w)
+    return _beside((dy, x2), launch, written=(db,)), db, True
+
+
+def _bias_left(want_bias, taken) -> bool:
+    """a wanted bias gradient that `_route_wgrad` did not settle: the caller owes `column_sum(dy)`"""
+    return bool(want_bias and not (taken and BIAS_IN_WGRAD))
+
+
+def _wgrad_one(w, dy, x2):
+    """dW of a bias-free layer by the common route, the library's product where nothing takes it"""
+    dw, _, taken = _route_wgrad(w, dy, x2)
+    return dw if taken else torch.mm(dy.t(), x2)
 
 
 def _wgrad_group(items):
     """Weight gradients dY_i^T x_i of up to three layers ``items = [(w, dy, x2), ...]`` as ONE grouped launch
-    (gemm_grouped_wgrad).  With a data-parallel engine's gradient sinks registered for ALL of them (one dtype, one
-    accumulate state) the launch writes the engine's staging views and the result is [None, ...]; with none it returns new
-    bf16 tensors; a mixed state falls back to one product per layer."""
-    def single(w, dy, x2):
-        return None if _sink_wgrad(w, dy, x2) else gemm([(dy, x2)], True, True)
-    sinks = []
-    for w, _, _ in items:
-        ref = GRAD_SINKS.get(id(w))
-        sk = ref() if ref is not None else None
-        sinks.append(sk if (sk is not None and sk.owns(w)) else None)
-    ok = all(_own(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True) and _bf16_rows(dy, x2) for _, dy, x2 in items)
-    if not ok or (any(sinks) and not all(sinks)):
-        return [single(*it) for it in items]
+    (gemm_grouped_wgrad), beside the backward's own stream like every weight gradient (`_beside`).  With a data-parallel
+    engine's gradient sinks registered for ALL of them (one dtype, one accumulate state) the launch writes the engine's
+    staging views and the result is [None, ...]; with none it returns new bf16 tensors; a mixed state, or operands the
+    kernel does not take, fall back to one routed product per layer."""
+    sinks = [_sink_of(w) for w, _, _ in items]
+    owned = sum(sk is not None for sk in sinks)
+    if not all(_takes_wgrad(dy, x2) for _, dy, x2 in items) or 0 < owned < len(items):
+        return [_wgrad_one(*it) for it in items]
     pairs = [(dy, x2) for _, dy, x2 in items]
-    if not any(sinks):
-        return gemm_grouped_wgrad(pairs)
-    taken = [sk.take(w) for sk, (w, _, _) in zip(sinks, items)]
-    if len({(v.dtype, bool(acc)) for v, acc in taken}) != 1:
-        outs = []
-        for (view, acc), (w, dy, x2), sk in zip(taken, items, sinks):     # (already taken: write each view by itself)
-            gemm([(dy, x2)], True, True, out=view, accumulate=acc)
+
+    def launch():
+        if not owned:
+            return gemm_grouped_wgrad(pairs)
+        taken = [sk.take(w) for sk, (w, _, _) in zip(sinks, items)]
+        if len({(v.dtype, bool(acc)) for v, acc in taken}) == 1:
+            gemm_grouped_wgrad(pairs, outs=[v for v, _ in taken], accumulate=bool(taken[0][1]))
+        else:                                                 # (already taken: write each view by itself)
+            for (view, acc), pair in zip(taken, pairs):
+                gemm([pair], True, True, out=view, accumulate=acc)
+        for sk, (w, _, _) in zip(sinks, items):
             sk.done(w)
-            outs.append(None)
-        return outs
-    gemm_grouped_wgrad(pairs, outs=[v for v, _ in taken], accumulate=bool(taken[0][1]))
-    for sk, (w, _, _) in zip(sinks, items):
-        sk.done(w)
-    return [None] * len(items)
+        return [None] * len(items)
+    return _beside([t for pair in pairs for t in pair], launch)
 
 
 def _stacked_view(ts):
@@ -1252,15 +1282,13 @@ class _LinearGroup(torch.autograd.Function):
         if need_x:
             if own:
                 dx = _dgrad(dys, [_c(w) for w in ws])
-            if dx is not None:
-                pass
-            elif hip_ok and ctx.dgrad_tn:
+            if dx is None and hip_ok and ctx.dgrad_tn:
                 wts = [transpose_2d(_c(w)) for w in ws]                                # W^T [K, N]: forward layout
                 dx = _mm_tn(dys[0], wts[0])
                 for d, wt in zip(dys[1:], wts[1:]):
                     _mm_tn(d, wt, out=dx, accumulate=True)
                 del wts
-            else:
+            elif dx is None:
                 dx = torch.mm(dys[0], ws[0])
                 for d, w in zip(dys[1:], ws[1:]):
                     dx.addmm_(d, w)
@@ -1269,29 +1297,15 @@ class _LinearGroup(torch.autograd.Function):
         need_b = [hb and ctx.needs_input_grad[4 + n + i] for i, hb in enumerate(ctx.has_bias)]
         dbs = [None] * n
         if any(need_w):
-            sunk = set()
+            todo = [i for i in range(n) if need_w[i]]
             if own:
                 x2c = _c(x2)
-                for i, (d, nw) in enumerate(zip(dys, need_w)):
-                    # a deferred-weight-gradient queue that owns the weight takes the product (and writes both gradients)
-                    if nw and _queue_wgrad(ws[i], d, x2c, bool(need_b[i] and BIAS_IN_WGRAD)):
-                        sunk.add(i)
-                        need_b[i] = need_b[i] and not BIAS_IN_WGRAD
-                        continue
-                    # the bias gradient rides on the weight-gradient launch (column sums of the dY fragments it reads anyway)
-                    bg = (torch.empty(Ns[i], dtype=x.dtype, device=x.device)
-                          if (nw and need_b[i] and BIAS_IN_WGRAD) else None)
-                    if nw and _beside((d, x2c), lambda: _sink_wgrad(ws[i], d, x2c, bg), written=(bg,)):
-                        sunk.add(i)
-                        dbs[i] = bg
-                    elif nw:
-                        dws[i] = _beside((d, x2c), lambda: _wgrad(d, x2c, bg), written=(bg,))
-                        if dws[i] is not None:
-                            dbs[i] = bg
-            todo = [i for i in range(n) if need_w[i] and dws[i] is None and i not in sunk]
-            if not todo:
-                pass
-            elif len(todo) < n:                           # (some layers of the group went to the hand-written kernel)
+                for i in list(todo):                      # queue, sink or the hand-written kernel: `_route_wgrad`
+                    dws[i], dbs[i], taken = _route_wgrad(ws[i], dys[i], x2c, need_b[i])
+                    need_b[i] = _bias_left(need_b[i], taken)
+                    if taken:
+                        todo.remove(i)
+            if len(todo) < n:                             # (some layers of the group have their gradient, or want none)
                 for i in todo:
                     dws[i] = torch.mm(dys[i].t(), x2)
             elif ctx.wgrad == "nt_fused" and n > 1:
@@ -1377,13 +1391,11 @@ class _SwiGLUMLP(torch.autograd.Function):
             kept = act
         else:
             gate, up = _mm_tn(x2, _c(wg)), _mm_tn(x2, _c(wu))
-        if fused:
-            pass
-        elif own:
-            act = L.swiglu_fwd(gate, up)
-            kept = act
-        else:
-            act, kept = L.swiglu_fwd_t(gate, up)                       # kept = act^T
+            if own:
+                act = L.swiglu_fwd(gate, up)
+                kept = act
+            else:
+                act, kept = L.swiglu_fwd_t(gate, up)                   # kept = act^T
         y = _mm_tn(act, _c(wd))
         if src is not None and own:
             # op-level selective recomputation (`norm_source`): neither the norm output x nor act = silu(gate) * up is
@@ -1408,9 +1420,8 @@ class _SwiGLUMLP(torch.autograd.Function):
         nx, ng, nu, nd = ctx.needs_input_grad[:4]
         if ctx.own and LINEAR_GEMM == "own":
             grouped = GROUPED_WGRAD and ng and nu and nd
-            if not grouped:
-                dwd = None if (not nd or _beside((dy2, kept), lambda: _sink_wgrad(wd, dy2, kept))) \
-                    else _beside((dy2, kept), lambda: gemm([(dy2, kept)], True, True))                   # dY^T act  [H, I]
+            if not grouped:                                   # one routed product each (`_route_wgrad`)
+                dwd = _wgrad_one(wd, dy2, kept) if nd else None                        # dY^T act  [H, I]
             if ctx.fused and H % 64 == 0 and _bf16_rows(dy2, wd):
                 dgate, dup = gemm_swiglu_bwd(dy2, wd, gate, up)     # d(act) = dY W_down lives in the accumulators only
             else:
@@ -1420,13 +1431,10 @@ class _SwiGLUMLP(torch.autograd.Function):
             dx = gemm([(dgate, _c(wg)), (dup, _c(wu))], b_kmaj=True).view(ctx.xshape) if nx else None
             if grouped:
                 # ONE launch for the three weight gradients (3 x 688 tiles = 8 whole rounds + 16 tiles split-K)
-                dwg, dwu, dwd = _beside((dgate, dup, dy2, x2, kept), lambda: _wgrad_group(
-                    [(wg, dgate, x2), (wu, dup, x2), (wd, dy2, kept)]))
-                return dx, dwg, dwu, dwd, None
-            dwg = None if (not ng or _beside((dgate, x2), lambda: _sink_wgrad(wg, dgate, x2))) \
-                else _beside((dgate, x2), lambda: gemm([(dgate, x2)], True, True))
-            dwu = None if (not nu or _beside((dup, x2), lambda: _sink_wgrad(wu, dup, x2))) \
-                else _beside((dup, x2), lambda: gemm([(dup, x2)], True, True))
+                dwg, dwu, dwd = _wgrad_group([(wg, dgate, x2), (wu, dup, x2), (wd, dy2, kept)])
+            else:
+                dwg = _wgrad_one(wg, dgate, x2) if ng else None
+                dwu = _wgrad_one(wu, dup, x2) if nu else None
             return dx, dwg, dwu, dwd, None
         act_t = kept if not ctx.own else transpose_2d(kept)
         dwd = _mm_tn(transpose_2d(dy2), act_t) if nd else None                      # [H, I], forward layout
@@ -1515,9 +1523,10 @@ GELU_EPILOGUE = os.environ.get("TN_GELU_EPILOGUE", "1") != "0"          # (A/B s
 class _GeluMLP(torch.autograd.Function):
     """``fc2(gelu(fc1(x)))`` of the Whisper-style encoder layer as ONE autograd node (round 6): GELU in fc1's epilogue (pre
     and act from one launch), its backward in the epilogue of fc2's input-gradient product (d(act) stays in the
-    accumulators); weight and bias gradients as `_LinearGroup` forms them (bias gradients ride on the weight-gradient
-    launches).  Every launch is bit-identical to the kernels it replaces.  Same box, interleaved: 707.5 -> 705.5 ms per
-    headline step (profiles/r06g_*: the two GELU passes, 9.3 ms, against 4.9 ms of epilogue time inside the GEMMs)."""
+    accumulators); weight and bias gradients by `_route_wgrad`, as in `_LinearGroup` (bias gradients ride on the
+    weight-gradient launches).  Every launch is bit-identical to the kernels it replaces.  Same box, interleaved:
+    707.5 -> 705.5 ms per headline step (profiles/r06g_*: the two GELU passes, 9.3 ms, against 4.9 ms of epilogue time
+    inside the GEMMs)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
@@ -1540,20 +1549,10 @@ class _GeluMLP(torch.autograd.Function):
         dx = gemm([(dpre, _c(w1))], b_kmaj=True).view(ctx.xshape) if nx else None
 
         def wgrad(w, d, a, want_w, want_b):
-            if want_w and _queue_wgrad(w, d, a, bool(want_b and BIAS_IN_WGRAD)):     # (deferred: the queue writes .grad)
-                return None, (None if BIAS_IN_WGRAD else (column_sum(d) if want_b else None))
-            bg = (torch.empty(d.shape[1], dtype=d.dtype, device=d.device)
-                  if (want_w and want_b and BIAS_IN_WGRAD) else None)
-            dw = None
-            if want_w:
-                if _beside((d, a), lambda: _sink_wgrad(w, d, a, bg), written=(bg,)):
-                    dw = None
-                else:
-                    dw = _beside((d, a), lambda: _wgrad(d, a, bg), written=(bg,))
-                    if dw is None:                                             # (a shape the kernel does not take)
-                        dw, bg = torch.mm(d.t(), a), None
-            db = bg if bg is not None else (column_sum(d) if want_b else None)
-            return dw, db
+            dw, db, taken = _route_wgrad(w, d, a, want_b) if want_w else (None, None, False)
+            if want_w and not taken:                                           # (a shape the kernel does not take)
+                dw = torch.mm(d.t(), a)
+            return dw, (column_sum(d) if _bias_left(want_b, taken) else db)
         dw2, db2 = wgrad(w2, dy2, act, n2, nb2 and ctx.has_b[1])
         dw1, db1 = wgrad(w1, dpre, x2, n1, nb1 and ctx.has_b[0])
         return dx, dw1, db1, dw2, db2
