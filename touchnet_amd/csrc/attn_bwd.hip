@@ -62,21 +62,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   // ONE LDS variable on purpose: with two, hipcc's module-LDS lowering attaches alias scopes to every access and the
   // waitcnt insertion then puts `s_waitcnt vmcnt(0)` in front of the first LDS read that may alias a pending LDS-DMA
   // (= every read of the ring), which serialises the ring (see attn_common.h, i32x4_t).
-  // Round 6 (attn_fwd_stream.hip's treatment), D = 128 only: the stored list of query tiles instead of dependent metadata
-  // loads; before the ring starts its area holds each wave's private K / V images (the 32 rows arrive by LDS-DMA as
-  // 64-byte runs); behind the last stage the dV / dK rows leave through it as whole rows.  Same box, interleaved
-  // (profiles/r06c_*): the D = 128 passes gain 1-8 % (most on short documents), the D = 64 pass LOSES 1-4 % (187 -> 228
-  // registers for the same two waves per SIMD; its row loads and stores are half as many) and keeps the direct form.
+  // D = 128 only (attn_fwd_stream.hip's treatment): before the ring starts its area holds each wave's private K / V images
+  // (the 32 rows arrive by LDS-DMA as 64-byte runs), and behind the last stage the dV / dK rows leave through it as whole
+  // rows.  Same box, interleaved (profiles/r06c_*): the D = 128 passes gain 1-8 % (most on short documents), the D = 64
+  // pass LOSES 1-4 % (187 -> 228 registers for the same two waves per SIMD; its row loads and stores are half as many) and
+  // keeps the direct form.  Both forms take their query tiles from the per-tile metadata (q_lo / kv_hi and the id
+  // statistics): the stored query-tile lists of the metadata are causal, and the causal D = 128 launches go to
+  // attn_bwd_fused.hip, so no launch of this kernel could follow them.
   using KTile = PTile<32, D>;
   constexpr int KIMGB = KTile::SIZE * 2;
   constexpr bool R6 = D == 128;
   constexpr int RING0 = NST * STAGEB, RING1 = 4 * 2 * WholeRows<D>::BYTES, RING2 = 4 * 2 * KIMGB;
   constexpr int RINGX = RING0 > RING1 ? (RING0 > RING2 ? RING0 : RING2) : (RING1 > RING2 ? RING1 : RING2);
   constexpr int RING = D == 128 ? RINGX : RING0;
-  __shared__ __attribute__((aligned(1024))) char smem[RING + (LCAP + NST) * 32 + 16 + kListPre * 16];
+  __shared__ __attribute__((aligned(1024))) char smem[RING + (LCAP + NST) * 32 + 16];
   i32x4_t* slist = reinterpret_cast<i32x4_t*>(smem + RING);             // entry e = {slist[2e], slist[2e + 1]}
   int* wcount = reinterpret_cast<int*>(smem + RING + (LCAP + NST) * 32);
-  i32x4_t* qent = reinterpret_cast<i32x4_t*>(smem + RING + (LCAP + NST) * 32 + 16);   // the stored q-tile list
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -89,17 +90,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   const bool kvalid = kvrow < T;
 
   const bool bidir = qv.bidir != 0;
-  // ---- round trip A: the stored list of query tiles, the id statistics of this wave's rows, this lane's id, and the
-  // wave's K / V rows — issued together
-  // (the stored lists are causal and name every query tile of the row: only a launch whose one segment IS the whole row
-  // may follow them — a shorter shard at offset 0 would be walked past its local [B, rpb] buffers)
-  const bool plain = R6 && qv.nseg == 1 && qv.off[0] == 0 && qv.row0[0] == 0 && qv.rows[0] == T && qv.rpb == T && !bidir;
-  i32x4_t ql_head = {kListPre + 1, 0, 0, 0}, ql_mine = {0, 0, 0, 0};
-  if (plain) {
-    const i32x4_t* ql = reinterpret_cast<const i32x4_t*>(meta.qlist) + ((size_t)b * meta.nq128 + kt) * (1 + kListPre);
-    ql_head = ql[0];
-    if (tid < kListPre) ql_mine = ql[1 + tid];
-  }
+  // ---- round trip A: the id statistics of this wave's rows, this lane's id, and the wave's K / V rows — issued together
   i32x4_t ws4 = {0x7fffffff, 0, 1, 0};          // {min positive id, max id, pad present, -} of the wave's 32 kv rows
   if (R6 && wk0 < T) ws4 = reinterpret_cast<const i32x4_t*>(meta.qstat)[(size_t)b * meta.nq32 + wk0 / 32];
   const int dkdoc = kvalid ? doc[(size_t)b * T + kvrow] : 0;
@@ -150,10 +141,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
       if (DO_DK) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vreg[s]));
     }
   }
-  const int n_pre = __builtin_amdgcn_readfirstlane(ql_head.x);
-  const bool pre = n_pre <= kListPre;          // the stored list is complete: use it
-  if (pre && tid < n_pre) qent[tid] = ql_mine;
-  // everybody has read its private images (the ring area is free) and the list is in LDS
+  // everybody has read its private images: the ring area is free
   __syncthreads();
 
   const int* m_min = meta.tmin + (size_t)b * meta.nt;
@@ -161,16 +149,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
   const int* m_minpos = meta.tminpos + (size_t)b * meta.nt;
   const int t0 = 2 * kt, t1 = min(2 * kt + 1, meta.nt - 1);
   const int kvcap = bidir ? -0x7fffffff : kvrow;            // `kvcap <= q`: the causal term of the predicate
-  int bminpos = 0, bmax = 0, qt_lo = k0 / kTile, qt_end = 0;
-  if (!pre) {
-    // first 64-position query tile, global index: q >= kv under the causal mask; bidirectional: the first tile that
-    // shares a document with these kv rows
-    if (bidir) qt_lo = min(meta.q_lo[(size_t)b * meta.nt + t0], meta.q_lo[(size_t)b * meta.nt + t1]);
-    bminpos = min(m_minpos[t0], m_minpos[t1]);
-    bmax = max(m_max[t0], m_max[t1]);
-    const int qhi64 = max(meta.kv_hi[(size_t)b * meta.nt + t0], meta.kv_hi[(size_t)b * meta.nt + t1]);
-    qt_end = min(qhi64 + 1, meta.nt);                       // exclusive
-  }
+  // first 64-position query tile, global index: q >= kv under the causal mask; bidirectional: the first tile that
+  // shares a document with these kv rows
+  int qt_lo = k0 / kTile;
+  if (bidir) qt_lo = min(meta.q_lo[(size_t)b * meta.nt + t0], meta.q_lo[(size_t)b * meta.nt + t1]);
+  const int bminpos = min(m_minpos[t0], m_minpos[t1]);
+  const int bmax = max(m_max[t0], m_max[t1]);
+  const int qhi64 = max(meta.kv_hi[(size_t)b * meta.nt + t0], meta.kv_hi[(size_t)b * meta.nt + t1]);
+  const int qt_end = min(qhi64 + 1, meta.nt);               // exclusive
   int wminpos, wmax;
   bool w_uniform;                                           // all 32 kv rows in one document
   if constexpr (R6) {
@@ -190,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
     seg_lo[s] = max(qt_lo, first);
     seg_n[s] = max(min(qt_end, first + cnt) - seg_lo[s], 0);
   }
-  const int nqt = pre ? n_pre : seg_n[0] + seg_n[1];
+  const int nqt = seg_n[0] + seg_n[1];
   // ---- the stream of stages: (head in group, BQ-row part of a 64-row q tile), skipping what cannot interact.
   // The per-stage bookkeeping used to be a scalar scan every wave ran between two stages (≈100 SALU instructions per
   // stage and wave: 7 SALU per MFMA in the dV kernel's PMC); now the workgroup compacts LCAP candidate stages at a time
@@ -202,23 +188,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(
     if (c < total_c) {
       const int g = c / per_head, r = c - g * per_head;
       const int idx = r / SPT, part = r % SPT;
-      int sg = 0, t64, lt, left;
-      if (pre) {                                  // (plain launch: local row = global position)
-        const i32x4_t qe = qent[idx];
-        t64 = qe.x; d.mn = qe.y; d.mx = qe.z; d.mp = qe.w;
-        lt = t64;
-        left = T - t64 * kTile - BQ * part;
-        d.valid = left > 0;
-      } else {
-        sg = idx >= seg_n[0] ? 1 : 0;
-        t64 = seg_lo[sg] + idx - (sg ? seg_n[0] : 0);
-        lt = t64 - qv.off[sg] / kTile;
-        left = min(qv.rows[sg] - lt * kTile, T - t64 * kTile) - BQ * part;
-        d.mp = m_minpos[t64];
-        d.mx = m_max[t64];
-        d.mn = m_min[t64];
-        d.valid = left > 0 && tile_may_interact(d.mp, d.mx, bminpos, bmax);
-      }
+      const int sg = idx >= seg_n[0] ? 1 : 0;
+      const int t64 = seg_lo[sg] + idx - (sg ? seg_n[0] : 0);
+      const int lt = t64 - qv.off[sg] / kTile;
+      const int left = min(qv.rows[sg] - lt * kTile, T - t64 * kTile) - BQ * part;
+      d.mp = m_minpos[t64];
+      d.mx = m_max[t64];
+      d.mn = m_min[t64];
+      d.valid = left > 0 && tile_may_interact(d.mp, d.mx, bminpos, bmax);
       d.qsb = t64 * kTile + BQ * part;
       d.lrow = qv.row0[sg] + lt * kTile + BQ * part;
       d.left = min(left, BQ);

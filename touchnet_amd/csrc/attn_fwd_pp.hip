@@ -45,10 +45,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
   __shared__ __attribute__((aligned(16))) bf16_t smem[3 * KSLOT + 2 * VSLOT];
   __shared__ __attribute__((aligned(16))) int4 tlist[kMaxList + 4];   // {tile, min id, max id, min positive id}
   __shared__ int wcount[8];
-  // D = 64 has 128 staging units for a group's 256 threads: the idle half runs the same (branch-free) pieces with
-  // zero-filled loads and stores into this dump area
-  constexpr bool ALL_STAGE = (BN / 4) * CPR == 256;
-  __shared__ __attribute__((aligned(16))) bf16_t dump[ALL_STAGE ? 8 : 4 * KLD + 256 * 8 + 8];
+  // Every thread of a group owns exactly one staging unit (4 tile rows x 8 columns): that holds for D = 128, the only
+  // head size the launcher builds (D = 64 would leave half of a group without a unit).
+  static_assert((BN / 4) * CPR == 256, "one staging unit per thread of a 256-thread group");
+  // The tile's 64 doc ids are stored by the first 64 threads of a group; the other 192 run the same branch-free store
+  // into this sink, one word per thread.
+  __shared__ int sink[256];
   bf16_t* const Kbuf = smem;
   bf16_t* const Vbuf = smem + 3 * KSLOT;
 
@@ -146,10 +148,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
   // (8-byte transposing stores of 16 consecutive lanes fill one V^T row).
   const int u_g = grp == 0 ? (gtid & 15) : gtid / CPR;        // 4-row group of the tile
   const int u_c = grp == 0 ? (gtid >> 4) : gtid % CPR;        // 8-column chunk
-  const bool u_ok = u_c < CPR && u_g < BN / 4;
   uint32_t soff[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) soff[k] = u_ok ? (uint32_t)(((size_t)(4 * u_g + k) * kvld + u_c * 8) * 2) : 0xffffffffu;
+  for (int k = 0; k < 4; ++k) soff[k] = (uint32_t)(((size_t)(4 * u_g + k) * kvld + u_c * 8) * 2);
   uint4 stg[4];
   int dstage = 0;
   const size_t head_off = ((size_t)b * T * Nkv + hk) * D;
@@ -189,16 +190,15 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(const bf16_t* __res
       if (i == 4) *dbase = dstage;
     }
   };
-  // this thread's spots in a slot (idle stagers: the dump area)
-  int* const dump_i = reinterpret_cast<int*>(dump);
+  // this thread's spots in a slot
   auto k_spot = [&](int slot) __attribute__((always_inline)) {
-    return (ALL_STAGE || u_ok) ? Kbuf + slot * KSLOT + (4 * u_g) * KLD + u_c * 8 : dump + gtid * 8;
+    return Kbuf + slot * KSLOT + (4 * u_g) * KLD + u_c * 8;
   };
   auto v_spot = [&](int slot) __attribute__((always_inline)) {
-    return (ALL_STAGE || u_ok) ? Vbuf + slot * VSLOT + (u_c * 8) * VLD + 4 * vt_pos(u_g) : dump + gtid * 4;
+    return Vbuf + slot * VSLOT + (u_c * 8) * VLD + 4 * vt_pos(u_g);
   };
   auto d_spot = [&](int slot) __attribute__((always_inline)) {
-    return gtid < BN ? reinterpret_cast<int*>(Kbuf + slot * KSLOT + BN * KLD) + gtid : dump_i + gtid;
+    return gtid < BN ? reinterpret_cast<int*>(Kbuf + slot * KSLOT + BN * KLD) + gtid : sink + gtid;
   };
   auto list_at = [&](int i) __attribute__((always_inline)) {               // list entry i as scalars
     const int4 e = tlist[i];
@@ -408,14 +408,9 @@ using namespace tn;
 int tn_attn_fwd_pp_launch(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc,
                           AttnMeta m, QView qv, int B, int T, int Nh, int Nkv, int D, float sl2, hipStream_t st) {
   dim3 grid(Nh, qv.tiles(0, 256) + qv.tiles(1, 256), B), block(512);
-  if (D == 128)
-    hipLaunchKernelGGL((attn_fwd_pp_kernel<128>), grid, block, 0, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (bf16_t*)o, lse2, doc, m, qv, T, Nh, Nkv, sl2);
-  else if (D == 64)
-    hipLaunchKernelGGL((attn_fwd_pp_kernel<64>), grid, block, 0, st, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (bf16_t*)o, lse2, doc, m, qv, T, Nh, Nkv, sl2);
-  else
-    return TN_EINVAL;
+  if (D != 128) return TN_EINVAL;             // (fwd_pingpong sends nothing else here)
+  hipLaunchKernelGGL((attn_fwd_pp_kernel<128>), grid, block, 0, st, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, lse2, doc, m, qv, T, Nh, Nkv, sl2);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }

@@ -91,10 +91,11 @@ def apply_rope(q, k, cos, sin):
 @dataclass
 class PackedMask:
     """Device-side form of the packers' document-id `attention_mask`
-    (touchnet/models/llama/processing_llama.py:38-40): int32 ids + per-64-tile range metadata.
+    (touchnet/models/llama/processing_llama.py:38-40): int32 ids + the range metadata of `library.attn_build_meta`
+    (statistics per 64 and per 32 positions, stored tile lists per 128: csrc/attn_common.h).
     Built once per batch and shared by all layers (the reference builds its BlockMask once per forward)."""
     doc: torch.Tensor     # int32 [B, T], 0 = pad
-    meta: torch.Tensor    # int32 [5 * B * ceil(T/64)]
+    meta: torch.Tensor    # int32 [library.attn_meta_ints(B, T)]
     B: int
     T: int
 
@@ -131,64 +132,38 @@ class _AttentionRopeGrad(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse2, doc, meta, cos, sin = ctx.saved_tensors
-        B, T, Nh, D = q.shape
-        Nkv = k.shape[2]
-        stacked = Nh == Nkv
-        out = L.attn_bwd_rope(q, k, v, o, _c(do), lse2, doc, meta, ctx.scale, cos, sin, stacked)
-        if stacked:                                        # (one buffer, three slices: library.attn_bwd_stacked)
-            dq, dk, dv = out.unbind(0)
-        else:
-            dq, dk, dv = out.split([B * T * Nh * D, B * T * Nkv * D, B * T * Nkv * D])
-            dq, dk, dv = dq.view(B, T, Nh, D), dk.view(B, T, Nkv, D), dv.view(B, T, Nkv, D)
+        stacked = q.shape == k.shape                       # (multi-head: one buffer, three slices; grouped-query: flat)
+        out = L.attn_bwd_rope(q, k, v, o, do, lse2, doc, meta, ctx.scale, cos, sin, stacked)
+        _, (dq, dk, dv) = L.attn_grads(q, k, "stacked" if stacked else "flat", out)
         return dq, dk, dv, None, None, None, None, None
+
+
+def _attention_scale(name: str, q, mask: PackedMask, scale: Optional[float], rows: Optional[int] = None) -> float:
+    """The check and the default that the attention entry points share: q is [B, rows, Nh, D] for a mask built for [B, T]
+    (rows = T, or the `rows_per_batch` of a sequence-sharded query side) -> scale, head_dim ** -0.5 unless given."""
+    rows = mask.T if rows is None else int(rows)
+    if tuple(q.shape[:2]) != (mask.B, rows):
+        raise _C.KernelError(f"{name}: mask built for {(mask.B, mask.T)}, {rows} query rows per batch; "
+                             f"got q {tuple(q.shape[:2])}")
+    return float(q.shape[-1] ** -0.5 if scale is None else scale)
 
 
 def packed_attention(q, k, v, mask: PackedMask, scale: Optional[float] = None, rope_grad=None):
     """softmax(scale * Q K^T + doc-causal mask) V with q [B,T,Nh,D], k/v [B,T,Nkv,D] -> [B,T,Nh,D].
     ``rope_grad = (cos, sin)``: q and k are ROTATED outputs of `linear_group(.., rope=(cos, sin, ..),
     rope_grad_in_attention=True)`; their gradients leave this node already rotated back (`_AttentionRopeGrad`)."""
-    if scale is None:
-        scale = q.shape[-1] ** -0.5
-    if tuple(q.shape[:2]) != (mask.B, mask.T):
-        raise _C.KernelError(f"mask built for {(mask.B, mask.T)}, got q {tuple(q.shape[:2])}")
+    scale = _attention_scale("packed_attention", q, mask, scale)
     if rope_grad is not None:
         cos, sin = rope_grad
-        return _AttentionRopeGrad.apply(q, k, v, mask.doc, mask.meta, float(scale), _c(cos.detach()), _c(sin.detach()))
-    return L.attn_fwd(q, k, v, mask.doc, mask.meta, float(scale))[0]
-
-
-class _BidirectionalAttention(torch.autograd.Function):
-    """softmax over ALL keys of the query's document (no causal restriction): `tn_attn_fwd_bidir` / `tn_attn_bwd_bidir`,
-    the packed-attention kernels with the causal term of the predicate switched off and the key range of a query tile
-    extended to the last tile that shares a document with it (csrc/attn_common.h QView::bidir).
-    Used by the Whisper speech encoder of Kimi-Audio (touchnet/models/kimi_audio/modeling_kimi_audio.py:337-339, 942-947:
-    transformers' WhisperEncoder, bidirectional self-attention over the 1500 frames of a clip).
-    (Round 4 first built it from two launches of the causal kernels — the batch and its time reversal — merged by their
-    log-sum-exp in torch: correct, but the flips and the fp32 merge were 32 % of the speech workload's step.)"""
-
-    @staticmethod
-    def forward(ctx, q, k, v, doc, meta, scale):
-        q, k, v = _c(q), _c(k), _c(v)
-        o, lse = L.attn_fwd_bidir(q, k, v, doc, meta, scale)
-        ctx.save_for_backward(q, k, v, o, lse, doc, meta)
-        ctx.scale = scale
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q, k, v, o, lse, doc, meta = ctx.saved_tensors
-        dq, dk, dv = L.attn_bwd_bidir(q, k, v, o, _c(do), lse, doc, meta, ctx.scale)
-        return dq, dk, dv, None, None, None
+        return _AttentionRopeGrad.apply(q, k, v, mask.doc, mask.meta, scale, _c(cos.detach()), _c(sin.detach()))
+    return L.attn_fwd(q, k, v, mask.doc, mask.meta, scale)[0]
 
 
 def bidirectional_attention(q, k, v, mask: PackedMask, scale: Optional[float] = None):
     """softmax(scale * Q K^T + same-document mask) V — every key of the query's document, before AND after it — with
-    q [B,T,Nh,D], k/v [B,T,Nkv,D] -> [B,T,Nh,D]; pad rows (document 0) give 0."""
-    if scale is None:
-        scale = q.shape[-1] ** -0.5
-    if tuple(q.shape[:2]) != (mask.B, mask.T):
-        raise _C.KernelError(f"mask built for {(mask.B, mask.T)}, got q {tuple(q.shape[:2])}")
-    return _BidirectionalAttention.apply(q, k, v, mask.doc, mask.meta, float(scale))
+    q [B,T,Nh,D], k/v [B,T,Nkv,D] -> [B,T,Nh,D]; pad rows (document 0) give 0 (`library.attn_fwd_bidir`)."""
+    scale = _attention_scale("bidirectional_attention", q, mask, scale)
+    return L.attn_fwd_bidir(q, k, v, mask.doc, mask.meta, scale)[0]
 
 
 @dataclass(frozen=True)
@@ -206,9 +181,8 @@ def packed_attention_sharded(q_local, k_full, v_full, mask: PackedMask, shard: S
                              scale: Optional[float] = None):
     """Context-parallel building block: local query rows (per `shard`) against the full, all-gathered K/V.
     The gradient w.r.t. k_full / v_full is this rank's PARTIAL sum (to be reduce-scattered by the caller)."""
-    if scale is None:
-        scale = q_local.shape[-1] ** -0.5
-    return L.attn_fwd_seg(q_local, k_full, v_full, mask.doc, mask.meta, float(scale), shard.flat(),
+    scale = _attention_scale("packed_attention_sharded", q_local, mask, scale, shard.rows_per_batch)
+    return L.attn_fwd_seg(q_local, k_full, v_full, mask.doc, mask.meta, scale, shard.flat(),
                           int(shard.rows_per_batch))[0]
 
 
@@ -243,10 +217,9 @@ def packed_attention_sharded_split(q_local, k_full, v_full, mask: PackedMask, sh
     """`packed_attention_sharded` as two key-side parts + an LSE merge: `own_chunks` / `remote_chunks` = indices of the
     sequence chunks (of `chunk_len` positions) the first / second part covers; `wait()` is called between the two (the
     halo exchange's completion: the remote chunks of k_full / v_full may still be in flight before it)."""
-    if scale is None:
-        scale = q_local.shape[-1] ** -0.5
+    scale = _attention_scale("packed_attention_sharded_split", q_local, mask, scale, shard.rows_per_batch)
     bits = lambda cs: sum(1 << int(c) for c in cs)
-    return _SplitAttention.apply(q_local, k_full, v_full, mask.doc, mask.meta, float(scale), shard.flat(),
+    return _SplitAttention.apply(q_local, k_full, v_full, mask.doc, mask.meta, scale, shard.flat(),
                                  int(shard.rows_per_batch), int(chunk_len), bits(own_chunks), bits(remote_chunks), wait)
 
 

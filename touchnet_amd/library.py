@@ -265,110 +265,160 @@ rope_apply.register_autograd(_rope_backward, setup_context=_rope_setup)
 
 
 # ===================================================================================================== attention
+# The ops differ in their C entry and its trailing arguments; every rule they share is stated once:
+#   _attn_forward / _attn_forward_fake   the forward prologue (checks, o and lse2 [B, Nh, rows]) of the four forward ops
+#   attn_grads                           the three layouts of (dq, dk, dv): real ops, fakes and functional read it
+#   _attn_backward                       the backward prologue (do, the delta scratch, the gradients) of the five backward ops
+#   _attn_autograd                       setup_context / backward of the forward ops that have a backward op
+def _attn_forward(name: str, entry: str, q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float,
+                  tail=(), rows_per_batch: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """q [B, rows, Nh, D], k / v [B, T, Nkv, D] bf16, doc int32 [B, T], meta from `attn_build_meta` ->
+    (o [B, rows, Nh, D], lse2 fp32 [B, Nh, rows]) by the C entry `entry(.., scale, *tail, stream)`.  rows = T, or the
+    `rows_per_batch` of a sequence-sharded query side; `name` is the public function the messages speak of."""
+    q, k, v = _c(q), _c(k), _c(v)
+    B, R, Nh, D = q.shape
+    T, Nkv = k.shape[1], k.shape[2]
+    if q.dtype != torch.bfloat16:
+        raise _C.KernelError(f"{name}: bf16 only (MFMA 32x32x16 bf16 kernels), got q {q.dtype}")
+    rows = T if rows_per_batch is None else rows_per_batch
+    if tuple(doc.shape) != (B, T) or R != rows:
+        raise _C.KernelError(f"{name}: mask built for {tuple(doc.shape)}, {rows} query rows per batch; "
+                             f"got q {(B, R)}, k {(B, T)}")
+    o = torch.empty_like(q)
+    lse2 = torch.empty(B, Nh, R, dtype=torch.float32, device=q.device)
+    _C.check(getattr(_lib(), entry)(_p(q), _p(k), _p(v), _p(o), _p(lse2), _p(doc), _p(meta), B, T, Nh, Nkv, D,
+                                    float(scale), *tail, _cur()), entry)
+    return o, lse2
+
+
+def _attn_forward_fake(q, k, v, doc, meta, scale, *tail):
+    B, R, Nh, D = q.shape
+    return torch.empty_like(q, memory_format=torch.contiguous_format), q.new_empty(B, Nh, R, dtype=torch.float32)
+
+
+def attn_grads(q: Tensor, k: Tensor, layout: str, out=None):
+    """-> (out, (dq, dk, dv)): what a backward op of `layout` returns, and its three gradients as q- / k- / v-shaped views.
+         "tuple"    three tensors of their own
+         "stacked"  ONE buffer [3, B, T, Nh, D] (Nh == Nkv), dq, dk, dv = its slices: a consumer that wants them side by
+                    side — the fused q/k/v weight gradient of the audio tower — runs a batched GEMM over the buffer instead
+                    of concatenating three tensors first (functional._LinearGroup, wgrad="nt_fused")
+         "flat"     ONE buffer [B * T * (Nh + 2 Nkv) * D] = dq | dk | dv
+    `out` = None allocates (works on fake tensors too); otherwise the views are taken of that result of a backward op."""
+    if layout == "tuple":
+        out = out if out is not None else (q.new_empty(q.shape), k.new_empty(k.shape), k.new_empty(k.shape))
+        return out, tuple(out)
+    if layout == "stacked":
+        if q.shape != k.shape:
+            raise _C.KernelError(f"stacked attention gradients need Nh == Nkv: q {tuple(q.shape)}, k {tuple(k.shape)}")
+        out = out if out is not None else q.new_empty(3, *q.shape)
+        return out, tuple(out.unbind(0))
+    if layout == "flat":
+        out = out if out is not None else q.new_empty(q.numel() + 2 * k.numel())
+        dq, dk, dv = out.split([q.numel(), k.numel(), k.numel()])
+        return out, (dq.view(q.shape), dk.view(k.shape), dv.view(k.shape))
+    raise ValueError(f"unknown attention gradient layout {layout!r}")
+
+
+def _attn_backward(entry: str, layout: str, q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor,
+                   doc: Tensor, meta: Tensor, scale: float, tail=()):
+    """dq / dk / dv in `layout` by the C entry `entry(.., scale, *tail, stream)`; q, k, v, o as the forward saved them
+    (contiguous).  delta fp32 [B, Nh, rows] is the call's scratch: the dQ pass fills it for the dK / dV pass behind it."""
+    do = _c(do)
+    B, R, Nh, D = q.shape
+    T, Nkv = k.shape[1], k.shape[2]
+    out, (dq, dk, dv) = attn_grads(q, k, layout)
+    delta = torch.empty_like(lse2)
+    _C.check(getattr(_lib(), entry)(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(dq), _p(dk), _p(dv),
+                                    _p(doc), _p(meta), B, T, Nh, Nkv, D, float(scale), *tail, _cur()), entry)
+    return out
+
+
+def _attn_autograd(fwd_op, grads):
+    """The autograd formula of `fwd_op(q, k, v, doc, meta, scale, *tail) -> (o, lse2)` over
+    `grads(q, k, v, o, do, lse2, doc, meta, scale, *tail) -> (dq, dk, dv)`."""
+    def setup(ctx, inputs, output):
+        q, k, v, doc, meta, scale, *tail = inputs
+        o, lse2 = output
+        ctx.save_for_backward(_c(q), _c(k), _c(v), o, lse2, doc, meta)
+        ctx.scale, ctx.tail = scale, tuple(tail)
+        ctx.set_materialize_grads(False)     # (the LSE output has no gradient: no [B, Nh, T] zero fill per layer)
+
+    def backward(ctx, do, _dlse):
+        q, k, v, o, lse2, doc, meta = ctx.saved_tensors
+        if do is None:
+            do = torch.zeros_like(o)
+        dq, dk, dv = grads(q, k, v, o, do, lse2, doc, meta, ctx.scale, *ctx.tail)
+        return (dq, dk, dv, None, None, None, *(None for _ in ctx.tail))
+
+    fwd_op.register_autograd(backward, setup_context=setup)
+
+
+def _segs_tail(segs: List[int], rows_per_batch: int):
+    """(nseg, int[6], rows_per_batch) of the sequence-sharded C entries; `segs` = up to two flattened triples"""
+    return len(segs) // 3, (ctypes.c_int * 6)(*segs, *([0] * (6 - len(segs)))), rows_per_batch
+
+
 @custom_op(f"{NS}::attn_fwd", mutates_args=(), device_types="cuda")
 def attn_fwd(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float) -> Tuple[Tensor, Tensor]:
     """Packed (document-masked causal) attention: q [B,T,Nh,D], k/v [B,T,Nkv,D] bf16, doc int32 [B,T], meta from
     `attn_build_meta` -> (o [B,T,Nh,D], lse2 fp32 [B,Nh,T])."""
-    q, k, v = _c(q), _c(k), _c(v)
-    if q.dtype != torch.bfloat16:
-        raise _C.KernelError("packed_attention: bf16 only (MFMA 32x32x16 bf16 kernel)")
-    B, T, Nh, D = q.shape
-    Nkv = k.shape[2]
-    if tuple(doc.shape) != (B, T):
-        raise _C.KernelError(f"mask built for {tuple(doc.shape)}, got q {(B, T)}")
-    o = torch.empty_like(q)
-    lse2 = torch.empty(B, Nh, T, dtype=torch.float32, device=q.device)
-    _C.check(_lib().tn_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse2), _p(doc), _p(meta), B, T, Nh, Nkv, D,
-                                float(scale), _cur()), "tn_attn_fwd")
-    return o, lse2
+    return _attn_forward("packed_attention", "tn_attn_fwd", q, k, v, doc, meta, scale)
 
 
-@attn_fwd.register_fake
-def _(q, k, v, doc, meta, scale):
-    B, T, Nh, D = q.shape
-    return torch.empty_like(q, memory_format=torch.contiguous_format), q.new_empty(B, Nh, T, dtype=torch.float32)
+@custom_op(f"{NS}::attn_fwd_bidir", mutates_args=(), device_types="cuda")
+def attn_fwd_bidir(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float) -> Tuple[Tensor, Tensor]:
+    """`attn_fwd` with the mask bidirectional inside a document: softmax over ALL keys of the query's document (no causal
+    restriction).  `tn_attn_fwd_bidir` / `tn_attn_bwd_bidir` are the packed-attention kernels with the causal term of the
+    predicate switched off and the key range of a query tile extended to the last tile that shares a document with it
+    (csrc/attn_common.h QView::bidir).  Used by the Whisper speech encoder of Kimi-Audio
+    (touchnet/models/kimi_audio/modeling_kimi_audio.py:337-339, 942-947: transformers' WhisperEncoder, bidirectional
+    self-attention over the 1500 frames of a clip)."""
+    return _attn_forward("bidirectional_attention", "tn_attn_fwd_bidir", q, k, v, doc, meta, scale)
+
+
+@custom_op(f"{NS}::attn_fwd_seg", mutates_args=(), device_types="cuda")
+def attn_fwd_seg(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float, segs: List[int],
+                 rows_per_batch: int) -> Tuple[Tensor, Tensor]:
+    """Sequence-sharded query side (context parallelism): q [B, R, Nh, D] local rows, k/v [B, T, Nkv, D] global;
+    `segs` = up to two (row0, rows, global_offset) triples, flattened."""
+    return _attn_forward("packed_attention_sharded", "tn_attn_fwd_seg", q, k, v, doc, meta, scale,
+                         _segs_tail(segs, rows_per_batch), rows_per_batch)
+
+
+@custom_op(f"{NS}::attn_fwd_seg_chunks", mutates_args=(), device_types="cuda")
+def attn_fwd_seg_chunks(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float, segs: List[int],
+                        rows_per_batch: int, chunk_len: int, chunk_mask: int) -> Tuple[Tensor, Tensor]:
+    """attn_fwd_seg with the KEY side restricted to the sequence chunks whose bit is set in `chunk_mask` (chunk c =
+    positions [c * chunk_len, (c + 1) * chunk_len)).  Rows without a key there: O = 0, LSE2 = +inf.  One half of the
+    local / remote split of context-parallel attention (no autograd formula of its own: functional._SplitAttention
+    differentiates the MERGED result with one attn_bwd_seg)."""
+    return _attn_forward("packed_attention_sharded_split", "tn_attn_fwd_seg_chunks", q, k, v, doc, meta, scale,
+                         (*_segs_tail(segs, rows_per_batch), int(chunk_len), int(chunk_mask)), rows_per_batch)
+
+
+for _op in (attn_fwd, attn_fwd_bidir, attn_fwd_seg, attn_fwd_seg_chunks):
+    _op.register_fake(_attn_forward_fake)
 
 
 @custom_op(f"{NS}::attn_bwd", mutates_args=(), device_types="cuda")
 def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
              scale: float) -> Tuple[Tensor, Tensor, Tensor]:
-    do = _c(do)
-    B, T, Nh, D = q.shape
-    Nkv = k.shape[2]
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    delta = torch.empty_like(lse2)
-    _C.check(_lib().tn_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(dq), _p(dk), _p(dv),
-                                _p(doc), _p(meta), B, T, Nh, Nkv, D, float(scale), _cur()), "tn_attn_bwd")
-    return dq, dk, dv
-
-
-@attn_bwd.register_fake
-def _(q, k, v, o, do, lse2, doc, meta, scale):
-    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
-    return e(q), e(k), e(v)
-
-
-@custom_op(f"{NS}::attn_fwd_bidir", mutates_args=(), device_types="cuda")
-def attn_fwd_bidir(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float) -> Tuple[Tensor, Tensor]:
-    """`attn_fwd` with the mask bidirectional inside a document (tn_attn_fwd_bidir)."""
-    q, k, v = _c(q), _c(k), _c(v)
-    if q.dtype != torch.bfloat16:
-        raise _C.KernelError("bidirectional_attention: bf16 only (MFMA 32x32x16 bf16 kernel)")
-    B, T, Nh, D = q.shape
-    Nkv = k.shape[2]
-    if tuple(doc.shape) != (B, T):
-        raise _C.KernelError(f"mask built for {tuple(doc.shape)}, got q {(B, T)}")
-    o = torch.empty_like(q)
-    lse2 = torch.empty(B, Nh, T, dtype=torch.float32, device=q.device)
-    _C.check(_lib().tn_attn_fwd_bidir(_p(q), _p(k), _p(v), _p(o), _p(lse2), _p(doc), _p(meta), B, T, Nh, Nkv, D,
-                                      float(scale), _cur()), "tn_attn_fwd_bidir")
-    return o, lse2
-
-
-@attn_fwd_bidir.register_fake
-def _(q, k, v, doc, meta, scale):
-    B, T, Nh, D = q.shape
-    return torch.empty_like(q, memory_format=torch.contiguous_format), q.new_empty(B, Nh, T, dtype=torch.float32)
+    return _attn_backward("tn_attn_bwd", "tuple", q, k, v, o, do, lse2, doc, meta, scale)
 
 
 @custom_op(f"{NS}::attn_bwd_bidir", mutates_args=(), device_types="cuda")
 def attn_bwd_bidir(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
                    scale: float) -> Tuple[Tensor, Tensor, Tensor]:
-    do = _c(do)
-    B, T, Nh, D = q.shape
-    Nkv = k.shape[2]
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    delta = torch.empty_like(lse2)
-    _C.check(_lib().tn_attn_bwd_bidir(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(dq), _p(dk), _p(dv),
-                                      _p(doc), _p(meta), B, T, Nh, Nkv, D, float(scale), _cur()), "tn_attn_bwd_bidir")
-    return dq, dk, dv
-
-
-@attn_bwd_bidir.register_fake
-def _(q, k, v, o, do, lse2, doc, meta, scale):
-    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
-    return e(q), e(k), e(v)
+    """Three tensors of their own also for Nh == Nkv: back-to-back gradients would send the audio tower's q/k/v weight
+    gradient down another launch (functional._stacked_view)."""
+    return _attn_backward("tn_attn_bwd_bidir", "tuple", q, k, v, o, do, lse2, doc, meta, scale)
 
 
 @custom_op(f"{NS}::attn_bwd_stacked", mutates_args=(), device_types="cuda")
 def attn_bwd_stacked(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
                      scale: float) -> Tensor:
-    """attn_bwd for Nh == Nkv with the three gradients in ONE buffer [3, B, T, Nh, D] (dq, dk, dv = its slices): a
-    consumer that wants them side by side — the fused q/k/v weight gradient of the audio tower — can then run a batched
-    GEMM over the buffer instead of concatenating three tensors first (functional._LinearGroup, wgrad="nt_fused")."""
-    do = _c(do)
-    B, T, Nh, D = q.shape
-    out = q.new_empty(3, B, T, Nh, D)
-    delta = torch.empty_like(lse2)
-    _C.check(_lib().tn_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(out[0]), _p(out[1]),
-                                _p(out[2]), _p(doc), _p(meta), B, T, Nh, Nh, D, float(scale), _cur()), "tn_attn_bwd")
-    return out
-
-
-@attn_bwd_stacked.register_fake
-def _(q, k, v, o, do, lse2, doc, meta, scale):
-    B, T, Nh, D = q.shape
-    return q.new_empty(3, B, T, Nh, D)
+    """attn_bwd for Nh == Nkv with the three gradients in ONE buffer [3, B, T, Nh, D] (`attn_grads`, "stacked")."""
+    return _attn_backward("tn_attn_bwd", "stacked", q, k, v, o, do, lse2, doc, meta, scale)
 
 
 @custom_op(f"{NS}::attn_bwd_rope", mutates_args=(), device_types="cuda")
@@ -376,52 +426,46 @@ def attn_bwd_rope(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: 
                   scale: float, cos: Tensor, sin: Tensor, stacked: bool) -> Tensor:
     """attn_bwd for ROTATED q / k whose gradients are wanted for the un-rotated projections (tn_attn_bwd_rope: the rotary
     embedding's backward in the attention kernels' epilogues; bit-identical to attn_bwd followed by rope_apply(backward)).
-    One buffer: stacked (Nh == Nkv) [3, B, T, Nh, D] = dq, dk, dv; otherwise flat [B * T * (Nh + 2 Nkv) * D] = dq | dk | dv."""
-    do = _c(do)
+    One buffer (`attn_grads`): "stacked" (Nh == Nkv) or "flat"."""
     B, T, Nh, D = q.shape
-    Nkv = k.shape[2]
     if not (cos.dtype == torch.bfloat16 and sin.dtype == torch.bfloat16 and cos.is_contiguous() and sin.is_contiguous()
             and cos.numel() == B * T * (D // 2) and sin.numel() == cos.numel()):
         raise _C.KernelError("attn_bwd_rope: cos / sin are the bf16 [B * T, head_dim / 2] tables of rope_tables")
-    if stacked:
-        out = q.new_empty(3, B, T, Nh, D)
-        dq, dk, dv = out[0], out[1], out[2]
-    else:
-        out = q.new_empty(B * T * (Nh + 2 * Nkv) * D)
-        dq, dk, dv = out.split([B * T * Nh * D, B * T * Nkv * D, B * T * Nkv * D])
-    delta = torch.empty_like(lse2)
-    _C.check(_lib().tn_attn_bwd_rope(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(dq), _p(dk), _p(dv),
-                                     _p(doc), _p(meta), B, T, Nh, Nkv, D, float(scale), _p(cos), _p(sin), _cur()),
-             "tn_attn_bwd_rope")
-    return out
+    return _attn_backward("tn_attn_bwd_rope", "stacked" if stacked else "flat", q, k, v, o, do, lse2, doc, meta, scale,
+                          (_p(cos), _p(sin)))
 
 
-@attn_bwd_rope.register_fake
-def _(q, k, v, o, do, lse2, doc, meta, scale, cos, sin, stacked):
-    B, T, Nh, D = q.shape
-    return q.new_empty(3, B, T, Nh, D) if stacked else q.new_empty(B * T * (Nh + 2 * k.shape[2]) * D)
+@custom_op(f"{NS}::attn_bwd_seg", mutates_args=(), device_types="cuda")
+def attn_bwd_seg(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
+                 scale: float, segs: List[int], rows_per_batch: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """dk / dv are this rank's PARTIAL sums over the global [B, T, Nkv, D]."""
+    return _attn_backward("tn_attn_bwd_seg", "tuple", q, k, v, o, do, lse2, doc, meta, scale,
+                          _segs_tail(segs, q.shape[1]))
 
 
-def _attn_setup(ctx, inputs, output):
-    q, k, v, doc, meta, scale = inputs
-    o, lse2 = output
-    ctx.save_for_backward(_c(q), _c(k), _c(v), o, lse2, doc, meta)
-    ctx.scale = scale
-    ctx.set_materialize_grads(False)     # (the LSE output has no gradient: no [B, Nh, T] zero fill per layer)
+for _op, _layout in ((attn_bwd, "tuple"), (attn_bwd_bidir, "tuple"), (attn_bwd_stacked, "stacked"), (attn_bwd_seg, "tuple")):
+    _op.register_fake(lambda q, k, *rest, _layout=_layout: attn_grads(q, k, _layout)[0])
+attn_bwd_rope.register_fake(lambda q, k, *rest: attn_grads(q, k, "stacked" if rest[-1] else "flat")[0])
 
 
-def _attn_backward(ctx, do, _dlse):
-    q, k, v, o, lse2, doc, meta = ctx.saved_tensors
-    if do is None:
-        do = torch.zeros_like(o)
-    if q.shape == k.shape:                  # multi-head attention: one buffer, three slices
-        dq, dk, dv = attn_bwd_stacked(q, k, v, o, do, lse2, doc, meta, ctx.scale).unbind(0)
-    else:
-        dq, dk, dv = attn_bwd(q, k, v, o, do, lse2, doc, meta, ctx.scale)
-    return dq, dk, dv, None, None, None
+def _attn_causal_grads(q, k, *rest):
+    """multi-head attention (Nh == Nkv): one buffer, three slices; grouped-query attention: three tensors"""
+    if q.shape == k.shape:
+        return attn_bwd_stacked(q, k, *rest).unbind(0)
+    return attn_bwd(q, k, *rest)
 
 
-attn_fwd.register_autograd(_attn_backward, setup_context=_attn_setup)
+_attn_autograd(attn_fwd, _attn_causal_grads)
+_attn_autograd(attn_fwd_bidir, attn_bwd_bidir)
+_attn_autograd(attn_fwd_seg, attn_bwd_seg)
+
+
+def attn_meta_ints(B: int, T: int) -> int:
+    """tn_attn_meta_ints restated for shapes without the library (csrc/attn_common.h attn_meta_ints is the owner; the
+    test suite holds the two together): 5 statistics per 64-position tile, 4 per 32 positions (qstat), and the two
+    stored tile lists (klist, qlist) of 4 + 4 * kListPre ints per 128 positions, kListPre = 64."""
+    nt, nq32, nq128 = (T + 63) // 64, (T + 31) // 32, (T + 127) // 128
+    return B * (5 * nt + 4 * nq32 + 2 * (4 + 4 * 64) * nq128)
 
 
 @custom_op(f"{NS}::attn_build_meta", mutates_args=(), device_types="cuda")
@@ -435,69 +479,7 @@ def attn_build_meta(doc: Tensor) -> Tensor:
 
 @attn_build_meta.register_fake
 def _(doc):
-    B, T = doc.shape
-    # (tn_attn_meta_ints: tile statistics + per-wave statistics + precomputed KV-tile lists, csrc/attn_common.h)
-    return doc.new_empty(5 * B * ((T + 63) // 64) + 4 * B * ((T + 31) // 32) + 520 * B * ((T + 127) // 128),
-                         dtype=torch.int32)
-
-
-def _segs_array(segs: List[int]):
-    import ctypes
-    flat = list(segs) + [0] * (6 - len(segs))
-    return (ctypes.c_int * 6)(*flat)
-
-
-@custom_op(f"{NS}::attn_fwd_seg", mutates_args=(), device_types="cuda")
-def attn_fwd_seg(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float, segs: List[int],
-                 rows_per_batch: int) -> Tuple[Tensor, Tensor]:
-    """Sequence-sharded query side (context parallelism): q [B, R, Nh, D] local rows, k/v [B, T, Nkv, D] global;
-    `segs` = up to two (row0, rows, global_offset) triples, flattened."""
-    q, k, v = _c(q), _c(k), _c(v)
-    if q.dtype != torch.bfloat16:
-        raise _C.KernelError("packed_attention_sharded: bf16 only")
-    B, R, Nh, D = q.shape
-    T, Nkv = k.shape[1], k.shape[2]
-    if tuple(doc.shape) != (B, T) or R != rows_per_batch:
-        raise _C.KernelError(f"mask {tuple(doc.shape)} / shard {rows_per_batch} vs q {(B, R)} k {(B, T)}")
-    o = torch.empty_like(q)
-    lse2 = torch.empty(B, Nh, R, dtype=torch.float32, device=q.device)
-    _C.check(_lib().tn_attn_fwd_seg(_p(q), _p(k), _p(v), _p(o), _p(lse2), _p(doc), _p(meta), B, T, Nh, Nkv, D,
-                                    float(scale), len(segs) // 3, _segs_array(segs), R, _cur()), "tn_attn_fwd_seg")
-    return o, lse2
-
-
-@attn_fwd_seg.register_fake
-def _(q, k, v, doc, meta, scale, segs, rows_per_batch):
-    B, R, Nh, D = q.shape
-    return torch.empty_like(q, memory_format=torch.contiguous_format), q.new_empty(B, Nh, R, dtype=torch.float32)
-
-
-@custom_op(f"{NS}::attn_fwd_seg_chunks", mutates_args=(), device_types="cuda")
-def attn_fwd_seg_chunks(q: Tensor, k: Tensor, v: Tensor, doc: Tensor, meta: Tensor, scale: float, segs: List[int],
-                        rows_per_batch: int, chunk_len: int, chunk_mask: int) -> Tuple[Tensor, Tensor]:
-    """attn_fwd_seg with the KEY side restricted to the sequence chunks whose bit is set in `chunk_mask` (chunk c =
-    positions [c * chunk_len, (c + 1) * chunk_len)).  Rows without a key there: O = 0, LSE2 = +inf.  One half of the
-    local / remote split of context-parallel attention (no autograd formula of its own: functional._SplitAttention
-    differentiates the MERGED result with one attn_bwd_seg)."""
-    q, k, v = _c(q), _c(k), _c(v)
-    if q.dtype != torch.bfloat16:
-        raise _C.KernelError("packed_attention_sharded: bf16 only")
-    B, R, Nh, D = q.shape
-    T, Nkv = k.shape[1], k.shape[2]
-    if tuple(doc.shape) != (B, T) or R != rows_per_batch:
-        raise _C.KernelError(f"mask {tuple(doc.shape)} / shard {rows_per_batch} vs q {(B, R)} k {(B, T)}")
-    o = torch.empty_like(q)
-    lse2 = torch.empty(B, Nh, R, dtype=torch.float32, device=q.device)
-    _C.check(_lib().tn_attn_fwd_seg_chunks(_p(q), _p(k), _p(v), _p(o), _p(lse2), _p(doc), _p(meta), B, T, Nh, Nkv, D,
-                                           float(scale), len(segs) // 3, _segs_array(segs), R, int(chunk_len),
-                                           int(chunk_mask), _cur()), "tn_attn_fwd_seg_chunks")
-    return o, lse2
-
-
-@attn_fwd_seg_chunks.register_fake
-def _(q, k, v, doc, meta, scale, segs, rows_per_batch, chunk_len, chunk_mask):
-    B, R, Nh, D = q.shape
-    return torch.empty_like(q, memory_format=torch.contiguous_format), q.new_empty(B, Nh, R, dtype=torch.float32)
+    return doc.new_empty(attn_meta_ints(*doc.shape), dtype=torch.int32)
 
 
 @custom_op(f"{NS}::attn_merge", mutates_args=(), device_types="cuda")
@@ -515,46 +497,6 @@ def attn_merge(o_a: Tensor, lse2_a: Tensor, o_b: Tensor, lse2_b: Tensor) -> Tupl
 def _(o_a, lse2_a, o_b, lse2_b):
     return (torch.empty_like(o_a, memory_format=torch.contiguous_format),
             torch.empty_like(lse2_a, memory_format=torch.contiguous_format))
-
-
-@custom_op(f"{NS}::attn_bwd_seg", mutates_args=(), device_types="cuda")
-def attn_bwd_seg(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse2: Tensor, doc: Tensor, meta: Tensor,
-                 scale: float, segs: List[int], rows_per_batch: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """dk / dv are this rank's PARTIAL sums over the global [B, T, Nkv, D]."""
-    do = _c(do)
-    B, R, Nh, D = q.shape
-    T, Nkv = k.shape[1], k.shape[2]
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    delta = torch.empty_like(lse2)
-    _C.check(_lib().tn_attn_bwd_seg(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse2), _p(delta), _p(dq), _p(dk), _p(dv),
-                                    _p(doc), _p(meta), B, T, Nh, Nkv, D, float(scale), len(segs) // 3,
-                                    _segs_array(segs), R, _cur()), "tn_attn_bwd_seg")
-    return dq, dk, dv
-
-
-@attn_bwd_seg.register_fake
-def _(q, k, v, o, do, lse2, doc, meta, scale, segs, rows_per_batch):
-    e = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
-    return e(q), e(k), e(v)
-
-
-def _attn_seg_setup(ctx, inputs, output):
-    q, k, v, doc, meta, scale, segs, rpb = inputs
-    o, lse2 = output
-    ctx.save_for_backward(_c(q), _c(k), _c(v), o, lse2, doc, meta)
-    ctx.scale, ctx.segs, ctx.rpb = scale, list(segs), rpb
-    ctx.set_materialize_grads(False)
-
-
-def _attn_seg_backward(ctx, do, _dlse):
-    q, k, v, o, lse2, doc, meta = ctx.saved_tensors
-    if do is None:
-        do = torch.zeros_like(o)
-    dq, dk, dv = attn_bwd_seg(q, k, v, o, do, lse2, doc, meta, ctx.scale, ctx.segs, ctx.rpb)
-    return dq, dk, dv, None, None, None, None, None
-
-
-attn_fwd_seg.register_autograd(_attn_seg_backward, setup_context=_attn_seg_setup)
 
 
 # ===================================================================================================== cross-entropy
@@ -1153,7 +1095,8 @@ def _(x, codebook, cnorm):
 
 
 OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
-       "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
+       "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked",
+       "attn_bwd_rope", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
