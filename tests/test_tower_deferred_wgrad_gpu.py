@@ -50,7 +50,7 @@ def test_deferred_tower_weight_gradients_equal_the_unsplit_per_layer_path(frames
     monkeypatch.setattr(F, "DEFERRED_WGRAD", False)                  # the switch: the queue is still registered
     default = run()                                                  # per layer, split-K where `split_k` says so
     assert len(q1) == 0
-    # per layer, every weight gradient as the unsplit launch.  (Not through the global switch TN_GEMM_SPLITK / F.SPLIT_K: at
+    # per layer, every weight gradient as the unsplit launch.  (Not through the global flag F.SPLIT_K: at
     # this width it would also change forward and input-gradient products of 1024-deep contractions, which `split_k` cuts
     # in two once `_OWN_MIN_TILES` lets the hand-written kernel take them — the loss would no longer be comparable.)
     split_k = F.split_k

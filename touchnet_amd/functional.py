@@ -112,8 +112,8 @@ def causal_mask(B: int, T: int, device) -> PackedMask:
     return build_packed_mask(torch.ones(B, T, dtype=torch.int32, device=device))
 
 
-# TN_ROPE_GRAD_IN_ATTENTION=0: the rotary embedding's backward as its own pass over dq / dk again (A/B switch; same bits)
-ROPE_GRAD_IN_ATTENTION = os.environ.get("TN_ROPE_GRAD_IN_ATTENTION", "1") != "0"
+# False: the rotary embedding's backward as its own pass over dq / dk (same bits; the tests' reference)
+ROPE_GRAD_IN_ATTENTION = True
 
 
 class _AttentionRopeGrad(torch.autograd.Function):
@@ -327,8 +327,7 @@ class _FusedLinearCE(torch.autograd.Function):
             lab_k = torch.where(lab == ignore_index, lab, torch.where(mine, lab - v0, torch.full_like(lab, V)))
         for s in range(0, n, chunk):
             e = min(s + chunk, n)
-            logits = _mm_tn(h2[s:e], weight) if (h2.is_cuda and h2.dtype == torch.bfloat16 and _bf16_rows(h2[s:e], weight)) \
-                else torch.nn.functional.linear(h2[s:e], weight)             # [c, V]: the only logits alive
+            logits = _mm_tn(h2[s:e], weight)                                  # [c, V]: the only logits alive
             nll_c, lse_c, hit_c = L.ce_fwd_rows(logits, lab_k[s:e], sl[s:e], ns, int(ignore_index))
             if tp is not None:
                 valid = lab[s:e] != ignore_index
@@ -353,27 +352,13 @@ class _FusedLinearCE(torch.autograd.Function):
                 hit_c = ((best[:, 1].to(torch.int64) == lab[s:e]) & valid).to(hit_c.dtype)
             L.ce_bwd_(logits, lab_k[s:e], sl[s:e], lse_c, ns, one, int(ignore_index))     # logits := dlogits
             parts.append((nll_c, hit_c))
-            hc = h2[s:e]
-            own_d = (logits.is_cuda and _own(e - s, H, (V,)) and _bf16_rows(logits, weight, dh[s:e]))
-            if own_d:
-                gemm([(logits, weight)], b_kmaj=True, out=dh[s:e])            # dh = dlogits @ W (W read contraction-major)
-            else:
-                torch.mm(logits, weight, out=dh[s:e])
-            own_w = (logits.is_cuda and _own(V, H, (e - s,), True, True) and _bf16_rows(logits, hc))
-            if n <= chunk:                                                    # one chunk: one product, one rounding
-                dw = gemm([(logits, hc)], True, True) if own_w else torch.mm(logits.t(), hc)     # dW = dlogits^T @ h
-            elif logits.dtype != torch.bfloat16:                              # (fp32 operands: nothing to gain)
-                dw = torch.mm(logits.t(), hc) if dw is None else dw.addmm_(logits.t(), hc)
-            else:
+            _dgrad([logits], [weight], out=dh[s:e], dgrad_tn=False)           # dh = dlogits @ W
+            if dw is None and n > chunk and logits.dtype == torch.bfloat16:
                 # several chunks: the sum over the chunks is kept in fp32 and rounded to bf16 ONCE behind the loop (a bf16
                 # buffer would round the partial sum once per chunk).  Costs V x H x 4 bytes while the loop runs and one
                 # cast pass; the step's usual shape (labelled rows <= chunk) does not come here.
-                if dw is None:
-                    dw = torch.zeros(V, H, dtype=torch.float32, device=h2.device)
-                if own_w:
-                    gemm([(logits, hc)], True, True, out=dw, accumulate=True)     # accumulate inside the GEMM epilogue
-                else:
-                    dw.addmm_(logits.t().float(), hc.float())
+                dw = torch.zeros(V, H, dtype=torch.float32, device=h2.device)
+            dw = _wgrad_unowned(logits, h2[s:e], out=dw, accumulate=dw is not None)      # dW (+)= dlogits^T @ h
             del logits
         if dw.dtype != h2.dtype:
             dw = dw.to(h2.dtype)
@@ -724,22 +709,36 @@ def gemm_rope(x2: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
 
 def rope_epilogue_ok(M: int, N: int, K: int, head_dim: int) -> bool:
     """shapes tn_gemm_bf16_rope takes (and the hand-written kernel is the configured GEMM for)"""
-    return (ROPE_EPILOGUE and _own(M, N, (K,)) and K % 64 == 0
-            and (not SPLIT_K or split_k(M, N, K, False, False) == 1)     # (a split-K product sums in another order)
+    return (ROPE_EPILOGUE and _own(M, N, (K,)) and _whole_unsplit(M, N, K)
             and ((head_dim == 128 and N % 256 == 0) or (head_dim == 64 and N % 64 == 0)))
 
 
-ROPE_EPILOGUE = os.environ.get("TN_ROPE_EPILOGUE", "1") != "0"          # (A/B switch)
+def _rope_epilogue_own(x2, w, rope) -> bool:
+    """`gemm_rope` runs ``rope(x2 w^T (+ b))`` for ``rope = (cos, sin, head_dim, ..)`` of `linear_group`"""
+    (M, K), cos, D = x2.shape, rope[0], rope[2]
+    return (rope_epilogue_ok(M, w.shape[0], K, D) and _bf16_rows(x2, w) and cos.dtype == torch.bfloat16
+            and tuple(cos.shape) == (M, D // 2))
 
-# A/B switches of the round-5 fusions (measurements; both default on): SwiGLU inside the gate/up and down-dgrad epilogues,
-# the MLP's three weight gradients as one grouped launch
-MLP_EPILOGUE = os.environ.get("TN_MLP_EPILOGUE", "1") != "0"
-GROUPED_WGRAD = os.environ.get("TN_GROUPED_WGRAD", "1") != "0"
 
-SPLIT_K = os.environ.get("TN_GEMM_SPLITK", "1") != "0"      # (A/B switch)
-# (Splitting only the LAST PARTIAL ROUND of a many-tile product — tn_gemm_bf16_splitk's tail_only = 1 — was measured
-# neutral-to-negative on the step in round 5 and its switch is gone; the grouped weight gradient's remainder split in
-# tn_gemm_bf16_grouped is the form that paid.  The C entry point keeps the mode, tested by a direct call.)
+def _rotated(y2, rope):
+    """the rotary embedding ``rope = (cos, sin, head_dim, ..)`` of y2 [M, heads * head_dim], behind its product"""
+    cos, sin, D = rope[:3]
+    M = y2.shape[0]
+    y4 = y2.view(1, M, -1, D)
+    return L.rope_apply(y4, y4.new_empty(1, M, 0, D), cos, sin, False)[0].view(M, -1)
+
+
+def _whole_unsplit(M: int, N: int, K: int) -> bool:
+    """x W^T runs as whole 64-deep stages in ONE pass over the contraction (a split-K product sums in another order): the
+    product a fused epilogue stands in for.  (The SwiGLU and GELU epilogues never asked for the unsplit half: DESIGN.md.)"""
+    return K % 64 == 0 and (not SPLIT_K or split_k(M, N, K, False, False) == 1)
+
+
+# Flags of the fusions: read at call time, set by the tests alone — the off side is the unfused reference of each.
+ROPE_EPILOGUE = True          # rotary embedding in the q / k projection's epilogue (off: rotated behind the product)
+MLP_EPILOGUE = True           # SwiGLU inside the gate/up and down-dgrad epilogues
+GROUPED_WGRAD = True          # the MLP's three weight gradients as one grouped launch
+SPLIT_K = True                # few-tile products cut along their contraction (`split_k`)
 _NUM_CU = 256
 
 
@@ -764,14 +763,6 @@ def gemm_supported(M: int, N: int, Ks, a_kmaj: bool = False, b_kmaj: bool = Fals
     return k_ok and N % 8 == 0 and M > 0 and (not a_kmaj or M % 8 == 0)
 
 
-def gemm_tn_supported(M: int, N: int, K: int) -> bool:
-    return gemm_supported(M, N, (K,))
-
-
-def _tn_ok(M: int, K: int, Ns) -> bool:
-    return M % 8 == 0 and K % 8 == 0 and all(n % 8 == 0 for n in Ns)
-
-
 # Which GEMM runs the products of the linear layers below:
 #   "own"  the hand-written MFMA kernel of csrc/gemm.hip in its three operand modes — forward x W^T, input gradient
 #          dY W (W contraction-major) and weight gradient dY^T x (both contraction-major): every product reads nn.Linear's
@@ -779,17 +770,24 @@ def _tn_ok(M: int, K: int, Ns) -> bool:
 #          multi-segment launch.  Shapes the kernel does not take (K % 64, fewer output tiles than half the CUs) go to the
 #          library.
 #   "lib"  hipBLASLt through torch, every product brought into the forward layout by transposed copies
-#          (tn_transpose_bf16; round 2's default).  Kept for A/B runs: on one box the Qwen2-Audio-7B step takes 742 ms
+#          (tn_transpose_bf16).  Kept for A/B runs: on one box the Qwen2-Audio-7B step takes 742 ms
 #          on "own" and 717 ms on "lib" (profiles/r03f_*): the library's kernel runs 12 % faster (same cycles within
 #          4 %, higher clock: 2/3 of our LDS read traffic), "own" saves the transposes and their extra stores.
 # TN_LINEAR_GEMM / `bench.py --linear-gemm` select; tests/test_kernels_gpu.py holds the two to each other.
+# WHO ANSWERS: per product kind one predicate, asked with the tensors (the integer rule `_own` + `_bf16_rows`), and one
+# function that runs the product on the kernel or in the library's form — forward `_fwd_own` / `_mm_tn`, input gradient
+# `_dgrad_own` / `_dgrad`, weight gradient `_wgrad_own` / `_wgrads` and `_wgrad_unowned` (DESIGN.md §5.4 has the table).
 LINEAR_GEMM = os.environ.get("TN_LINEAR_GEMM", "own")
 _OWN_MIN_TILES = 96          # below this many 256 x 256 output tiles most CUs would idle: the library's split-K wins
 
 
+def _own_configured() -> bool:
+    return LINEAR_GEMM == "own"
+
+
 def _own(M: int, N: int, Ks, a_kmaj: bool = False, b_kmaj: bool = False) -> bool:
     """The hand-written kernel takes this product (and is the configured choice)."""
-    if not (LINEAR_GEMM == "own" and gemm_supported(M, N, Ks, a_kmaj, b_kmaj)):
+    if not (_own_configured() and gemm_supported(M, N, Ks, a_kmaj, b_kmaj)):
         return False
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     if tiles >= _OWN_MIN_TILES:
@@ -805,21 +803,22 @@ def _bf16_rows(*ts, meta_ok: bool = False) -> bool:
                and t.stride(0) % 8 == 0 and (t.is_meta or t.data_ptr() % 16 == 0) for t in ts)
 
 
+def _transposable(*ts) -> bool:
+    """`transpose_2d`, which brings the library forms' operands into the forward layout, applies: bf16, extents % 8 == 0"""
+    return all(t.dtype == torch.bfloat16 and (t.is_cuda or t.is_meta) and t.shape[0] % 8 == 0 and t.shape[1] % 8 == 0
+               for t in ts)
+
+
+def _fwd_own(a, b, bias=None) -> bool:
+    """The hand-written kernel runs the forward product a [M, K] b [N, K]^T (+ bias)."""
+    return (_own(a.shape[0], b.shape[0], (a.shape[1],)) and _bf16_rows(a, b)
+            and (bias is None or bias.dtype == torch.bfloat16))
+
+
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-           accumulate: bool = False, addend: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``a @ b.T (+ bias)`` (``out += ...`` if accumulate; ``+ addend`` [M, N] if given) for contraction-contiguous
-    a [M, K], b [N, K]."""
-    M, K = a.shape
-    N = b.shape[0]
-    if addend is not None:
-        # (a product that would be cut along its contraction — few output tiles, the last layer on the labelled rows — keeps
-        #  its split-K form and gets the addition behind it: the epilogue variant is for whole-tile products)
-        if (RESIDUAL_EPILOGUE and _own(M, N, (K,)) and _bf16_rows(a, b, addend) and (bias is None or bias.dtype == torch.bfloat16)
-                and K % 64 == 0
-                and (not SPLIT_K or split_k(M, N, K, False, False) == 1)):
-            return gemm([(a, b)], bias=bias, addend=addend)
-        return _mm_tn(a, b, bias) + addend           # (same bits: the product is rounded before the addition either way)
-    if (_own(M, N, (K,)) and _bf16_rows(a, b) and (bias is None or bias.dtype == torch.bfloat16)):
+           accumulate: bool = False) -> torch.Tensor:
+    """``a @ b.T (+ bias)`` (``out += ...`` if accumulate) for contraction-contiguous a [M, K], b [N, K]."""
+    if _fwd_own(a, b, bias):
         return gemm([(a, b)], bias=bias, out=out, accumulate=accumulate)
     if accumulate:
         return out.addmm_(a, b.t())
@@ -828,34 +827,43 @@ def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None
     return torch.nn.functional.linear(a, b, bias)
 
 
-def _dgrad(dys, ws) -> Optional[torch.Tensor]:
-    """sum_i dY_i W_i on the hand-written kernel (W_i [N_i, K] read contraction-major; one launch for up to three
-    layers), or None when it does not take the shapes."""
-    M, K = dys[0].shape[0], ws[0].shape[1]
-    if not (_own(M, K, [w.shape[0] for w in ws]) and _bf16_rows(*dys, *ws)):
-        return None
-    dx = None
-    for i in range(0, len(ws), 3):
-        segs = list(zip(dys[i:i + 3], ws[i:i + 3]))
-        dx = gemm(segs, b_kmaj=True, out=dx, accumulate=dx is not None)
-    return dx
+def _dgrad_own(dys, ws, out=None) -> bool:
+    """The hand-written kernel runs the input gradient sum_i dY_i [M, N_i] W_i [N_i, K] (into ``out``, if given)."""
+    return (_own(dys[0].shape[0], ws[0].shape[1], [w.shape[0] for w in ws])
+            and _bf16_rows(*dys, *ws, *(() if out is None else (out,))))
 
 
-# `_mm_tn(addend=...)` / `gemm(addend=...)`: C = bf16(A B^T + bias) + addend in the GEMM's epilogue (tn_gemm_bf16_addend).  Built
-# in round 6 to add the residual stream where o_proj / down_proj / out_proj / fc2 produce their output, bit-identical to
-# GEMM + the norm kernel's residual add, and MEASURED A NET LOSS on the headline step (profiles/r06g_*, same box): the norm
-# kernels got 6.3 ms cheaper (one input), the epilogue's read of the residual tile is exposed in a persistent GEMM (+53 us per
-# launch, +6.8 ms), and the residual gradient — which the fused norm backward adds in passing — became a separate addition
-# per block (+6.0 ms).  The models do not use it; the entry point stays in the library, tested.
-RESIDUAL_EPILOGUE = True
+def _dgrad(dys, ws, out: Optional[torch.Tensor] = None, dgrad_tn: bool = True) -> torch.Tensor:
+    """``sum_i dY_i W_i`` [M, K] (written to ``out``, if given).  The hand-written kernel reads W_i [N_i, K] contraction-major,
+    one launch for up to three layers.  The library form sums in the GEMM epilogue (addmm, beta = 1), ``dgrad_tn`` on W_i^T
+    in the forward layout where the transposes apply, else on W_i as stored."""
+    if _dgrad_own(dys, ws, out):
+        for i in range(0, len(ws), 3):
+            out = gemm(list(zip(dys[i:i + 3], ws[i:i + 3])), b_kmaj=True, out=out, accumulate=i > 0)
+        return out
+    if dgrad_tn and _transposable(*dys, *ws):
+        wts = [transpose_2d(w) for w in ws]                                    # W^T [K, N]: forward layout
+        out = _mm_tn(dys[0], wts[0], out=out)
+        for d, wt in zip(dys[1:], wts[1:]):
+            _mm_tn(d, wt, out=out, accumulate=True)
+        return out
+    out = torch.mm(dys[0], ws[0]) if out is None else torch.mm(dys[0], ws[0], out=out)
+    for d, w in zip(dys[1:], ws[1:]):
+        out.addmm_(d, w)
+    return out
 
-# bias gradients dY.sum(0) from the weight-gradient launch itself (EPI_BIASG, csrc/gemm.hip) instead of a column-sum pass
-BIAS_IN_WGRAD = os.environ.get("TN_BIAS_IN_WGRAD", "1") != "0"          # (A/B switch)
+
+BIAS_IN_WGRAD = True          # bias gradients dY.sum(0) from the weight-gradient launch itself (EPI_BIASG, csrc/gemm.hip)
 
 
-def _takes_wgrad(dy, x2) -> bool:
-    """The hand-written kernel takes dY^T x [N, K] (both operands contraction-major: the contraction runs over tokens)."""
-    return _own(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True) and _bf16_rows(dy, x2)
+def _wgrad_own(dy, x2, queued: bool = False) -> bool:
+    """The hand-written kernel runs the weight gradient dy [M, N]^T x2 [M, K] (both operands contraction-major: the
+    contraction runs over tokens).  ``queued``: as one product of the deferred queue's table launch, which fills the chip
+    with the tiles of many layers — the tile-count rule is not asked, and meta tensors pass (the queue's bookkeeping runs
+    without a device)."""
+    shape = (dy.shape[1], x2.shape[1], (dy.shape[0],), True, True)
+    return (dy.shape[0] == x2.shape[0] and _bf16_rows(dy, x2, meta_ok=queued)
+            and (_own_configured() and gemm_supported(*shape) if queued else _own(*shape)))
 
 
 # Weight-gradient GEMMs on a side stream.  Nothing in the backward consumes a weight gradient, so these products can
@@ -962,8 +970,8 @@ def _sink_of(w):
 #                    decoder's activations are freed, so the step's peak (end of the decoder's forward) does not move
 # Kept on the per-layer path: weights a data-parallel engine's sink owns, the side stream (`enable_wgrad_stream`), operands
 # the kernel does not take, an existing ``.grad`` that is not a bf16 matrix; tensor / context parallelism and activation
-# checkpointing never install a queue (bin/train.py).  TN_DEFERRED_WGRAD=0: the per-layer path everywhere (A/B switch).
-DEFERRED_WGRAD = os.environ.get("TN_DEFERRED_WGRAD", "1") != "0"
+# checkpointing never install a queue (bin/train.py).
+DEFERRED_WGRAD = True         # (False: the per-layer path everywhere — the tests' reference)
 DEFERRED_WGRAD_FLUSH_LAYERS = 11
 WGRAD_QUEUES = {}        # id(weight) -> weakref to its queue (a dead queue's entries are ignored)
 
@@ -1017,9 +1025,7 @@ class DeferredWgrad:
         if id(w) in self._waiting:
             raise _C.KernelError("DeferredWgrad: a weight was queued twice without a flush in between "
                                  "(two backward passes through one layer: flush between them)")
-        ok = (LINEAR_GEMM == "own" and w.dtype == torch.bfloat16 and w.dim() == 2 and _bf16_rows(dy, x2, meta_ok=True)
-              and dy.shape[0] == x2.shape[0] and tuple(w.shape) == (dy.shape[1], x2.shape[1])
-              and gemm_supported(dy.shape[1], x2.shape[1], (dy.shape[0],), True, True)
+        ok = (_wgrad_own(dy, x2, queued=True) and w.dtype == torch.bfloat16 and tuple(w.shape) == (dy.shape[1], x2.shape[1])
               and (not with_bias or (bias is not None and bias.dtype == torch.bfloat16))
               and (w.grad is None or (w.grad.dtype == torch.bfloat16 and w.grad.is_contiguous()
                                       and (w.grad.is_meta or w.grad.data_ptr() % 16 == 0))))
@@ -1076,26 +1082,26 @@ def _queue_wgrad(w, dy, x2, with_bias: bool) -> bool:
 
 
 # WHERE A WEIGHT GRADIENT GOES.  `_route_wgrad` is the one owner of that decision for a single product dW = dY^T x of a
-# linear layer: `_LinearGroup`, `_GeluMLP` and `_SwiGLUMLP` (and the per-product fallback of `_wgrad_group`) ask it and
-# nothing else.  The rule, first match wins:
+# linear layer: `_LinearGroup`, `_GeluMLP` and `_SwiGLUMLP` (and the per-product fallback of `_wgrad_group`) ask it, through
+# `_wgrads`, and nothing else.  The rule, first match wins:
 #   1. queue       DEFERRED_WGRAD is on, no side stream is enabled, a live queue owns the weight, no live sink owns it, and
 #                  `DeferredWgrad.push` accepts the product (`_queue_wgrad`).  The queue is asked for the bias gradient exactly
 #                  when it is wanted and BIAS_IN_WGRAD is on; it writes ``.grad`` itself, autograd gets no gradient.
-#   2. sink        the kernel takes the product (`_takes_wgrad`) and a live sink owns the weight (`_sink_of`): the launch
+#   2. sink        the kernel takes the product (`_wgrad_own`) and a live sink owns the weight (`_sink_of`): the launch
 #                  writes the view the sink hands out (`take` ... `done`), autograd gets no gradient for the weight.
 #   3. own kernel  the kernel takes the product: the same launch returns a new bf16 tensor.
-#   4. not taken   the caller runs its library form.
+#   4. not taken   `_wgrads` runs the library form (`_wgrad_lib`).
 # In 2 and 3 a wanted bias gradient rides on the launch when BIAS_IN_WGRAD is on (column sums of the dY fragments it reads
 # anyway): a bf16 [N] vector allocated on the current stream, that `_beside` is told about as `written`.  Everywhere else
-# a wanted bias gradient is left to the caller's `column_sum(dy)` — `_bias_left` says when; the callers keep that pass where
-# it has always run in their launch order (`_LinearGroup`: behind all its weight gradients).
+# a wanted bias gradient is left to `column_sum(dy)` — `_bias_left` says when; `_wgrads` runs that pass behind all the weight
+# gradients of its call.
 def _route_wgrad(w, dy, x2, want_bias: bool = False):
     """``(dw, db, taken)`` for ``dW = dy^T x2`` of the weight ``w``; see the rule above.  ``dw``: the new gradient, None where
     a queue or a sink received it or nothing took it; ``db``: the bias gradient that rode on the launch, else None."""
     ride = bool(want_bias and BIAS_IN_WGRAD)
     if _queue_wgrad(w, dy, x2, ride):
         return None, None, True
-    if not _takes_wgrad(dy, x2):
+    if not _wgrad_own(dy, x2):
         return None, None, False
     sink = _sink_of(w)
     db = torch.empty(dy.shape[1], dtype=torch.bfloat16, device=dy.device) if ride else None
@@ -1114,10 +1120,66 @@ def _bias_left(want_bias, taken) -> bool:
     return bool(want_bias and not (taken and BIAS_IN_WGRAD))
 
 
+def _wgrad_lib(dys, x2, layout: str = "nt", out: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """The library's weight gradients ``dW_i = dY_i^T x2`` of layers that share x2 [M, K], as a list.  ``layout``:
+        "nt"        one product per layer in autograd's layout, dY_i^T read as a view (``out (+)= ..`` for a single layer;
+                    an fp32 ``out`` takes the operands as fp32: the loss path's sum over chunks)
+        "nt_fused"  ONE product over the column-concatenated dY (three 1280 x 1280 outputs of the audio tower are 25 tiles
+                    each) — a batched one without the concatenation where the dY_i already lie back to back in one
+                    storage (library.attn_bwd_stacked)
+        "tn"        dY_i and x2 transposed by a HIP kernel and ONE product over the whole group [sum N_i, M] x [M, K] in the
+                    forward layout: hipBLASLt contracts over the slow dimension of both operands at ~1.0 PFLOP/s only."""
+    n, (M, K), Ns = len(dys), x2.shape, [d.shape[1] for d in dys]
+    if layout == "nt_fused" and n > 1:
+        st = _stacked_view(dys)
+        if st is not None:
+            return list(torch.bmm(st.transpose(1, 2), x2.unsqueeze(0).expand(n, M, K)).unbind(0))
+        return list(torch.split(torch.mm(torch.cat(dys, dim=1).t(), x2), Ns, dim=0))
+    if layout == "tn" and _transposable(x2, *dys):
+        xt = transpose_2d(_c(x2))                                          # [K, M]
+        dyt = torch.empty(sum(Ns), M, dtype=x2.dtype, device=x2.device)    # [sum N, M]
+        o = 0
+        for d, N in zip(dys, Ns):
+            transpose_2d(d, out=dyt[o:o + N])
+            o += N
+        return list(torch.split(_mm_tn(dyt, xt), Ns, dim=0))               # TN: both contraction-contiguous
+    if out is None:
+        return [torch.mm(d.t(), x2) for d in dys]
+    (d,) = dys
+    if out.dtype != d.dtype:
+        d, x2 = d.float(), x2.float()
+    return [out.addmm_(d.t(), x2) if accumulate else torch.mm(d.t(), x2, out=out)]
+
+
+def _wgrad_unowned(dy, x2, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """``dW = dy^T x2`` (``out (+)= ..``) of a weight whose gradient the caller keeps to itself — no queue, no sink, no side
+    stream: the lm_head inside the loss, which sums its chunks."""
+    if _wgrad_own(dy, x2):
+        return gemm([(dy, x2)], True, True, out=out, accumulate=accumulate)
+    return _wgrad_lib([dy], x2, out=out, accumulate=accumulate)[0]
+
+
+def _wgrads(ws, dys, x2, want_w, want_b, layout: str = "nt"):
+    """``(dws, dbs)`` of the layers ``ws`` that share the input x2 [M, K]: each wanted ``dW_i = dY_i^T x2`` where
+    `_route_wgrad` puts it (None: a queue or a sink has it), what nothing takes by the library (`_wgrad_lib` — its group
+    layouts only for a whole group), and behind all of them the wanted bias gradients no launch carried (`column_sum`)."""
+    n = len(ws)
+    dws, dbs, want_b = [None] * n, [None] * n, list(want_b)
+    left = [i for i in range(n) if want_w[i]]
+    for i in [i for i in left if dys[i].is_cuda]:         # (meta tensors: the library form; a queue would take them)
+        dws[i], dbs[i], taken = _route_wgrad(ws[i], dys[i], x2, want_b[i])
+        want_b[i] = _bias_left(want_b[i], taken)
+        if taken:
+            left.remove(i)
+    if left:
+        for i, dw in zip(left, _wgrad_lib([dys[i] for i in left], x2, layout if len(left) == n else "nt")):
+            dws[i] = dw
+    return dws, [column_sum(d) if nb else b for b, nb, d in zip(dbs, want_b, dys)]
+
+
 def _wgrad_one(w, dy, x2):
-    """dW of a bias-free layer by the common route, the library's product where nothing takes it"""
-    dw, _, taken = _route_wgrad(w, dy, x2)
-    return dw if taken else torch.mm(dy.t(), x2)
+    """dW of a bias-free layer"""
+    return _wgrads([w], [dy], x2, [True], [False])[0][0]
 
 
 def _wgrad_group(items):
@@ -1128,7 +1190,7 @@ def _wgrad_group(items):
     kernel does not take, fall back to one routed product per layer."""
     sinks = [_sink_of(w) for w, _, _ in items]
     owned = sum(sk is not None for sk in sinks)
-    if not all(_takes_wgrad(dy, x2) for _, dy, x2 in items) or 0 < owned < len(items):
+    if not all(_wgrad_own(dy, x2) for _, dy, x2 in items) or 0 < owned < len(items):
         return [_wgrad_one(*it) for it in items]
     pairs = [(dy, x2) for _, dy, x2 in items]
 
@@ -1167,22 +1229,16 @@ def _stacked_view(ts):
 class _LinearGroup(torch.autograd.Function):
     """``y_i = x W_i^T + b_i`` for a group of linear layers that share their input (q/k/v, gate/up, or one layer).
 
-    Forward is what nn.Linear does.  LINEAR_GEMM == "own": all three products run on the hand-written kernel in their
-    native layouts (see above).  Otherwise the library path of round 2: its WEIGHT gradient dW_i = dY_i^T x contracts
-    over tokens, the slow dimension of both operands, which hipBLASLt runs at ~1.0 PFLOP/s on MI355X; there dY_i and x are
-    transposed by a HIP kernel (tn_transpose_bf16) and ONE GEMM over the whole group ``[sum N_i, M] x [M, K]`` runs in
-    the forward GEMM's layout; the INPUT gradient dX = sum_i dY_i W_i uses W_i transposed first and accumulates over the
-    group inside the GEMM epilogue (addmm, beta = 1).
-    ``wgrad`` (library path): "tn" (above) | "nt" autograd's layout per layer | "nt_fused" one NT GEMM over the
-    column-concatenated dY (the 1280-wide audio tower: three 1280 x 1280 outputs are 25 tiles each).
-    ``dgrad_tn=False`` keeps W as stored for the library's input gradient (no gain at 1280 x 1280)."""
+    Forward is what nn.Linear does.  Each product runs where its kind's function puts it (`_mm_tn`, `_dgrad`, `_wgrads`):
+    on the hand-written kernel in its native layout, or in the library's form — ``wgrad`` names the layout of the library's
+    weight gradient ("tn" | "nt" | "nt_fused": `_wgrad_lib`), ``dgrad_tn=False`` keeps W as stored for the library's input
+    gradient (no gain at 1280 x 1280).  ``extra = (norm_src, rope)``: op-level selective recomputation (`norm_source`) and
+    the rotary embedding of some outputs (`linear_group`), either may be None."""
 
     @staticmethod
-    def forward(ctx, x, n, wgrad, dgrad_tn, *wb):
+    def forward(ctx, x, n, wgrad, dgrad_tn, extra, *wb):
         ws, bs = wb[:n], wb[n:]
-        src = rope = None
-        if isinstance(wgrad, tuple):                       # (wgrad, norm_src, rope): op-level selective recomputation
-            wgrad, src, rope = wgrad                       # (`norm_source`) / rotary embedding of outputs (`linear_group`)
+        src, rope = extra
         ctx.rope = rope
         if src is not None:
             # x = RMSNorm(h) * w_norm is a ROW kernel's output: keep its input (which the norm's own backward saves
@@ -1194,33 +1250,25 @@ class _LinearGroup(torch.autograd.Function):
             ctx.src_eps = None
         ctx.has_bias = [b is not None for b in bs]
         ctx.wgrad, ctx.dgrad_tn = wgrad, dgrad_tn
-        if LINEAR_GEMM == "own" and x.is_cuda:
-            x2 = _c(x.reshape(-1, x.shape[-1]))
-            outs = []
-            for i, (w, b) in enumerate(zip(ws, bs)):
-                if rope is not None and i in rope[3]:
-                    # the rotary embedding of this projection in the GEMM's epilogue (or, for shapes the epilogue does not
-                    # take, behind it: same bits)
-                    cos, sin, D = rope[0], rope[1], rope[2]
-                    M_ = x2.shape[0]
-                    if (rope_epilogue_ok(M_, w.shape[0], x2.shape[1], D) and _bf16_rows(x2, w)
-                            and cos.dtype == torch.bfloat16 and tuple(cos.shape) == (M_, D // 2)):
-                        y = gemm_rope(x2, _c(w), b, cos, sin, D)
-                    else:
-                        y = _mm_tn(x2, _c(w), b)
-                        y4 = y.view(1, M_, -1, D)
-                        y = L.rope_apply(y4, y4.new_empty(1, M_, 0, D), cos, sin, False)[0].view(M_, -1)
-                    outs.append(y.view(*x.shape[:-1], w.shape[0]))
-                else:
-                    outs.append(_mm_tn(x2, _c(w), b).view(*x.shape[:-1], w.shape[0]))
-            return tuple(outs)
-        outs = [torch.nn.functional.linear(x, w, b) for w, b in zip(ws, bs)]
-        if rope is not None:                               # (library GEMM path / meta tensors: rotate behind the product)
-            cos, sin, D = rope[0], rope[1], rope[2]
+        x2 = _c(x.reshape(-1, x.shape[-1]))
+        # (launch order, kept as it has always been: the library configuration rotates behind ALL its products)
+        at_once = _own_configured() and x.is_cuda
+        outs = []
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            w = _c(w)
+            if rope is None or i not in rope[3]:
+                y = _mm_tn(x2, w, b)
+            elif _rope_epilogue_own(x2, w, rope):          # the rotary embedding in the product's epilogue
+                y = gemm_rope(x2, w, b, *rope[:3])
+            else:                                          # ... or behind it: same bits
+                y = _mm_tn(x2, w, b)
+                if at_once:
+                    y = _rotated(y, rope)
+            outs.append(y)
+        if rope is not None and not at_once:
             for i in rope[3]:
-                y4 = outs[i].reshape(1, -1, outs[i].shape[-1] // D, D)
-                outs[i] = L.rope_apply(y4, y4.new_empty(1, y4.shape[1], 0, D), cos, sin, False)[0].reshape(outs[i].shape)
-        return tuple(outs)
+                outs[i] = _rotated(outs[i], rope)
+        return tuple(y.view(*x.shape[:-1], y.shape[-1]) for y in outs)
 
     @staticmethod
     def backward(ctx, *dys):
@@ -1229,8 +1277,7 @@ class _LinearGroup(torch.autograd.Function):
             norm_w = ws.pop()
             x = L.rmsnorm_fwd(x, None, norm_w, ctx.src_eps)[0].view(ctx.xshape)
         n = len(ws)
-        K = x.shape[-1]
-        x2 = x.reshape(-1, K)
+        x2 = _c(x.reshape(-1, x.shape[-1]))
         M = x2.shape[0]
         dys = [torch.zeros(M, w.shape[0], dtype=x.dtype, device=x.device) if d is None else _c(d).reshape(M, -1)
                for d, w in zip(dys, ws)]
@@ -1247,60 +1294,10 @@ class _LinearGroup(torch.autograd.Function):
                 dys[i] = ri.view(M, -1)
                 if j is not None:
                     dys[j] = rj.view(M, -1)
-        need_x, need_w = ctx.needs_input_grad[0], [ctx.needs_input_grad[4 + i] for i in range(n)]
-        Ns = [w.shape[0] for w in ws]
-        hip_ok = x.dtype == torch.bfloat16 and (x.is_cuda or x.is_meta) and _tn_ok(M, K, Ns)
-        own = LINEAR_GEMM == "own" and x.is_cuda and x.dtype == torch.bfloat16
-        dx = None
-        if need_x:
-            if own:
-                dx = _dgrad(dys, [_c(w) for w in ws])
-            if dx is None and hip_ok and ctx.dgrad_tn:
-                wts = [transpose_2d(_c(w)) for w in ws]                                # W^T [K, N]: forward layout
-                dx = _mm_tn(dys[0], wts[0])
-                for d, wt in zip(dys[1:], wts[1:]):
-                    _mm_tn(d, wt, out=dx, accumulate=True)
-                del wts
-            elif dx is None:
-                dx = torch.mm(dys[0], ws[0])
-                for d, w in zip(dys[1:], ws[1:]):
-                    dx.addmm_(d, w)
-            dx = dx.view(x.shape)
-        dws = [None] * n
-        need_b = [hb and ctx.needs_input_grad[4 + n + i] for i, hb in enumerate(ctx.has_bias)]
-        dbs = [None] * n
-        if any(need_w):
-            todo = [i for i in range(n) if need_w[i]]
-            if own:
-                x2c = _c(x2)
-                for i in list(todo):                      # queue, sink or the hand-written kernel: `_route_wgrad`
-                    dws[i], dbs[i], taken = _route_wgrad(ws[i], dys[i], x2c, need_b[i])
-                    need_b[i] = _bias_left(need_b[i], taken)
-                    if taken:
-                        todo.remove(i)
-            if len(todo) < n:                             # (some layers of the group have their gradient, or want none)
-                for i in todo:
-                    dws[i] = torch.mm(dys[i].t(), x2)
-            elif ctx.wgrad == "nt_fused" and n > 1:
-                st = _stacked_view(dys)
-                if st is not None:            # the gradients already lie side by side (library.attn_bwd_stacked): no cat
-                    dws = list(torch.bmm(st.transpose(1, 2), x2.unsqueeze(0).expand(n, M, K)).unbind(0))
-                else:
-                    dws = list(torch.split(torch.mm(torch.cat(dys, dim=1).t(), x2), Ns, dim=0))
-            elif hip_ok and ctx.wgrad == "tn":
-                xt = transpose_2d(_c(x2))                                          # [K, M]
-                dyt = torch.empty(sum(Ns), M, dtype=x.dtype, device=x.device)      # [sum N, M]
-                o = 0
-                for d, N in zip(dys, Ns):
-                    transpose_2d(d, out=dyt[o:o + N])
-                    o += N
-                dw = _mm_tn(dyt, xt)                                               # TN: both contraction-contiguous
-                dws = list(torch.split(dw, Ns, dim=0))
-            else:
-                dws = [torch.mm(d.t(), x2) for d in dys]
-            dws = [g if nw else None for g, nw in zip(dws, need_w)]
-        dbs = [b if (b is not None or not nb) else column_sum(d) for b, nb, d in zip(dbs, need_b, dys)]
-        return (dx, None, None, None, *dws, *dbs)
+        need = ctx.needs_input_grad
+        dx = _dgrad(dys, [_c(w) for w in ws], dgrad_tn=ctx.dgrad_tn).view(x.shape) if need[0] else None
+        dws, dbs = _wgrads(ws, dys, x2, need[5:5 + n], [hb and nb for hb, nb in zip(ctx.has_bias, need[5 + n:])], ctx.wgrad)
+        return (dx, None, None, None, None, *dws, *dbs)
 
 
 def norm_source(h, norm_weight, eps):
@@ -1339,16 +1336,16 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
     if rope is not None:
         rope = (rope[0].detach(), rope[1].detach(), int(rope[2]), tuple(int(i) for i in rope[3]),
                 bool(rope_grad_in_attention))
-    packed = (wgrad, norm_src, rope) if (norm_src is not None or rope is not None) else wgrad
-    return list(_LinearGroup.apply(x, len(ws), packed, dgrad_tn, *ws, *bs))
+    return list(_LinearGroup.apply(x, len(ws), wgrad, dgrad_tn, (norm_src, rope), *ws, *bs))
 
 
 class _SwiGLUMLP(torch.autograd.Function):
     """``down(silu(gate(x)) * up(x))`` as ONE autograd node (modeling_llama.py:174-176, three bias-free nn.Linear).
 
-    LINEAR_GEMM == "own": seven launches of the hand-written kernel (gate, up, down; dW_down, d(act), dX over the
-    (gate, up) pair as one two-segment launch, dW_gate, dW_up) + the two SwiGLU kernels; nothing is transposed.
-    Library path: same GEMMs in the forward layout, the transposed operands they need — act^T for dW_down,
+    ``ctx.own`` (the kernel takes all four product shapes, decided once in the forward): seven launches of the hand-written
+    kernel (gate, up, down; dW_down, d(act), dX over the (gate, up) pair as one two-segment launch, dW_gate, dW_up) + the two
+    SwiGLU kernels, which ``ctx.fused`` folds into epilogues; nothing is transposed.  Otherwise the library body
+    (`_backward_lib`): same GEMMs in the forward layout, the transposed operands they need — act^T for dW_down,
     [d_gate^T; d_up^T] for the grouped dW_gate/up — written by the SwiGLU kernels themselves (tn_swiglu_fwd_t /
     tn_swiglu_bwd_t: one extra store each) instead of by separate transpose passes."""
 
@@ -1358,7 +1355,7 @@ class _SwiGLUMLP(torch.autograd.Function):
         x2 = _c(x.reshape(-1, K))
         M = x2.shape[0]
         own = _own(M, I, (K,)) and _own(M, K, (I,)) and _own(I, K, (M,), True, True) and _own(K, I, (M,), True, True)
-        fused = own and MLP_EPILOGUE and K % 64 == 0 and _bf16_rows(x2, wg, wu, wd) and wg.stride(0) == wu.stride(0)
+        fused = own and MLP_EPILOGUE and _bf16_rows(x2, wg, wu, wd) and wg.stride(0) == wu.stride(0)
         if fused:
             gate, up, act = gemm_swiglu_fwd(x2, wg, wu)       # SwiGLU in the epilogue of ONE gate + up launch
             kept = act
@@ -1391,26 +1388,32 @@ class _SwiGLUMLP(torch.autograd.Function):
         I, H = wg.shape[0], wd.shape[0]
         dy2 = _c(dy).reshape(M, H)
         nx, ng, nu, nd = ctx.needs_input_grad[:4]
-        if ctx.own and LINEAR_GEMM == "own":
-            grouped = GROUPED_WGRAD and ng and nu and nd
-            if not grouped:                                   # one routed product each (`_route_wgrad`)
-                dwd = _wgrad_one(wd, dy2, kept) if nd else None                        # dY^T act  [H, I]
-            if ctx.fused and H % 64 == 0 and _bf16_rows(dy2, wd):
-                dgate, dup = gemm_swiglu_bwd(dy2, wd, gate, up)     # d(act) = dY W_down lives in the accumulators only
-            else:
-                dact = gemm([(dy2, _c(wd))], b_kmaj=True)                              # dY W_down [M, I]
-                dgate, dup = L.swiglu_bwd(dact, gate, up)
-                del dact
-            dx = gemm([(dgate, _c(wg)), (dup, _c(wu))], b_kmaj=True).view(ctx.xshape) if nx else None
-            if grouped:
-                # ONE launch for the three weight gradients (3 x 688 tiles = 8 whole rounds + 16 tiles split-K)
-                dwg, dwu, dwd = _wgrad_group([(wg, dgate, x2), (wu, dup, x2), (wd, dy2, kept)])
-            else:
-                dwg = _wgrad_one(wg, dgate, x2) if ng else None
-                dwu = _wgrad_one(wu, dup, x2) if nu else None
-            return dx, dwg, dwu, dwd, None
-        act_t = kept if not ctx.own else transpose_2d(kept)
-        dwd = _mm_tn(transpose_2d(dy2), act_t) if nd else None                      # [H, I], forward layout
+        if not ctx.own:
+            return (*_SwiGLUMLP._backward_lib(x2, gate, up, kept, wg, wu, wd, dy2, nx, ng, nu, nd, ctx.xshape), None)
+        grouped = GROUPED_WGRAD and ng and nu and nd
+        if not grouped:                                   # one routed product each (`_route_wgrad`)
+            dwd = _wgrad_one(wd, dy2, kept) if nd else None                        # dY^T act  [H, I]
+        if ctx.fused and H % 64 == 0 and _bf16_rows(dy2, wd):
+            dgate, dup = gemm_swiglu_bwd(dy2, wd, gate, up)     # d(act) = dY W_down lives in the accumulators only
+        else:
+            dact = gemm([(dy2, _c(wd))], b_kmaj=True)                              # dY W_down [M, I]
+            dgate, dup = L.swiglu_bwd(dact, gate, up)
+            del dact
+        dx = gemm([(dgate, _c(wg)), (dup, _c(wu))], b_kmaj=True).view(ctx.xshape) if nx else None
+        if grouped:
+            # ONE launch for the three weight gradients (3 x 688 tiles = 8 whole rounds + 16 tiles split-K)
+            dwg, dwu, dwd = _wgrad_group([(wg, dgate, x2), (wu, dup, x2), (wd, dy2, kept)])
+        else:
+            dwg = _wgrad_one(wg, dgate, x2) if ng else None
+            dwu = _wgrad_one(wu, dup, x2) if nu else None
+        return dx, dwg, dwu, dwd, None
+
+    @staticmethod
+    def _backward_lib(x2, gate, up, act_t, wg, wu, wd, dy2, nx, ng, nu, nd, xshape):
+        """``(dx, dW_gate, dW_up, dW_down)`` of the library body: every product in the forward layout (`_mm_tn`), act^T kept
+        by the forward's SwiGLU kernel, [d_gate^T; d_up^T] written by the backward's."""
+        I = wg.shape[0]
+        dwd = _mm_tn(transpose_2d(dy2), act_t) if nd else None                      # [H, I]
         dact = _mm_tn(dy2, transpose_2d(_c(wd)))                                    # [M, I]
         dgate, dup, dgu_t = L.swiglu_bwd_t(dact, gate, up)
         del dact
@@ -1418,11 +1421,11 @@ class _SwiGLUMLP(torch.autograd.Function):
         if nx:
             dx = _mm_tn(dgate, transpose_2d(_c(wg)))
             _mm_tn(dup, transpose_2d(_c(wu)), out=dx, accumulate=True)
-            dx = dx.view(ctx.xshape)
+            dx = dx.view(xshape)
         dwg = dwu = None
         if ng or nu:
             dwg, dwu = torch.split(_mm_tn(dgu_t, transpose_2d(x2)), [I, I], dim=0)
-        return dx, dwg if ng else None, dwu if nu else None, dwd, None
+        return dx, dwg if ng else None, dwu if nu else None, dwd
 
 
 class _Conv1dK3(torch.autograd.Function):
@@ -1487,19 +1490,17 @@ def conv1d_k3(x, weight, bias, stride: int = 1, need_dx: bool = True):
     return _Conv1dK3.apply(_c(x), weight, bias, stride, need_dx), (T + 2 - 3) // stride + 1
 
 
-_MLP_FUSED = os.environ.get("TN_MLP_FUSED", "1") != "0"       # (A/B switch for measurements)
-
-
-GELU_EPILOGUE = os.environ.get("TN_GELU_EPILOGUE", "1") != "0"          # (A/B switch; same bits either way)
+_MLP_FUSED = True             # `swiglu_mlp` as the one node `_SwiGLUMLP` (off: composed of `linear_group` and `swiglu`)
+GELU_EPILOGUE = True          # `gelu_mlp` as the one node `_GeluMLP` (off: composed of `linear_group` and `gelu`; same bits)
 
 
 class _GeluMLP(torch.autograd.Function):
-    """``fc2(gelu(fc1(x)))`` of the Whisper-style encoder layer as ONE autograd node (round 6): GELU in fc1's epilogue (pre
-    and act from one launch), its backward in the epilogue of fc2's input-gradient product (d(act) stays in the
-    accumulators); weight and bias gradients by `_route_wgrad`, as in `_LinearGroup` (bias gradients ride on the
-    weight-gradient launches).  Every launch is bit-identical to the kernels it replaces.  Same box, interleaved:
-    707.5 -> 705.5 ms per headline step (profiles/r06g_*: the two GELU passes, 9.3 ms, against 4.9 ms of epilogue time
-    inside the GEMMs)."""
+    """``fc2(gelu(fc1(x)))`` of the Whisper-style encoder layer as ONE autograd node: GELU in fc1's epilogue (pre and act
+    from one launch), its backward in the epilogue of fc2's input-gradient product (d(act) stays in the accumulators);
+    weight and bias gradients by `_wgrads`, as in `_LinearGroup` (bias gradients ride on the weight-gradient launches).
+    Every launch is bit-identical to the kernels it replaces.  Same box, interleaved: 707.5 -> 705.5 ms per headline step
+    (profiles/r06g_*: the two GELU passes, 9.3 ms, against 4.9 ms of epilogue time inside the GEMMs).  `gelu_mlp` enters
+    only where the hand-written kernel takes all four products (`_gelu_mlp_own`): the node launches them itself."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
@@ -1521,14 +1522,19 @@ class _GeluMLP(torch.autograd.Function):
         dpre = gemm_gelu_bwd(dy2, _c(w2), pre)                                   # (dY W2) o gelu'(pre)   [M, I]
         dx = gemm([(dpre, _c(w1))], b_kmaj=True).view(ctx.xshape) if nx else None
 
-        def wgrad(w, d, a, want_w, want_b):
-            dw, db, taken = _route_wgrad(w, d, a, want_b) if want_w else (None, None, False)
-            if want_w and not taken:                                           # (a shape the kernel does not take)
-                dw = torch.mm(d.t(), a)
-            return dw, (column_sum(d) if _bias_left(want_b, taken) else db)
-        dw2, db2 = wgrad(w2, dy2, act, n2, nb2 and ctx.has_b[1])
-        dw1, db1 = wgrad(w1, dpre, x2, n1, nb1 and ctx.has_b[0])
+        (dw2,), (db2,) = _wgrads([w2], [dy2], act, [n2], [nb2 and ctx.has_b[1]])
+        (dw1,), (db1,) = _wgrads([w1], [dpre], x2, [n1], [nb1 and ctx.has_b[0]])
         return dx, dw1, db1, dw2, db2
+
+
+def _gelu_mlp_own(x, w1, b1, w2, b2) -> bool:
+    """The hand-written kernel takes fc1, fc2 and both input gradients of `_GeluMLP` (their extents; the weight gradients
+    ask for themselves), on bf16 device operands."""
+    M, K = x.numel() // x.shape[-1], x.shape[-1]
+    I, H = w1.shape[0], w2.shape[0]
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and _own(M, I, (K,)) and _own(M, H, (I,)) and _own(M, I, (H,), False, True) and _own(M, K, (I,), False, True)
+            and _bf16_rows(w1, w2) and all(b is None or b.dtype == torch.bfloat16 for b in (b1, b2)))
 
 
 def gelu_mlp(x, w1, b1, w2, b2):
@@ -1536,12 +1542,7 @@ def gelu_mlp(x, w1, b1, w2, b2):
     epilogues take go through the fused node above, anything else composes the individual ops (same bits)."""
     if not (x.is_cuda or x.is_meta):
         raise _C.KernelError("gelu_mlp: device tensors only (the product path has no CPU fallback)")
-    M, K = x.numel() // x.shape[-1], x.shape[-1]
-    I, H = w1.shape[0], w2.shape[0]
-    ok = (GELU_EPILOGUE and x.is_cuda and LINEAR_GEMM == "own" and x.dtype == torch.bfloat16 and K % 64 == 0 and I % 64 == 0
-          and _own(M, I, (K,)) and _own(M, H, (I,)) and _own(M, I, (H,), False, True) and _own(M, K, (I,), False, True)
-          and _bf16_rows(w1, w2) and all(b is None or b.dtype == torch.bfloat16 for b in (b1, b2)))
-    if ok:
+    if GELU_EPILOGUE and _gelu_mlp_own(x, w1, b1, w2, b2):
         return _GeluMLP.apply(x, w1, b1, w2, b2)
     h = linear_group(x, [(w1, b1)], wgrad="nt", dgrad_tn=False)[0]
     return linear_group(gelu(h), [(w2, b2)], wgrad="nt", dgrad_tn=False)[0]
@@ -1555,9 +1556,8 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
     M = x.numel() // x.shape[-1]
     if not _norm_src_describes(norm_src, x):
         norm_src = None
-    if (_MLP_FUSED and x.dtype == torch.bfloat16
-            and all(w.dtype == torch.bfloat16 for w in (w_gate, w_up, w_down))
-            and _tn_ok(M, x.shape[-1], (w_gate.shape[0], w_down.shape[0]))):
+    # (the node's library body transposes x, the weights and dY: `_transposable`)
+    if _MLP_FUSED and x.dtype == torch.bfloat16 and M % 8 == 0 and _transposable(w_gate, w_up, w_down):
         return _SwiGLUMLP.apply(x, w_gate, w_up, w_down, norm_src)
     gate, up = linear_group(x, [(w_gate, None), (w_up, None)], norm_src=norm_src)
     return linear_group(swiglu(gate, up), [(w_down, None)])[0]
