@@ -192,6 +192,28 @@ int tn_resample_polyphase(const float* x, float* y, const float* tab, long long 
  * 48 KiB of LDS). */
 int tn_resample_sinc(const void* x, int x_is_pcm16, float* y, const float* tab, long long n_in, long long n_out,
                      int orig, int new_, int ntap, void* stream);
+/* Kaldi log-fbank / MFCC at any sample rate and frame geometry, touchnet/data/functions.py:117-156
+ * (`torchaudio.compliance.kaldi.fbank` / `.mfcc`: snip_edges, dither 0, waveform * 32768, DC removal, pre-emphasis 0.97,
+ * Povey window, power spectrum of the frame zero-padded to `padded`, mel triangles in 1127 ln(1 + f / 700),
+ * log(max(e, FLT_EPSILON)); use_energy false).  wav fp32 [n_samples] in [-1, 1) -> out fp32 [frames, C],
+ * frames = n_samples < win ? 0 : 1 + (n_samples - win) / shift; C = num_mel_bins when num_ceps == 0 (fbank rows),
+ * else num_ceps (MFCC rows: out = dct . log energies).  The fbank rows behind both modes carry the same bits.
+ * Tables, device memory, built by touchnet_amd/functional.py::kaldi_feature_tables in float64 and rounded to float32:
+ *   window   float [win]                      the Povey window
+ *   bank_idx int   [num_mel_bins][3]          (first FFT bin, count, offset into bank_w) of each mel triangle's
+ *                                             non-zero weights; count 0 = no FFT bin inside it: log(FLT_EPSILON)
+ *   bank_w   float [n_bank_w]                 the non-zero weights, packed; n_bank_w <= padded
+ *   dct      float [num_ceps][num_mel_bins]   lifter[k] * DCT-II[k][n], orthonormal (row 0 sqrt(1/N), row k
+ *                                             sqrt(2/N) cos(pi/N (n + 1/2) k)), lifter 1 + 11 sin(pi k / 22); MFCC only
+ * sample_rate, low_freq and high_freq (<= 0: offset from Nyquist) are checked, not used: the tables carry them.
+ * One launch (none for 0 frames), no allocation, no synchronisation.
+ * -22 (before any launch) unless: padded a power of two in [32, 2048] with padded / 2 < win <= padded; shift >= 1;
+ * 4 <= num_mel_bins <= 256; 0 <= num_ceps <= num_mel_bins; 0 <= low_freq < high <= sample_rate / 2;
+ * 0 <= n_bank_w <= padded; no null table that the mode reads; frames < 2^31; with at least one frame, wav and out
+ * non-null and out != wav. */
+int tn_kaldi_feats(const float* wav, float* out, long long n_samples, int sample_rate, int win, int shift, int padded,
+                   int num_mel_bins, int num_ceps, float low_freq, float high_freq, const float* window,
+                   const int* bank_idx, const float* bank_w, int n_bank_w, const float* dct, void* stream);
 
 /* ---- fused AdamW on fp32 master weights with bf16 shadow write-back and device-side
  *      skip-on-nonfinite — touchnet/utils/optimizer.py:157-172 + touchnet/bin/train.py:458-474.

@@ -53,6 +53,17 @@ def docs(B, T, mean_len, seed=0):
     return torch.from_numpy(out)
 
 
+def frontend():
+    """the feature kernels on one 30 s clip (`--frontend`: these lines alone, printed and not stored)"""
+    wav = (torch.randn(16000 * 30, device=DEV) * 0.1).clamp(-1, 1)
+    rec("kaldi fbank 30 s", timeit(lambda: F.kaldi_fbank(wav, 80)), bytes_=wav.numel() * 4 + 2998 * 80 * 4)
+    rec("kaldi fbank 30 s, general kernel (16 kHz 25 / 10, 80 bins)",
+        timeit(lambda: F.kaldi_fbank_general(wav, 16000, 80, 25, 10)), bytes_=wav.numel() * 4 + 2998 * 80 * 4)
+    rec("kaldi mfcc 30 s (16 kHz 25 / 10, 23 bins, 13 cepstra)",
+        timeit(lambda: F.kaldi_mfcc(wav, 16000, 23, 13, 25, 10)), bytes_=wav.numel() * 4 + 2998 * 13 * 4)
+    rec("log-mel 30 s", timeit(lambda: F.log_mel_spectrogram(wav, 128)), bytes_=wav.numel() * 4 + 3000 * 128 * 4)
+
+
 def main():
     torch.manual_seed(0)
     print(torch.cuda.get_device_name(0), torch.__version__, flush=True)
@@ -143,14 +154,11 @@ def main():
     do = torch.randn_like(o)
     rec("attn bwd D64 gqa docs~400", timeit(lambda: torch.autograd.grad(o, [qg, kg, vg], do, retain_graph=True), 10, 3),
         flops=2.5 * fl_f)
-    # ---- frontend
-    wav = (torch.randn(16000 * 30, device=DEV) * 0.1).clamp(-1, 1)
-    rec("kaldi fbank 30 s", timeit(lambda: F.kaldi_fbank(wav, 80)), bytes_=wav.numel() * 4 + 2998 * 80 * 4)
-    rec("log-mel 30 s", timeit(lambda: F.log_mel_spectrogram(wav, 128)), bytes_=wav.numel() * 4 + 3000 * 128 * 4)
+    frontend()
     json.dump(OUT, open("gpurun_out/microbench.json", "w"), indent=1)
 
 
 if __name__ == "__main__":
     import os
     os.makedirs("gpurun_out", exist_ok=True)
-    main()
+    frontend() if "--frontend" in sys.argv else main()

@@ -6,9 +6,10 @@ touchnet/models/touch_audio/inference_touch_audio.py (same inputs, same output l
 
 CKPT_DIR holds HF-format `*.safetensors` (the parameter names of TouchAudioForCausalLM are Hugging Face's) and a model
 config (`config.json` in the directory, else `../../model_config.json` as the reference reads it); the data config comes
-from `--data_config` or `CKPT_DIR/../../data_config.json` (fbank, 80 bins, stacking to the projector width when absent).
+from `--data_config` or `CKPT_DIR/../../data_config.json` (fbank, 80 bins, stacking to the projector width when absent;
+`audio_feat_type` fbank, mfcc or log_mel_spectrogram as the reference's command takes them).
 `data.list`: one JSON object per line with at least "key" and "wav" (16-bit PCM wav of any sample rate; other rates
-than 16 kHz are resampled on the device, see read_wav).  Output:
+than the data config's `audio_resample_rate`, 16 kHz by default, are resampled on the device, see read_wav).  Output:
 OUT/part_{i+1}_of_{n}, one JSON line per utterance: {"label": the input line, "predict_ids": [...], "predict": text} —
 "predict" only when CKPT_DIR has a tokenizer.  One GPU per process; `--shard_index / --num_shards` split the list
 without collectives.
@@ -34,7 +35,7 @@ from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
 _DATA_DEFAULTS = dict(audio_feat_type="fbank", audiofeat_num_mel_bins=80, audiofeat_dither=0.0, audiofeat_frame_length=25,
                       audiofeat_frame_shift=10, audiofeat_n_fft=400, audiofeat_hop_length=160, audiofeat_padding=0,
                       audiofeat_stack_length=None, audiofeat_stride_length=None, audiofeat_normalize=True,
-                      audio_resample_rate=16000)
+                      audio_resample_rate=16000, audiofeat_num_ceps=40, audiofeat_low_freq=20.0, audiofeat_high_freq=0.0)
 
 
 def _first(*paths):
@@ -83,34 +84,38 @@ def data_config(args, model) -> types.SimpleNamespace:
     return types.SimpleNamespace(**d)
 
 
-def read_wav(path: str) -> torch.Tensor:
-    """16-bit PCM wav (first channel) -> the 16 kHz waveform [1, N]: the int16 samples themselves, on the host, for a
-    16 kHz file; a file of any other rate is resampled on the device (functional.resample: torchaudio's windowed-sinc
-    formula) and comes back as fp32 [1, ceil(N 16000 / rate)] there.  The reference's scripts resample with
-    `ffmpeg -ar 16000`, a different algorithm: the same band-limited signal, not the same samples, and no parity with it
-    is claimed."""
+def read_wav(path: str, target_rate: int = 16000) -> torch.Tensor:
+    """16-bit PCM wav (first channel) -> the waveform [1, N] at `target_rate` Hz (the data config's `audio_resample_rate`;
+    16 kHz in every recipe): the int16 samples themselves, on the host, for a file at that rate; a file of any other rate
+    is resampled on the device (functional.resample: torchaudio's windowed-sinc formula) and comes back as fp32
+    [1, ceil(N target_rate / rate)] there.  The reference's scripts resample with `ffmpeg -ar 16000`, a different
+    algorithm: the same band-limited signal, not the same samples, and no parity with it is claimed."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: 16-bit PCM only")
         ch, rate = w.getnchannels(), w.getframerate()
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, ch)[:, 0].copy()
     pcm = torch.from_numpy(pcm)
-    if rate != 16000:
+    if rate != target_rate:
         if not torch.cuda.is_available():
             raise RuntimeError(f"{path}: {rate} Hz is resampled on the MI355X (there is no CPU path)")
-        return ops().resample(pcm.to(torch.device("cuda", torch.cuda.current_device())), rate, 16000)[None]
+        return ops().resample(pcm.to(torch.device("cuda", torch.cuda.current_device())), rate, int(target_rate))[None]
     return pcm[None]
 
 
 def features(wavs, dcfg) -> list:
-    """The device frontend stages of the data config: fbank / log-mel, then stacking."""
+    """The device frontend stages of the data config: fbank / MFCC / log-mel, then stacking.  The waveforms are at the
+    data config's `audio_resample_rate` (read_wav) and the samples say so."""
     if dcfg.audio_feat_type == "fbank":
         feat_stage = stages.audio_compute_fbank
+    elif dcfg.audio_feat_type == "mfcc":
+        feat_stage = stages.audio_compute_mfcc
     elif dcfg.audio_feat_type == "log_mel_spectrogram":
         feat_stage = stages.audio_compute_log_mel_spectrogram
     else:
         raise ValueError(f"unsupported audio_feat_type {dcfg.audio_feat_type!r}")
-    samples = [{"sample_rate": 16000, "waveform": w} for w in wavs]
+    rate = int(getattr(dcfg, "audio_resample_rate", 16000))
+    samples = [{"sample_rate": rate, "waveform": w} for w in wavs]
     return [s["audiofeat"] for s in stages.audiofeat_stack(feat_stage(iter(samples), dcfg), dcfg)]
 
 
@@ -152,7 +157,7 @@ def main(argv=None):
     with open(out_path, "w") as writer:
         for i in range(0, len(items), args.batch_size):
             batch = items[i:i + args.batch_size]
-            feats = features([read_wav(it["wav"]) for it in batch], dcfg)
+            feats = features([read_wav(it["wav"], int(dcfg.audio_resample_rate)) for it in batch], dcfg)
             ids = transcribe(model, feats, cfg)
             for it, row in zip(batch, ids):
                 rec = {"label": json.dumps(it, ensure_ascii=False), "predict_ids": row}

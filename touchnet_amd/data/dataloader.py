@@ -190,8 +190,22 @@ def build_datapipe(cfg, tokenizer, dp_rank: int, dp_world_size: int):
         pipe = stage(functions.audio_resample, cfg)
         if getattr(cfg, "audio_speed_perturb", False):            # wav-level augmentation (processing_touch_audio.py:457-459)
             pipe = stage(functions.audio_speed_perturb, cfg)
-        if cfg.audio_feat_type == "fbank":
-            pipe = stage(functions.audio_compute_fbank, cfg)
+        if cfg.audio_feat_type in ("fbank", "mfcc"):
+            # csrc/kaldi_feats.hip takes FFT sizes 32 .. 2048, 4 .. 256 mel bins and num_ceps <= num_mel_bins (torchaudio
+            # asserts the last too; the reference's defaults, 40 cepstra over 23 bins, fail it there): refuse a config it
+            # cannot run here, by field name, not as a -22 on the first utterance.  Every sample leaves audio_resample
+            # at audio_resample_rate.
+            from touchnet_amd.functional import kaldi_feature_geometry
+            mfcc = cfg.audio_feat_type == "mfcc"
+            if getattr(cfg, "audiofeat_dither", 0.0) != 0.0:
+                raise ValueError(f"audiofeat_dither = {cfg.audiofeat_dither}: the MI355X feature kernels draw no random "
+                                 f"numbers (no recipe sets it); use 0.0")
+            get = lambda k, default: getattr(cfg, k, default)           # (absent fields: the reference's DataConfig defaults)
+            kaldi_feature_geometry(get("audio_resample_rate", 16000), get("audiofeat_frame_length", 25),
+                                   get("audiofeat_frame_shift", 10), get("audiofeat_num_mel_bins", 23),
+                                   *((get("audiofeat_low_freq", 20.0), get("audiofeat_high_freq", 0.0),
+                                      get("audiofeat_num_ceps", 40)) if mfcc else ()))
+            pipe = stage(functions.audio_compute_mfcc if mfcc else functions.audio_compute_fbank, cfg)
         elif cfg.audio_feat_type == "log_mel_spectrogram":
             pipe = stage(functions.audio_compute_log_mel_spectrogram, cfg)
         else:

@@ -4,6 +4,7 @@ MidLevelTouchDatapipe(source, f, *args) (touchnet/data/datapipe.py:183-213) unch
 
     audio_resample                      functions.py:83-96
     audio_compute_fbank                 functions.py:117-134
+    audio_compute_mfcc                  functions.py:137-156
     audio_compute_log_mel_spectrogram   functions.py:159-190
     audiofeat_spec_aug / _sub / _trim   functions.py:193-255   (draws on the host, applied in one device pass)
     audiofeat_stack                     functions.py:258-286
@@ -45,12 +46,36 @@ def audio_speed_perturb(data, config):
         yield sample
 
 
+def _refuse_dither(config, stage):
+    if getattr(config, "audiofeat_dither", 0.0) != 0.0:
+        raise ValueError(f"{stage}: audiofeat_dither = {config.audiofeat_dither} adds random noise to every sample; the "
+                         f"device kernels draw no random numbers and no recipe sets it. Use audiofeat_dither 0.0")
+
+
 def audio_compute_fbank(data, config):
+    """functions.py:117-134.  At the recipes' geometry (16 kHz, 25 ms / 10 ms) the frame geometry is compiled into
+    `kaldi_fbank`; a sample of any other rate, or any other frame length / shift, goes to the kernel that takes them as
+    arguments (functional.kaldi_fbank_general, 20 Hz .. Nyquist as torchaudio's defaults)."""
     for sample in data:
-        assert sample["sample_rate"] == 16000, "device frontend: 16 kHz only (all reference recipes)"
-        assert config.audiofeat_dither == 0.0 and config.audiofeat_frame_length == 25 and \
-            config.audiofeat_frame_shift == 10
-        sample["audiofeat"] = ops().kaldi_fbank(_dev_wave(sample), config.audiofeat_num_mel_bins)
+        _refuse_dither(config, "audio_compute_fbank")
+        if sample["sample_rate"] == 16000 and config.audiofeat_frame_length == 25 and config.audiofeat_frame_shift == 10:
+            sample["audiofeat"] = ops().kaldi_fbank(_dev_wave(sample), config.audiofeat_num_mel_bins)
+        else:
+            sample["audiofeat"] = ops().kaldi_fbank_general(_dev_wave(sample), sample["sample_rate"],
+                                                            config.audiofeat_num_mel_bins, config.audiofeat_frame_length,
+                                                            config.audiofeat_frame_shift)
+        yield sample
+
+
+def audio_compute_mfcc(data, config):
+    """functions.py:137-156: Kaldi MFCC (`audiofeat_num_ceps` cepstra over `audiofeat_num_mel_bins` mel bins between
+    `audiofeat_low_freq` and `audiofeat_high_freq`) at the sample's own rate, in one launch per utterance."""
+    for sample in data:
+        _refuse_dither(config, "audio_compute_mfcc")
+        sample["audiofeat"] = ops().kaldi_mfcc(_dev_wave(sample), sample["sample_rate"], config.audiofeat_num_mel_bins,
+                                               config.audiofeat_num_ceps, config.audiofeat_frame_length,
+                                               config.audiofeat_frame_shift, config.audiofeat_low_freq,
+                                               config.audiofeat_high_freq)
         yield sample
 
 

@@ -1594,6 +1594,125 @@ def kaldi_fbank(wav: torch.Tensor, num_mel_bins: int = 80) -> torch.Tensor:
     return L.kaldi_fbank(_c(wav).float().view(-1), int(num_mel_bins))
 
 
+KALDI_MIN_PADDED, KALDI_MAX_PADDED = 32, 2048     # FFT sizes of csrc/kaldi_feats.hip (8 .. 48 kHz at 25 ms, 16 kHz to 128 ms)
+KALDI_MIN_BINS, KALDI_MAX_BINS = 4, 256           # torchaudio asks for more than 3 bins; one thread per bin
+KALDI_LIFTER = 22.0                               # torchaudio's / Kaldi's cepstral_lifter
+_KALDI_TABLES = {}
+
+
+def kaldi_feature_geometry(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq=20.0, high_freq=0.0,
+                           num_ceps=None):
+    """(win, shift, padded, high) of a Kaldi feature configuration in samples and Hz — `win = int(sr frame_length / 1000)`,
+    `padded` the next power of two, `high` after Kaldi's rule (high_freq <= 0: offset from Nyquist) — or a ValueError that
+    names the field csrc/kaldi_feats.hip cannot take.  Pure host arithmetic: callers check a config with it before any
+    sample is read."""
+    sr = int(sample_rate)
+    if sr < 1 or sr != sample_rate:
+        raise ValueError(f"sample_rate = {sample_rate}: a positive integer number of Hz")
+    win, shift = int(sr * frame_length * 0.001), int(sr * frame_shift * 0.001)
+    if shift < 1:
+        raise ValueError(f"audiofeat_frame_shift = {frame_shift} ms is less than one sample at {sr} Hz")
+    padded = 1 << max(win - 1, 0).bit_length()
+    if not KALDI_MIN_PADDED <= padded <= KALDI_MAX_PADDED:
+        raise ValueError(f"audiofeat_frame_length = {frame_length} ms at {sr} Hz is a window of {win} samples, FFT size "
+                         f"{padded}: the MI355X feature kernel takes FFT sizes {KALDI_MIN_PADDED} .. {KALDI_MAX_PADDED}")
+    bins = int(num_mel_bins)
+    if not KALDI_MIN_BINS <= bins <= KALDI_MAX_BINS:
+        raise ValueError(f"audiofeat_num_mel_bins = {num_mel_bins}: the feature kernel takes {KALDI_MIN_BINS} .. "
+                         f"{KALDI_MAX_BINS} mel bins (torchaudio needs more than 3)")
+    if num_ceps is not None and not 1 <= int(num_ceps) <= bins:
+        raise ValueError(f"audiofeat_num_ceps = {num_ceps} must lie in 1 .. audiofeat_num_mel_bins = {bins} "
+                         f"(torchaudio asserts the same; the reference's own defaults, 40 over 23, do not pass it)")
+    nyquist = 0.5 * sr
+    high = float(high_freq) if high_freq > 0.0 else nyquist + float(high_freq)
+    if not 0.0 <= float(low_freq) < high <= nyquist:
+        raise ValueError(f"audiofeat_low_freq = {low_freq} / audiofeat_high_freq = {high_freq} (= {high} Hz): need "
+                         f"0 <= low < high <= Nyquist = {nyquist} Hz")
+    return win, shift, padded, high
+
+
+def kaldi_feature_tables(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq=20.0, high_freq=0.0,
+                         num_ceps=None):
+    """The host tables of csrc/kaldi_feats.hip in float64 (numpy; no GPU needed), as torchaudio.compliance.kaldi builds
+    them:
+        window    [win]         Povey: (0.5 - 0.5 cos(2 pi n / (win - 1)))^0.85
+        bank_idx  [bins, 3]     int32 (first FFT bin, count, offset into bank_w) of the weights of each mel triangle
+                                max(0, min(up, down)) over the padded / 2 FFT bins that are non-zero AS FLOAT32 — what
+                                is left out is exactly 0.0f; a triangle no FFT bin falls into has count 0
+        bank_w    [sum count]   those weights, packed in bin order
+        dct       [num_ceps, bins]   lifter[k] DCT[k][n] with torchaudio's orthonormal DCT-II (row 0 = sqrt(1 / N)) and
+                                lifter 1 + 0.5 Q sin(pi k / Q), Q = 22; None without num_ceps
+    plus win, shift, padded.  The kernel reads the float32 cast of each."""
+    import numpy as np
+    win, shift, padded, high = kaldi_feature_geometry(sample_rate, frame_length, frame_shift, num_mel_bins, low_freq,
+                                                      high_freq, num_ceps)
+    sr, bins = int(sample_rate), int(num_mel_bins)
+    n = np.arange(win, dtype=np.float64)
+    window = (0.5 - 0.5 * np.cos(2.0 * math.pi * n / (win - 1))) ** 0.85
+    mel = lambda f: 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+    mel_lo, mel_hi = mel(float(low_freq)), mel(high)
+    delta = (mel_hi - mel_lo) / (bins + 1)
+    b = np.arange(bins, dtype=np.float64)[:, None]
+    left, center, right = mel_lo + b * delta, mel_lo + (b + 1.0) * delta, mel_lo + (b + 2.0) * delta
+    m = mel((sr / padded) * np.arange(padded // 2, dtype=np.float64))[None, :]
+    dense = np.maximum(0.0, np.minimum((m - left) / (center - left), (right - m) / (right - center)))
+    idx = np.zeros((bins, 3), dtype=np.int32)
+    packed = []
+    for r in range(bins):
+        nz = np.flatnonzero(dense[r].astype(np.float32))
+        if nz.size:
+            idx[r] = (nz[0], nz[-1] - nz[0] + 1, sum(p.size for p in packed))
+            packed.append(dense[r, nz[0]:nz[-1] + 1])
+        else:
+            idx[r] = (0, 0, sum(p.size for p in packed))
+    tables = dict(win=win, shift=shift, padded=padded, window=window, bank_idx=idx,
+                  bank_w=np.concatenate(packed) if packed else np.zeros(0), dct=None)
+    if num_ceps is not None:
+        k = np.arange(int(num_ceps), dtype=np.float64)[:, None]
+        dct = np.cos(math.pi / bins * (np.arange(bins, dtype=np.float64)[None, :] + 0.5) * k) * math.sqrt(2.0 / bins)
+        dct[0] = math.sqrt(1.0 / bins)
+        tables["dct"] = (1.0 + 0.5 * KALDI_LIFTER * np.sin(math.pi * k / KALDI_LIFTER)) * dct
+    return tables
+
+
+def _kaldi_device_tables(device, *key):
+    if (key, device) not in _KALDI_TABLES:
+        t = kaldi_feature_tables(*key)
+        dev = lambda a, dt: None if a is None else torch.from_numpy(a).to(dt).to(device).contiguous()
+        _KALDI_TABLES[(key, device)] = (t["shift"], dev(t["window"], torch.float32), dev(t["bank_idx"], torch.int32),
+                                        dev(t["bank_w"], torch.float32), dev(t["dct"], torch.float32))
+    return _KALDI_TABLES[(key, device)]
+
+
+def _kaldi_wave(wav, what):
+    if not wav.is_cuda:
+        raise RuntimeError(f"{what}: expects a device waveform (there is no CPU path)")
+    return _c(wav).float().view(-1)
+
+
+def kaldi_fbank_general(wav: torch.Tensor, sample_rate: int, num_mel_bins: int, frame_length, frame_shift,
+                        low_freq: float = 20.0, high_freq: float = 0.0) -> torch.Tensor:
+    """wav fp32 [N] in [-1, 1) at `sample_rate` Hz -> Kaldi log-fbank fp32 [frames, num_mel_bins] with windows of
+    `frame_length` ms every `frame_shift` ms (functions.py:117-134 at any rate and geometry; `kaldi_fbank` is the
+    recipes' 16 kHz 25 / 10 kernel)."""
+    key = (int(sample_rate), frame_length, frame_shift, int(num_mel_bins), float(low_freq), float(high_freq), None)
+    wav = _kaldi_wave(wav, "kaldi_fbank_general")
+    shift, window, idx, w, _ = _kaldi_device_tables(wav.device, *key)
+    return L.kaldi_feats(wav, window, idx, w, key[0], shift, key[4], key[5])
+
+
+def kaldi_mfcc(wav: torch.Tensor, sample_rate: int, num_mel_bins: int, num_ceps: int, frame_length, frame_shift,
+               low_freq: float = 20.0, high_freq: float = 0.0) -> torch.Tensor:
+    """wav fp32 [N] in [-1, 1) at `sample_rate` Hz -> Kaldi MFCC fp32 [frames, num_ceps] (functions.py:137-156:
+    torchaudio.compliance.kaldi.mfcc, use_energy false, cepstral lifter 22): the liftered orthonormal DCT-II of the
+    log-fbank row, computed in the same launch."""
+    key = (int(sample_rate), frame_length, frame_shift, int(num_mel_bins), float(low_freq), float(high_freq),
+           int(num_ceps))
+    wav = _kaldi_wave(wav, "kaldi_mfcc")
+    shift, window, idx, w, dct = _kaldi_device_tables(wav.device, *key)
+    return L.kaldi_mfcc(wav, window, idx, w, dct, key[0], shift, key[4], key[5])
+
+
 def log_mel_spectrogram(wav: torch.Tensor, num_mel_bins: int = 128, padding: int = 0) -> torch.Tensor:
     """wav fp32 [N] at 16 kHz -> fp32 [N // 160, num_mel_bins] (functions.py:159-190)."""
     wav = _c(wav).float().view(-1)

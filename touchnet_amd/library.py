@@ -772,6 +772,56 @@ def resample_sinc(wave: Tensor, tab: Tensor, orig: int, new: int, n_out: int) ->
     return out
 
 
+def _kaldi_frames(n_samples: int, win: int, shift: int) -> int:
+    """Kaldi's snip_edges frame count"""
+    return 0 if n_samples < win or shift < 1 else 1 + (n_samples - win) // shift
+
+
+def _kaldi_feats(wav, window, bank_idx, bank_w, dct, sample_rate, shift, low_freq, high_freq) -> Tensor:
+    """tn_kaldi_feats on a 1-D fp32 device waveform and the tables of functional.kaldi_feature_tables: fbank rows when
+    dct is None, MFCC rows otherwise.  The geometry comes from the tables' shapes; the entry point refuses what does not
+    fit (-22) before it launches anything."""
+    win, bins = int(window.shape[0]), int(bank_idx.shape[0])
+    ceps = 0 if dct is None else int(dct.shape[0])
+    for t, dt in ((wav, torch.float32), (window, torch.float32), (bank_idx, torch.int32), (bank_w, torch.float32),
+                  (dct, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise _C.KernelError("tn_kaldi_feats: contiguous fp32 waveform / window / weights / dct and int32 bank indices")
+    if wav.dim() != 1 or bank_idx.dim() != 2 or bank_idx.shape[1] != 3 or (dct is not None and (
+            dct.dim() != 2 or dct.shape[1] != bins or ceps < 1)):
+        raise _C.KernelError("tn_kaldi_feats: wav [N], bank_idx [bins, 3], dct [num_ceps >= 1, bins]")
+    out = torch.empty(_kaldi_frames(wav.numel(), win, int(shift)), ceps or bins, dtype=torch.float32, device=wav.device)
+    _C.check(_lib().tn_kaldi_feats(_p(wav), _p(out), wav.numel(), int(sample_rate), win, int(shift),
+                                   1 << max(win - 1, 0).bit_length(), bins, ceps, float(low_freq), float(high_freq),
+                                   _p(window), _p(bank_idx), _p(bank_w), bank_w.numel(), _p(dct), _cur()),
+             "tn_kaldi_feats")
+    return out
+
+
+@custom_op(f"{NS}::kaldi_feats", mutates_args=(), device_types="cuda")
+def kaldi_feats(wav: Tensor, window: Tensor, bank_idx: Tensor, bank_w: Tensor, sample_rate: int, shift: int,
+                low_freq: float, high_freq: float) -> Tensor:
+    """-> log-fbank fp32 [frames, num_mel_bins] at the geometry of the tables (csrc/kaldi_feats.hip)"""
+    return _kaldi_feats(wav, window, bank_idx, bank_w, None, sample_rate, shift, low_freq, high_freq)
+
+
+@kaldi_feats.register_fake
+def _(wav, window, bank_idx, bank_w, sample_rate, shift, low_freq, high_freq):
+    return wav.new_empty(_kaldi_frames(wav.numel(), window.shape[0], shift), bank_idx.shape[0])
+
+
+@custom_op(f"{NS}::kaldi_mfcc", mutates_args=(), device_types="cuda")
+def kaldi_mfcc(wav: Tensor, window: Tensor, bank_idx: Tensor, bank_w: Tensor, dct: Tensor, sample_rate: int, shift: int,
+               low_freq: float, high_freq: float) -> Tensor:
+    """-> MFCC fp32 [frames, num_ceps]: dct [num_ceps, num_mel_bins] applied to the log-fbank row inside the kernel"""
+    return _kaldi_feats(wav, window, bank_idx, bank_w, dct, sample_rate, shift, low_freq, high_freq)
+
+
+@kaldi_mfcc.register_fake
+def _(wav, window, bank_idx, bank_w, dct, sample_rate, shift, low_freq, high_freq):
+    return wav.new_empty(_kaldi_frames(wav.numel(), window.shape[0], shift), dct.shape[0])
+
+
 def feat_augment(feat: Tensor, t_masks, f_masks, subs, out_rows: int) -> Tensor:
     """tn_feat_augment: the draws travel as kernel arguments (host int arrays), so this is a plain function, not a
     registered op (no tensor carries them)."""
@@ -1100,4 +1150,4 @@ OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_f
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
-       "beam_step_", "kimi_text_step_")
+       "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc")
