@@ -555,6 +555,31 @@ int tn_attn_block_causal_fwd(const void* q, const void* k, const void* v, void* 
  *      the result is deterministic).  -22 before any launch for d % 64 != 0, V < 1, NULL or misaligned pointers. */
 int tn_vq_nearest(const void* x, const void* codebook, const float* cnorm, long long* ids, int M, int V, int d, void* stream);
 
+/* ---- scoring: edit-distance alignment of token sequences --------------------------------------
+ * `EditDistance` and `CountEdits` of the recipe's scorer, touchnet/bin/error_rate_zh:44-149,192-205, for P (reference,
+ * hypothesis) pairs at once: match 0, substitution / insertion / deletion 1 each, and the reference's tie rule (its
+ * backpointer is updated in the order diagonal, deletion, insertion, each with `>=`): the insertion arc wins if it is at
+ * least as good as both others, otherwise the deletion arc if it is at least as good as the diagonal, otherwise the
+ * diagonal; first row insertions only, first column deletions only, backtrace from (R, H).
+ *   ref_tok  int [n_ref], hyp_tok int [n_hyp]   packed token ids
+ *   host_desc int [P][6] on the HOST            {ref_start, R, hyp_start, H, ws_base, ops_base} per pair
+ *   desc_dev int [P][6]                         device room for the table: the entry uploads it, stream-ordered
+ *   ws       unsigned [ws_words]                scratch: pair p owns tn_edit_align_ws_words(R, H) words from ws_base
+ *                                               (2 bits of direction per cell, 16 rows of a column per word, the columns
+ *                                               padded to a multiple of 64; + R words when R > 2048)
+ *   ops      unsigned char [n_ops]              0 = C, 1 = S, 2 = I, 3 = D: pair p's arcs in path order, RIGHT-aligned in
+ *                                               its R + H bytes from ops_base; the bytes to their left are not written
+ *   counts   int [P][5]                         C, S, I, D, number of arcs; the reference's score is -(S + I + D)
+ * Two launches (one wave per pair forward, one lane per pair back), no atomics, no synchronisation; deterministic.
+ * -22 before the upload and any launch unless, for every pair: 1 <= R <= 16383, 0 <= H <= 16383, the token ranges lie
+ * inside the two arrays, the workspace ranges lie inside ws_words and ascend without overlap in table order, the ops
+ * ranges lie inside n_ops without overlap; and no buffer that is used is NULL.  P == 0: 0, nothing launched.
+ * tn_edit_align_ws_words: the words of one pair, -1 for lengths outside those limits. */
+long long tn_edit_align_ws_words(int R, int H);
+int tn_edit_align(const int* ref_tok, long long n_ref, const int* hyp_tok, long long n_hyp, const int* host_desc,
+                  int* desc_dev, int P, unsigned int* ws, long long ws_words, unsigned char* ops, long long n_ops,
+                  int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,12 +106,14 @@ PROTOTYPES = {
     "tn_beam_step": [_vp] * 17 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _f, _i, _i, _vp],
     "tn_attn_block_causal_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "tn_vq_nearest": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "tn_edit_align_ws_words": [_i, _i],
+    "tn_edit_align": [_vp, _ll, _vp, _ll, _vp, _vp, _i, _vp, _ll, _vp, _ll, _vp, _vp],
 }
 _RESTYPE = {"tn_gemm_set_persistent": None, "tn_version": C.c_char_p, "tn_sumsq_multi_chunk": C.c_longlong, "tn_adamw_multi_chunk": C.c_longlong,
             "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_splitk_workspace_bytes": C.c_longlong,
             "tn_gemm_grouped_workspace_bytes": C.c_longlong, "tn_gemm_grouped_table_bytes": C.c_longlong,
             "tn_attn_decode_workspace_bytes": C.c_longlong, "tn_beam_step_workspace_bytes": C.c_longlong,
-            "tn_philox4x32_10": None}
+            "tn_edit_align_ws_words": C.c_longlong, "tn_philox4x32_10": None}
 
 # kernel-development entry points: exported by the library, deliberately NOT part of the C ABI (include/touchnet_amd.h)
 DEV_PROTOTYPES = {

@@ -1974,3 +1974,95 @@ def vq_nearest(x: torch.Tensor, codebook: torch.Tensor, cnorm: Optional[torch.Te
 def codebook_sqnorm(codebook: torch.Tensor) -> torch.Tensor:
     """fp32 |c|^2 [V] of a codebook: the per-code constant of the nearest-code distance (once per frozen codebook)."""
     return codebook.detach().float().pow(2).sum(1)
+
+
+# ===================================================================================================== scoring
+EDIT_ALIGN_MAX_LEN = 16383                      # tn_edit_align: a cost fits the 16-bit carry column, a length an int32 table
+
+
+def edit_align_tables(R, H, workspace_bytes: int = 256 << 20):
+    """The launches of a batch of pairs with reference lengths R and hypothesis lengths H (int arrays, already within the
+    kernel's limits): [(idx, desc)], idx the pairs of the launch, heaviest first by (R + 64) * ceil(max(H, 1) / 64) — the
+    forward kernel's steps of one wave —, desc the int32 [len(idx), 6] table {ref_start, R, hyp_start, H, ws_base, ops_base}
+    over tokens packed in that order; no launch's workspace exceeds `workspace_bytes`.  ValueError for a single pair above it."""
+    import numpy as np
+    R, H = np.asarray(R, dtype=np.int64), np.asarray(H, dtype=np.int64)
+    words = np.fromiter((L.edit_align_ws_words(int(r), int(h)) for r, h in zip(R, H)), dtype=np.int64, count=R.size)
+    cap = int(workspace_bytes) // 4
+    if (words > cap).any():
+        p = int(np.argmax(words > cap))
+        raise ValueError(f"edit_align: workspace_bytes = {int(workspace_bytes)} is below the {int(words[p]) * 4} bytes that pair "
+                         f"{p} ({int(R[p])} x {int(H[p])}) needs")
+    order = np.argsort(-((R + 64) * np.maximum((H + 63) // 64, 1)), kind="stable")
+    starts = lambda a: np.concatenate([[0], np.cumsum(a)[:-1]])
+    tables, first = [], 0
+    while first < R.size:
+        last, used = first, 0
+        while last < R.size and used + words[order[last]] <= cap:
+            used += words[order[last]]
+            last += 1
+        idx = order[first:last]
+        r, h, w = R[idx], H[idx], words[idx]
+        tables.append((idx, np.stack([starts(r), r, starts(h), h, starts(w), starts(r + h)], axis=1).astype(np.int32)))
+        first = last
+    return tables
+
+
+def edit_align(refs, hyps, ref_offsets=None, hyp_offsets=None, *, workspace_bytes: int = 256 << 20, device=None):
+    """Edit-distance alignment of P (reference, hypothesis) token pairs with the tie rule of the recipe's scorer
+    (touchnet/bin/error_rate_zh:44-149: insertion before deletion before the diagonal; tn_edit_align).
+
+    refs / hyps: lists of int sequences, or packed 1-D int tensors with `ref_offsets` / `hyp_offsets` [P + 1].
+    -> a list of (C, S, I, D, ops), one per pair in the input order; ops is a numpy uint8 array of the arcs in path order,
+    0 = C, 1 = S, 2 = I, 3 = D.  The score the reference prints is -(S + I + D).
+
+    The pairs go to the device heaviest first ((R + 64) * ceil(max(H, 1) / 64): the forward kernel's steps of one wave),
+    in as many launches as keep each launch's direction workspace within `workspace_bytes`; the results come back in
+    the input order.  ValueError, by name, for an empty reference, a length above 16383 and a single pair whose
+    workspace exceeds `workspace_bytes`."""
+    import numpy as np
+
+    def packed(seqs, offsets, what):
+        if offsets is None:
+            lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
+            off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            flat = [t for s in seqs for t in s]
+            tok = np.asarray(flat, dtype=np.int64) if flat else np.zeros(0, dtype=np.int64)
+        else:
+            tok = (seqs.detach().cpu().numpy() if isinstance(seqs, torch.Tensor) else np.asarray(seqs)).astype(np.int64).ravel()
+            off = (offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)).astype(np.int64)
+            if off.ndim != 1 or off.size < 1 or off[0] != 0 or off[-1] != tok.size or (np.diff(off) < 0).any():
+                raise ValueError(f"edit_align: {what}_offsets must ascend from 0 to the number of {what} tokens")
+        if tok.size and (tok.min() < -2 ** 31 or tok.max() >= 2 ** 31):
+            raise ValueError(f"edit_align: {what} token ids must fit int32")
+        return tok.astype(np.int32), off
+
+    rtok, roff = packed(refs, ref_offsets, "ref")
+    htok, hoff = packed(hyps, hyp_offsets, "hyp")
+    P = roff.size - 1
+    if hoff.size - 1 != P:
+        raise ValueError(f"edit_align: {P} references but {hoff.size - 1} hypotheses")
+    if P == 0:
+        return []
+    R, H = np.diff(roff), np.diff(hoff)
+    if (R < 1).any():
+        raise ValueError(f"edit_align: empty reference (pair {int(np.argmax(R < 1))}); the scorer skips such utterances")
+    if (R > EDIT_ALIGN_MAX_LEN).any() or (H > EDIT_ALIGN_MAX_LEN).any():
+        p = int(np.argmax((R > EDIT_ALIGN_MAX_LEN) | (H > EDIT_ALIGN_MAX_LEN)))
+        raise ValueError(f"edit_align: length over {EDIT_ALIGN_MAX_LEN} (pair {p}: reference {int(R[p])}, hypothesis {int(H[p])})")
+    tables = edit_align_tables(R, H, workspace_bytes)    # (refuses before the device is touched)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pending = []
+    for idx, desc in tables:
+        ref_l = np.concatenate([rtok[roff[i]:roff[i + 1]] for i in idx])
+        hyp_l = np.concatenate([htok[hoff[i]:hoff[i + 1]] for i in idx])
+        counts, ops = L.edit_align(torch.from_numpy(ref_l).to(dev), torch.from_numpy(hyp_l).to(dev), torch.from_numpy(desc))
+        pending.append((idx, desc, counts, ops))
+    out = [None] * P
+    for idx, desc, counts, ops in pending:       # the only synchronisation: the results' way back
+        counts, ops = counts.cpu().numpy(), ops.cpu().numpy()
+        for k, i in enumerate(idx):
+            c, s, ins, d, n = (int(v) for v in counts[k])
+            stop = int(desc[k, 5]) + int(desc[k, 1]) + int(desc[k, 3])
+            out[int(i)] = (c, s, ins, d, ops[stop - n:stop].copy())
+    return out

@@ -1144,10 +1144,51 @@ def _(x, codebook, cnorm):
     return x.new_empty(x.shape[0], dtype=torch.int64)
 
 
+# ===================================================================================================== scoring
+def edit_align_ws_words(R: int, H: int) -> int:
+    """words of tn_edit_align's workspace that one (R, H) pair needs; -1 for lengths the kernel does not take"""
+    return int(_lib().tn_edit_align_ws_words(int(R), int(H)))
+
+
+@custom_op(f"{NS}::edit_align", mutates_args=(), device_types="cuda")
+def edit_align(ref_tok: Tensor, hyp_tok: Tensor, desc: Tensor) -> Tuple[Tensor, Tensor]:
+    """Edit-distance alignment with the reference scorer's tie rule (tn_edit_align, csrc/edit_align.hip): ref_tok / hyp_tok
+    packed int32 device tokens, desc a CPU int32 [P, 6] table {ref_start, R, hyp_start, H, ws_base, ops_base} whose
+    workspace ranges ascend.  -> counts int32 [P, 5] (C, S, I, D, arcs) and ops uint8 [n_ref + n_hyp] (0 C, 1 S, 2 I, 3 D,
+    each pair's arcs right-aligned in its R + H bytes; the bytes to their left are zero).  The entry point checks the whole
+    table on the host and refuses (-22) before it launches anything."""
+    if (ref_tok.dtype != torch.int32 or hyp_tok.dtype != torch.int32 or ref_tok.dim() != 1 or hyp_tok.dim() != 1
+            or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 6 or desc.is_cuda):
+        raise _C.KernelError("edit_align: int32 device tokens ref_tok [n_ref] / hyp_tok [n_hyp], int32 CPU desc [P, 6]")
+    ref_tok, hyp_tok, desc = _c(ref_tok), _c(hyp_tok), _c(desc)
+    P, dev = desc.shape[0], ref_tok.device
+    n_ops = ref_tok.numel() + hyp_tok.numel()
+    counts = torch.empty(P, 5, dtype=torch.int32, device=dev)
+    ops = torch.zeros(n_ops, dtype=torch.uint8, device=dev)
+    if P == 0:
+        return counts, ops
+    last = desc[-1].tolist()                            # the ranges ascend, so the last pair's end is the workspace's
+    if last[4] < 0 or edit_align_ws_words(last[1], last[3]) < 0:
+        raise _C.KernelError("edit_align: 1 <= R <= 16383, 0 <= H <= 16383 and ws_base >= 0 for every pair")
+    ws_words = last[4] + edit_align_ws_words(last[1], last[3])
+    ws = torch.empty(ws_words, dtype=torch.int32, device=dev)
+    desc_dev = torch.empty(P, 6, dtype=torch.int32, device=dev)
+    _C.check(_lib().tn_edit_align(_p(ref_tok), ref_tok.numel(), _p(hyp_tok), hyp_tok.numel(),
+                                  ctypes.c_void_p(desc.data_ptr()), _p(desc_dev), P, _p(ws), ws_words, _p(ops), n_ops,
+                                  _p(counts), _cur()), "tn_edit_align")
+    return counts, ops
+
+
+@edit_align.register_fake
+def _(ref_tok, hyp_tok, desc):
+    return (ref_tok.new_empty(desc.shape[0], 5, dtype=torch.int32),
+            ref_tok.new_empty(ref_tok.numel() + hyp_tok.numel(), dtype=torch.uint8))
+
+
 OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked",
        "attn_bwd_rope", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
-       "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc")
+       "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align")
