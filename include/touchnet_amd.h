@@ -538,6 +538,43 @@ int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, i
                  int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V, int S_hist, float penalty,
                  int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty, int early_stopping, int dtype,
                  void* stream);
+/* logits_constrain: hotword biasing and forbidden sequences — transformers/generation/logits_process.py
+ *      SequenceBiasLogitsProcessor and MinNewTokensLengthLogitsProcessor, the `sequence_bias` and `min_new_tokens` of a
+ *      generation_config.json (touchnet/models/qwen2_audio/inference_qwen2_audio.py hands that file to model.generate()).
+ *      hist int32 [R, S_hist], hist_len / prompt_len int32 [R] (prompt_len may be NULL when min_new == 0).  Logits row
+ *      `row_in` of R_in belongs to history row (row_in / K_in) K + row_in % K_in (greedy and sampling: K = K_in = 1; beam
+ *      search: K_in = 1 right after the prefill, K afterwards).
+ *      The table: seq_off int32 [n_seq + 1] and seq_ids int32 [n_ids] (the sequences' ids, packed), seq_bias fp32 [n_seq]
+ *      (finite or -inf); grp_off int32 [n_grp + 1], grp_tok int32 [n_grp], grp_eos int32 [n_grp]: the sequences grouped by
+ *      their last id, grp_tok ascending, within a group the length-1 sequence first and then the longer ones in the order
+ *      of the caller's dict — HF's order of summation; grp_eos marks eos ids (such a group may be empty).
+ *      With n = hist_len[r]: a sequence of length L matches when L == 1, or L <= n and hist[r, n-L+1 .. n-1] equals its
+ *      first L - 1 ids.  total(t) = the fp32 sum of the matching biases of t's group in listed order, each addition rounded
+ *      on its own; -inf for an eos id while n - prompt_len[r] < min_new.
+ *      mode 0 (apply): logits [R_in, V] (`dtype`), logits[row_in, t] = T(fp32(logits[row_in, t]) + total(t)) for every t
+ *      with a matching sequence or under the eos rule; no other element is written.  mode 1 (emit): logits is not read
+ *      (NULL allowed); edit_ids int32 [R_in, n_grp] = t where apply would write, else -1 - t; edit_val fp32 [R_in, n_grp] =
+ *      total(t); edit_cnt int32 [R_in] = the number of ids apply would write — the list tn_beam_step_edits takes.
+ *      Every id has one writer: no atomics, bit-identical repeats.  Finished rows and rows of done utterances are edited
+ *      like any other (the step kernels ignore them).  Limits: n_seq <= 16384, every sequence 1 .. 64 ids, V <= 262144;
+ *      a sequence outside them or a group id outside [0, V) is ignored by the kernel (the Python plan refuses it).
+ *      -22 before any launch for NULL or misaligned pointers, counts outside those limits, n_grp outside [1, n_seq + 8],
+ *      K_in not 1 or K, R_in % K_in != 0, min_new < 0, mode outside [0, 1]. */
+int tn_logits_constrain(void* logits, const int* hist, const int* hist_len, const int* prompt_len, const int* seq_off,
+                        const int* seq_ids, const float* seq_bias, const int* grp_off, const int* grp_tok,
+                        const int* grp_eos, int* edit_ids, float* edit_val, int* edit_cnt, int R_in, int K, int K_in, int V,
+                        int S_hist, int n_seq, int n_ids, int n_grp, int min_new, int mode, int dtype, void* stream);
+/* beam_step_edits: beam_step with the edit list of logits_constrain's emit mode (edit_ids / edit_val [B * K_in, n_edit],
+ *      edit_cnt [B * K_in]): lp[t] = log_softmax(..)[t] + edit_val of t's slot for every slot with edit_ids >= 0, BEFORE
+ *      the repetition penalty — HF's processor order on the log-probabilities (editing the logits instead would move the
+ *      normaliser).  All three NULL: exactly beam_step.  -22 as for beam_step, and for a partly NULL or misaligned list or
+ *      n_edit < 1. */
+int tn_beam_step_edits(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score,
+                       int* fin_ids, int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done,
+                       int* n_unfinished, int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V,
+                       int S_hist, float penalty, int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty,
+                       int early_stopping, int dtype, const int* edit_ids, const float* edit_val, const int* edit_cnt,
+                       int n_edit, void* stream);
 
 /* ---- Kimi-Audio's speech tokenizer (GLM-4-voice WhisperVQEncoder, touchnet/models/kimi_audio/modeling_kimi_audio.py:140-319,
  *      run by MoonshotKimiaForCausalLM.prepare_audio_input_embs under no_grad, :957-963).  Forward only: it is frozen.

@@ -6,6 +6,7 @@ generate() (sdpa, same knobs, same weights).  Prints one JSON object per measure
     python scripts/decode_bench.py --qwen2-audio-7b [--batch 12]
     python scripts/decode_bench.py --num-beams 4 [--batch 12]
     python scripts/decode_bench.py --kimi-audio-7b [--batch 12]
+    python scripts/decode_bench.py --hotwords 1024 [--batch 12]
 
 --qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
 per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
@@ -21,6 +22,10 @@ of 300 rows, eos unreachable): tn_kimi_text_step per call (µs) in greedy and to
 tn_sample_step's greedy mode beside it at the same shape, prefill ms, and ms per decode step (decode_logits on the row the
 step kernel wrote + tn_kimi_text_step) against the same step with the row built by torch (history gather, two embedding
 lookups, add) — the launches the fused write removes.
+
+--hotwords N: tn_logits_constrain with a table of N phrases x 4 prefixes on bf16 logits [B, 156 032]: per call (µs, apply
+and emit mode), its share of the Qwen2-Audio-7B sampled decode step timed in the same run (with an A/B of the whole step
+with and without the plan), and tn_beam_step with and without the edit list (K 4).
 
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
@@ -367,6 +372,88 @@ def bench_beams(K, B, steps=24, iters=100):
     return rows
 
 
+def bench_hotwords(N, B, K=4, steps=32, iters=200):
+    """tn_logits_constrain with a table of N phrases x 4 prefixes (generation.hotword_bias) at Qwen2-Audio-7B's width:
+    alone on bf16 logits [B, 156 032] (apply and emit mode), inside the sampled decode step (decode_logits + constrain +
+    tn_sample_step against the same step without a plan, A/B twice in one process), and the beam step with and without
+    the edit list.  B phrases continue a row's history, so every row has one sequence of each length that matches."""
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    V, P = 156032, 300
+    g = torch.Generator().manual_seed(0)
+    prompts = G.Prompts([torch.randint(0, 150000, (P,), generator=g) for _ in range(B)])
+    phrases = [p[-3:].tolist() + [int(torch.randint(0, V, (1,), generator=g))] for p in prompts.input_ids]
+    while len(phrases) < N:
+        phrases.append(torch.randint(0, V, (4,), generator=g).tolist())
+    sb = G.hotword_bias(phrases[:N], 2.0)
+    plan = G.ConstraintPlan.build(sb, 0, [], V, DEV)
+    rows = [dict(table="hotwords", phrases=N, sequences=len(sb), groups=int(plan.grp_tok.shape[0]))]
+    text = DecoderConfig.from_dict(dict(model_type="qwen2", hidden_size=4096, intermediate_size=11008, num_attention_heads=32,
+                                        num_key_value_heads=32, head_dim=128, num_hidden_layers=32, vocab_size=V,
+                                        rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=False,
+                                        initializer_range=0.02, eos_token_id=151643, pad_token_id=151643))
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        lm = PackedCausalLM(text)
+    lm.post_init()
+    lm = lm.to(torch.bfloat16).eval()
+    keys = torch.arange(B, device=DEV)
+    cache = G.KVCache.allocate(32, B, P + 4 * steps + 8, 32, 128, DEV)
+    sample = lambda lg: F.sample_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
+                                      1.1, True, 0.7, 50, 0.9, 1, [151643, 151645], 151643, row_key=keys)
+    with torch.no_grad():
+        logits = G._prefill(lm, None, prompts, cache, DEV)
+        # the kernel alone, at the state right after the prefill (the matching phrases match); the logits drift by the
+        # bias per call, which the kernel's time does not depend on
+        edits = plan.edit_buffers(B)
+        F.constrain_logits_(logits, cache.hist, cache.hist_len, plan)
+        us_apply = _events_time(lambda: F.constrain_logits_(logits, cache.hist, cache.hist_len, plan), iters)
+        us_emit = _events_time(lambda: F.constrain_logits_(logits, cache.hist, cache.hist_len, plan, edits=edits), iters)
+        matched = int(edits[2].sum())
+        sample(logits)
+
+        def step_plain():
+            sample(G.decode_logits(lm, cache))
+
+        def step_plan():
+            lg = G.decode_logits(lm, cache)
+            F.constrain_logits_(lg, cache.hist, cache.hist_len, plan)
+            sample(lg)
+        step_plain(), step_plan()
+        ab = [[_events_time(step_plain, steps - 2) / 1e3, _events_time(step_plan, steps - 2) / 1e3] for _ in range(2)]
+    ms = min(a for a, _ in ab)
+    rows.append(dict(kernel="tn_logits_constrain", B=B, V=V, sequences=len(sb), apply_us=round(us_apply, 2),
+                     emit_us=round(us_emit, 2), ids_edited_per_call=matched))
+    rows.append(dict(e2e="qwen2_audio_7b_decode_step", B=B, ms_per_step_without_plan=round(ms, 3),
+                     ms_per_step_with_plan=round(min(b for _, b in ab), 3),
+                     ab_runs_ms=[[round(a, 3), round(b, 3)] for a, b in ab],
+                     constrain_share_of_step=round(us_apply / (ms * 1e3), 4)))
+    del cache
+    torch.cuda.empty_cache()
+    # beam search: the step with and without the edit list, on fixed logits at the state after the prefill
+    n_new = 4 * iters + 16
+    st = G.BeamState.allocate(32, B, K, P + n_new, 32, 128, DEV)
+    kw = dict(penalty=1.1, ngram=0, eos=[-1, -2], n_new=n_new, length_penalty=1.0, early_stopping=False)
+    edits = plan.edit_buffers(B * K)
+    with torch.no_grad():
+        F.beam_step(G._prefill(lm, None, prompts, st, DEV, row_stride=K), st, **kw)
+        logits = G.decode_logits(lm, st, table=st.src)
+
+        def with_list():
+            F.constrain_logits_(logits, st.hist, st.hist_len, plan, num_beams=K, edits=edits)
+            F.beam_step(logits, st, edits=edits, **kw)
+        F.beam_step(logits, st, **kw), with_list()
+        ab = [[_events_time(lambda: F.beam_step(logits, st, **kw), iters), _events_time(with_list, iters)]
+              for _ in range(2)]
+        us_emit = _events_time(lambda: F.constrain_logits_(logits, st.hist, st.hist_len, plan, num_beams=K, edits=edits),
+                               iters)
+    rows.append(dict(kernel="tn_beam_step", B=B, K=K, V=V, beam_step_us=round(min(a for a, _ in ab), 2),
+                     emit_plus_beam_step_edits_us=round(min(b for _, b in ab), 2), emit_alone_us=round(us_emit, 2),
+                     ab_runs_us=[[round(a, 2), round(b, 2)] for a, b in ab]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -377,12 +464,17 @@ def main():
     ap.add_argument("--qwen2-audio-7b", action="store_true")
     ap.add_argument("--num-beams", type=int, default=0, help="K > 1: the beam-search measurements")
     ap.add_argument("--kimi-audio-7b", action="store_true")
+    ap.add_argument("--hotwords", type=int, default=0, help="N > 0: tn_logits_constrain with N phrases x 4 prefixes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.hotwords > 0:
+        for r in bench_hotwords(a.hotwords, a.batch):
+            print(json.dumps(r), flush=True)
+        return
     if a.num_beams > 1:
         for r in bench_beams(a.num_beams, a.batch):
             print(json.dumps(r), flush=True)

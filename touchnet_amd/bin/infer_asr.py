@@ -13,6 +13,11 @@ than the data config's `audio_resample_rate`, 16 kHz by default, are resampled o
 OUT/part_{i+1}_of_{n}, one JSON line per utterance: {"label": the input line, "predict_ids": [...], "predict": text} —
 "predict" only when CKPT_DIR has a tokenizer.  One GPU per process; `--shard_index / --num_shards` split the list
 without collectives.
+Hotwords and forbidden words: `--hotwords FILE` (one phrase per line, tokenised with the checkpoint's tokenizer without
+special tokens; every token along a phrase gets `--hotword_bias`, default 2.0 — a starting point that nobody has tuned —
+once the tokens before it were emitted), `--forbid_words FILE` (phrases whose token sequence can never be completed) and
+`--min_new_tokens N` (no eos before N tokens); see generation.hotword_bias and DESIGN 9.6.  A phrase file needs the
+tokenizer: without one in CKPT_DIR the command refuses.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import numpy as np
 import torch
 
 from touchnet_amd.data import functions as stages
-from touchnet_amd.generation import GenerationConfig
+from touchnet_amd.generation import GenerationConfig, add_constraint_arguments, constraints_from_args
 from touchnet_amd.models.backend import ops
 from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
 from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
@@ -134,6 +139,7 @@ def main(argv=None):
     ap.add_argument("--early_stopping", default="false", choices=["true", "false", "never"])
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
+    add_constraint_arguments(ap)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
@@ -150,7 +156,8 @@ def main(argv=None):
     cfg = GenerationConfig(max_new_tokens=args.max_new_tokens, repetition_penalty=args.repetition_penalty,
                            no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
                            length_penalty=args.length_penalty,
-                           early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"))
+                           early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
+                           sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0)
     cfg.check_beams()
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f"part_{args.shard_index + 1}_of_{args.num_shards}")

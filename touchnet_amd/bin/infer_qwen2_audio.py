@@ -16,6 +16,11 @@ prompt exceeds --max_length is skipped; the budget is max_length minus the longe
 sets max_new_tokens.  Output: OUT/part_{i+1}_of_{n}, one JSON line per utterance, {"label": the input line, "predict":
 text}.  The draws of an utterance are keyed by its line number in the data list, so it decodes the same whatever its
 batch or shard.
+Hotwords and forbidden words: `--hotwords FILE` (one phrase per line, tokenised with the checkpoint's tokenizer without
+special tokens; every token along a phrase gets `--hotword_bias`, default 2.0 — a starting point that nobody has tuned —
+once the tokens before it were emitted), `--forbid_words FILE` (phrases whose token sequence can never be completed) and
+`--min_new_tokens N` (no eos before N tokens); see generation.hotword_bias and DESIGN 9.6.  They merge with the `sequence_bias` of
+generation_config.json: the file's entries first, then the hotwords, then the forbidden phrases.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import GenerationConfig
+from touchnet_amd.generation import GenerationConfig, add_constraint_arguments, constraints_from_args
 from touchnet_amd.models.qwen2_audio import Qwen2AudioConfig, Qwen2AudioPackedForConditionalGeneration
 from touchnet_amd.models.qwen2_audio.inference_qwen2_audio import build_prompts, transcribe, valid_frames
 from touchnet_amd.models.qwen2_audio.processing_qwen2_audio import DEFAULT_INSTRUCT
@@ -88,6 +93,7 @@ def main(argv=None):
     ap.add_argument("--early_stopping", default=None, choices=["true", "false", "never"])
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
+    add_constraint_arguments(ap)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_qwen2_audio needs the MI355X (there is no CPU path)")
@@ -106,6 +112,9 @@ def main(argv=None):
     cfg = GenerationConfig.from_hf(gen_file if os.path.exists(gen_file) else {}, **over)
     if args.max_new_tokens is not None:
         cfg.max_new_tokens = args.max_new_tokens
+    cfg.sequence_bias = constraints_from_args(args, tokenizer, cfg.sequence_bias)
+    if args.min_new_tokens is not None:
+        cfg.min_new_tokens = args.min_new_tokens
     with open(args.data_list) as f:
         items = [(n, json.loads(line)) for n, line in enumerate(f) if line.strip()]
     items = items[args.shard_index::args.num_shards]

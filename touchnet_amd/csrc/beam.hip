@@ -31,6 +31,11 @@
 // sorted (acc, id) pairs go to a workspace of 32 pairs per row: no [R, V] intermediate.  beam_book_kernel, one workgroup per
 // utterance: thread 0 merges the K_in sorted lists and does the bookkeeping in LDS, then every thread owns columns of the
 // history, the table and the finished set, reads the K entries of its column and writes them permuted (no second buffer).
+//
+// tn_beam_step_edits: the same two kernels with the per-row edit list of tn_logits_constrain (constrain.hip: sequence_bias
+// and min_new_tokens).  HF's SequenceBiasLogitsProcessor is the first of the processors, so lp = log_softmax(..) + total,
+// then the penalty, then the ban.  beam_topk_kernel is a template on kEdits: without a list the instantiation that runs is
+// the one tn_beam_step always ran.
 #include "history_sets.h"
 
 namespace tn {
@@ -60,27 +65,84 @@ __device__ __forceinline__ unsigned long long make_key(float v, int idx) {
 }
 __device__ __forceinline__ unsigned long long max_u64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
-// acc of candidate i: HF's arithmetic, every operation rounded on its own
-template <typename T>
+// The optional per-row edit list of tn_logits_constrain's emit mode (constrain.hip): n slots in ascending order of their
+// distinct ids; ids[s] >= 0: val[s] is added to the log-probability of that id; ids[s] = -1 - id: the slot is idle this
+// step; cnt: the active slots of the row (0: the index below stays empty).
+struct Edits {
+  const int* ids;
+  const float* val;
+  const int* cnt;
+  int n;
+};
+
+// The slots' ids as a bitmap of V bits (`edited`, active or idle alike) and, per word, the number of slots with a lower id
+// (`rank`): the slot of id i is rank[i >> 5] + popc(the word's bits below i) — no search, no dependent loads.  Called by
+// every thread of the workgroup (it synchronises).
+__device__ __forceinline__ void fill_edit_index(uint32_t* edited, uint16_t* rank, uint32_t* wave_total,
+                                                const int* __restrict__ ids, int n, int V, int tid) {
+  const int words = (V + 31) / 32;
+  for (int w = tid; w < words; w += kThreads) edited[w] = 0u;
+  __syncthreads();
+  for (int s = tid; s < n; s += kThreads) {
+    const int e = ids[s], t = e >= 0 ? e : -1 - e;
+    if (t >= 0 && t < V) atomicOr(&edited[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+  const int per = (words + kThreads - 1) / kThreads, w0 = tid * per, w1 = min(w0 + per, words);
+  int own = 0;
+  for (int w = w0; w < w1; ++w) own += __popc(edited[w]);
+  int incl = own;
+  const int lane = tid & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += up;
+  }
+  if (lane == 63) wave_total[tid >> 6] = (uint32_t)incl;
+  __syncthreads();
+  int before = incl - own;
+  for (int i = 0; i < (tid >> 6); ++i) before += (int)wave_total[i];
+  for (int w = w0; w < w1; ++w) {
+    rank[w] = (uint16_t)before;
+    before += __popc(edited[w]);
+  }
+  __syncthreads();
+}
+
+// acc of candidate i: HF's arithmetic, every operation rounded on its own.  kEdits: SequenceBiasLogitsProcessor comes
+// first in HF's processor list, so the total is added to the log-probability before the penalty divides or multiplies.
+template <typename T, bool kEdits>
 __device__ __forceinline__ float candidate(const T* __restrict__ row, int i, float mx, float lse, const uint32_t* seen,
-                                           const uint32_t* banned, float penalty, float base) {
+                                           const uint32_t* banned, float penalty, float base, const uint32_t* edited,
+                                           const uint16_t* rank, const int* __restrict__ e_ids,
+                                           const float* __restrict__ e_val) {
 #pragma clang fp contract(off)
   float lp = (Elem<T>::ld(row + i) - mx) - lse;
   const uint32_t bit = 1u << (i & 31);
+  if (kEdits) {
+    const uint32_t word = edited[i >> 5];
+    if (word & bit) {
+      const int slot = rank[i >> 5] + __popc(word & (bit - 1u));
+      if (e_ids[slot] >= 0) lp = lp + e_val[slot];
+    }
+  }
   if (seen[i >> 5] & bit) lp = lp < 0.f ? lp * penalty : lp / penalty;
   if (banned[i >> 5] & bit) lp = -INFINITY;
   return (lp + base) + 0.f;                                  // (+ 0: no -0 among the keys)
 }
 
-template <typename T>
+template <typename T, bool kEdits>
 __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict__ logits, const int* __restrict__ hist,
                                                               const int* __restrict__ hist_len,
                                                               const float* __restrict__ run_score,
                                                               const int* __restrict__ done, float* __restrict__ ws_val,
                                                               int* __restrict__ ws_idx, int K, int K_in, int V, int S_hist,
-                                                              float penalty, int ngram, int keep) {
+                                                              float penalty, int ngram, int keep, Edits edits) {
   __shared__ uint32_t seen[histsets::kWords];
   __shared__ uint32_t banned[histsets::kWords];
+  __shared__ uint32_t edited[kEdits ? histsets::kWords : 1];   // (with the two above and `rank`: 112 KB of the CU's 160,
+  __shared__ uint16_t rank[kEdits ? histsets::kWords : 1];     // so one workgroup per CU; a step launches at most B K)
+  __shared__ uint32_t wave_total[kThreads / 64];
   __shared__ float red[kThreads / 64];
   __shared__ unsigned long long red_key[kThreads / 64];
   const int row_in = blockIdx.x, tid = threadIdx.x;
@@ -88,6 +150,9 @@ __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict
   if (done[b] != 0) return;
   const int len = min(max(hist_len[r], 0), S_hist);
   histsets::fill(seen, banned, hist + (size_t)r * S_hist, len, V, penalty != 1.f, ngram, tid, kThreads);
+  const int* __restrict__ e_ids = kEdits ? edits.ids + (size_t)row_in * edits.n : nullptr;
+  const float* __restrict__ e_val = kEdits ? edits.val + (size_t)row_in * edits.n : nullptr;
+  if (kEdits) fill_edit_index(edited, rank, wave_total, e_ids, edits.cnt[row_in] > 0 ? edits.n : 0, V, tid);
 
   const T* row = logits + (size_t)row_in * V;
   float mx = -INFINITY;
@@ -101,7 +166,7 @@ __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict
 
   unsigned long long best = 0ull;                            // (no candidate: every real key is larger)
   for (int i = tid; i < V; i += kThreads)
-    best = max_u64(best, make_key(candidate<T>(row, i, mx, lse, seen, banned, penalty, base), i));
+    best = max_u64(best, make_key(candidate<T, kEdits>(row, i, mx, lse, seen, banned, penalty, base, edited, rank, e_ids, e_val), i));
 
   for (int round = 0; round < keep; ++round) {
     unsigned long long w = best;
@@ -125,7 +190,7 @@ __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict
     if (best == top) {                                       // the owner: its next best below the one just taken
       unsigned long long nb = 0ull;
       for (int i = tid; i < V; i += kThreads) {
-        const unsigned long long k = make_key(candidate<T>(row, i, mx, lse, seen, banned, penalty, base), i);
+        const unsigned long long k = make_key(candidate<T, kEdits>(row, i, mx, lse, seen, banned, penalty, base, edited, rank, e_ids, e_val), i);
         if (k < top) nb = max_u64(nb, k);
       }
       best = nb;
@@ -273,11 +338,11 @@ long long tn_beam_step_workspace_bytes(int B, int K) {
   return (long long)B * K * tn::beam::kMaxKeep * 8;
 }
 
-int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score, int* fin_ids,
-                 int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done, int* n_unfinished,
-                 int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V, int S_hist, float penalty,
-                 int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty, int early_stopping, int dtype,
-                 void* stream) {
+static int beam_step_launch(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score,
+                            int* fin_ids, int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done,
+                            int* n_unfinished, int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V,
+                            int S_hist, float penalty, int ngram, const int* eos_ids, int n_eos, int n_new,
+                            float length_penalty, int early_stopping, int dtype, tn::beam::Edits edits, void* stream) {
   using namespace tn::beam;
   const void* ptrs[] = {logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen,
                         unsat, done, n_unfinished, out_ids, out_parent, workspace};
@@ -297,12 +362,18 @@ int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, i
   float* ws_val = (float*)workspace;
   int* ws_idx = (int*)workspace + (size_t)B * K * kMaxKeep;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0)
-    hipLaunchKernelGGL(beam_topk_kernel<float>, dim3(B * K_in), dim3(kThreads), 0, st, (const float*)logits, hist,
-                       hist_len, run_score, done, ws_val, ws_idx, K, K_in, V, S_hist, penalty, ngram, keep);
-  else
-    hipLaunchKernelGGL(beam_topk_kernel<tn::bf16_t>, dim3(B * K_in), dim3(kThreads), 0, st, (const tn::bf16_t*)logits,
-                       hist, hist_len, run_score, done, ws_val, ws_idx, K, K_in, V, S_hist, penalty, ngram, keep);
+  const bool with_edits = edits.ids != nullptr;
+#define TN_BEAM_TOPK(T, E)                                                                                              \
+  hipLaunchKernelGGL((beam_topk_kernel<T, E>), dim3(B * K_in), dim3(kThreads), 0, st, (const T*)logits, hist, hist_len,  \
+                     run_score, done, ws_val, ws_idx, K, K_in, V, S_hist, penalty, ngram, keep, edits)
+  if (dtype == 0) {
+    if (with_edits) TN_BEAM_TOPK(float, true);
+    else TN_BEAM_TOPK(float, false);
+  } else {
+    if (with_edits) TN_BEAM_TOPK(tn::bf16_t, true);
+    else TN_BEAM_TOPK(tn::bf16_t, false);
+  }
+#undef TN_BEAM_TOPK
   TN_LAUNCH_CHECK();
   hipLaunchKernelGGL(beam_book_kernel, dim3(B), dim3(kBookThreads), 0, st, (const float*)ws_val, (const int*)ws_idx, hist,
                      hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat, done,
@@ -310,6 +381,35 @@ int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, i
                      early_stopping);
   TN_LAUNCH_CHECK();
   return TN_OK;
+}
+
+int tn_beam_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score, int* fin_ids,
+                 int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done, int* n_unfinished,
+                 int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V, int S_hist, float penalty,
+                 int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty, int early_stopping, int dtype,
+                 void* stream) {
+  return beam_step_launch(logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen,
+                          unsat, done, n_unfinished, out_ids, out_parent, workspace, B, K, K_in, V, S_hist, penalty, ngram,
+                          eos_ids, n_eos, n_new, length_penalty, early_stopping, dtype,
+                          tn::beam::Edits{nullptr, nullptr, nullptr, 0}, stream);
+}
+
+int tn_beam_step_edits(const void* logits, int* hist, int* hist_len, int* cache_len, int* src, float* run_score,
+                       int* fin_ids, int* fin_len, float* fin_score, int* fin_flag, int* gen, int* unsat, int* done,
+                       int* n_unfinished, int* out_ids, int* out_parent, void* workspace, int B, int K, int K_in, int V,
+                       int S_hist, float penalty, int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty,
+                       int early_stopping, int dtype, const int* edit_ids, const float* edit_val, const int* edit_cnt,
+                       int n_edit, void* stream) {
+  tn::beam::Edits edits{nullptr, nullptr, nullptr, 0};
+  if (edit_ids != nullptr || edit_val != nullptr || edit_cnt != nullptr) {
+    if (edit_ids == nullptr || edit_val == nullptr || edit_cnt == nullptr || n_edit < 1 ||
+        (((uintptr_t)edit_ids | (uintptr_t)edit_val | (uintptr_t)edit_cnt) & 3))
+      return TN_EINVAL;
+    edits = tn::beam::Edits{edit_ids, edit_val, edit_cnt, n_edit};
+  }
+  return beam_step_launch(logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen,
+                          unsat, done, n_unfinished, out_ids, out_parent, workspace, B, K, K_in, V, S_hist, penalty, ngram,
+                          eos_ids, n_eos, n_new, length_penalty, early_stopping, dtype, edits, stream);
 }
 
 }  // extern "C"

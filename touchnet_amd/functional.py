@@ -1917,20 +1917,46 @@ def attn_decode_beam(q, k_new, v_new, k_cache, v_cache, cache_len, src, scale: O
 EARLY_STOPPING_CODE = {False: 0, True: 1, "never": 2}
 
 
+def constrain_logits_(logits, hist, hist_len, plan, prompt_len=None, num_beams: int = 1, edits=None) -> None:
+    """`sequence_bias` (hotword boosts, forbidden sequences at -inf) and `min_new_tokens` of HF generate() on logits
+    [R_in, V], matched against the device history `hist` [R, S_hist] / `hist_len` [R] (tn_logits_constrain).  `plan`: a
+    `generation.ConstraintPlan` (its table tensors, `min_new`, `vocab`); `prompt_len` int32 [R] is needed when
+    plan.min_new > 0.  Without `edits` the logits are edited in place, in their own dtype: logits[t] = T(fp32(logits[t]) +
+    total) — for fp32 logits HF's arithmetic, for bf16 logits the sum rounded to bf16 — and only at ids that a matching
+    sequence or the eos rule names.  With `edits` = plan.edit_buffers(rows) the logits are left alone and the per-row edit
+    list is written for `beam_step(..., edits=edits)`, which adds it to the log-probabilities (`num_beams`: the beam row
+    layout, R_in = R / num_beams right after the prefill).  At most 16384 sequences of at most 64 ids each."""
+    if logits.shape[1] < plan.vocab:
+        raise ValueError(f"constrain_logits_: the plan was checked against a vocabulary of {plan.vocab} ids, the logits have "
+                         f"{logits.shape[1]}")
+    e_ids, e_val, e_cnt = edits if edits is not None else (None, None, None)
+    L.constrain_logits_(logits, hist, hist_len, prompt_len, plan.seq_off, plan.seq_ids, plan.seq_bias, plan.grp_off,
+                        plan.grp_tok, plan.grp_eos, e_ids, e_val, e_cnt, int(num_beams), int(plan.min_new))
+
+
 def beam_step(logits, state, penalty: float = 1.0, ngram: int = 0, eos=(), n_new: int = 1, length_penalty: float = 1.0,
-              early_stopping=False) -> None:
+              early_stopping=False, edits=None) -> None:
     """One step of HF's beam search (`_beam_search` of transformers) on the device: log_softmax, repetition penalty and
     n-gram ban on the log-probabilities, the top continuations of every utterance, running beams, finished set, early-stop
     heuristic, and the reordering of history and ancestry table by parent.  `state`: an object with the tensors of
     `generation.BeamState` (num_beams, hist, hist_len, cache_len, src, run_score, fin_*, gen, unsat, done, n_unfinished,
-    out_ids, out_parent).  logits [B, V] on the first step (one live row per utterance), [B * num_beams, V] afterwards."""
+    out_ids, out_parent).  logits [B, V] on the first step (one live row per utterance), [B * num_beams, V] afterwards.
+    `edits`: the (edit_ids, edit_val, edit_cnt) that `constrain_logits_` wrote for these logits rows; the totals are added
+    to the log-probabilities before the repetition penalty (HF's processor order)."""
     if early_stopping not in (True, False, "never"):
         raise ValueError(f"early_stopping must be True, False or 'never' (got {early_stopping!r})")
     eos = [int(e) for e in ([eos] if isinstance(eos, int) else eos)]
     s = state
-    L.beam_step_(logits, s.hist, s.hist_len, s.cache_len, s.src, s.run_score, s.fin_ids, s.fin_len, s.fin_score,
-                 s.fin_flag, s.gen, s.unsat, s.done, s.n_unfinished, s.out_ids, s.out_parent, int(s.num_beams),
-                 float(penalty), int(ngram), eos, int(n_new), float(length_penalty), EARLY_STOPPING_CODE[early_stopping])
+    if edits is None:
+        L.beam_step_(logits, s.hist, s.hist_len, s.cache_len, s.src, s.run_score, s.fin_ids, s.fin_len, s.fin_score,
+                     s.fin_flag, s.gen, s.unsat, s.done, s.n_unfinished, s.out_ids, s.out_parent, int(s.num_beams),
+                     float(penalty), int(ngram), eos, int(n_new), float(length_penalty),
+                     EARLY_STOPPING_CODE[early_stopping])
+    else:
+        L.beam_step_edits_(logits, s.hist, s.hist_len, s.cache_len, s.src, s.run_score, s.fin_ids, s.fin_len, s.fin_score,
+                           s.fin_flag, s.gen, s.unsat, s.done, s.n_unfinished, s.out_ids, s.out_parent, *edits,
+                           int(s.num_beams), float(penalty), int(ngram), eos, int(n_new), float(length_penalty),
+                           EARLY_STOPPING_CODE[early_stopping])
 
 
 # ------------------------------------------------------------------------------------ Kimi-Audio speech tokenizer (frozen)

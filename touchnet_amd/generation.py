@@ -17,6 +17,14 @@ Sampling (do_sample, several eos ids: what a Qwen2-Audio checkpoint's generation
 `GenerationConfig.from_hf`) runs the same loop with tn_sample_step in place of tn_greedy_step.  The caches start at
 `longest prompt + min(new tokens, cache_chunk)` rows and double when the host's step counter reaches their capacity (the
 host knows the step count: no sync), so a max_length of 70 000 does not allocate 70 000 rows per layer up front.
+
+`sequence_bias` (hotword boosts; -inf forbids a sequence) and `min_new_tokens` — transformers' SequenceBiasLogitsProcessor
+and MinNewTokensLengthLogitsProcessor — are matched against the device history by tn_logits_constrain, one launch right before
+the step kernel and only when the config carries them (`ConstraintPlan`, built once per call).  Greedy and sampling: the logits
+are edited in place, logit[t] = T(fp32(logit[t]) + total) in the logits' own dtype (bf16 logits: the sum is rounded to bf16;
+fp32: HF's arithmetic), before penalty, n-gram ban and the warpers: HF's order.  Beam search: the kernel emits the edits and
+tn_beam_step_edits adds them to the log-probabilities, after log_softmax and before the penalty.  At most MAX_BIAS_SEQS
+sequences of at most MAX_BIAS_LEN ids.
 """
 from __future__ import annotations
 
@@ -34,16 +42,138 @@ from . import functional as F
 # generation_config.json keys this path does not implement, with the value that leaves them inert (HF's defaults)
 _UNSUPPORTED = {"num_beam_groups": 1, "penalty_alpha": None, "typical_p": 1.0, "min_p": None,
                 "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "top_h": None, "bad_words_ids": None, "force_words_ids": None,
-                "sequence_bias": None, "constraints": None, "min_length": 0, "min_new_tokens": None,
-                "suppress_tokens": None, "begin_suppress_tokens": None, "forced_bos_token_id": None,
-                "forced_eos_token_id": None, "encoder_repetition_penalty": 1.0, "encoder_no_repeat_ngram_size": 0,
-                "exponential_decay_length_penalty": None, "guidance_scale": None, "watermarking_config": None,
-                "renormalize_logits": False, "num_return_sequences": 1, "assistant_model": None,
+                "constraints": None, "min_length": 0, "suppress_tokens": None, "begin_suppress_tokens": None,
+                "forced_bos_token_id": None, "forced_eos_token_id": None, "encoder_repetition_penalty": 1.0,
+                "encoder_no_repeat_ngram_size": 0, "exponential_decay_length_penalty": None, "guidance_scale": None,
+                "watermarking_config": None, "renormalize_logits": False, "num_return_sequences": 1, "assistant_model": None,
                 "prompt_lookup_num_tokens": None, "max_time": None, "stop_strings": None, "dola_layers": None,
                 "diversity_penalty": 0.0}
 
 
 MAX_BEAMS, MAX_BEAM_EOS = 8, 3             # tn_beam_step's limits
+MAX_BIAS_SEQS, MAX_BIAS_LEN = 16384, 64    # tn_logits_constrain's limits: biased sequences, ids per sequence
+
+# what replaces the two refused keys that forbid tokens (NoBadWordsLogitsProcessor is a SequenceBiasLogitsProcessor at -inf)
+_FORBID_HINT = {k: "; forbid token sequences with sequence_bias instead: [[ids], -inf] per sequence, which is what "
+                   "NoBadWordsLogitsProcessor reduces to" for k in ("bad_words_ids", "suppress_tokens")}
+
+
+def normalize_sequence_bias(value) -> Optional[dict]:
+    """`sequence_bias` as a dict {tuple(ids): float}, from that dict or from HF's list form [[ids], bias].  Duplicates
+    resolve as a Python dict resolves them: the later value wins and the first position is kept.  Refused: an empty
+    sequence, ids that are no non-negative integers, more than MAX_BIAS_SEQS sequences or MAX_BIAS_LEN ids in one, and
+    biases of +inf or NaN (-inf forbids the sequence)."""
+    if value is None or (isinstance(value, (list, tuple, dict)) and len(value) == 0):
+        return None
+    if isinstance(value, dict):
+        pairs = list(value.items())
+    elif isinstance(value, (list, tuple)):
+        if any(not isinstance(e, (list, tuple)) or len(e) != 2 for e in value):
+            raise ValueError("generation config: sequence_bias must be a dict {tuple(ids): bias} or a list of [[ids], bias]")
+        pairs = [(e[0], e[1]) for e in value]
+    else:
+        raise ValueError("generation config: sequence_bias must be a dict {tuple(ids): bias} or a list of [[ids], bias]")
+    out = {}
+    for ids, bias in pairs:
+        if isinstance(ids, (int, str)) or not hasattr(ids, "__len__"):
+            raise ValueError(f"generation config: sequence_bias key {ids!r} must be a sequence of token ids")
+        if len(ids) == 0:
+            raise ValueError("generation config: sequence_bias holds an empty sequence")
+        if len(ids) > MAX_BIAS_LEN:
+            raise ValueError(f"generation config: a biased sequence of {len(ids)} ids exceeds {MAX_BIAS_LEN}")
+        if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in ids):
+            raise ValueError(f"generation config: sequence_bias ids must be non-negative integers (got {list(ids)!r})")
+        if isinstance(bias, bool) or not isinstance(bias, (int, float)):
+            raise ValueError(f"generation config: sequence_bias value {bias!r} must be a number")
+        b = float(bias)
+        if b != b or b == float("inf"):
+            raise ValueError(f"generation config: sequence_bias value {b} must be finite or -inf")
+        out[tuple(int(t) for t in ids)] = b
+    if len(out) > MAX_BIAS_SEQS:
+        raise ValueError(f"generation config: {len(out)} biased sequences exceed {MAX_BIAS_SEQS}")
+    return out
+
+
+def hotword_bias(phrases_ids, bias: float = 2.0) -> dict:
+    """A `sequence_bias` dict that boosts every token along every phrase (shallow-fusion style): every prefix of every
+    phrase (each a list of token ids) is a biased sequence with `bias`, so the first token is boosted always, the second
+    once the first was emitted, and so on.  Prefixes that different phrases share appear once.  There is no back-off: a
+    phrase abandoned halfway keeps the boost its emitted tokens already received.  `bias` 2.0 is a starting point that
+    nobody has tuned."""
+    out = {}
+    for ids in phrases_ids:
+        ids = tuple(int(t) for t in ids)
+        for n in range(1, len(ids) + 1):
+            out.setdefault(ids[:n], float(bias))
+    return normalize_sequence_bias(out) or {}
+
+
+def constraint_tables(sequence_bias: Optional[dict], min_new_tokens: int, eos: Sequence[int], vocab: int) -> Optional[dict]:
+    """The host side of tn_logits_constrain's table, as Python lists (None: nothing to do).  Sequences are grouped by their
+    last id, the groups in ascending order of that id; within a group the length-1 sequence first, then the longer ones in
+    dict order — HF's order of summation (SequenceBiasLogitsProcessor adds the length-1 biases first).  With
+    min_new_tokens > 0 every eos id is a group of its own (possibly empty), marked in grp_eos."""
+    seqs = normalize_sequence_bias(sequence_bias) or {}
+    m = int(min_new_tokens or 0)
+    if m < 0:
+        raise ValueError(f"generation config: min_new_tokens = {min_new_tokens} must be >= 0")
+    for ids in seqs:
+        if any(t >= vocab for t in ids):
+            raise ValueError(f"generation config: sequence_bias id in {list(ids)} is outside the vocabulary [0, {vocab})")
+    groups = {}
+    for ids, b in seqs.items():
+        groups.setdefault(ids[-1], []).append((ids, b))
+    hold = sorted({int(e) for e in eos if 0 <= int(e) < vocab}) if m > 0 else []
+    for e in hold:
+        groups.setdefault(e, [])
+    if not groups:
+        return None
+    t = dict(seq_off=[0], seq_ids=[], seq_bias=[], grp_off=[0], grp_tok=[], grp_eos=[], min_new=m if hold else 0,
+             vocab=int(vocab))
+    for tok in sorted(groups):
+        members = sorted(groups[tok], key=lambda sb: len(sb[0]) != 1)           # (stable: dict order otherwise)
+        for ids, b in members:
+            t["seq_ids"].extend(ids)
+            t["seq_off"].append(len(t["seq_ids"]))
+            t["seq_bias"].append(b)
+        t["grp_off"].append(len(t["seq_bias"]))
+        t["grp_tok"].append(tok)
+        t["grp_eos"].append(int(tok in hold))
+    return t
+
+
+@dataclass
+class ConstraintPlan:
+    """tn_logits_constrain's table on the device (see `constraint_tables`), built once per generate() call."""
+    seq_off: torch.Tensor
+    seq_ids: torch.Tensor
+    seq_bias: torch.Tensor
+    grp_off: torch.Tensor
+    grp_tok: torch.Tensor
+    grp_eos: torch.Tensor
+    min_new: int
+    vocab: int
+
+    @classmethod
+    def build(cls, sequence_bias, min_new_tokens, eos, vocab, device) -> Optional["ConstraintPlan"]:
+        t = constraint_tables(sequence_bias, min_new_tokens, eos, vocab)
+        if t is None:
+            return None
+        parts = [t["seq_off"], t["seq_ids"] or [0], t["grp_off"], t["grp_tok"], t["grp_eos"]]
+        ints = torch.tensor([x for p in parts for x in p], dtype=torch.int32).to(device)        # one upload
+        cuts, o = [], 0
+        for p in parts:
+            cuts.append(ints[o:o + len(p)])
+            o += len(p)
+        bias = torch.tensor(t["seq_bias"] or [0.0], dtype=torch.float32).to(device)[:len(t["seq_bias"])]
+        return cls(seq_off=cuts[0], seq_ids=cuts[1][:len(t["seq_ids"])], seq_bias=bias,
+                   grp_off=cuts[2], grp_tok=cuts[3], grp_eos=cuts[4], min_new=t["min_new"], vocab=t["vocab"])
+
+    def edit_buffers(self, rows: int):
+        """(edit_ids int32, edit_val fp32 [rows, n_grp], edit_cnt int32 [rows]): the workspace of the emit mode."""
+        n, dev = self.grp_tok.shape[0], self.grp_tok.device
+        return (torch.empty(rows, n, dtype=torch.int32, device=dev), torch.empty(rows, n, dtype=torch.float32, device=dev),
+                torch.empty(rows, dtype=torch.int32, device=dev))
 
 
 @dataclass
@@ -67,6 +197,8 @@ class GenerationConfig:
     num_beams: int = 1                       # > 1: beam search (tn_beam_step), without do_sample
     length_penalty: float = 1.0              # finished hypotheses score sum(log p) / length ** length_penalty
     early_stopping: Union[bool, str] = False  # True, False or "never" (HF's three heuristics)
+    sequence_bias: Optional[dict] = None     # {tuple(ids): bias}: hotword boosts; -inf forbids a sequence (`hotword_bias`)
+    min_new_tokens: int = 0                  # every eos id is held at -inf until this many tokens were generated
 
     @classmethod
     def from_hf(cls, path_or_dict, **overrides) -> "GenerationConfig":
@@ -90,7 +222,7 @@ class GenerationConfig:
             v = overrides.get(k, d.get(k, inert))
             if v not in (inert, None, [], {}):
                 raise ValueError(f"generation config: {k} = {v!r} is not supported by this decoder "
-                                 f"(greedy, sampled or beam search, one sequence per prompt)")
+                                 f"(greedy, sampled or beam search, one sequence per prompt){_FORBID_HINT.get(k, '')}")
         num = lambda k, default: overrides[k] if k in overrides else d.get(k, default)
         cfg = cls(max_new_tokens=d.get("max_new_tokens"), repetition_penalty=float(num("repetition_penalty", 1.0)),
                   no_repeat_ngram_size=int(num("no_repeat_ngram_size", 0)), eos_token_id=num("eos_token_id", None),
@@ -99,7 +231,11 @@ class GenerationConfig:
                   top_k=int(num("top_k", 50) or 0), top_p=float(num("top_p", 1.0)), seed=int(num("seed", 0)),
                   max_length=int(num("max_length", 20)), check_every=int(num("check_every", 16)),
                   cache_chunk=int(num("cache_chunk", 1024)), num_beams=int(num("num_beams", 1) or 1),
-                  length_penalty=float(num("length_penalty", 1.0)), early_stopping=num("early_stopping", False))
+                  length_penalty=float(num("length_penalty", 1.0)), early_stopping=num("early_stopping", False),
+                  sequence_bias=normalize_sequence_bias(num("sequence_bias", None)),
+                  min_new_tokens=int(num("min_new_tokens", 0) or 0))
+        if cfg.min_new_tokens < 0:
+            raise ValueError(f"generation config: min_new_tokens = {cfg.min_new_tokens} must be >= 0")
         if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
             cfg.max_new_tokens = overrides["max_new_tokens"]
         if cfg.do_sample:
@@ -509,8 +645,12 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
                              device)
     S_full = max(lens) + n_new
+    plan = ConstraintPlan.build(cfg.sequence_bias, cfg.min_new_tokens, eos, int(c.vocab_size), device)
+    prompt_len = torch.tensor(lens, dtype=torch.int32, device=device) if plan is not None else None
 
     def step(logits):
+        if plan is not None:                       # HF's order: SequenceBiasLogitsProcessor before the repetition penalty
+            F.constrain_logits_(logits, cache.hist, cache.hist_len, plan, prompt_len)
         if greedy:
             F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
                           ngram, eos[0] if eos else -1, pad)
@@ -549,14 +689,26 @@ def _beam_search(lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos, pad, 
     S_full = max(lens) + n_new
     kw = dict(penalty=float(cfg.repetition_penalty), ngram=int(cfg.no_repeat_ngram_size), eos=eos, n_new=n_new,
               length_penalty=float(cfg.length_penalty), early_stopping=cfg.early_stopping)
-    F.beam_step(_prefill(lm, proj_w, prompts, st, device, embed, row_stride=K), st, **kw)     # one live row per utterance
+    plan = ConstraintPlan.build(cfg.sequence_bias, cfg.min_new_tokens, eos, int(c.vocab_size), device)
+    if plan is not None:
+        prompt_len = torch.tensor(lens, dtype=torch.int32, device=device).repeat_interleave(K)
+        edits = plan.edit_buffers(len(lens) * K)
+
+    def step(logits):
+        if plan is None:
+            F.beam_step(logits, st, **kw)
+        else:                                      # the totals go onto the log-probabilities inside the step
+            F.constrain_logits_(logits, st.hist, st.hist_len, plan, prompt_len, num_beams=K, edits=edits)
+            F.beam_step(logits, st, edits=edits, **kw)
+
+    step(_prefill(lm, proj_w, prompts, st, device, embed, row_stride=K))                      # one live row per utterance
     steps = 1
     while steps < n_new:
         if steps % max(1, int(cfg.check_every)) == 0 and int(st.n_unfinished.item()) == 0:
             break
         if max(lens) + steps >= st.capacity:
             st.grow(min(S_full, 2 * st.capacity))
-        F.beam_step(decode_logits(lm, st, table=st.src), st, **kw)
+        step(decode_logits(lm, st, table=st.src))
         steps += 1
     out, _ = st.best(lens, pad)
     return (out, st) if return_cache else out
@@ -571,3 +723,46 @@ def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[
         cut = next((i for i, t in enumerate(r) if t in stop), len(r))
         rows.append(r[:cut])
     return rows
+
+
+# ------------------------------------------------------------------------------------ command-line side of the constraints
+def add_constraint_arguments(ap) -> None:
+    """--hotwords / --hotword_bias / --forbid_words / --min_new_tokens of the inference command lines."""
+    ap.add_argument("--hotwords", default=None, metavar="FILE",
+                    help="one phrase per line, tokenised with the checkpoint's tokenizer (no special tokens); every token "
+                         "along a phrase is boosted by --hotword_bias once the tokens before it were emitted")
+    ap.add_argument("--hotword_bias", type=float, default=2.0,
+                    help="added to the logit (beam search: the log-probability) of a hotword's next token; 2.0 is a "
+                         "starting point that nobody has tuned")
+    ap.add_argument("--forbid_words", default=None, metavar="FILE",
+                    help="one phrase per line; its token sequence can never be completed (sequence_bias at -inf)")
+    ap.add_argument("--min_new_tokens", type=int, default=None, help="no eos before this many generated tokens")
+
+
+def read_phrases(path: str, tokenizer) -> List[List[int]]:
+    """The token ids of every non-empty line of `path`, without special tokens.  No tokenizer: refused."""
+    if tokenizer is None:
+        raise ValueError(f"{path}: phrases are tokenised with the checkpoint's tokenizer, and the checkpoint directory "
+                         "holds none (tokenizer.json / tokenizer_config.json)")
+    out = []
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f, 1):
+            text = line.strip()
+            if not text:
+                continue
+            ids = [int(t) for t in tokenizer.encode(text, add_special_tokens=False)]
+            if not ids:
+                raise ValueError(f"{path}:{n}: {text!r} has no tokens")
+            out.append(ids)
+    return out
+
+
+def constraints_from_args(args, tokenizer, sequence_bias: Optional[dict] = None) -> Optional[dict]:
+    """`sequence_bias` of a command line: what the generation config carries, then the hotwords (every prefix at
+    --hotword_bias), then the forbidden phrases (whole sequences at -inf); a later entry replaces an earlier one."""
+    out = dict(normalize_sequence_bias(sequence_bias) or {})
+    if args.hotwords:
+        out.update(hotword_bias(read_phrases(args.hotwords, tokenizer), args.hotword_bias))
+    if args.forbid_words:
+        out.update({tuple(ids): float("-inf") for ids in read_phrases(args.forbid_words, tokenizer)})
+    return normalize_sequence_bias(out)

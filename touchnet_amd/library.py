@@ -1058,18 +1058,37 @@ def beam_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor
     live row per utterance) or [R, V], fp32 / bf16; hist / fin_ids / src int32 [R, S_hist]; hist_len / cache_len / fin_len /
     fin_flag / out_ids / out_parent int32 [R]; run_score / fin_score fp32 [R]; gen / unsat / done int32 [B]; n_unfinished
     int32 [1] — all advanced on the device.  early_stopping: 0 False, 1 True, 2 "never"."""
-    _no_grad_inputs("beam_step_", logits)
+    _beam_step("beam_step_", logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen,
+               unsat, done, n_unfinished, out_ids, out_parent, num_beams, penalty, ngram, eos, n_new, length_penalty,
+               early_stopping, None)
+
+
+def _beam_step(what, logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat,
+               done, n_unfinished, out_ids, out_parent, num_beams, penalty, ngram, eos, n_new, length_penalty,
+               early_stopping, edits):
+    """The checks and the launch of beam_step_ (edits None: tn_beam_step) and beam_step_edits_ (edits = (ids, val, cnt):
+    tn_beam_step_edits)."""
+    _no_grad_inputs(what, logits)
     K = int(num_beams)
     if not 2 <= K <= BEAM_MAX_K:
-        raise _C.KernelError(f"beam_step_: num_beams must be in [2, {BEAM_MAX_K}]")
+        raise _C.KernelError(f"{what}: num_beams must be in [2, {BEAM_MAX_K}]")
     if len(eos) > BEAM_MAX_EOS:
-        raise _C.KernelError(f"beam_step_: at most {BEAM_MAX_EOS} eos ids")
+        raise _C.KernelError(f"{what}: at most {BEAM_MAX_EOS} eos ids")
     if hist.dim() != 2 or hist.shape[0] % K or logits.dim() != 2:
-        raise _C.KernelError("beam_step_: hist [B * num_beams, S_hist], logits [B or B * num_beams, V]")
+        raise _C.KernelError(f"{what}: hist [B * num_beams, S_hist], logits [B or B * num_beams, V]")
     R, S_hist = hist.shape
     B, V = R // K, logits.shape[1]
     if logits.shape[0] not in (B, R):
-        raise _C.KernelError("beam_step_: logits must have B (first step) or B * num_beams rows")
+        raise _C.KernelError(f"{what}: logits must have B (first step) or B * num_beams rows")
+    if edits is not None:
+        e_ids, e_val, e_cnt = edits
+        n_edit = e_ids.shape[1] if e_ids.dim() == 2 else 0
+        for name, t, dt, ok in (("edit_ids", e_ids, torch.int32, e_ids.dim() == 2 and e_ids.shape[0] >= logits.shape[0]),
+                                ("edit_val", e_val, torch.float32, tuple(e_val.shape) == tuple(e_ids.shape)),
+                                ("edit_cnt", e_cnt, torch.int32, tuple(e_cnt.shape) == (e_ids.shape[0],))):
+            if t.dtype != dt or not ok or not t.is_contiguous() or n_edit < 1:
+                raise _C.KernelError(f"{what}: {name} must be a contiguous {dt} tensor: edit_ids / edit_val [rows >= the "
+                                     "logits' rows, n_edit >= 1], edit_cnt [rows]")
     for name, t, dt, shape in (("hist", hist, torch.int32, (R, S_hist)), ("fin_ids", fin_ids, torch.int32, (R, S_hist)),
                                ("src", src, torch.int32, (R, S_hist)), ("hist_len", hist_len, torch.int32, (R,)),
                                ("cache_len", cache_len, torch.int32, (R,)), ("fin_len", fin_len, torch.int32, (R,)),
@@ -1079,20 +1098,106 @@ def beam_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor
                                ("unsat", unsat, torch.int32, (B,)), ("done", done, torch.int32, (B,)),
                                ("n_unfinished", n_unfinished, torch.int32, (1,))):
         if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _C.KernelError(f"beam_step_: {name} must be a contiguous {dt} tensor of shape {list(shape)}")
+            raise _C.KernelError(f"{what}: {name} must be a contiguous {dt} tensor of shape {list(shape)}")
     logits = _c(logits)
     eos_arr = (ctypes.c_int * max(1, len(eos)))(*[int(e) for e in eos])
     ws = torch.empty(int(_lib().tn_beam_step_workspace_bytes(B, K)) // 4, dtype=torch.float32, device=logits.device)
-    _C.check(_lib().tn_beam_step(_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(src), _p(run_score), _p(fin_ids),
-                                 _p(fin_len), _p(fin_score), _p(fin_flag), _p(gen), _p(unsat), _p(done), _p(n_unfinished),
-                                 _p(out_ids), _p(out_parent), _p(ws), B, K, logits.shape[0] // B, V, S_hist, float(penalty),
-                                 int(ngram), eos_arr, len(eos), int(n_new), float(length_penalty), int(early_stopping),
-                                 _C.dcode(logits), _cur()), "tn_beam_step")
+    args = (_p(logits), _p(hist), _p(hist_len), _p(cache_len), _p(src), _p(run_score), _p(fin_ids), _p(fin_len),
+            _p(fin_score), _p(fin_flag), _p(gen), _p(unsat), _p(done), _p(n_unfinished), _p(out_ids), _p(out_parent), _p(ws),
+            B, K, logits.shape[0] // B, V, S_hist, float(penalty), int(ngram), eos_arr, len(eos), int(n_new),
+            float(length_penalty), int(early_stopping), _C.dcode(logits))
+    if edits is None:
+        _C.check(_lib().tn_beam_step(*args, _cur()), "tn_beam_step")
+    else:
+        _C.check(_lib().tn_beam_step_edits(*args, _p(e_ids), _p(e_val), _p(e_cnt), int(n_edit), _cur()),
+                 "tn_beam_step_edits")
 
 
 @beam_step_.register_fake
 def _(logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat, done,
       n_unfinished, out_ids, out_parent, num_beams, penalty, ngram, eos, n_new, length_penalty, early_stopping):
+    return None
+
+
+@custom_op(f"{NS}::beam_step_edits_", mutates_args=_BEAM_STATE, device_types="cuda")
+def beam_step_edits_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, src: Tensor, run_score: Tensor,
+                     fin_ids: Tensor, fin_len: Tensor, fin_score: Tensor, fin_flag: Tensor, gen: Tensor, unsat: Tensor,
+                     done: Tensor, n_unfinished: Tensor, out_ids: Tensor, out_parent: Tensor, edit_ids: Tensor,
+                     edit_val: Tensor, edit_cnt: Tensor, num_beams: int, penalty: float, ngram: int, eos: List[int],
+                     n_new: int, length_penalty: float, early_stopping: int) -> None:
+    """beam_step_ with the edit list that constrain_logits_ emitted for the same logits rows (tn_beam_step_edits): edit_ids
+    int32 / edit_val fp32 [rows, n_edit], edit_cnt int32 [rows]; edit_val is added to the log-probability of every id with
+    edit_ids >= 0, before the repetition penalty."""
+    _beam_step("beam_step_edits_", logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag,
+               gen, unsat, done, n_unfinished, out_ids, out_parent, num_beams, penalty, ngram, eos, n_new, length_penalty,
+               early_stopping, (edit_ids, edit_val, edit_cnt))
+
+
+@beam_step_edits_.register_fake
+def _(logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat, done,
+      n_unfinished, out_ids, out_parent, edit_ids, edit_val, edit_cnt, num_beams, penalty, ngram, eos, n_new,
+      length_penalty, early_stopping):
+    return None
+
+
+CONSTRAIN_MAX_SEQS, CONSTRAIN_MAX_LEN = 16384, 64          # tn_logits_constrain's limits
+
+
+@custom_op(f"{NS}::constrain_logits_", mutates_args=("logits", "edit_ids", "edit_val", "edit_cnt"), device_types="cuda")
+def constrain_logits_(logits: Tensor, hist: Tensor, hist_len: Tensor, prompt_len: Optional[Tensor], seq_off: Tensor,
+                      seq_ids: Tensor, seq_bias: Tensor, grp_off: Tensor, grp_tok: Tensor, grp_eos: Tensor,
+                      edit_ids: Optional[Tensor], edit_val: Optional[Tensor], edit_cnt: Optional[Tensor], num_beams: int,
+                      min_new: int) -> None:
+    """`sequence_bias` and `min_new_tokens` of HF generate() on the device (tn_logits_constrain): logits [R_in, V] fp32 /
+    bf16, contiguous; hist int32 [R, S_hist], hist_len / prompt_len int32 [R]; R_in == R, or R_in == R / num_beams right
+    after a beam search's prefill.  The table of `generation.ConstraintPlan`: seq_off int32 [n_seq + 1], seq_ids int32,
+    seq_bias fp32 [n_seq], grp_off int32 [n_grp + 1], grp_tok / grp_eos int32 [n_grp]; at most 16384 sequences of at most
+    64 ids.  Without edit tensors the logits are edited in place (logits[t] = T(fp32(logits[t]) + total)); with edit_ids
+    int32 / edit_val fp32 [>= R_in, n_grp] and edit_cnt int32 [rows] the logits are left alone and the edit list of
+    beam_step_edits_ is written."""
+    _no_grad_inputs("constrain_logits_", logits)
+    K = int(num_beams)
+    if logits.dim() != 2 or hist.dim() != 2 or K < 1 or hist.shape[0] % K:
+        raise _C.KernelError("constrain_logits_: logits [R_in, V], hist [R, S_hist] with R a multiple of num_beams")
+    R_in, V = logits.shape
+    R, S_hist = hist.shape
+    if R_in not in (R, R // K):
+        raise _C.KernelError("constrain_logits_: logits must have R or R / num_beams rows")
+    if not logits.is_contiguous():
+        raise _C.KernelError("constrain_logits_: the logits are edited in place and must be contiguous")
+    n_seq, n_grp = seq_bias.shape[0], grp_tok.shape[0]
+    if n_seq > CONSTRAIN_MAX_SEQS:
+        raise _C.KernelError(f"constrain_logits_: at most {CONSTRAIN_MAX_SEQS} sequences")
+    for name, t, dt, shape in (("hist", hist, torch.int32, (R, S_hist)), ("hist_len", hist_len, torch.int32, (R,)),
+                               ("prompt_len", prompt_len, torch.int32, (R,)),
+                               ("seq_off", seq_off, torch.int32, (n_seq + 1,)),
+                               ("seq_ids", seq_ids, torch.int32, (seq_ids.numel(),)),
+                               ("seq_bias", seq_bias, torch.float32, (n_seq,)),
+                               ("grp_off", grp_off, torch.int32, (n_grp + 1,)), ("grp_tok", grp_tok, torch.int32, (n_grp,)),
+                               ("grp_eos", grp_eos, torch.int32, (n_grp,))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _C.KernelError(f"constrain_logits_: {name} must be a contiguous {dt} tensor of shape {list(shape)}")
+    emit = edit_ids is not None
+    if emit:
+        if edit_val is None or edit_cnt is None:
+            raise _C.KernelError("constrain_logits_: edit_ids, edit_val and edit_cnt go together")
+        rows = edit_ids.shape[0]
+        for name, t, dt, shape in (("edit_ids", edit_ids, torch.int32, (rows, n_grp)),
+                                   ("edit_val", edit_val, torch.float32, (rows, n_grp)),
+                                   ("edit_cnt", edit_cnt, torch.int32, (rows,))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or rows < R_in:
+                raise _C.KernelError(f"constrain_logits_: {name} must be a contiguous {dt} tensor of shape "
+                                     f"{list(shape)} with at least {R_in} rows")
+    _C.check(_lib().tn_logits_constrain(_p(logits), _p(hist), _p(hist_len), _p(prompt_len), _p(seq_off),
+                                        _p(seq_ids) if n_seq else None, _p(seq_bias) if n_seq else None, _p(grp_off),
+                                        _p(grp_tok), _p(grp_eos), _p(edit_ids), _p(edit_val), _p(edit_cnt), R_in, K,
+                                        K if R_in == R and K > 1 else 1, V, S_hist, n_seq, int(seq_ids.numel()), n_grp,
+                                        int(min_new), int(emit), _C.dcode(logits), _cur()), "tn_logits_constrain")
+
+
+@constrain_logits_.register_fake
+def _(logits, hist, hist_len, prompt_len, seq_off, seq_ids, seq_bias, grp_off, grp_tok, grp_eos, edit_ids, edit_val,
+      edit_cnt, num_beams, min_new):
     return None
 
 
@@ -1191,4 +1296,5 @@ OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_f
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
-       "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align")
+       "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
+       "constrain_logits_")

@@ -50,6 +50,7 @@ def transcribe(model, feats: List[torch.Tensor], cfg: Optional[GenerationConfig]
     gcfg = GenerationConfig(max_new_tokens=cfg.max_new_tokens, repetition_penalty=cfg.repetition_penalty,
                             no_repeat_ngram_size=cfg.no_repeat_ngram_size, eos_token_id=eos, pad_token_id=pad,
                             bos_token_id=bos, check_every=cfg.check_every, num_beams=cfg.num_beams,
-                            length_penalty=cfg.length_penalty, early_stopping=cfg.early_stopping)
+                            length_penalty=cfg.length_penalty, early_stopping=cfg.early_stopping,
+                            sequence_bias=cfg.sequence_bias, min_new_tokens=cfg.min_new_tokens)
     out = generate(model, build_prompts(feats, pad, bos), gcfg)
     return trim_at_eos(out, eos)
