@@ -60,7 +60,8 @@ constexpr long long DMA_SPAN = 0x7fffffffLL;
 // Row-stored operand X[rows, K] (pitch ld): whole 64-deep stages (behind K a stage would read the row's own next columns),
 // 16-byte base, pitch % 8, the 288 rows a tile's descriptor spans below 2 GB.  min_ld is the entries' one difference: the
 // fused ones pass K; the general entry passes 1, because it also takes OVERLAPPING rows (ld < K) — the im2col view of a
-// k = 3 convolution over a channels-last sequence, row r = 3 C elements from r * stride * C on.
+// k = 3 convolution over a channels-last sequence, row r = 3 C elements from r * stride * C on.  Every row is read in
+// full, the last ones too: a tile's descriptor ends with the last row's last element, (rows - 1) * ld + K (Stream::open).
 bool row_operand_ok(const void* X, long long ld, int K, long long min_ld) {
   return K > 0 && (K % 64) == 0 && aligned(15, X) && (ld % 8) == 0 && ld >= min_ld && 288 * ld * 2 < DMA_SPAN;
 }

@@ -265,7 +265,10 @@ struct Stream {
   __device__ __forceinline__ void open(const bf16_t* X, long long ld, int K, int R, int origin, int wave, int lane) {
     ld2 = (int)(ld * 2);
     if constexpr (!KMAJ) {
-      const long long bytes = max((long long)(R - origin) * ld2, 0LL);     // (origin >= R: nothing to read, all zeros)
+      // up to the END of the last row, which with overlapping rows (ld < K) lies behind (R - origin) * ld; rows >= R are
+      // zero-filled for ld >= K and may read the last rows' own tails for ld < K: they feed accumulator rows / columns that
+      // are never stored, as with a contraction-major operand  (origin >= R: nothing to read, all zeros)
+      const long long bytes = R > origin ? (long long)(R - origin - 1) * ld2 + 2LL * K : 0LL;
       rs = __builtin_amdgcn_make_buffer_rsrc((void*)(X + (long long)origin * ld), 0, (int)min(bytes, 0x7fffffffLL),
                                              0x00020000);
       step = 128;
