@@ -575,6 +575,26 @@ int tn_beam_step_edits(const void* logits, int* hist, int* hist_len, int* cache_
                        int S_hist, float penalty, int ngram, const int* eos_ids, int n_eos, int n_new, float length_penalty,
                        int early_stopping, int dtype, const int* edit_ids, const float* edit_val, const int* edit_cnt,
                        int n_edit, void* stream);
+/* token_scores: per-token confidences — transformers' compute_transition_scores(sequences, out.logits,
+ *      normalize_logits=True) of a generate(output_logits=True) call (the generate() of
+ *      touchnet/models/touch_audio/inference_touch_audio.py:177-192 returns ids only), plus the row's entropy and its k
+ *      most likely tokens.  logits [R, V] (`dtype`: 0 fp32, 1 bf16) contiguous, read in fp32; row r starts at
+ *      r * V * sizeof(T) and needs no more than its element's alignment.  The scored token t is named in one of two ways:
+ *      token mode: tok int32 [R] (hist and hist_len NULL, S_hist ignored); outputs logp / entropy fp32 [R], alt_id int32 and
+ *      alt_logp fp32 [R, k].  history mode: tok NULL, hist int32 [R, S_hist], hist_len int32 [R]: with n = hist_len[r],
+ *      t = hist[r, n - 1] (the id a step kernel has just appended) and the outputs go to column n - 1 of logp / entropy
+ *      [R, S_hist] and alt_id / alt_logp [R, S_hist, k]; a row with n outside [1, S_hist] writes nothing.
+ *      With lse = log sum_v exp(l_v): logp = l_t - lse; entropy = lse - sum_v p_v l_v (a -inf logit contributes 0);
+ *      alt_id = the ids of the k largest logits, descending, ties to the lower id, alt_logp their logp; for k > V the tail
+ *      is id -1, logp -inf (k == 0: alt_id / alt_logp may be NULL).  t outside [0, V): logp = NaN, nothing is read out of
+ *      bounds, entropy and the alternatives are still written.  A row that holds a NaN or +inf, or only -inf: every fp32
+ *      output of the row is NaN and the ids are -1.  One workgroup per row; which thread sums which id depends on the id
+ *      alone and the reduction order is fixed: repeats are bit-identical and a row scores the same in any batch and at any
+ *      address.  No atomics; nothing but the outputs is written.  -22 before any launch for NULL or misaligned pointers
+ *      (logits to its element, all others to 4 bytes), V outside [1, 262144], k outside [0, 8], R < 0, both or neither of
+ *      tok and (hist, hist_len), S_hist < 1 in history mode, dtype outside [0, 1].  R == 0: 0, nothing launched. */
+int tn_token_scores(const void* logits, const int* tok, const int* hist, const int* hist_len, float* logp, float* entropy,
+                    int* alt_id, float* alt_logp, int R, int V, int S_hist, int k, int dtype, void* stream);
 
 /* ---- Kimi-Audio's speech tokenizer (GLM-4-voice WhisperVQEncoder, touchnet/models/kimi_audio/modeling_kimi_audio.py:140-319,
  *      run by MoonshotKimiaForCausalLM.prepare_audio_input_embs under no_grad, :957-963).  Forward only: it is frozen.

@@ -7,6 +7,7 @@ generate() (sdpa, same knobs, same weights).  Prints one JSON object per measure
     python scripts/decode_bench.py --num-beams 4 [--batch 12]
     python scripts/decode_bench.py --kimi-audio-7b [--batch 12]
     python scripts/decode_bench.py --hotwords 1024 [--batch 12]
+    python scripts/decode_bench.py --token-scores [K] [--batch 12]
 
 --qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
 per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
@@ -26,6 +27,10 @@ lookups, add) — the launches the fused write removes.
 --hotwords N: tn_logits_constrain with a table of N phrases x 4 prefixes on bf16 logits [B, 156 032]: per call (µs, apply
 and emit mode), its share of the Qwen2-Audio-7B sampled decode step timed in the same run (with an A/B of the whole step
 with and without the plan), and tn_beam_step with and without the edit list (K 4).
+
+--token-scores [K]: tn_token_scores per call (µs) in history mode on bf16 logits [B, V] at V = 128 256 and 152 064 with k = 0
+and k = K (default 8), rows/s in token mode on [4096, V] (the rescoring shape), and its share of the Qwen2-Audio-7B sampled
+decode step timed in the same run (with an A/B of the whole step with and without the launch).
 
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
@@ -454,6 +459,77 @@ def bench_hotwords(N, B, K=4, steps=32, iters=200):
     return rows
 
 
+def bench_token_scores(K, B, steps=32, iters=200):
+    """tn_token_scores alone (history mode at the decode batch, token mode at 4096 rows) and inside the sampled decode
+    step of Qwen2-Audio-7B's decoder (decode_logits + tn_sample_step + the scores, against the step without them, A/B
+    twice in one process)."""
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    rows = []
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for V in (128256, 152064):
+        logits = (torch.randn(B, V, generator=g, device=DEV) * 4).to(torch.bfloat16)
+        S = 64
+        hist = torch.randint(0, V, (B, S), generator=g, device=DEV, dtype=torch.int32)
+        hist_len = torch.full((B,), 40, dtype=torch.int32, device=DEV)
+        r = dict(kernel="tn_token_scores", mode="history", B=B, V=V, MB_read_per_pass=round(B * V * 2 / 1e6, 2))
+        for k in sorted({0, K}):
+            out = G.TokenScores.buffers(B, S, k, DEV)
+            F.token_scores_(logits, hist, hist_len, out, k)
+            r[f"us_k{k}"] = round(_events_time(lambda: F.token_scores_(logits, hist, hist_len, out, k), iters), 2)
+        rows.append(r)
+        R = 4096
+        big = (torch.randn(R, V, generator=g, device=DEV) * 4).to(torch.bfloat16)
+        tok = torch.randint(0, V, (R,), generator=g, device=DEV, dtype=torch.int32)
+        r = dict(kernel="tn_token_scores", mode="token", R=R, V=V)
+        for k in sorted({0, K}):
+            F.token_scores(big, tok, k)
+            us = _events_time(lambda: F.token_scores(big, tok, k), 20)
+            r[f"us_k{k}"], r[f"rows_per_s_k{k}"] = round(us, 1), round(R / us * 1e6)
+            r[f"TBps_one_pass_k{k}"] = round(R * V * 2 / us / 1e6, 3)
+        rows.append(r)
+        del big
+        torch.cuda.empty_cache()
+    V, P = 156032, 300
+    gc = torch.Generator().manual_seed(0)
+    prompts = G.Prompts([torch.randint(0, 150000, (P,), generator=gc) for _ in range(B)])
+    text = DecoderConfig.from_dict(dict(model_type="qwen2", hidden_size=4096, intermediate_size=11008, num_attention_heads=32,
+                                        num_key_value_heads=32, head_dim=128, num_hidden_layers=32, vocab_size=V,
+                                        rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=False,
+                                        initializer_range=0.02, eos_token_id=151643, pad_token_id=151643))
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        lm = PackedCausalLM(text)
+    lm.post_init()
+    lm = lm.to(torch.bfloat16).eval()
+    keys = torch.arange(B, device=DEV)
+    cache = G.KVCache.allocate(32, B, P + 8 * steps + 8, 32, 128, DEV)
+    out = G.TokenScores.buffers(B, cache.capacity, K, DEV)
+    sample = lambda lg: F.sample_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
+                                      1.1, True, 0.7, 50, 0.9, 1, [151643, 151645], 151643, row_key=keys)
+    with torch.no_grad():
+        sample(G._prefill(lm, None, prompts, cache, DEV))
+
+        def step_plain():
+            sample(G.decode_logits(lm, cache))
+
+        def step_scored():
+            lg = G.decode_logits(lm, cache)
+            sample(lg)
+            F.token_scores_(lg, cache.hist, cache.hist_len, out, K)
+        step_plain(), step_scored()
+        ab = [[_events_time(step_plain, steps - 2) / 1e3, _events_time(step_scored, steps - 2) / 1e3] for _ in range(2)]
+        lg = G.decode_logits(lm, cache)
+        us = _events_time(lambda: F.token_scores_(lg, cache.hist, cache.hist_len, out, K), iters)
+    ms = min(a for a, _ in ab)
+    rows.append(dict(e2e="qwen2_audio_7b_decode_step", B=B, V=V, k=K, ms_per_step_without_scores=round(ms, 3),
+                     ms_per_step_with_scores=round(min(b for _, b in ab), 3),
+                     ab_runs_ms=[[round(a, 3), round(b, 3)] for a, b in ab], token_scores_us=round(us, 2),
+                     token_scores_share_of_step=round(us / (ms * 1e3), 4)))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -465,12 +541,18 @@ def main():
     ap.add_argument("--num-beams", type=int, default=0, help="K > 1: the beam-search measurements")
     ap.add_argument("--kimi-audio-7b", action="store_true")
     ap.add_argument("--hotwords", type=int, default=0, help="N > 0: tn_logits_constrain with N phrases x 4 prefixes")
+    ap.add_argument("--token-scores", type=int, nargs="?", const=8, default=None, metavar="K",
+                    help="tn_token_scores with k = 0 and k = K (default 8) alternatives")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.token_scores is not None:
+        for r in bench_token_scores(a.token_scores, a.batch):
+            print(json.dumps(r), flush=True)
+        return
     if a.hotwords > 0:
         for r in bench_hotwords(a.hotwords, a.batch):
             print(json.dumps(r), flush=True)

@@ -106,6 +106,7 @@ PROTOTYPES = {
     "tn_beam_step": [_vp] * 17 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _f, _i, _i, _vp],
     "tn_logits_constrain": [_vp] * 13 + [_i] * 11 + [_vp],
     "tn_beam_step_edits": [_vp] * 17 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "tn_token_scores": [_vp] * 8 + [_i] * 5 + [_vp],
     "tn_attn_block_causal_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "tn_vq_nearest": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "tn_edit_align_ws_words": [_i, _i],

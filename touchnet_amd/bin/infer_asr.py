@@ -18,6 +18,10 @@ special tokens; every token along a phrase gets `--hotword_bias`, default 2.0 â€
 once the tokens before it were emitted), `--forbid_words FILE` (phrases whose token sequence can never be completed) and
 `--min_new_tokens N` (no eos before N tokens); see generation.hotword_bias and DESIGN 9.6.  A phrase file needs the
 tokenizer: without one in CKPT_DIR the command refuses.
+Confidences and N-best lists: `--output_scores` adds "confidence", "token_logprobs" and "token_entropy" to every record
+(one entry per generated token up to and including the eos), `--top_alternatives K` adds "alternatives" ([[id, logp], ...]
+per token), `--nbest N` (with --num_beams >= N) adds "nbest", the N best finished hypotheses; see DESIGN 9.7.  Without
+these flags the output file is what it was.
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ import numpy as np
 import torch
 
 from touchnet_amd.data import functions as stages
-from touchnet_amd.generation import GenerationConfig, add_constraint_arguments, constraints_from_args
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_score_arguments,
+                                     constraints_from_args)
 from touchnet_amd.models.backend import ops
 from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
 from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
@@ -124,6 +129,21 @@ def features(wavs, dcfg) -> list:
     return [s["audiofeat"] for s in stages.audiofeat_stack(feat_stage(iter(samples), dcfg), dcfg)]
 
 
+def record_line(item, ids, extra: dict, tokenizer=None) -> str:
+    """One output line: {"label", "predict_ids"[, "predict"]} and the extra keys of generation.record_fields behind them
+    (every "nbest" entry gains its "predict" too).  No extra keys: the line this command has always written."""
+    text = lambda row: tokenizer.decode(row, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+    rec = {"label": json.dumps(item, ensure_ascii=False), "predict_ids": ids}
+    if tokenizer is not None:
+        rec["predict"] = text(ids)
+    for key, value in extra.items():
+        if key == "nbest" and tokenizer is not None:
+            value = [{"predict_ids": h["predict_ids"], "predict": text(h["predict_ids"]),
+                      **{k: v for k, v in h.items() if k != "predict_ids"}} for h in value]
+        rec[key] = value
+    return json.dumps(rec, ensure_ascii=False) + "\n"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model_path", required=True)
@@ -140,6 +160,7 @@ def main(argv=None):
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
+    add_score_arguments(ap)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
@@ -157,7 +178,8 @@ def main(argv=None):
                            no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
                            length_penalty=args.length_penalty,
                            early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
-                           sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0)
+                           sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0,
+                           output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
     cfg.check_beams()
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f"part_{args.shard_index + 1}_of_{args.num_shards}")
@@ -165,12 +187,9 @@ def main(argv=None):
         for i in range(0, len(items), args.batch_size):
             batch = items[i:i + args.batch_size]
             feats = features([read_wav(it["wav"], int(dcfg.audio_resample_rate)) for it in batch], dcfg)
-            ids = transcribe(model, feats, cfg)
-            for it, row in zip(batch, ids):
-                rec = {"label": json.dumps(it, ensure_ascii=False), "predict_ids": row}
-                if tokenizer is not None:
-                    rec["predict"] = tokenizer.decode(row, skip_special_tokens=True, clean_up_tokenization_spaces=False)
-                writer.write(json.dumps(rec, ensure_ascii=False) + "\n")
+            ids, extras = transcribe(model, feats, cfg, details=True)
+            for it, row, extra in zip(batch, ids, extras):
+                writer.write(record_line(it, row, extra, tokenizer))
     return out_path
 
 

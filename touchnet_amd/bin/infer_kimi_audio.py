@@ -25,7 +25,7 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import KimiGenerationConfig
+from touchnet_amd.generation import KimiGenerationConfig, add_score_arguments
 from touchnet_amd.models.kimi_audio import KimiAudioConfig, KimiAudioPackedForCausalLM
 from touchnet_amd.models.kimi_audio.inference_kimi_audio import transcribe
 from touchnet_amd.models.kimi_audio.processing_kimi_audio import BLANK, DEFAULT_INSTRUCT, EOS
@@ -70,11 +70,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
+    add_score_arguments(ap, nbest=False)
     args = ap.parse_args(argv)
     cfg = KimiGenerationConfig(text_temperature=args.text_temperature, text_top_k=args.text_top_k,
                                text_repetition_penalty=args.text_repetition_penalty,
                                text_repetition_window_size=args.text_repetition_window_size,
-                               max_new_tokens=args.max_new_tokens, seed=args.seed)
+                               max_new_tokens=args.max_new_tokens, seed=args.seed, output_scores=args.output_scores,
+                               top_alternatives=args.top_alternatives)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_kimi_audio needs the MI355X (there is no CPU path)")
     from transformers import AutoTokenizer
@@ -93,9 +95,9 @@ def main(argv=None):
             batch = items[i:i + args.batch_size]
             wavs = [read_wav(it["wav"]) for _, it in batch]
             keys = torch.tensor([n for n, _ in batch], dtype=torch.int64)
-            _, texts = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys)
-            for (_, it), text in zip(batch, texts):
-                writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text},
+            _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
+            for (_, it), text, extra in zip(batch, texts, extras):
+                writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text, **extra},
                                         ensure_ascii=False) + "\n")
     return out_path
 

@@ -21,6 +21,10 @@ special tokens; every token along a phrase gets `--hotword_bias`, default 2.0 â€
 once the tokens before it were emitted), `--forbid_words FILE` (phrases whose token sequence can never be completed) and
 `--min_new_tokens N` (no eos before N tokens); see generation.hotword_bias and DESIGN 9.6.  They merge with the `sequence_bias` of
 generation_config.json: the file's entries first, then the hotwords, then the forbidden phrases.
+Confidences and N-best lists: `--output_scores` adds "confidence", "token_logprobs" and "token_entropy" to every record
+(one entry per generated token up to and including the eos), `--top_alternatives K` adds "alternatives" ([[id, logp], ...]
+per token), `--nbest N` (beam search with at least N beams) adds "nbest", the N best finished hypotheses with their ids;
+see DESIGN 9.7.  Without these flags the output file is what it was.
 """
 from __future__ import annotations
 
@@ -32,7 +36,8 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import GenerationConfig, add_constraint_arguments, constraints_from_args
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_score_arguments,
+                                     constraints_from_args)
 from touchnet_amd.models.qwen2_audio import Qwen2AudioConfig, Qwen2AudioPackedForConditionalGeneration
 from touchnet_amd.models.qwen2_audio.inference_qwen2_audio import build_prompts, transcribe, valid_frames
 from touchnet_amd.models.qwen2_audio.processing_qwen2_audio import DEFAULT_INSTRUCT
@@ -94,6 +99,7 @@ def main(argv=None):
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
+    add_score_arguments(ap)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_qwen2_audio needs the MI355X (there is no CPU path)")
@@ -102,6 +108,8 @@ def main(argv=None):
     model = load_model(args.model_path, device)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path)
     over = dict(max_length=args.max_length, seed=args.seed)
+    if args.output_scores or args.top_alternatives or args.nbest != 1:
+        over.update(output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
     if args.num_beams is not None:
         over["num_beams"] = args.num_beams
     if args.length_penalty is not None:
@@ -130,9 +138,9 @@ def main(argv=None):
                 print(f"longest prompt {longest} > max_length {args.max_length}, skip")
                 continue
             keys = torch.tensor([n for n, _ in batch], dtype=torch.int64)
-            _, texts = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys)
-            for (_, it), text in zip(batch, texts):
-                writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text},
+            _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
+            for (_, it), text, extra in zip(batch, texts, extras):
+                writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text, **extra},
                                         ensure_ascii=False) + "\n")
     return out_path
 

@@ -1934,6 +1934,23 @@ def constrain_logits_(logits, hist, hist_len, plan, prompt_len=None, num_beams: 
                         plan.grp_tok, plan.grp_eos, e_ids, e_val, e_cnt, int(num_beams), int(plan.min_new))
 
 
+def token_scores(logits, tok, k: int = 0):
+    """How sure was the model of token tok[r] on logits [R, V] (fp32 / bf16)?  -> (logp fp32 [R] = log_softmax(logits)[r,
+    tok[r]] — transformers' compute_transition_scores(..., normalize_logits=True) on `output_logits` —, entropy fp32 [R],
+    alt_id int32 [R, k], alt_logp fp32 [R, k]: the k <= 8 most likely ids, descending, ties to the lower id, id -1 / -inf
+    behind the V-th).  An id outside [0, V) scores NaN; a row with a NaN, a +inf or nothing but -inf gives NaN and ids -1."""
+    return L.token_scores(logits, tok.to(torch.int32), int(k))
+
+
+def token_scores_(logits, hist, hist_len, out, k: int = 0) -> None:
+    """`token_scores` behind a step kernel, without a gather: the token is the newest of the device history, hist[r,
+    hist_len[r] - 1], and its scores go to column hist_len[r] - 1 of `out`: an object with logp / entropy fp32 [R, S_hist]
+    and, for k > 0, alt_id int32 / alt_logp fp32 [R, S_hist, k] (`generation.TokenScores.buffers`).  Hand it the logits as
+    lm_head wrote them, not what a logits processor left of them."""
+    k = int(k)
+    L.token_scores_(logits, hist, hist_len, out.logp, out.entropy, out.alt_id if k else None, out.alt_logp if k else None, k)
+
+
 def beam_step(logits, state, penalty: float = 1.0, ngram: int = 0, eos=(), n_new: int = 1, length_penalty: float = 1.0,
               early_stopping=False, edits=None) -> None:
     """One step of HF's beam search (`_beam_search` of transformers) on the device: log_softmax, repetition penalty and

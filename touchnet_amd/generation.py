@@ -25,10 +25,19 @@ are edited in place, logit[t] = T(fp32(logit[t]) + total) in the logits' own dty
 fp32: HF's arithmetic), before penalty, n-gram ban and the warpers: HF's order.  Beam search: the kernel emits the edits and
 tn_beam_step_edits adds them to the log-probabilities, after log_softmax and before the penalty.  At most MAX_BIAS_SEQS
 sequences of at most MAX_BIAS_LEN ids.
+
+Confidences and N-best lists (`output_scores`, `top_alternatives`, `nbest`; all off by default, and then nothing of this
+runs).  Greedy, sampling and Kimi-Audio: one tn_token_scores launch per step behind the step kernel, in history mode, on the
+logits as lm_head wrote them (a `sequence_bias` plan edits a copy then): log-probability and entropy of the appended token and
+the k most likely ids, written to that token's history column of a `TokenScores` workspace that grows with the cache.  Beam
+search keeps sums, not per-token terms: `BeamState.nbest` reads the finished set, and the per-token scores of the returned
+hypotheses come from ONE teacher-forced packed forward behind the search, `score_continuations`, which is also the rescoring
+entry point.
 """
 from __future__ import annotations
 
 import json
+import math
 import os
 from dataclasses import dataclass, fields
 from typing import Callable, List, Optional, Sequence, Union
@@ -56,6 +65,10 @@ MAX_BIAS_SEQS, MAX_BIAS_LEN = 16384, 64    # tn_logits_constrain's limits: biase
 # what replaces the two refused keys that forbid tokens (NoBadWordsLogitsProcessor is a SequenceBiasLogitsProcessor at -inf)
 _FORBID_HINT = {k: "; forbid token sequences with sequence_bias instead: [[ids], -inf] per sequence, which is what "
                    "NoBadWordsLogitsProcessor reduces to" for k in ("bad_words_ids", "suppress_tokens")}
+# N-best lists are a knob of this decoder, not the HF key (which also multiplies sampled rows)
+_FORBID_HINT["num_return_sequences"] = ("; for the N best hypotheses of a beam search set this decoder's own knob instead: "
+                                        "nbest = N with num_beams >= N (GenerationConfig(nbest=N) or from_hf(..., nbest=N))")
+MAX_ALTERNATIVES = 8                       # tn_token_scores' limit: runner-up tokens per position
 
 
 def normalize_sequence_bias(value) -> Optional[dict]:
@@ -176,6 +189,11 @@ class ConstraintPlan:
                 torch.empty(rows, dtype=torch.int32, device=dev))
 
 
+def _check_alternatives(what: str, k) -> None:
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= MAX_ALTERNATIVES:
+        raise ValueError(f"{what}: top_alternatives = {k!r} must be an integer in [0, {MAX_ALTERNATIVES}]")
+
+
 @dataclass
 class GenerationConfig:
     """The knobs of the reference's generate() call (top_k / top_p / temperature are inert there: do_sample=False).
@@ -199,6 +217,30 @@ class GenerationConfig:
     early_stopping: Union[bool, str] = False  # True, False or "never" (HF's three heuristics)
     sequence_bias: Optional[dict] = None     # {tuple(ids): bias}: hotword boosts; -inf forbids a sequence (`hotword_bias`)
     min_new_tokens: int = 0                  # every eos id is held at -inf until this many tokens were generated
+    output_scores: bool = False              # per-token log-probability and entropy of the raw lm_head logits (`TokenScores`)
+    top_alternatives: int = 0                # 0 .. 8 most likely tokens per position with their log-probabilities (implies output_scores)
+    nbest: int = 1                           # beam search: the first `nbest` finished hypotheses (1 .. num_beams) — not HF's
+                                             # num_return_sequences key, which from_hf goes on refusing
+
+    def __post_init__(self):
+        self.check_scores()
+
+    def check_scores(self) -> None:
+        """What the three score knobs accept."""
+        _check_alternatives("generation config", self.top_alternatives)
+        n = self.nbest
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"generation config: nbest = {n!r} must be an integer >= 1")
+        if n > 1 and int(self.num_beams) <= 1:
+            raise ValueError(f"generation config: nbest = {n} needs beam search (num_beams > 1): greedy search and sampling "
+                             "follow one hypothesis")
+        if n > int(self.num_beams):
+            raise ValueError(f"generation config: nbest = {n} exceeds num_beams = {self.num_beams} (the finished set holds "
+                             "num_beams hypotheses)")
+
+    @property
+    def wants_scores(self) -> bool:
+        return bool(self.output_scores) or int(self.top_alternatives) > 0
 
     @classmethod
     def from_hf(cls, path_or_dict, **overrides) -> "GenerationConfig":
@@ -233,7 +275,10 @@ class GenerationConfig:
                   cache_chunk=int(num("cache_chunk", 1024)), num_beams=int(num("num_beams", 1) or 1),
                   length_penalty=float(num("length_penalty", 1.0)), early_stopping=num("early_stopping", False),
                   sequence_bias=normalize_sequence_bias(num("sequence_bias", None)),
-                  min_new_tokens=int(num("min_new_tokens", 0) or 0))
+                  min_new_tokens=int(num("min_new_tokens", 0) or 0),
+                  # this decoder's own knobs: overrides only (the file's `output_scores` means HF's processed scores)
+                  output_scores=bool(overrides.get("output_scores", False)),
+                  top_alternatives=overrides.get("top_alternatives", 0), nbest=overrides.get("nbest", 1))
         if cfg.min_new_tokens < 0:
             raise ValueError(f"generation config: min_new_tokens = {cfg.min_new_tokens} must be >= 0")
         if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
@@ -302,12 +347,19 @@ class KimiGenerationConfig:
     cache_chunk: int = 1024                  # new-token rows of the first KV-cache allocation (it doubles on demand)
     check_every: int = 16                    # steps between two host reads of the unfinished count
     seed: int = 0                            # Philox key of the draws (with the row key and the step)
+    output_scores: bool = False              # per-token log-probability and entropy of the raw lm_head logits (`TokenScores`)
+    top_alternatives: int = 0                # 0 .. 8 most likely tokens per position (implies output_scores)
 
     def __post_init__(self):
         self.check()
 
+    @property
+    def wants_scores(self) -> bool:
+        return bool(self.output_scores) or int(self.top_alternatives) > 0
+
     def check(self) -> None:
         """Refuses what tn_kimi_text_step refuses."""
+        _check_alternatives("Kimi generation config", self.top_alternatives)
         if not self.text_repetition_penalty > 0.0:
             raise ValueError(f"Kimi generation config: text_repetition_penalty {self.text_repetition_penalty} must be > 0")
         if not 1 <= int(self.text_repetition_window_size) <= KIMI_MAX_WINDOW:
@@ -375,6 +427,69 @@ class KVCache:
         self.k = [bigger(t) for t in self.k]
         self.v = [bigger(t) for t in self.v]
         self.hist = bigger(self.hist)
+
+
+@dataclass
+class TokenScores:
+    """How sure the model was of every generated token, from the logits as lm_head wrote them (transformers'
+    `output_logits`; no hotword edit, penalty or temperature): logp fp32 [B, N] = log_softmax(logits)[token] — equal to
+    compute_transition_scores(sequences, out.logits, normalize_logits=True) —, entropy fp32 [B, N] of the step's
+    distribution, alt_id int32 / alt_logp fp32 [B, N, k]: the k most likely tokens of the step, best first (ties to the
+    lower id).  confidence fp32 [B] = exp(mean logp) over a row's tokens up to and including its first eos (all of them
+    when it never finished).  Columns behind a row's end read 0 (ids: -1).  The same class is the in-loop workspace
+    (`buffers`): one column per HISTORY slot, prompt included, written by tn_token_scores in history mode."""
+    logp: torch.Tensor
+    entropy: torch.Tensor
+    alt_id: Optional[torch.Tensor] = None
+    alt_logp: Optional[torch.Tensor] = None
+    confidence: Optional[torch.Tensor] = None
+
+    @classmethod
+    def buffers(cls, rows: int, S: int, k: int, device) -> "TokenScores":
+        f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
+        return cls(logp=f(rows, S), entropy=f(rows, S), alt_logp=f(rows, S, k),
+                   alt_id=torch.full((rows, S, k), -1, dtype=torch.int32, device=device))
+
+    @property
+    def k(self) -> int:
+        return 0 if self.alt_id is None else int(self.alt_id.shape[-1])
+
+    def grow(self, S_new: int) -> None:
+        """More history columns, as KVCache.grow (contents kept)."""
+        S = self.logp.shape[1]
+        if S_new <= S:
+            return
+        new = TokenScores.buffers(self.logp.shape[0], S_new, self.k, self.logp.device)
+        for name in ("logp", "entropy", "alt_id", "alt_logp"):
+            getattr(new, name)[:, :S].copy_(getattr(self, name))
+            setattr(self, name, getattr(new, name))
+
+    def columns(self, idx: torch.Tensor) -> "TokenScores":
+        """The history columns idx int64 [B, N] of the workspace, as a result of N columns."""
+        i3 = idx[:, :, None].expand(-1, -1, self.k)
+        return TokenScores(logp=self.logp.gather(1, idx), entropy=self.entropy.gather(1, idx),
+                           alt_id=self.alt_id.gather(1, i3), alt_logp=self.alt_logp.gather(1, i3))
+
+    def close(self, n_tokens: torch.Tensor) -> "TokenScores":
+        """Blank the columns behind every row's n_tokens [B] tokens (the kernel scored padding there) and set `confidence`."""
+        N = self.logp.shape[1]
+        n = n_tokens.to(device=self.logp.device, dtype=torch.int64).clamp(max=N)
+        live = torch.arange(N, device=n.device)[None] < n[:, None]
+        self.logp = torch.where(live, self.logp, torch.zeros_like(self.logp))
+        self.entropy = torch.where(live, self.entropy, torch.zeros_like(self.entropy))
+        self.alt_id = torch.where(live[:, :, None], self.alt_id, torch.full_like(self.alt_id, -1))
+        self.alt_logp = torch.where(live[:, :, None], self.alt_logp, torch.zeros_like(self.alt_logp))
+        self.confidence = torch.exp(self.logp.sum(1) / n.clamp(min=1).to(torch.float32))
+        return self
+
+
+def _generated_lengths(ids: torch.Tensor, eos: Sequence[int]) -> torch.Tensor:
+    """[B, N] generated ids -> int64 [B]: the tokens up to and including a row's first eos, N when it has none."""
+    N = ids.shape[1]
+    if not len(eos) or N == 0:
+        return torch.full((ids.shape[0],), N, dtype=torch.int64, device=ids.device)
+    is_eos = torch.isin(ids, torch.tensor(list(eos), dtype=ids.dtype, device=ids.device))
+    return torch.where(is_eos.any(1), is_eos.to(torch.int8).argmax(1) + 1, torch.full_like(ids[:, 0], N))
 
 
 @dataclass
@@ -451,6 +566,28 @@ class BeamState:
         ids = self.fin_ids[::K].gather(1, idx.clamp(max=self.capacity - 1)).to(torch.int64)
         ids = torch.where(torch.arange(N, device=lens.device)[None] < n[:, None], ids, torch.full_like(ids, pad))
         return ids, self.fin_score[::K].clone()
+
+    def nbest(self, prompt_lens: Sequence[int], pad: int, n: int):
+        """-> (ids int64 [B, n, N]: every utterance's first `n` finished hypotheses behind its prompt, best first, `pad`
+        after their ends; scores fp32 [B, n]; count int64 [B]).  The finished set is kept best first and its empty slots
+        (fin_score <= -1e9) come last, so these are slots 0 .. n - 1.  An utterance that finished fewer than n hypotheses
+        says so in `count`; its remaining entries are all `pad` with score -inf.  (transformers' num_return_sequences fills
+        such entries with whatever rows its scorer has left; here they are marked.)"""
+        K = self.num_beams
+        if not 1 <= int(n) <= K:
+            raise ValueError(f"nbest: n = {n} must be in [1, num_beams = {K}]")
+        B = self.fin_len.shape[0] // K
+        dev = self.hist.device
+        lens = torch.tensor(list(prompt_lens), dtype=torch.int64, device=dev)
+        score = self.fin_score.view(B, K)[:, :n]
+        have = score > -1.0e9
+        m = torch.where(have, self.fin_len.view(B, K)[:, :n].to(torch.int64) - lens[:, None], torch.zeros_like(lens[:, None]))
+        N = max(int(m.max()), 0)
+        col = torch.arange(N, device=dev)
+        idx = (lens[:, None, None] + col[None, None]).clamp(max=self.capacity - 1).expand(B, n, N)
+        ids = self.fin_ids.view(B, K, -1)[:, :n].gather(2, idx).to(torch.int64)
+        ids = torch.where(col[None, None] < m[:, :, None], ids, torch.full_like(ids, pad))
+        return ids, torch.where(have, score, torch.full_like(score, -math.inf)), have.sum(1)
 
 
 def _parts(model):
@@ -600,7 +737,7 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
 
 @torch.no_grad()
 def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, return_cache: bool = False,
-             row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None):
+             row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None, return_scores: bool = False):
     """Greedy, sampled or beam-search generation for a batch of prompts -> int64 [B, N] generated ids (the prompt
     excluded), `pad` after a row's eos — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM,
     Qwen2AudioPackedForConditionalGeneration (with its `embed` builder) or PackedCausalLM, bf16, on the device.
@@ -610,8 +747,17 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     the draws with cfg.seed and the step: a row draws the same tokens whatever batch it is decoded in.
 
     With cfg.num_beams > 1 (and no do_sample): HF's beam search, tn_beam_step per token; the result is every utterance's
-    best finished hypothesis, and `return_cache` hands out the BeamState that holds the scores."""
+    best finished hypothesis, and `return_cache` hands out the BeamState that holds the scores.
+
+    `return_scores`, cfg.output_scores or cfg.top_alternatives > 0: a `TokenScores` of the generated tokens comes back as
+    the last element, (ids, scores) or (ids, cache, scores) — one tn_token_scores launch per step on the raw logits (when a
+    `sequence_bias` plan edits the logits, it edits a copy).  cfg.nbest > 1 (beam search): (ids [B, nbest, N], scores
+    [B, nbest], count [B]) of `BeamState.nbest` in place of ids, the TokenScores then [B * nbest, N] in that order.  With
+    no knob set nothing of this runs."""
     cfg = cfg or GenerationConfig()
+    cfg.check_scores()
+    scored = bool(return_scores) or cfg.wants_scores
+    n_alt = int(cfg.top_alternatives)
     lm, proj_w = _parts(model)
     _check_model(model, lm)
     if len(prompts) == 0:
@@ -625,10 +771,12 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     lens = [int(t.numel()) for t in prompts.input_ids]
     n_new = cfg.new_tokens(max(lens))
     if n_new <= 0:
+        if scored or int(cfg.nbest) > 1:
+            raise ValueError("generate: no room for a new token (max_length <= the longest prompt): nothing to score")
         return torch.empty(B, 0, dtype=torch.int64, device=device)
     penalty, ngram = float(cfg.repetition_penalty), int(cfg.no_repeat_ngram_size)
     if int(cfg.num_beams) != 1:
-        return _beam_search(lm, proj_w, prompts, cfg, eos, pad, lens, n_new, device, embed, return_cache)
+        return _beam_search(model, lm, proj_w, prompts, cfg, eos, pad, lens, n_new, device, embed, return_cache, scored)
     greedy = not cfg.do_sample and len(eos) <= 1
     if not greedy:
         if ngram > 0:
@@ -647,9 +795,13 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     S_full = max(lens) + n_new
     plan = ConstraintPlan.build(cfg.sequence_bias, cfg.min_new_tokens, eos, int(c.vocab_size), device)
     prompt_len = torch.tensor(lens, dtype=torch.int32, device=device) if plan is not None else None
+    scores = TokenScores.buffers(B, cache.capacity, n_alt, device) if scored else None
 
-    def step(logits):
+    def step(raw):
+        logits = raw
         if plan is not None:                       # HF's order: SequenceBiasLogitsProcessor before the repetition penalty
+            if scored:
+                logits = raw.clone()               # the scores are those of lm_head's logits, not of the edited ones
             F.constrain_logits_(logits, cache.hist, cache.hist_len, plan, prompt_len)
         if greedy:
             F.greedy_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
@@ -657,6 +809,8 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         else:
             F.sample_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished, penalty,
                           cfg.do_sample, cfg.temperature, cfg.top_k, cfg.top_p, cfg.seed, eos, pad, row_key=row_keys)
+        if scored:                                 # the token the step kernel has just appended, in its history column
+            F.token_scores_(raw, cache.hist, cache.hist_len, scores, n_alt)
 
     step(_prefill(lm, proj_w, prompts, cache, device, embed))
     steps = 1
@@ -666,6 +820,8 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         # the next step writes key / value slot lens[b] + steps - 1 and history slot lens[b] + steps
         if max(lens) + steps >= cache.capacity:
             cache.grow(min(S_full, 2 * cache.capacity))
+            if scored:
+                scores.grow(cache.capacity)
         step(decode_logits(lm, cache))
         steps += 1
     idx = torch.tensor(lens, dtype=torch.int64, device=device)[:, None] + torch.arange(steps, device=device)[None]
@@ -675,10 +831,14 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         is_eos = torch.isin(out, torch.tensor(eos, dtype=torch.int64, device=device))
         first = torch.where(is_eos.any(1), is_eos.to(torch.int8).argmax(1), torch.full_like(out[:, 0], steps - 1))
         out = out[:, :int(first.max()) + 1]
+    if scored:
+        result = scores.columns(idx[:, :out.shape[1]]).close(_generated_lengths(out, eos))
+        return (out, cache, result) if return_cache else (out, result)
     return (out, cache) if return_cache else out
 
 
-def _beam_search(lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos, pad, lens, n_new, device, embed, return_cache):
+def _beam_search(model, lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos, pad, lens, n_new, device, embed,
+                 return_cache, scored: bool = False):
     """generate() with num_beams > 1: HF's beam search, one tn_beam_step per token.  The prompts are prefilled once, into
     the first row of every utterance; the K beams of an utterance read them, and every later key, through the table."""
     cfg.check_beams(eos)
@@ -710,8 +870,107 @@ def _beam_search(lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos, pad, 
             st.grow(min(S_full, 2 * st.capacity))
         step(decode_logits(lm, st, table=st.src))
         steps += 1
-    out, _ = st.best(lens, pad)
-    return (out, st) if return_cache else out
+    n_best = int(cfg.nbest)
+    if n_best == 1 and not scored:
+        out, _ = st.best(lens, pad)
+        return (out, st) if return_cache else out
+    # N-best lists and per-token scores read the finished set; the scores of every returned hypothesis come from ONE
+    # teacher-forced forward behind the search (tn_beam_step keeps sums, not per-token terms)
+    ids, hyp_score, count = st.nbest(lens, pad, n_best)
+    out = (ids, hyp_score, count) if n_best > 1 else (ids[:, 0],)
+    if return_cache:
+        out += (st,)
+    if scored:
+        rows = ids.reshape(len(lens) * n_best, -1)
+        n_tok = _generated_lengths(rows, eos)
+        n_tok = torch.where((hyp_score.reshape(-1) > -math.inf), n_tok, torch.zeros_like(n_tok))     # (missing hypotheses)
+        repeated = Prompts(input_ids=[t for t in prompts.input_ids for _ in range(n_best)],
+                           input_features=None if prompts.input_features is None
+                           else [f for f in prompts.input_features for _ in range(n_best)])
+        conts = [r[:int(n)].cpu() for r, n in zip(rows, n_tok.tolist())]
+        if embed is not None:                      # the builder was made for the prompts alone: ask it for the documents'
+            rebuild = getattr(embed, "for_documents", None)
+            if rebuild is None:
+                raise ValueError("generate: per-token scores of a beam search need an `embed` builder that offers "
+                                 "for_documents(documents, repeat) (models.qwen2_audio.inference_qwen2_audio.audio_embedder)")
+            embed = rebuild(with_continuations(repeated, conts), n_best)
+        out += (score_continuations(model, repeated, conts, k=int(cfg.top_alternatives), embed=embed),)
+    return out[0] if len(out) == 1 else out
+
+
+def with_continuations(prompts: Prompts, continuations) -> Prompts:
+    """Every prompt with its continuation appended: the documents `score_continuations` packs (feature rows of the
+    continuation's slots are zero).  An `embed` builder for those documents is built from this."""
+    if len(continuations) != len(prompts):
+        raise ValueError(f"score_continuations: {len(continuations)} continuations for {len(prompts)} prompts")
+    conts = [torch.as_tensor(c, dtype=torch.int64).reshape(-1).cpu() for c in continuations]
+    ids = [torch.cat([p.reshape(-1).cpu().to(torch.int64), c]) for p, c in zip(prompts.input_ids, conts)]
+    feats = None
+    if prompts.input_features is not None:
+        feats = [torch.cat([f, f.new_zeros(c.numel(), f.shape[1])]) for f, c in zip(prompts.input_features, conts)]
+    return Prompts(input_ids=ids, input_features=feats)
+
+
+@torch.no_grad()
+def score_continuations(model, prompts: Prompts, continuations, k: int = 0, embed: Optional[EmbedFn] = None,
+                        rows_per_chunk: int = 4096) -> TokenScores:
+    """Teacher-forced scores of given continuations — the rescoring entry point: `TokenScores` [B, N] (N the longest
+    continuation; columns behind a shorter one read 0 / -1) of continuation b (token ids, possibly none) behind prompt b.
+    One packed, document-masked forward over prompt + continuation, the prefill's construction with `keep_rows` = the row
+    in front of every continuation token; lm_head runs on at most `rows_per_chunk` of those rows at a time and
+    tn_token_scores (token mode) scores each chunk, so the [rows, V] logits never exist as a whole.  `confidence` is
+    exp(mean logp) over the whole continuation (1 for an empty one).  `model` as for `generate`; `embed`: the embedding
+    builder of the documents `with_continuations(prompts, continuations)` (Qwen2-Audio: audio_embedder over them)."""
+    _check_alternatives("score_continuations", k)
+    if int(rows_per_chunk) < 1:
+        raise ValueError(f"score_continuations: rows_per_chunk = {rows_per_chunk} must be >= 1")
+    lm, proj_w = _parts(model)
+    _check_model(model, lm)
+    if len(prompts) == 0:
+        raise ValueError("score_continuations: no prompts")
+    if any(int(t.numel()) == 0 for t in prompts.input_ids):
+        raise ValueError("score_continuations: empty prompt")
+    device = lm.model.embed_tokens.weight.device
+    docs = with_continuations(prompts, continuations)
+    plens = [int(t.numel()) for t in prompts.input_ids]
+    lens = [int(t.numel()) for t in docs.input_ids]
+    clens = [n - p for n, p in zip(lens, plens)]
+    B, T, N = len(lens), sum(lens), max(clens)
+    result = TokenScores.buffers(B, N, int(k), device)
+    n_rows = sum(clens)
+    if n_rows == 0:
+        return result.close(torch.tensor(clens))
+    Tp = (T + 255) // 256 * 256
+    ids = torch.zeros(Tp, dtype=torch.int64)
+    pos = torch.zeros(Tp, dtype=torch.int64)
+    doc = torch.zeros(Tp, dtype=torch.int32)
+    rows, toks, slot = [], [], []
+    o = 0
+    for b, t in enumerate(docs.input_ids):
+        n, p, c = lens[b], plens[b], clens[b]
+        ids[o:o + n] = t
+        pos[o:o + n] = torch.arange(n)
+        doc[o:o + n] = b + 1
+        rows.append(torch.arange(c) + (o + p - 1))                # the row in front of continuation token j
+        toks.append(t[p:])
+        slot.append(torch.arange(c) + b * N)
+        o += n
+    ids, pos, doc, rows, toks, slot = (x.to(device, non_blocking=True) for x in
+                                       (ids, pos, doc, torch.cat(rows), torch.cat(toks).to(torch.int32), torch.cat(slot)))
+    if embed is not None:
+        emb = embed(ids, lens, Tp)
+    else:
+        emb = _embed_touch_audio(lm, proj_w, docs, ids, lens, Tp, device)
+    h = lm.model(inputs_embeds=emb[None], position_ids=pos[None], attention_mask=doc[None], keep_rows=rows)[0]   # [n_rows, H]
+    step = int(rows_per_chunk)
+    for a in range(0, n_rows, step):
+        logp, ent, alt_id, alt_logp = F.token_scores(lm.lm_head(h[a:a + step]), toks[a:a + step], int(k))
+        at = slot[a:a + step]
+        result.logp.view(-1).index_copy_(0, at, logp)
+        result.entropy.view(-1).index_copy_(0, at, ent)
+        result.alt_id.view(B * N, -1).index_copy_(0, at, alt_id)
+        result.alt_logp.view(B * N, -1).index_copy_(0, at, alt_logp)
+    return result.close(torch.tensor(clens))
 
 
 def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[int]]:
@@ -723,6 +982,69 @@ def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[
         cut = next((i for i, t in enumerate(r) if t in stop), len(r))
         rows.append(r[:cut])
     return rows
+
+
+# ------------------------------------------------------------------------------------ command-line side of the scores
+def add_score_arguments(ap, nbest: bool = True) -> None:
+    """--output_scores / --top_alternatives (and --nbest) of the inference command lines."""
+    ap.add_argument("--output_scores", action="store_true",
+                    help='records gain "confidence" (exp of the mean token log-probability), "token_logprobs" and '
+                         '"token_entropy": one entry per generated token up to and including the eos, from the logits as '
+                         "lm_head wrote them (no hotword edit, penalty or temperature)")
+    ap.add_argument("--top_alternatives", type=int, default=0, metavar="K",
+                    help=f'records gain "alternatives": per token its K <= {MAX_ALTERNATIVES} most likely ids as [id, logp] '
+                         "(implies --output_scores)")
+    if nbest:
+        ap.add_argument("--nbest", type=int, default=1, metavar="N",
+                        help='beam search (--num_beams >= N): records gain "nbest", the N best finished hypotheses as '
+                             '{"predict_ids", "predict", "score"[, "confidence"]}, rank 1 being the prediction itself; an '
+                             "utterance that finished fewer lists fewer")
+
+
+def _json_number(x: float):
+    return x if math.isfinite(x) else None
+
+
+def score_fields(scores: TokenScores, row: int, n: Optional[int] = None, keep: Optional[Sequence[int]] = None) -> dict:
+    """The record keys of one row of a `TokenScores` (tensors anywhere): "confidence", "token_logprobs", "token_entropy"
+    and, with alternatives, "alternatives" ([[id, logp], ...] per token; a logp of -inf reads null).  `n`: the row's tokens
+    (default: all columns); `keep`: the columns to list instead (Kimi-Audio: the tokens that are text)."""
+    cols = list(range(scores.logp.shape[1] if n is None else int(n))) if keep is None else [int(c) for c in keep]
+    lp, ent = scores.logp[row].tolist(), scores.entropy[row].tolist()
+    out = {"confidence": _json_number(float(scores.confidence[row])),
+           "token_logprobs": [_json_number(lp[c]) for c in cols], "token_entropy": [_json_number(ent[c]) for c in cols]}
+    if scores.k:
+        ai, al = scores.alt_id[row].tolist(), scores.alt_logp[row].tolist()
+        out["alternatives"] = [[[int(i), _json_number(v)] for i, v in zip(ai[c], al[c]) if i >= 0] for c in cols]
+    return out
+
+
+def record_fields(out, cfg: GenerationConfig, eos: Sequence[int]):
+    """What generate() returned under `cfg` -> (per utterance the ids in front of the first eos, per utterance the extra
+    record keys as a dict: the `score_fields` of the prediction and "nbest", a list of {"predict_ids", "score"[,
+    "confidence"]} — the command line adds "predict").  No knob set: empty dicts."""
+    n_best, scored = int(cfg.nbest), cfg.wants_scores
+    if n_best == 1 and not scored:
+        return trim_at_eos(out, eos), [{} for _ in range(out.shape[0])]
+    parts = list(out) if isinstance(out, tuple) else [out]
+    ts = parts.pop() if scored else None
+    if n_best > 1:
+        ids3, hyp_score, count = (t.cpu() for t in parts[:3])
+    else:
+        ids3, hyp_score, count = parts[0].cpu()[:, None], None, None
+    B = ids3.shape[0]
+    n_tok = _generated_lengths(ids3.reshape(B * n_best, -1), eos).tolist()
+    top = trim_at_eos(ids3[:, 0], eos)
+    extras = []
+    for b in range(B):
+        extra = score_fields(ts, b * n_best, n_tok[b * n_best]) if scored else {}
+        if n_best > 1:
+            hyps = trim_at_eos(ids3[b, :int(count[b])], eos)
+            extra["nbest"] = [dict(predict_ids=h, score=float(hyp_score[b, j]),
+                                   **({"confidence": _json_number(float(ts.confidence[b * n_best + j]))} if scored else {}))
+                              for j, h in enumerate(hyps)]
+        extras.append(extra)
+    return top, extras
 
 
 # ------------------------------------------------------------------------------------ command-line side of the constraints

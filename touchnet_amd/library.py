@@ -1290,11 +1290,83 @@ def _(ref_tok, hyp_tok, desc):
             ref_tok.new_empty(ref_tok.numel() + hyp_tok.numel(), dtype=torch.uint8))
 
 
-OPS = ("rmsnorm_fwd", "rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
+TOKEN_SCORES_MAX_ALT, TOKEN_SCORES_MAX_VOCAB = 8, 262144          # tn_token_scores' limits
+
+
+def _token_scores_logits(what: str, logits: Tensor, k: int) -> Tensor:
+    _no_grad_inputs(what, logits)
+    if logits.dim() != 2 or not 1 <= logits.shape[1] <= TOKEN_SCORES_MAX_VOCAB:
+        raise _C.KernelError(f"{what}: logits [R, V] with 1 <= V <= {TOKEN_SCORES_MAX_VOCAB}")
+    if not 0 <= k <= TOKEN_SCORES_MAX_ALT:
+        raise _C.KernelError(f"{what}: k = {k} must be in [0, {TOKEN_SCORES_MAX_ALT}]")
+    return _c(logits)
+
+
+@custom_op(f"{NS}::token_scores", mutates_args=(), device_types="cuda")
+def token_scores(logits: Tensor, tok: Tensor, k: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Per-token confidences in token mode (tn_token_scores): logits [R, V] fp32 / bf16, tok int32 [R] -> logp fp32 [R] =
+    log_softmax(logits)[r, tok[r]] (NaN for an id outside [0, V)), entropy fp32 [R], alt_id int32 [R, k] (the k most
+    likely ids, ties to the lower id; -1 behind the V-th) and alt_logp fp32 [R, k].  A row with a NaN or +inf, or with
+    nothing but -inf: NaN and ids -1."""
+    logits = _token_scores_logits("token_scores", logits, k)
+    R, V = logits.shape
+    if tok.dtype != torch.int32 or tuple(tok.shape) != (R,):
+        raise _C.KernelError("token_scores: int32 tok [R]")
+    tok, dev = _c(tok), logits.device
+    logp = torch.empty(R, dtype=torch.float32, device=dev)
+    entropy = torch.empty(R, dtype=torch.float32, device=dev)
+    alt_id = torch.empty(R, k, dtype=torch.int32, device=dev)
+    alt_logp = torch.empty(R, k, dtype=torch.float32, device=dev)
+    if R:
+        _C.check(_lib().tn_token_scores(_p(logits), _p(tok), None, None, _p(logp), _p(entropy), _p(alt_id) if k else None,
+                                        _p(alt_logp) if k else None, R, V, 0, int(k), _C.dcode(logits), _cur()),
+                 "tn_token_scores")
+    return logp, entropy, alt_id, alt_logp
+
+
+@token_scores.register_fake
+def _(logits, tok, k):
+    R = logits.shape[0]
+    return (logits.new_empty(R, dtype=torch.float32), logits.new_empty(R, dtype=torch.float32),
+            logits.new_empty(R, k, dtype=torch.int32), logits.new_empty(R, k, dtype=torch.float32))
+
+
+@custom_op(f"{NS}::token_scores_", mutates_args=("logp", "entropy", "alt_id", "alt_logp"), device_types="cuda")
+def token_scores_(logits: Tensor, hist: Tensor, hist_len: Tensor, logp: Tensor, entropy: Tensor, alt_id: Optional[Tensor],
+                  alt_logp: Optional[Tensor], k: int) -> None:
+    """Per-token confidences in history mode (tn_token_scores), one launch behind a step kernel: logits [R, V], hist int32
+    [R, S_hist], hist_len int32 [R]; the token is hist[r, hist_len[r] - 1] and its scores are written to column
+    hist_len[r] - 1 of logp / entropy fp32 [R, S_hist] and alt_id int32 / alt_logp fp32 [R, S_hist, k] (None with k == 0).
+    A row whose hist_len is outside [1, S_hist] writes nothing."""
+    logits = _token_scores_logits("token_scores_", logits, k)
+    R, V = logits.shape
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != R or hist.shape[1] < 1 or not hist.is_contiguous():
+        raise _C.KernelError("token_scores_: int32 contiguous hist [R, S_hist]")
+    S = hist.shape[1]
+    if hist_len.dtype != torch.int32 or tuple(hist_len.shape) != (R,) or not hist_len.is_contiguous():
+        raise _C.KernelError("token_scores_: int32 hist_len [R]")
+    for name, t, dt, shape in (("logp", logp, torch.float32, (R, S)), ("entropy", entropy, torch.float32, (R, S)),
+                               ("alt_id", alt_id, torch.int32, (R, S, k)), ("alt_logp", alt_logp, torch.float32, (R, S, k))):
+        if t is None and k == 0 and name.startswith("alt_"):
+            continue
+        if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
+            raise _C.KernelError(f"token_scores_: {name} must be a contiguous {dt} tensor of shape {list(shape)}")
+    if R:
+        _C.check(_lib().tn_token_scores(_p(logits), None, _p(hist), _p(hist_len), _p(logp), _p(entropy),
+                                        _p(alt_id) if k else None, _p(alt_logp) if k else None, R, V, S, int(k),
+                                        _C.dcode(logits), _cur()), "tn_token_scores")
+
+
+@token_scores_.register_fake
+def _(logits, hist, hist_len, logp, entropy, alt_id, alt_logp, k):
+    return None
+
+
+OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fwd", "swiglu_bwd", "gelu_fwd",
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked",
        "attn_bwd_rope", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
        "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
-       "constrain_logits_")
+       "constrain_logits_", "token_scores", "token_scores_")

@@ -149,27 +149,69 @@ def evaluate(ref_utts: Dict[str, Utterance], hyp_utts: Dict[str, Utterance], tok
     refs = [tokenize_text(ref_utts[u].text, tokenizer) for u in uids]
     hyps = [tokenize_text(hyp_utts[u].text, tokenizer) for u in uids]
     aligned = align_fn([to_ids(t) for t in refs], [to_ids(t) for t in hyps])
-    for uid, ref, hyp, (c, s, i, d, ops) in zip(uids, refs, hyps, aligned):
-        ter = token_error_rate(c, s, i, d)
-        res.details.append(f'{{"uid":{uid}, "score":{0.0 - (s + i + d)}, "ter":{ter:.2f}, "cor":{c}, "sub":{s}, "ins":{i}, '
-                           f'"del":{d}}}')
-        res.details.extend(alignment_lines(ref, hyp, [int(k) for k in ops]))
-        res.C, res.S, res.I, res.D = res.C + c, res.S + s, res.I + i, res.D + d
-        res.num_utts_with_error += ter > 0
+    for uid, ref, hyp, pair in zip(uids, refs, hyps, aligned):
+        _count(res, uid, ref, hyp, pair)
+    return _close(res)
+
+
+def _count(res: EvaluationResult, uid: str, ref: Sequence[str], hyp: Sequence[str], pair) -> None:
+    """one aligned utterance into the result: its detail lines and its counts"""
+    c, s, i, d, ops = pair
+    ter = token_error_rate(c, s, i, d)
+    res.details.append(f'{{"uid":{uid}, "score":{0.0 - (s + i + d)}, "ter":{ter:.2f}, "cor":{c}, "sub":{s}, "ins":{i}, '
+                       f'"del":{d}}}')
+    res.details.extend(alignment_lines(ref, hyp, [int(k) for k in ops]))
+    res.C, res.S, res.I, res.D = res.C + c, res.S + s, res.I + i, res.D + d
+    res.num_utts_with_error += ter > 0
+
+
+def _close(res: EvaluationResult) -> EvaluationResult:
     res.sentence_error_rate = 100.0 * res.num_utts_with_error / res.num_eval_utts
     res.token_error_rate = token_error_rate(res.C, res.S, res.I, res.D)
     return res
+
+
+def evaluate_oracle(ref_utts: Dict[str, Utterance], hyp_sets: Sequence[Dict[str, Utterance]], tokenizer: str,
+                    align_fn: Optional[Callable] = None) -> EvaluationResult:
+    """The oracle error rate of an N-best list: `hyp_sets` holds the hypothesis files in rank order (the scored file
+    first); for every utterance that `evaluate` scores for the first set, the hypothesis with the fewest errors (S + I + D)
+    among the sets that hold its key — ties to the earlier set, a set without the key is skipped — is the one counted.  All
+    (utterance, set) pairs are aligned in ONE `align_fn` call.  The record's utterance counts are the first set's."""
+    align_fn = align_fn or device_align
+    first = hyp_sets[0]
+    res = EvaluationResult(num_ref_utts=len(ref_utts), num_hyp_utts=len(first))
+    uids = [u for u in sorted(first) if u in ref_utts and ref_utts[u].text.strip()]
+    res.num_hyp_without_ref = sum(u not in ref_utts for u in first)
+    res.num_eval_utts = len(uids)
+    if not uids:
+        raise ValueError("no hypothesis has a non-empty reference: there is nothing to score")
+    ids: Dict[str, int] = {}
+    to_ids = lambda tokens: [ids.setdefault(t, len(ids)) for t in tokens]
+    pairs = [(u, n) for u in uids for n, hs in enumerate(hyp_sets) if u in hs]
+    refs = {u: tokenize_text(ref_utts[u].text, tokenizer) for u in uids}
+    hyps = [tokenize_text(hyp_sets[n][u].text, tokenizer) for u, n in pairs]
+    aligned = align_fn([to_ids(refs[u]) for u, _ in pairs], [to_ids(h) for h in hyps])
+    best: Dict[str, int] = {}
+    for k, ((u, _), (c, s, i, d, _ops)) in enumerate(zip(pairs, aligned)):
+        if u not in best or s + i + d < sum(aligned[best[u]][1:4]):          # (strictly fewer: ties stay with the earlier set)
+            best[u] = k
+    for u in uids:
+        _count(res, u, refs[u], hyps[best[u]], aligned[best[u]])
+    return _close(res)
 
 
 def extract_trans_and_pred(jsonl_path: str, warn=None) -> Tuple[str, str]:
     """One decoder output file (a `part_i_of_n` or their concatenation `final.jsonl`) -> `trans.txt` and `raw_rec.txt` beside
     it, the scorer's two inputs.  A line is {"label": a JSON string holding `key` and `txt`, "predict": text, or a JSON
     object with `transcription`}; the first line of a key wins; a prediction that is empty once its spaces are removed
-    leaves no `raw_rec.txt` line; a line that cannot be read is reported to `warn` and skipped."""
+    leaves no `raw_rec.txt` line; a line that cannot be read is reported to `warn` and skipped.  Records with an "nbest" list
+    (the decoders' --nbest) also leave `raw_rec.2.txt` .. `raw_rec.N.txt`, the lower-ranked hypotheses in the same format
+    (`nbest_rec_path`), so the text normaliser applies to each file as it is."""
     warn = warn or (lambda message: None)
     out_dir = os.path.dirname(jsonl_path)
     trans_path, rec_path = os.path.join(out_dir, "trans.txt"), os.path.join(out_dir, "raw_rec.txt")
     seen = set()
+    ranked = {}                                                   # rank (2 ..) -> the open raw_rec.{rank}.txt
     with open(jsonl_path, "r", encoding="utf-8") as fin, open(trans_path, "w", encoding="utf-8") as ftrans, \
             open(rec_path, "w", encoding="utf-8") as frec:
         for line in fin:
@@ -192,9 +234,24 @@ def extract_trans_and_pred(jsonl_path: str, warn=None) -> Tuple[str, str]:
                 ftrans.write(f"{key} {txt}\n")
                 if text.replace(" ", ""):
                     frec.write(f"{key} {text}\n")
+                for rank, hyp in enumerate(record.get("nbest") or [], 1):
+                    if rank == 1:                                 # rank 1 is the prediction itself: raw_rec.txt
+                        continue
+                    if rank not in ranked:
+                        ranked[rank] = open(nbest_rec_path(jsonl_path, rank), "w", encoding="utf-8")
+                    if str(hyp["predict"]).replace(" ", ""):
+                        ranked[rank].write(f"{key} {hyp['predict']}\n")
             except Exception as e:                                # noqa: BLE001  (a damaged line costs one utterance, not the run)
                 warn(f"skipping a line of {jsonl_path}: {e!r}")
+    for f in ranked.values():
+        f.close()
     return trans_path, rec_path
+
+
+def nbest_rec_path(jsonl_path: str, rank: int) -> str:
+    """`raw_rec.{rank}.txt` beside a decoder output file: the rank-th hypothesis of every record that carries an "nbest"
+    list of at least that length, in raw_rec.txt's format (rank 1 is raw_rec.txt itself)."""
+    return os.path.join(os.path.dirname(jsonl_path), f"raw_rec.{int(rank)}.txt")
 
 
 def main(argv=None) -> int:
@@ -209,6 +266,10 @@ def main(argv=None) -> int:
     ap.add_argument("--jsonl", type=str, nargs="+", metavar="FILE",
                     help="decoder outputs (part_i_of_n / final.jsonl): write trans.txt and raw_rec.txt beside each one; alone, "
                          "nothing is scored (text normalisation comes between the two steps)")
+    ap.add_argument("--oracle", type=str, nargs="+", metavar="FILE", default=None,
+                    help="further hypothesis files of the same utterances (raw_rec.2.txt ...): after the normal output, the "
+                         "error rate of the per-utterance best hypothesis among --hyp and these, ties to the earlier file, "
+                         "printed with the prefix `oracle: `")
     ap.add_argument("result_file", type=str, nargs="?")
     args = ap.parse_args(argv)
     logging.basicConfig(stream=sys.stderr, level=logging.INFO, format="[%(levelname)s] %(message)s")
@@ -227,4 +288,9 @@ def main(argv=None) -> int:
         res.write_details(fo)
     print(res.to_json())
     print(res.to_kaldi())
+    if args.oracle:
+        sets = [load_utterances(hyp, args.hyp_format)] + [load_utterances(p, args.hyp_format) for p in args.oracle]
+        best = evaluate_oracle(load_utterances(ref, args.ref_format), sets, args.tokenizer)
+        print("oracle: " + best.to_json())
+        print("".join(f"oracle: {line}\n" for line in best.to_kaldi().splitlines()))
     return 0

@@ -129,14 +129,18 @@ def kimi_embedder(model, prompts: KimiPrompts):
 
 @torch.no_grad()
 def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfig] = None,
-                  row_keys: Optional[torch.Tensor] = None, return_raw: bool = False):
+                  row_keys: Optional[torch.Tensor] = None, return_raw: bool = False, return_scores: bool = False):
     """MoonshotKimiaForCausalLM.generate() for a batch of prompts -> per utterance the text ids it returns: what the row
     emitted before its `<|im_kimia_text_eos|>`, blanks and ids >= kimia_token_offset dropped.  `model`:
     KimiAudioPackedForCausalLM, bf16, on the device.  `row_keys` int64 [B] (default arange(B)) key the draws of a sampled
     run with cfg.seed and the step.  `return_raw`: also the raw tokens int64 [B, steps] of every step (eos and blanks
-    included) and the KV cache."""
+    included) and the KV cache.  `return_scores`, cfg.output_scores or cfg.top_alternatives > 0: a generation.TokenScores
+    over the raw tokens [B, steps] (one tn_token_scores launch per step on lm_head's logits) comes back as the last
+    element; its confidence covers a row's tokens up to and including its eos."""
     cfg = cfg or KimiGenerationConfig()
     cfg.check()
+    scored = bool(return_scores) or cfg.wants_scores
+    n_alt = int(cfg.top_alternatives)
     lm = _TextDecoder(model)
     G._check_model(model, lm)
     B = len(prompts)
@@ -152,6 +156,8 @@ def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfi
     if not 0 <= blank < c.vocab_size:
         raise ValueError(f"generate_kimi: kimia_text_blank {blank} is outside the vocabulary ({c.vocab_size})")
     n_new = cfg.new_tokens(max(lens))
+    if n_new <= 0 and scored:
+        raise ValueError("generate_kimi: no room for a new token: nothing to score")
     if n_new <= 0:
         return ([[] for _ in range(B)], torch.empty(B, 0, dtype=torch.int64, device=device), None) if return_raw \
             else [[] for _ in range(B)]
@@ -166,11 +172,14 @@ def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfi
     S_full = max(lens) + n_new
     prompt_len = torch.tensor(lens, dtype=torch.int32, device=device)
     x_next = torch.empty(B, c.hidden_size, dtype=torch.bfloat16, device=device)
+    scores = G.TokenScores.buffers(B, cache.capacity, n_alt, device) if scored else None
 
     def step(logits):
         F.kimi_text_step(logits, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
                          prompt_len, w, x_next, cfg.text_repetition_penalty, cfg.text_repetition_window_size,
                          cfg.text_temperature, cfg.text_top_k, cfg.seed, eos, blank, blank, row_key=row_keys)
+        if scored:                                 # the token the step kernel has just appended, in its history column
+            F.token_scores_(logits, cache.hist, cache.hist_len, scores, n_alt)
 
     step(G._prefill(lm, None, Prompts(input_ids=list(prompts.text_ids)), cache, device, kimi_embedder(model, prompts)))
     steps = 1
@@ -179,26 +188,43 @@ def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfi
             break
         if max(lens) + steps >= cache.capacity:
             cache.grow(min(S_full, 2 * cache.capacity))
+            if scored:
+                scores.grow(cache.capacity)
         step(G.decode_logits(lm, cache, inputs_embeds=x_next))
         steps += 1
     idx = prompt_len.to(torch.int64)[:, None] + torch.arange(steps, device=device)[None]
     raw = cache.hist.gather(1, idx).to(torch.int64)
     off = int(c.kimia_token_offset)
     out = [[t for t in row if t != blank and t != eos and t < off] for row in raw.tolist()]
+    if scored:
+        result = scores.columns(idx).close(G._generated_lengths(raw, [eos]))
+        return (out, raw, cache, result) if return_raw else (out, result)
     return (out, raw, cache) if return_raw else out
 
 
 def transcribe(model, wavs: Sequence[torch.Tensor], tokenizer, instruct: str = DEFAULT_INSTRUCT,
-               cfg: Optional[KimiGenerationConfig] = None, row_keys: Optional[torch.Tensor] = None
-               ) -> Tuple[List[List[int]], List[str]]:
+               cfg: Optional[KimiGenerationConfig] = None, row_keys: Optional[torch.Tensor] = None, details: bool = False):
     """Transcripts of a batch of utterances (int16 PCM or float waveforms, 16 kHz) -> (the text ids generate() returns,
-    their text: `tokenizer.detokenize(ids)` as in the reference's script, `decode` where a tokenizer has no such method)."""
+    their text: `tokenizer.detokenize(ids)` as in the reference's script, `decode` where a tokenizer has no such method).
+    `details`: a third element, per utterance the extra record keys that cfg.output_scores / top_alternatives ask for
+    (generation.score_fields): the per-token lists cover the tokens that are text — what `ids` holds —, the confidence
+    every raw token up to and including the eos."""
     device = model.model.embed_tokens.weight.device
     mel, valid = features(wavs, device)
     if mel.shape[-1] != WHISPER_FRAMES:
         raise ValueError(f"features: {mel.shape[-1]} frames, expected {WHISPER_FRAMES}")
     prompts = build_prompts(tokenizer, instruct, [audio_token_count(L) for L in valid])
     prompts.whisper_input_features, prompts.valid_frames = mel, list(valid)
-    ids = generate_kimi(model, prompts, cfg, row_keys=row_keys)
     to_text = getattr(tokenizer, "detokenize", None) or tokenizer.decode
-    return ids, [to_text(r) for r in ids]
+    cfg = cfg or KimiGenerationConfig()
+    if not cfg.wants_scores:
+        ids = generate_kimi(model, prompts, cfg, row_keys=row_keys)
+        texts = [to_text(r) for r in ids]
+        return (ids, texts, [{} for _ in ids]) if details else (ids, texts)
+    ids, raw, _, scores = generate_kimi(model, prompts, cfg, row_keys=row_keys, return_raw=True)
+    blank, eos, off = int(cfg.kimia_text_blank), int(cfg.kimia_text_eos), int(model.config.kimia_token_offset)
+    n_tok = G._generated_lengths(raw, [eos]).tolist()
+    extras = [G.score_fields(scores, b, keep=[c for c, t in enumerate(row[:n_tok[b]]) if t != blank and t != eos and t < off])
+              for b, row in enumerate(raw.tolist())]
+    texts = [to_text(r) for r in ids]
+    return (ids, texts, extras) if details else (ids, texts)

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from ...generation import GenerationConfig, Prompts, eos_ids, generate, trim_at_eos
+from ...generation import GenerationConfig, Prompts, eos_ids, generate, record_fields
 from ..backend import ops
 from .processing_qwen2_audio import DEFAULT_INSTRUCT, HOP, TEMPLATE_S2T, WHISPER_FRAMES, audio_token_count
 
@@ -80,19 +80,32 @@ def audio_embedder(model, mel: torch.Tensor, valid: Sequence[int], prompts: Prom
         emb = lm.model.embed_tokens(ids)
         feats = model.multi_modal_projector(model.audio_tower.forward_valid(mel.to(device), lengths, positions.numel()))
         return emb.index_copy(0, positions, feats.to(emb.dtype))
+
+    # the same builder for other documents over the same clips, each clip `repeat` times in a row (generation.
+    # score_continuations: prompt + hypothesis, one document per returned hypothesis)
+    embed.for_documents = lambda documents, repeat=1: audio_embedder(
+        model, mel.repeat_interleave(repeat, 0), [L for L in valid for _ in range(repeat)], documents)
     return embed
 
 
 def transcribe(model, wavs: Sequence[torch.Tensor], tokenizer, instruct: str = DEFAULT_INSTRUCT,
-               cfg: Optional[GenerationConfig] = None, row_keys: Optional[torch.Tensor] = None
-               ) -> Tuple[List[List[int]], List[str]]:
+               cfg: Optional[GenerationConfig] = None, row_keys: Optional[torch.Tensor] = None, details: bool = False):
     """Transcripts of a batch of utterances -> (per utterance the generated ids cut at the first eos, their text decoded
-    with skip_special_tokens=True).  `row_keys` int64 [B] key the draws when sampling (default: the batch index)."""
+    with skip_special_tokens=True).  `row_keys` int64 [B] key the draws when sampling (default: the batch index).
+    `details`: a third element, per utterance the extra record keys that cfg.output_scores / top_alternatives / nbest ask
+    for (generation.record_fields; every "nbest" entry with its "predict")."""
     cfg = cfg or GenerationConfig.from_hf({})
     device = model.language_model.model.embed_tokens.weight.device
     mel, valid = features(wavs, device)
     prompts = build_prompts(tokenizer, valid, instruct)
     out = generate(model, prompts, cfg, row_keys=row_keys, embed=audio_embedder(model, mel, valid, prompts))
-    ids = trim_at_eos(out, eos_ids(cfg, model.language_model))
-    texts = [tokenizer.decode(r, skip_special_tokens=True, clean_up_tokenization_spaces=False) for r in ids]
-    return ids, texts
+    ids, extras = record_fields(out, cfg, eos_ids(cfg, model.language_model))
+    decode = lambda r: tokenizer.decode(r, skip_special_tokens=True, clean_up_tokenization_spaces=False)
+    texts = [decode(r) for r in ids]
+    if not details:
+        return ids, texts
+    for extra in extras:
+        if "nbest" in extra:
+            extra["nbest"] = [{"predict_ids": h["predict_ids"], "predict": decode(h["predict_ids"]),
+                               **{k: v for k, v in h.items() if k != "predict_ids"}} for h in extra["nbest"]]
+    return ids, texts, extras

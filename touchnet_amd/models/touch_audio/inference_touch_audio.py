@@ -11,7 +11,7 @@ from typing import List, Optional
 
 import torch
 
-from ...generation import GenerationConfig, Prompts, generate, trim_at_eos
+from ...generation import GenerationConfig, Prompts, generate, record_fields
 
 
 def build_prompts(feats: List[torch.Tensor], pad_token_id: int, bos_token_id: int) -> Prompts:
@@ -42,15 +42,18 @@ def _special_ids(model, cfg: GenerationConfig):
     return int(pad), int(bos), int(eos)
 
 
-def transcribe(model, feats: List[torch.Tensor], cfg: Optional[GenerationConfig] = None) -> List[List[int]]:
+def transcribe(model, feats: List[torch.Tensor], cfg: Optional[GenerationConfig] = None, details: bool = False):
     """Greedy (or, with cfg.num_beams > 1, beam-search) transcripts of a batch of utterances -> per utterance the
-    generated ids (the prompt excluded), cut in front of the first eos."""
+    generated ids (the prompt excluded), cut in front of the first eos.  `details`: (those ids, per utterance the extra
+    record keys that cfg.output_scores / top_alternatives / nbest ask for — generation.record_fields)."""
     cfg = cfg or GenerationConfig()
     pad, bos, eos = _special_ids(model, cfg)
     gcfg = GenerationConfig(max_new_tokens=cfg.max_new_tokens, repetition_penalty=cfg.repetition_penalty,
                             no_repeat_ngram_size=cfg.no_repeat_ngram_size, eos_token_id=eos, pad_token_id=pad,
                             bos_token_id=bos, check_every=cfg.check_every, num_beams=cfg.num_beams,
                             length_penalty=cfg.length_penalty, early_stopping=cfg.early_stopping,
-                            sequence_bias=cfg.sequence_bias, min_new_tokens=cfg.min_new_tokens)
+                            sequence_bias=cfg.sequence_bias, min_new_tokens=cfg.min_new_tokens,
+                            output_scores=cfg.output_scores, top_alternatives=cfg.top_alternatives, nbest=cfg.nbest)
     out = generate(model, build_prompts(feats, pad, bos), gcfg)
-    return trim_at_eos(out, eos)
+    ids, extras = record_fields(out, gcfg, [eos])
+    return (ids, extras) if details else ids
