@@ -181,6 +181,72 @@ def test_greedy_step_matches_transformers_processors():
         assert f[0] == 1 and f[7] == 1 and int(f.sum()) == 2 and int(nu) == B - 2
 
 
+# ------------------------------------------------------------------------------------- (2b) the argmax rule at its edges
+def _planted_rows(V, dtype):
+    """Six rows of seeded normal logits with the argmax decided by a tie, a NaN or an infinity.  A thread of the
+    1024-thread workgroup owns ids tid, tid + 1024, ...; wave w owns the ids with (id % 1024) // 64 == w."""
+    g = torch.Generator(device="cpu").manual_seed(V)
+    x = torch.randn(6, V, generator=g)
+    big = V > 1024
+    a, b = (100, 700) if big else (5, 37)               # equal maxima in waves 1 and 10 (V = 50: one wave, two lanes)
+    x[0, a] = x[0, b] = 9.0
+    x[1, 3] = float("inf")                              # one NaN at the highest id (a later stride where V > 1024) beats +inf
+    x[1, V - 1] = float("nan")
+    a, b = (200, 1224) if big else (11, 30)             # two NaNs in one thread's stride (V = 50: in one wave)
+    x[2, a] = x[2, b] = float("nan")
+    a, b = (70, 1031) if big else (7, 40)               # two NaNs, the lower id in the higher wave (70: wave 1, 1031: wave 0)
+    x[3, a] = x[3, b] = float("nan")
+    x[4] = float("-inf")                                # nothing to choose: token 0
+    a, b = (300, 1100) if big else (20, 45)
+    x[5, a] = x[5, b] = float("inf")
+    x = x.to(dtype)
+    return x, torch.argmax(x.float(), dim=-1).tolist()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("V", [50, 1500, 2051])
+def test_step_kernels_share_torch_argmax_at_ties_nan_and_inf(V, dtype):
+    """tn_greedy_step, tn_sample_step (do_sample = 0) and tn_kimi_text_step (temperature = 0) on the same planted rows:
+    the token is torch.argmax of the fp32 row (the lowest NaN id beats +inf, ties go to the lower id, an all -inf row
+    gives 0), and the books advance by exactly that token."""
+    import touchnet_amd.functional as F
+    logits, expect = _planted_rows(V, dtype)
+    big = V > 1024
+    assert expect == [100 if big else 5, V - 1, 200 if big else 11, 70 if big else 7, 0, 300 if big else 20]
+    B, S_hist, H = 6, 8, 16
+    eos = next(i for i in range(V) if i not in expect)              # no row emits it
+    g = torch.Generator(device="cpu").manual_seed(V + 1)
+    hl = torch.tensor([1, 2, 3, 1, 2, 3], dtype=torch.int32)
+    hist = torch.randint(0, V, (B, S_hist), generator=g, dtype=torch.int32)
+    embed = torch.randn(V, H, generator=g).to(torch.bfloat16)
+    audio_token = 1
+    want = hist.clone()
+    for b in range(B):
+        want[b, hl[b]] = expect[b]
+    dl = logits.to(DEV)
+    for entry in ("greedy", "sample", "kimi"):
+        d = {k: v.to(DEV) for k, v in dict(hist=hist, hl=hl, cl=hl - 1, fin=torch.zeros(B, dtype=torch.int32)).items()}
+        nu = torch.tensor([B], dtype=torch.int32, device=DEV)
+        state = (dl, d["hist"], d["hl"], d["cl"], d["fin"], nu)
+        if entry == "greedy":
+            F.greedy_step(*state, penalty=1.0, ngram=0, eos=eos, pad=0)
+        elif entry == "sample":
+            F.sample_step(*state, penalty=1.0, do_sample=False, eos=[eos], pad=0)
+        else:
+            x_next = torch.zeros(B, H, dtype=torch.bfloat16, device=DEV)
+            F.kimi_text_step(*state, torch.ones(B, dtype=torch.int32, device=DEV), embed.to(DEV), x_next, penalty=1.0,
+                             temperature=0.0, eos=eos, blank=0, audio_token=audio_token)
+        torch.cuda.synchronize()
+        got = [int(d["hist"][b, hl[b]]) for b in range(B)]
+        assert got == expect, (entry, got, expect)
+        assert torch.equal(d["hist"].cpu(), want), entry
+        assert torch.equal(d["hl"].cpu(), hl + 1) and torch.equal(d["cl"].cpu(), hl), entry
+        assert int(d["fin"].sum()) == 0 and int(nu) == B, entry
+        if entry == "kimi":
+            x_want = embed[torch.tensor(expect)] + embed[audio_token]          # one bf16 add
+            assert torch.equal(x_next.cpu().view(torch.int16), x_want.view(torch.int16))
+
+
 # ---------------------------------------------------------------------------------------------------- helpers: tiny models
 def _tiny_touch_audio(kind, seed, F_in=80):
     from touchnet_amd.models.llama import DecoderConfig

@@ -24,7 +24,7 @@
 // _update_finished_beams (set full under early_stopping, heuristic satisfied) are exactly the conditions that froze the
 // utterance one step earlier, so a live utterance never needs them.
 //
-// Two launches.  beam_topk_kernel, one 1024-thread workgroup per live row: the history's bitmaps (history_sets.h), one pass
+// Two launches.  beam_topk_kernel, one 1024-thread workgroup per live row: the history's bitmaps (decode_step.h), one pass
 // for the row maximum, one for the sum of exponentials, one in which every thread finds the best of its strided
 // candidates as a 64-bit key (order-preserving bits of acc, then the inverted index: all keys differ, ties cost nothing);
 // then `keep` rounds of a workgroup argmax, after each of which only the winner's owner rescans its candidates.  The
@@ -36,7 +36,7 @@
 // and min_new_tokens).  HF's SequenceBiasLogitsProcessor is the first of the processors, so lp = log_softmax(..) + total,
 // then the penalty, then the ban.  beam_topk_kernel is a template on kEdits: without a list the instantiation that runs is
 // the one tn_beam_step always ran.
-#include "history_sets.h"
+#include "decode_step.h"
 
 namespace tn {
 namespace beam {
@@ -126,7 +126,7 @@ __device__ __forceinline__ float candidate(const T* __restrict__ row, int i, flo
       if (e_ids[slot] >= 0) lp = lp + e_val[slot];
     }
   }
-  if (seen[i >> 5] & bit) lp = lp < 0.f ? lp * penalty : lp / penalty;
+  if (seen[i >> 5] & bit) lp = step::penalise(lp, penalty);
   if (banned[i >> 5] & bit) lp = -INFINITY;
   return (lp + base) + 0.f;                                  // (+ 0: no -0 among the keys)
 }
@@ -138,10 +138,10 @@ __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict
                                                               const int* __restrict__ done, float* __restrict__ ws_val,
                                                               int* __restrict__ ws_idx, int K, int K_in, int V, int S_hist,
                                                               float penalty, int ngram, int keep, Edits edits) {
-  __shared__ uint32_t seen[histsets::kWords];
-  __shared__ uint32_t banned[histsets::kWords];
-  __shared__ uint32_t edited[kEdits ? histsets::kWords : 1];   // (with the two above and `rank`: 112 KB of the CU's 160,
-  __shared__ uint16_t rank[kEdits ? histsets::kWords : 1];     // so one workgroup per CU; a step launches at most B K)
+  __shared__ uint32_t seen[step::kWords];
+  __shared__ uint32_t banned[step::kWords];
+  __shared__ uint32_t edited[kEdits ? step::kWords : 1];   // (with the two above and `rank`: 112 KB of the CU's 160,
+  __shared__ uint16_t rank[kEdits ? step::kWords : 1];     // so one workgroup per CU; a step launches at most B K)
   __shared__ uint32_t wave_total[kThreads / 64];
   __shared__ float red[kThreads / 64];
   __shared__ unsigned long long red_key[kThreads / 64];
@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(kThreads) beam_topk_kernel(const T* __restrict
   const int b = row_in / K_in, r = b * K + row_in % K_in;
   if (done[b] != 0) return;
   const int len = min(max(hist_len[r], 0), S_hist);
-  histsets::fill(seen, banned, hist + (size_t)r * S_hist, len, V, penalty != 1.f, ngram, tid, kThreads);
+  step::fill(seen, banned, hist + (size_t)r * S_hist, len, V, penalty != 1.f, ngram, tid, kThreads);
   const int* __restrict__ e_ids = kEdits ? edits.ids + (size_t)row_in * edits.n : nullptr;
   const float* __restrict__ e_val = kEdits ? edits.val + (size_t)row_in * edits.n : nullptr;
   if (kEdits) fill_edit_index(edited, rank, wave_total, e_ids, edits.cnt[row_in] > 0 ? edits.n : 0, V, tid);
@@ -344,17 +344,15 @@ static int beam_step_launch(const void* logits, int* hist, int* hist_len, int* c
                             int S_hist, float penalty, int ngram, const int* eos_ids, int n_eos, int n_new,
                             float length_penalty, int early_stopping, int dtype, tn::beam::Edits edits, void* stream) {
   using namespace tn::beam;
-  const void* ptrs[] = {logits, hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen,
-                        unsat, done, n_unfinished, out_ids, out_parent, workspace};
-  for (const void* p : ptrs)
-    if (p == nullptr) return TN_EINVAL;
-  for (size_t i = 1; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
-    if ((uintptr_t)ptrs[i] & 3) return TN_EINVAL;
-  if (B <= 0 || K < 2 || K > kMaxK || (K_in != 1 && K_in != K) || V < 64 || V > tn::histsets::kMaxVocab || S_hist <= 0 ||
+  if (!tn::step::logits_ok(logits, dtype)) return TN_EINVAL;
+  const void* state[] = {hist, hist_len, cache_len, src, run_score, fin_ids, fin_len, fin_score, fin_flag, gen, unsat, done,
+                         n_unfinished, out_ids, out_parent, workspace};
+  for (const void* p : state)
+    if (p == nullptr || ((uintptr_t)p & 3)) return TN_EINVAL;
+  if (B <= 0 || K < 2 || K > kMaxK || (K_in != 1 && K_in != K) || V < 64 || V > tn::step::kMaxVocab || S_hist <= 0 ||
       ngram < 0 || !(penalty > 0.f) || n_eos < 0 || n_eos > kMaxEos || (n_eos > 0 && eos_ids == nullptr) || n_new <= 0 ||
-      early_stopping < 0 || early_stopping > 2 || (dtype != 0 && dtype != 1) || !(length_penalty == length_penalty))
+      early_stopping < 0 || early_stopping > 2 || !(length_penalty == length_penalty))
     return TN_EINVAL;
-  if ((uintptr_t)logits & (dtype == 0 ? 3 : 1)) return TN_EINVAL;
   Eos eos;
   eos.n = n_eos;
   for (int e = 0; e < kMaxEos; ++e) eos.id[e] = e < n_eos ? eos_ids[e] : -1;
@@ -366,13 +364,11 @@ static int beam_step_launch(const void* logits, int* hist, int* hist_len, int* c
 #define TN_BEAM_TOPK(T, E)                                                                                              \
   hipLaunchKernelGGL((beam_topk_kernel<T, E>), dim3(B * K_in), dim3(kThreads), 0, st, (const T*)logits, hist, hist_len,  \
                      run_score, done, ws_val, ws_idx, K, K_in, V, S_hist, penalty, ngram, keep, edits)
-  if (dtype == 0) {
-    if (with_edits) TN_BEAM_TOPK(float, true);
-    else TN_BEAM_TOPK(float, false);
-  } else {
-    if (with_edits) TN_BEAM_TOPK(tn::bf16_t, true);
-    else TN_BEAM_TOPK(tn::bf16_t, false);
-  }
+#define TN_BEAM_LAUNCH(T)                    \
+  if (with_edits) TN_BEAM_TOPK(T, true);     \
+  else TN_BEAM_TOPK(T, false)
+  TN_STEP_DISPATCH(dtype, TN_BEAM_LAUNCH);
+#undef TN_BEAM_LAUNCH
 #undef TN_BEAM_TOPK
   TN_LAUNCH_CHECK();
   hipLaunchKernelGGL(beam_book_kernel, dim3(B), dim3(kBookThreads), 0, st, (const float*)ws_val, (const int*)ws_idx, hist,
@@ -403,7 +399,7 @@ int tn_beam_step_edits(const void* logits, int* hist, int* hist_len, int* cache_
   tn::beam::Edits edits{nullptr, nullptr, nullptr, 0};
   if (edit_ids != nullptr || edit_val != nullptr || edit_cnt != nullptr) {
     if (edit_ids == nullptr || edit_val == nullptr || edit_cnt == nullptr || n_edit < 1 ||
-        (((uintptr_t)edit_ids | (uintptr_t)edit_val | (uintptr_t)edit_cnt) & 3))
+        !tn::step::aligned(3, {edit_ids, edit_val, edit_cnt}))
       return TN_EINVAL;
     edits = tn::beam::Edits{edit_ids, edit_val, edit_cnt, n_edit};
   }

@@ -21,15 +21,18 @@
 //   apply  logits[row, t] = T(fp32(logits[row, t]) + total), only where a sequence matched or the eos rule holds
 //   emit   edit_ids[row, g] = t where that is so, else -1 - t;  edit_val[row, g] = total;  edit_cnt[row] = active groups
 // Finished rows (greedy, sampling) and rows of done utterances (beam) are edited like any other: the step kernels ignore them.
-#include "common.h"
+#include "decode_step.h"
 
 namespace tn {
 namespace constrain {
 
+using step::aligned;
+using step::kMaxVocab;
+using step::logits_ok;
+
 constexpr int kThreads = 256;
 constexpr int kMaxSeqs = 16384;
 constexpr int kMaxLen = 64;
-constexpr int kMaxVocab = 262144;
 
 template <typename T, bool kApply>
 __global__ void __launch_bounds__(kThreads) constrain_kernel(
@@ -101,28 +104,22 @@ int tn_logits_constrain(void* logits, const int* hist, const int* hist_len, cons
       n_seq < 0 || n_seq > kMaxSeqs || n_ids < n_seq || (long long)n_ids > (long long)kMaxSeqs * kMaxLen || n_grp < 1 ||
       n_grp > n_seq + 8 || min_new < 0 || (mode != 0 && mode != 1) || (dtype != 0 && dtype != 1))
     return TN_EINVAL;
-  const void* need[] = {hist, hist_len, seq_off, grp_off, grp_tok, grp_eos};
-  for (const void* p : need)
-    if (p == nullptr || ((uintptr_t)p & 3)) return TN_EINVAL;
+  if (!hist || !hist_len || !seq_off || !grp_off || !grp_tok || !grp_eos) return TN_EINVAL;
   if (n_seq > 0 && (seq_ids == nullptr || seq_bias == nullptr)) return TN_EINVAL;
-  if (((uintptr_t)seq_ids & 3) || ((uintptr_t)seq_bias & 3) || ((uintptr_t)prompt_len & 3)) return TN_EINVAL;
   if (min_new > 0 && prompt_len == nullptr) return TN_EINVAL;
+  if (!aligned(3, {hist, hist_len, seq_off, grp_off, grp_tok, grp_eos, seq_ids, seq_bias, prompt_len})) return TN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
 #define TN_CONSTRAIN_ARGS                                                                                              \
   hist, hist_len, prompt_len, seq_off, seq_ids, seq_bias, grp_off, grp_tok, grp_eos, edit_ids, edit_val, edit_cnt, K, K_in, \
       V, S_hist, n_seq, n_ids, n_grp, min_new
   if (mode == 0) {
-    if (logits == nullptr || ((uintptr_t)logits & (dtype == 0 ? 3 : 1))) return TN_EINVAL;
-    if (dtype == 0)
-      hipLaunchKernelGGL((constrain_kernel<float, true>), dim3(R_in), dim3(kThreads), 0, st, (float*)logits,
-                         TN_CONSTRAIN_ARGS);
-    else
-      hipLaunchKernelGGL((constrain_kernel<tn::bf16_t, true>), dim3(R_in), dim3(kThreads), 0, st, (tn::bf16_t*)logits,
-                         TN_CONSTRAIN_ARGS);
+    if (!logits_ok(logits, dtype)) return TN_EINVAL;
+#define TN_CONSTRAIN_APPLY(T) \
+  hipLaunchKernelGGL((constrain_kernel<T, true>), dim3(R_in), dim3(kThreads), 0, st, (T*)logits, TN_CONSTRAIN_ARGS)
+    TN_STEP_DISPATCH(dtype, TN_CONSTRAIN_APPLY);
+#undef TN_CONSTRAIN_APPLY
   } else {
-    const void* out[] = {edit_ids, edit_val, edit_cnt};
-    for (const void* p : out)
-      if (p == nullptr || ((uintptr_t)p & 3)) return TN_EINVAL;
+    if (!edit_ids || !edit_val || !edit_cnt || !aligned(3, {edit_ids, edit_val, edit_cnt})) return TN_EINVAL;
     hipLaunchKernelGGL((constrain_kernel<float, false>), dim3(R_in), dim3(kThreads), 0, st, (float*)nullptr,
                        TN_CONSTRAIN_ARGS);
   }

@@ -27,10 +27,12 @@
 // the workgroup reduces them to the argmax.  Sampling: the top_k-th best of the 1024 thread maxima bounds the top_k-th best
 // of the row from below, so a second pass gathers the few elements at or above it into LDS, where they are ranked exactly.
 // If they do not fit (rows of ties), top_k reduction passes pick the candidates one by one instead.
-#include "history_sets.h"
+#include "decode_step.h"
 
 namespace tn {
 namespace kimi {
+
+using namespace step;
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
@@ -38,32 +40,12 @@ constexpr int kCap = 2048;                 // candidates gathered into LDS
 constexpr int kMaxK = 64;
 constexpr int kMaxWindow = 64;
 constexpr int kNone = 0x7fffffff;
-using histsets::kMaxVocab;
-using histsets::kWords;
-
-typedef unsigned long long u64;
 
 struct Params {
   int V, S_hist, H, window, top_k, eos, blank, audio_token;
   float penalty, temperature;
   uint32_t seed_lo, seed_hi;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) — the generator of tn_sample_step
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; ++r) {
-    const u64 p0 = (u64)0xD2511F53u * c[0];
-    const u64 p1 = (u64)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 // a penalised value as the reference leaves it in the logits tensor
 template <typename T>
@@ -72,16 +54,6 @@ template <>
 __device__ __forceinline__ float round_to<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf2f(f2bf(v)); }
-
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-// (NaN wins, the lowest id among NaNs: torch.argmax)
-__device__ __forceinline__ void take(float v, int i, float& bv, int& bi) {
-  if (better(v, i, bv, bi) || (v != v && (bv == bv || i < bi))) {
-    bv = v;
-    bi = i;
-  }
-}
 
 struct Smem {
   uint32_t seen[kWords];
@@ -97,26 +69,6 @@ struct Smem {
   int thr_i, n_cand, tok;
 };
 
-// workgroup argmax of one (value, id) per thread; every thread gets the result
-__device__ __forceinline__ void block_best(float& bv, int& bi, Smem& s) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    take(ov, oi, bv, bi);
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) {
-    s.red_v[tid >> 6] = bv;
-    s.red_i[tid >> 6] = bi;
-  }
-  __syncthreads();
-  bv = s.red_v[0];
-  bi = s.red_i[0];
-  for (int w = 1; w < kWaves; ++w) take(s.red_v[w], s.red_i[w], bv, bi);
-}
-
 template <typename T>
 struct Row {
   const T* row;
@@ -125,7 +77,7 @@ struct Row {
   bool use_pen;
   __device__ __forceinline__ float value(int i) const {
     float v = Elem<T>::ld(row + i);
-    if (use_pen && (seen[i >> 5] & (1u << (i & 31)))) v = round_to<T>(v < 0.f ? v * penalty : v / penalty);
+    if (use_pen && (seen[i >> 5] & (1u << (i & 31)))) v = round_to<T>(penalise(v, penalty));
     return v;
   }
 };
@@ -150,10 +102,7 @@ __global__ void __launch_bounds__(kThreads) kimi_text_step_kernel(
       const int words = (V + 31) / 32;
       for (int w = tid; w < words; w += kThreads) s.seen[w] = 0u;
       __syncthreads();
-      if (tid < W) {
-        const int t = h[len - W + tid];
-        if (t >= 0 && t < V) atomicOr(&s.seen[t >> 5], 1u << (t & 31));
-      }
+      mark_seen(s.seen, h, len - W, len, V, tid, kThreads);
       __syncthreads();
     }
     const Row<T> r{logits + (size_t)b * V, s.seen, p.penalty, use_pen};
@@ -163,7 +112,7 @@ __global__ void __launch_bounds__(kThreads) kimi_text_step_kernel(
     for (int i = tid; i < V; i += kThreads) take(r.value(i), i, bv, bi);
     const float my_v = bv;
     const int my_i = bi;
-    block_best(bv, bi, s);
+    block_argmax(bv, bi, s.red_v, s.red_i);
     tok = bi < V ? bi : 0;
     const float M = bv;
     const bool finite_max = M == M && M > -INFINITY && M < INFINITY;
@@ -221,7 +170,7 @@ __global__ void __launch_bounds__(kThreads) kimi_text_step_kernel(
               cib = i;
             }
           }
-          block_best(cvb, cib, s);
+          block_argmax(cvb, cib, s.red_v, s.red_i);
           if (tid == 0) {
             s.sv[c] = cvb;
             s.si[c] = cib;
@@ -232,16 +181,7 @@ __global__ void __launch_bounds__(kThreads) kimi_text_step_kernel(
       }
       __syncthreads();
       if (tid == 0) {
-        double u;
-        if (uniforms) {
-          u = (double)uniforms[b];
-        } else {
-          const u64 key = row_key ? (u64)row_key[b] : (u64)b;
-          uint32_t ctr[4] = {(uint32_t)len, (uint32_t)key, (uint32_t)(key >> 32), 0u};
-          philox4x32_10(ctr, p.seed_lo, p.seed_hi);
-          u = (double)(((u64)ctr[0] << 21) ^ (u64)(ctr[1] >> 11)) * 0x1p-53;
-        }
-        u = fmin(fmax(u, 0.0), 1.0);
+        const double u = row_uniform(uniforms, row_key, b, len, p.seed_lo, p.seed_hi);
         float total = 0.f;
         for (int c = 0; c < k; ++c) total += expf((s.sv[c] - M) / p.temperature);
         const double target = u * (double)total;
@@ -260,17 +200,8 @@ __global__ void __launch_bounds__(kThreads) kimi_text_step_kernel(
       tok = s.tok;
     }
   }
-  if (tid == 0) {
-    if (len < p.S_hist) {
-      hist[(size_t)b * p.S_hist + len] = tok;
-      hist_len[b] = len + 1;
-      cache_len[b] += 1;
-    }
-    if (!done && tok == p.eos) {
-      finished[b] = 1;
-      atomicSub(n_unfinished, 1);
-    }
-  }
+  if (tid == 0)
+    append_token(hist, hist_len, cache_len, finished, n_unfinished, b, p.S_hist, len, tok, done, tok == p.eos);
   // the next input row: embed[token] + embed[audio_token], one bf16 rounding (torch's bf16 add)
   const bf16_t* et = embed + (size_t)tok * p.H;
   const bf16_t* ea = embed + (size_t)p.audio_token * p.H;
@@ -299,15 +230,13 @@ int tn_kimi_text_step(const void* logits, int* hist, int* hist_len, int* cache_l
                       const float* uniforms, int B, int V, int S_hist, int H, float penalty, int window, float temperature,
                       int top_k, unsigned long long seed, int eos, int blank, int audio_token, int dtype, void* stream) {
   using namespace tn::kimi;
-  if (!logits || !hist || !hist_len || !cache_len || !finished || !n_unfinished || !prompt_len || !embed || !x_next)
+  if (!logits_ok(logits, dtype) || !hist || !hist_len || !cache_len || !finished || !n_unfinished || !prompt_len || !embed ||
+      !x_next)
     return TN_EINVAL;
-  if (((uintptr_t)hist | (uintptr_t)hist_len | (uintptr_t)cache_len | (uintptr_t)finished | (uintptr_t)n_unfinished |
-       (uintptr_t)prompt_len | (uintptr_t)uniforms) & 3)
+  if (!aligned(3, {hist, hist_len, cache_len, finished, n_unfinished, prompt_len, uniforms}) || !aligned(7, {row_key}) ||
+      !aligned(15, {embed, x_next}))
     return TN_EINVAL;
-  if ((uintptr_t)row_key & 7) return TN_EINVAL;
-  if (((uintptr_t)embed | (uintptr_t)x_next) & 15) return TN_EINVAL;
-  if (B <= 0 || V <= 0 || V > kMaxVocab || S_hist <= 0 || H <= 0 || H % 8 || (dtype != 0 && dtype != 1)) return TN_EINVAL;
-  if ((uintptr_t)logits & (dtype == 0 ? 3 : 1)) return TN_EINVAL;
+  if (B <= 0 || V <= 0 || V > kMaxVocab || S_hist <= 0 || H <= 0 || H % 8) return TN_EINVAL;
   if (!(penalty > 0.f) || window < 1 || window > kMaxWindow || top_k < 0 || top_k > kMaxK) return TN_EINVAL;
   if (temperature > 1e-6f && top_k == 0) return TN_EINVAL;       // full-vocabulary multinomial: out of scope
   if (blank < 0 || blank >= V || audio_token < 0 || audio_token >= V) return TN_EINVAL;    // rows of `embed`
@@ -325,14 +254,12 @@ int tn_kimi_text_step(const void* logits, int* hist, int* hist_len, int* cache_l
   p.seed_lo = (uint32_t)seed;
   p.seed_hi = (uint32_t)(seed >> 32);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0)
-    hipLaunchKernelGGL(kimi_text_step_kernel<float>, dim3(B), dim3(kThreads), 0, st, (const float*)logits, hist, hist_len,
-                       cache_len, finished, n_unfinished, prompt_len, (const tn::bf16_t*)embed, (tn::bf16_t*)x_next,
-                       row_key, uniforms, p);
-  else
-    hipLaunchKernelGGL(kimi_text_step_kernel<tn::bf16_t>, dim3(B), dim3(kThreads), 0, st, (const tn::bf16_t*)logits, hist,
-                       hist_len, cache_len, finished, n_unfinished, prompt_len, (const tn::bf16_t*)embed,
-                       (tn::bf16_t*)x_next, row_key, uniforms, p);
+#define TN_KIMI_LAUNCH(T)                                                                                              \
+  hipLaunchKernelGGL(kimi_text_step_kernel<T>, dim3(B), dim3(kThreads), 0, st, (const T*)logits, hist, hist_len,        \
+                     cache_len, finished, n_unfinished, prompt_len, (const tn::bf16_t*)embed, (tn::bf16_t*)x_next, row_key, \
+                     uniforms, p)
+  TN_STEP_DISPATCH(dtype, TN_KIMI_LAUNCH);
+#undef TN_KIMI_LAUNCH
   TN_LAUNCH_CHECK();
   return TN_OK;
 }

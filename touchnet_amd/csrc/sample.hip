@@ -30,15 +30,15 @@
 //   * 0 < top_k <= 1024: after top-k the candidates (d <= d_k) are compacted into LDS; top-p and the draw then work on
 //     them alone (all-pairs sums over <= 2048 entries).  Otherwise the draw scans the row in id order, one contiguous
 //     chunk per thread, with a workgroup prefix sum of the chunk masses.
-#include "common.h"
+#include "decode_step.h"
 
 namespace tn {
 namespace sample {
 
+using namespace step;
+
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxVocab = 262144;
-constexpr int kWords = kMaxVocab / 32;
 constexpr int kBins = 1024;
 constexpr int kCap = 2048;                 // tokens gathered into LDS
 constexpr int kMaxEos = 8;
@@ -46,39 +46,12 @@ constexpr int kMaxLevels = 8;
 constexpr float kStep0 = 16.f;             // level-0 bins per unit of d: [0, 64) over 1024 bins
 constexpr float kFix = 1099511627776.f;    // 2^40
 
-typedef unsigned long long u64;
-
 struct Params {
   int V, S_hist, do_sample, top_k, n_eos, pad;
   float penalty, temperature, top_p;
   uint32_t seed_lo, seed_hi;
   int eos[kMaxEos];
 };
-
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
-__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; ++r) {
-    const u64 p0 = (u64)0xD2511F53u * c[0];
-    const u64 p1 = (u64)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ float ld(const T* p);
-template <>
-__device__ __forceinline__ float ld<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ld<bf16_t>(const bf16_t* p) { return bf2f(*p); }
-
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 __device__ __forceinline__ u64 weight(float d) { return (u64)(__expf(-d) * kFix); }
 
@@ -135,8 +108,8 @@ struct Row {
   float penalty, temperature, M;
   bool use_pen, do_sample;
   __device__ __forceinline__ float value(int i) const {
-    float v = ld<T>(row + i);
-    if (use_pen && (seen[i >> 5] & (1u << (i & 31)))) v = v < 0.f ? v * penalty : v / penalty;
+    float v = Elem<T>::ld(row + i);
+    if (use_pen && (seen[i >> 5] & (1u << (i & 31)))) v = penalise(v, penalty);
     if (do_sample) v = v / temperature;
     return v;
   }
@@ -305,61 +278,20 @@ __global__ void __launch_bounds__(kThreads) sample_step_kernel(const T* __restri
     if (use_pen) {
       for (int w = tid; w < words; w += kThreads) s.seen[w] = 0u;
       __syncthreads();
-      for (int i = tid; i < len; i += kThreads) {
-        const int t = h[i];
-        if (t >= 0 && t < V) atomicOr(&s.seen[t >> 5], 1u << (t & 31));
-      }
+      mark_seen(s.seen, h, 0, len, V, tid, kThreads);
       __syncthreads();
     }
     Row<T> r{logits + (size_t)b * V, s.seen, p.penalty, p.temperature, 0.f, use_pen, p.do_sample != 0};
     // pass 1: the maximum (argmax with torch.argmax's rules)
     float bv = -INFINITY;
     int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += kThreads) {
-      const float v = r.value(i);
-      if (better(v, i, bv, bi) || (v != v && bv == bv)) {
-        bv = v;
-        bi = i;
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (better(ov, oi, bv, bi) || (ov != ov && (bv == bv || oi < bi))) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      s.red_f[tid >> 6] = bv;
-      s.red_i[tid >> 6] = bi;
-    }
-    __syncthreads();
-    bv = s.red_f[0];
-    bi = s.red_i[0];
-    for (int w = 1; w < kWaves; ++w) {
-      const float ov = s.red_f[w];
-      const int oi = s.red_i[w];
-      if (better(ov, oi, bv, bi) || (ov != ov && (bv == bv || oi < bi))) {
-        bv = ov;
-        bi = oi;
-      }
-    }
+    for (int i = tid; i < V; i += kThreads) take(r.value(i), i, bv, bi);
+    block_argmax(bv, bi, s.red_f, s.red_i);
     tok = bi < V ? bi : 0;
     const bool finite_max = bv == bv && bv > -INFINITY && bv < INFINITY;
     if (p.do_sample && finite_max) {
       r.M = bv;
-      // the uniform of this row and step
-      double u;
-      if (uniforms) {
-        u = (double)uniforms[b];
-      } else {
-        const u64 key = row_key ? (u64)row_key[b] : (u64)b;
-        uint32_t ctr[4] = {(uint32_t)len, (uint32_t)key, (uint32_t)(key >> 32), 0u};
-        philox4x32_10(ctr, p.seed_lo, p.seed_hi);
-        u = (double)(((u64)ctr[0] << 21) ^ (u64)(ctr[1] >> 11)) * 0x1p-53;
-      }
-      u = fmin(fmax(u, 0.0), 1.0);
+      const double u = row_uniform(uniforms, row_key, b, len, p.seed_lo, p.seed_hi);
       const int k = (p.top_k > 0 && p.top_k < V) ? p.top_k : 0;
       const bool use_p = p.top_p < 1.f;
       float dk = INFINITY;
@@ -473,17 +405,9 @@ __global__ void __launch_bounds__(kThreads) sample_step_kernel(const T* __restri
     n_kept[b] = 0;
   }
   if (tid == 0) {
-    if (len < p.S_hist) {
-      hist[(size_t)b * p.S_hist + len] = tok;
-      hist_len[b] = len + 1;
-      cache_len[b] += 1;
-    }
     bool is_eos = false;
     for (int e = 0; e < p.n_eos; ++e) is_eos |= tok == p.eos[e];
-    if (!done && is_eos) {
-      finished[b] = 1;
-      atomicSub(n_unfinished, 1);
-    }
+    append_token(hist, hist_len, cache_len, finished, n_unfinished, b, p.S_hist, len, tok, done, is_eos);
   }
 }
 
@@ -497,15 +421,12 @@ int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len,
                    int do_sample, float temperature, int top_k, float top_p, unsigned long long seed, const int* eos_ids,
                    int n_eos, int pad, int dtype, void* stream) {
   using namespace tn::sample;
-  if (!logits || !hist || !hist_len || !cache_len || !finished || !n_unfinished) return TN_EINVAL;
-  if (((uintptr_t)hist | (uintptr_t)hist_len | (uintptr_t)cache_len | (uintptr_t)finished | (uintptr_t)n_unfinished |
-       (uintptr_t)uniforms | (uintptr_t)n_kept) & 3)
+  if (!logits_ok(logits, dtype) || !hist || !hist_len || !cache_len || !finished || !n_unfinished) return TN_EINVAL;
+  if (!aligned(3, {hist, hist_len, cache_len, finished, n_unfinished, uniforms, n_kept}) || !aligned(7, {row_key}))
     return TN_EINVAL;
-  if ((uintptr_t)row_key & 7) return TN_EINVAL;
-  if (B <= 0 || V <= 0 || V > kMaxVocab || S_hist <= 0 || !(penalty > 0.f) || (dtype != 0 && dtype != 1)) return TN_EINVAL;
+  if (B <= 0 || V <= 0 || V > kMaxVocab || S_hist <= 0 || !(penalty > 0.f)) return TN_EINVAL;
   if (n_eos < 0 || n_eos > kMaxEos || (n_eos > 0 && !eos_ids)) return TN_EINVAL;
   if (do_sample && (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) return TN_EINVAL;
-  if ((uintptr_t)logits & (dtype == 0 ? 3 : 1)) return TN_EINVAL;
   Params p;
   p.V = V;
   p.S_hist = S_hist;
@@ -520,19 +441,18 @@ int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len,
   p.seed_hi = (uint32_t)(seed >> 32);
   for (int e = 0; e < kMaxEos; ++e) p.eos[e] = e < n_eos ? eos_ids[e] : -1;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0)
-    hipLaunchKernelGGL(sample_step_kernel<float>, dim3(B), dim3(kThreads), 0, st, (const float*)logits, hist, hist_len,
-                       cache_len, finished, n_unfinished, row_key, uniforms, n_kept, p);
-  else
-    hipLaunchKernelGGL(sample_step_kernel<tn::bf16_t>, dim3(B), dim3(kThreads), 0, st, (const tn::bf16_t*)logits, hist,
-                       hist_len, cache_len, finished, n_unfinished, row_key, uniforms, n_kept, p);
+#define TN_SAMPLE_LAUNCH(T)                                                                                             \
+  hipLaunchKernelGGL(sample_step_kernel<T>, dim3(B), dim3(kThreads), 0, st, (const T*)logits, hist, hist_len, cache_len, \
+                     finished, n_unfinished, row_key, uniforms, n_kept, p)
+  TN_STEP_DISPATCH(dtype, TN_SAMPLE_LAUNCH);
+#undef TN_SAMPLE_LAUNCH
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
 // Philox4x32-10 on the host (tests compare the device draws against it)
 void tn_philox4x32_10(unsigned int* ctr4, unsigned long long key) {
-  tn::sample::philox4x32_10(ctr4, (uint32_t)key, (uint32_t)(key >> 32));
+  tn::step::philox4x32_10(ctr4, (uint32_t)key, (uint32_t)(key >> 32));
 }
 
 }  // extern "C"

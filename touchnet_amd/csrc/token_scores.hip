@@ -21,20 +21,20 @@
 // max per logit), and k rounds of "best head of all lists" merge them.  A flat row (everything >= tau) takes the
 // insertion path everywhere: slower, the same result.
 // No atomics; nothing is written but the outputs.
-#include "common.h"
+#include "decode_step.h"
 
 namespace tn {
 namespace tokscore {
 
+using namespace step;
+
 constexpr int kThreads = 1024;
 constexpr int kMaxAlt = 8;
-constexpr int kMaxVocab = 262144;
 constexpr int kNone = 0x7fffffff;        // id of an empty candidate slot
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-// the best (value, id) pair of the workgroup, handed to every thread (pairs with distinct ids: a total order)
-__device__ __forceinline__ void block_best(float& bv, int& bi, float* red_v, int* red_i) {
+// the best (value, id) pair of the workgroup, handed to every thread — by `better` alone, a total order on pairs with
+// distinct ids and no NaN (a row with a NaN is flagged `sick` before this runs), not step::block_argmax's torch.argmax
+__device__ __forceinline__ void block_best_finite(float& bv, int& bi, float* red_v, int* red_i) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(bv, off, 64);
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(kThreads) token_scores_kernel(const T* __restr
     for (int j = 0; j < k; ++j) {
       float bv = tv[0];
       int bi = ti[0];
-      block_best(bv, bi, red_v, red_i);
+      block_best_finite(bv, bi, red_v, red_i);
       if (tid == j) {
         my_v = bv;
         my_i = bi;
@@ -266,22 +266,20 @@ extern "C" {
 int tn_token_scores(const void* logits, const int* tok, const int* hist, const int* hist_len, float* logp, float* entropy,
                     int* alt_id, float* alt_logp, int R, int V, int S_hist, int k, int dtype, void* stream) {
   using namespace tn::tokscore;
-  if (!logits || !logp || !entropy) return TN_EINVAL;
-  if (dtype != 0 && dtype != 1) return TN_EINVAL;
+  if (!logits_ok(logits, dtype) || !logp || !entropy) return TN_EINVAL;
   if (R < 0 || V < 1 || V > kMaxVocab || k < 0 || k > kMaxAlt) return TN_EINVAL;
   const bool by_tok = tok != nullptr, by_hist = hist != nullptr || hist_len != nullptr;
   if (by_tok == by_hist) return TN_EINVAL;                         // both ways of naming the token, or neither
   if (by_hist && (!hist || !hist_len || S_hist < 1)) return TN_EINVAL;
   if (k > 0 && (!alt_id || !alt_logp)) return TN_EINVAL;
-  if ((uintptr_t)logits & (dtype == 0 ? 3 : 1)) return TN_EINVAL;
-  if (((uintptr_t)tok | (uintptr_t)hist | (uintptr_t)hist_len | (uintptr_t)logp | (uintptr_t)entropy | (uintptr_t)alt_id |
-       (uintptr_t)alt_logp) & 3)
-    return TN_EINVAL;
+  if (!aligned(3, {tok, hist, hist_len, logp, entropy, alt_id, alt_logp})) return TN_EINVAL;
   if (R == 0) return TN_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0)
-    return launch<float>(logits, tok, hist, hist_len, logp, entropy, alt_id, alt_logp, R, V, S_hist, k, st);
-  return launch<tn::bf16_t>(logits, tok, hist, hist_len, logp, entropy, alt_id, alt_logp, R, V, S_hist, k, st);
+  int rc = TN_OK;
+#define TN_TOKSCORE_LAUNCH(T) rc = launch<T>(logits, tok, hist, hist_len, logp, entropy, alt_id, alt_logp, R, V, S_hist, k, st)
+  TN_STEP_DISPATCH(dtype, TN_TOKSCORE_LAUNCH);
+#undef TN_TOKSCORE_LAUNCH
+  return rc;
 }
 
 }  // extern "C"
