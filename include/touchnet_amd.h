@@ -154,16 +154,11 @@ int tn_attn_bwd_seg(const void* q, const void* k, const void* v, const void* o, 
                     int B, int T, int Nh, int Nkv, int D, float scale, int nseg, const int* host_segs,
                     int rows_per_batch, void* stream);
 
-/* ---- audio frontend on device — touchnet/data/functions.py:117-134 (kaldi fbank),
- *      :159-190 (whisper log-mel), :258-286 (stack / stride / normalise).
- * fbank:  wav fp32 [n_samples] in [-1,1) -> feat fp32 [tn_fbank_frames(n_samples), n_mels]
- *         (x32768, 25 ms / 10 ms frames at 16 kHz, dc removal, pre-emphasis 0.97, povey window, 512-pt
- *         power spectrum, kaldi mel (20 Hz..Nyquist), log(max(., FLT_EPSILON)))
+/* ---- audio frontend on device — touchnet/data/functions.py:159-190 (whisper log-mel), :258-286 (stack / stride /
+ *      normalise); Kaldi fbank / MFCC (:117-156) is tn_kaldi_feats below, at any sample rate and frame geometry.
  * logmel: wav fp32 [n_samples] -> feat fp32 [n_samples/160, n_mels]; `mel_fb` = slaney filter bank
  *         fp32 [n_mels, 201] supplied by the host (it is a constant table)
  * stack:  feat fp32 [T, F] -> out fp32 [ceil(T/stride), F*stack], optional per-row normalisation */
-int tn_fbank_frames(int n_samples);
-int tn_kaldi_fbank(const float* wav, float* feat, int n_samples, int n_mels, void* stream);
 int tn_log_mel(const float* wav, const float* mel_fb, float* feat, float* scratch_max, int n_samples, int n_mels,
                void* stream);
 int tn_audiofeat_stack(const float* feat, float* out, int T, int F, int stack, int stride, int normalize,
@@ -175,11 +170,6 @@ int tn_audiofeat_stack(const float* feat, float* out, int T, int F, int stack, i
  * entries each; y must not alias x. */
 int tn_feat_augment(const float* x, float* y, int T, int F, int out_rows, const int* t_masks, int n_t,
                     const int* f_masks, int n_f, const int* subs, int n_sub, void* stream);
-/* Waveform-level speed perturbation, touchnet/data/functions.py:99-114 (sox `speed s` + `rate`): x [n_in] resampled to
- * y [n_out], output n at input position n p / q, by a polyphase band-limited interpolation table tab [q][ntap] (device,
- * float; built by the host side, touchnet_amd/functional.py::speed_perturb).  Not bit-comparable with libsox. */
-int tn_resample_polyphase(const float* x, float* y, const float* tab, long long n_in, long long n_out, int p, int q,
-                          int ntap, void* stream);
 /* Sample-rate conversion, touchnet/data/functions.py:83-96 (`torchaudio.transforms.Resample(orig, new)`, torchaudio's
  * defaults: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99): x [n_in] -> y [n_out] fp32.  With o = orig / gcd,
  * n = new_ / gcd, output m sits at input position m o / n (integer part i, phase r = (m o) mod n) and
@@ -187,6 +177,9 @@ int tn_resample_polyphase(const float* x, float* y, const float* tab, long long 
  * kernel in float32 without its zero columns (touchnet_amd/functional.py::sinc_resample_table).  x is fp32, or int16 PCM
  * read as v * 2^-15 when x_is_pcm16 (exact: the same bits as converting first).  One launch, no allocation, no
  * synchronisation; all index arithmetic is 64-bit.
+ * Waveform-level speed perturbation, touchnet/data/functions.py:99-114 (sox `speed s` + `rate`), is the same sum with
+ * orig / new_ = the speed p / q and the band-limited interpolation table tab [q][ntap] of
+ * touchnet_amd/functional.py::speed_filter_bank.  Not bit-comparable with libsox.
  * -22 (before any launch) for a null pointer, y == x, n_in < 1, n_out outside [1, ceil(n_in new_ / orig)], orig < 1,
  * new_ < 1, ntap < 2, odd or above 12286 (a workgroup stages the samples of its outputs, ntap of them for one, in
  * 48 KiB of LDS). */

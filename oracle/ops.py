@@ -211,9 +211,10 @@ def packed_attention_sharded_split(q_local, k_full, v_full, mask, shard, chunk_l
 
 
 # ---- frontend (same call signatures as touchnet_amd.functional; numpy restatements of oracle/frontend.py) ----------
-def kaldi_fbank(wav, num_mel_bins=80):
+def kaldi_fbank(wav, num_mel_bins=80, sample_rate=16000, frame_length=25.0, frame_shift=10.0):
     from . import frontend as _fe
-    return torch.from_numpy(_fe.kaldi_fbank(wav.detach().cpu().numpy().reshape(-1), num_mel_bins=num_mel_bins)).float()
+    return torch.from_numpy(_fe.kaldi_fbank(wav.detach().cpu().numpy().reshape(-1), sample_rate, num_mel_bins,
+                                            frame_length, frame_shift)).float()
 
 
 def log_mel_spectrogram(wav, num_mel_bins=128, padding=0):

@@ -56,9 +56,8 @@ def docs(B, T, mean_len, seed=0):
 def frontend():
     """the feature kernels on one 30 s clip (`--frontend`: these lines alone, printed and not stored)"""
     wav = (torch.randn(16000 * 30, device=DEV) * 0.1).clamp(-1, 1)
-    rec("kaldi fbank 30 s", timeit(lambda: F.kaldi_fbank(wav, 80)), bytes_=wav.numel() * 4 + 2998 * 80 * 4)
-    rec("kaldi fbank 30 s, general kernel (16 kHz 25 / 10, 80 bins)",
-        timeit(lambda: F.kaldi_fbank_general(wav, 16000, 80, 25, 10)), bytes_=wav.numel() * 4 + 2998 * 80 * 4)
+    rec("kaldi fbank 30 s (16 kHz 25 / 10, 80 bins)", timeit(lambda: F.kaldi_fbank(wav, 80)),
+        bytes_=wav.numel() * 4 + 2998 * 80 * 4)
     rec("kaldi mfcc 30 s (16 kHz 25 / 10, 23 bins, 13 cepstra)",
         timeit(lambda: F.kaldi_mfcc(wav, 16000, 23, 13, 25, 10)), bytes_=wav.numel() * 4 + 2998 * 13 * 4)
     rec("log-mel 30 s", timeit(lambda: F.log_mel_spectrogram(wav, 128)), bytes_=wav.numel() * 4 + 3000 * 128 * 4)

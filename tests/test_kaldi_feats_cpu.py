@@ -248,5 +248,5 @@ def test_ops_are_registered_with_fake_kernels():
 
 def test_backend_exposes_the_new_functions():
     from touchnet_amd.models.backend import ops
-    for name in ("kaldi_fbank", "kaldi_fbank_general", "kaldi_mfcc", "kaldi_feature_tables"):
+    for name in ("kaldi_fbank", "kaldi_mfcc", "kaldi_feature_tables"):
         assert callable(getattr(ops(), name))

@@ -93,6 +93,58 @@ def test_widest_ratios_take_fewer_outputs_per_workgroup():
     _check(got.cpu().numpy(), x, tab32, o, n, np.arange(3200), "1000->64000 N=50")
 
 
+def _speed_table(speed):
+    p, q, tab = _F().speed_filter_bank(speed)
+    assert tab.shape[0] == q and tab.shape[1] % 2 == 0
+    return p, q, tab.shape[1], tab.astype(np.float32)
+
+
+@pytest.mark.parametrize("speed", [0.9, 1.1])
+def test_speed_perturbation_against_float64_sum_of_its_table(speed):
+    """functional.speed_perturb runs its own table (speed = p / q: q phases, the input position of output m is m p / q) on
+    the same kernel: the lengths and the bound of test_kernel_against_float64_sum_of_the_same_table, the output lengths
+    max(floor(N q / p), 1)."""
+    F, L = _F(), _L()
+    p, q, ntap, tab32 = _speed_table(speed)
+    tab_dev = torch.from_numpy(tab32).to(DEV)
+    for N in (1, 2, ntap - 1, -(-(3 * BLOCK + 77) * p // q)):
+        x = _noise(N, N)
+        got = F.speed_perturb(torch.from_numpy(x).to(DEV), speed)
+        assert got.dtype == torch.float32 and got.shape == (max(N * q // p, 1),)
+        _check(got.cpu().numpy(), x, tab32, p, q, np.arange(got.shape[0]), f"speed {speed} N={N}")
+    assert got.shape[0] >= 3 * BLOCK + 77
+    for n_out in (BLOCK - 1, BLOCK, BLOCK + 1):
+        N = -((-n_out * p) // q)
+        assert max(N * q // p, 1) >= n_out
+        x = _noise(N, 1000 + n_out)
+        got = L.resample_sinc(torch.from_numpy(x).to(DEV), tab_dev, p, q, n_out)
+        _check(got.cpu().numpy(), x, tab32, p, q, np.arange(n_out), f"speed {speed} n_out={n_out}")
+
+
+def test_speed_perturbation_refuses_exactly_the_filters_the_entry_refuses():
+    """The widest filter: functional.RESAMPLE_MAX_SPAN - 2 = 12286 taps is the most tn_resample_sinc takes (-22 from 12288
+    on, before any launch), and speed_perturb raises from the first speed whose filter passes it — 183 (12330 taps), while
+    182 (12262 taps, one output per workgroup) still runs and holds the bound."""
+    from touchnet_amd import _C
+    F = _F()
+    most = F.RESAMPLE_MAX_SPAN - 2
+    x = torch.from_numpy(_noise(400, 182)).to(DEV)
+    y = torch.zeros(8, device=DEV)
+    tab = torch.zeros(most + 2, device=DEV)
+    for ntap, code in ((most, 0), (most + 2, -22)):
+        assert _C.lib().tn_resample_sinc(C.c_void_p(x.data_ptr()), 0, C.c_void_p(y.data_ptr()), C.c_void_p(tab.data_ptr()),
+                                         400, 8, 1, 1, ntap, _C.stream()) == code, ntap
+    torch.cuda.synchronize()
+    p, q, ntap, tab32 = _speed_table(182.0)
+    assert (p, q) == (182, 1) and ntap <= most
+    got = F.speed_perturb(x, 182.0)
+    assert got.shape == (2,)
+    _check(got.cpu().numpy(), x.cpu().numpy(), tab32, p, q, np.arange(2), "speed 182")
+    assert F.speed_filter_bank(183.0)[2].shape[1] > most
+    with pytest.raises(ValueError, match="speed = 183"):
+        F.speed_perturb(x, 183.0)
+
+
 def test_thirty_second_clip_at_48k():
     o, n, ntap, tab32 = _table(48000, 16000)
     x = _noise(30 * 48000, 30)
@@ -101,18 +153,26 @@ def test_thirty_second_clip_at_48k():
     _check(got.cpu().numpy(), x, tab32, o, n, np.arange(got.shape[0]), "30 s 48000->16000")
 
 
-@pytest.mark.parametrize("orig,new", [(44100, 16000), (8000, 16000), (48000, 16000)])
+@pytest.mark.parametrize("orig,new", [(44100, 16000), (8000, 16000), (48000, 16000), (0.9, None)])
 def test_int16_source_is_bit_equal_to_converting_first(orig, new):
     """v * 2^-15 is exact, so reading int16 PCM in the kernel gives the bits of pcm16_to_float followed by the fp32 path —
-    also from an address that is not 16-byte aligned and over every int16 value."""
-    F = _F()
+    also from an address that is not 16-byte aligned and over every int16 value.  (0.9, None): the table of that speed,
+    the entry on int16 PCM against pcm16_to_float followed by speed_perturb."""
+    F, L = _F(), _L()
     allv = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16)
-    pcm = torch.cat([allv[torch.randperm(65536, generator=torch.Generator().manual_seed(orig))], allv[:4097]]).to(DEV)
+    pcm = torch.cat([allv[torch.randperm(65536, generator=torch.Generator().manual_seed(int(orig)))], allv[:4097]]).to(DEV)
+    if new is None:
+        p, q, _, tab32 = _speed_table(orig)
+        tab_dev = torch.from_numpy(tab32).to(DEV)
     for off in (0, 1, 3):
         src = pcm[off:]
         assert off == 0 or src.data_ptr() % 16 != 0
-        a = F.resample(src, orig, new)
-        b = F.resample(F.pcm16_to_float(src), orig, new)
+        if new is None:
+            a = L.resample_sinc(src, tab_dev, p, q, src.numel() * q // p)
+            b = F.speed_perturb(F.pcm16_to_float(src), orig)
+        else:
+            a = F.resample(src, orig, new)
+            b = F.resample(F.pcm16_to_float(src), orig, new)
         assert a.dtype == torch.float32 and torch.equal(a, b), (orig, new, off)
     assert float(a.abs().max()) > 0.5
 

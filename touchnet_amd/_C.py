@@ -46,11 +46,8 @@ PROTOTYPES = {
     "tn_attn_merge": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "tn_attn_bwd_seg": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp,
                         _i, _vp],
-    "tn_fbank_frames": [_i],
-    "tn_kaldi_fbank": [_vp, _vp, _i, _i, _vp],
     "tn_log_mel": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "tn_audiofeat_stack": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "tn_resample_polyphase": [_vp, _vp, _vp, _ll, _ll, _i, _i, _i, _vp],
     "tn_resample_sinc": [_vp, _i, _vp, _vp, _ll, _ll, _i, _i, _i, _vp],
     "tn_kaldi_feats": [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp, _vp],
     "tn_feat_augment": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp],

@@ -1,99 +1,23 @@
-// Audio frontend on the GPU: waveform -> Kaldi log-fbank / Whisper log-mel -> stack+stride+normalise.
+// Audio frontend on the GPU: waveform -> Whisper log-mel; feature rows -> stack+stride+normalise, augmentation;
+// int16 PCM -> float.
 //
 // Replaces the CPU dataloader-worker stages
-//   audio_compute_fbank               touchnet/data/functions.py:117-134 (torchaudio.compliance.kaldi.fbank,
-//                                     energy_floor=0.0, dither=0.0, waveform * 32768)
 //   audio_compute_log_mel_spectrogram touchnet/data/functions.py:159-190 (torch.stft hann-400 hop-160
 //                                     center/reflect, drop last frame, slaney mel, log10, max-8, (x+4)/4);
 //                                     same numbers as HF WhisperFeatureExtractor used by
 //                                     touchnet/models/qwen2_audio/processing_qwen2_audio.py:63-70
 //   audiofeat_stack                   touchnet/data/functions.py:258-286
-// so the dataloader can hand raw PCM to the device (SURVEY.md §8b hook 4).  16 kHz only (every recipe).
+//   audiofeat_spec_aug / _sub / _trim touchnet/data/functions.py:193-255
+// so the dataloader can hand raw PCM to the device (SURVEY.md §8b hook 4).  Log-mel is 16 kHz only (every recipe).
+// The Kaldi features (audio_compute_fbank / audio_compute_mfcc) are csrc/kaldi_feats.hip; resampling and speed
+// perturbation are csrc/resample.hip.
 //
-// All three are HBM-trivial (320 B in, 320-512 B out per 10 ms frame); the kernels keep one frame's
-// working set in LDS and are bounded by LDS/VALU, not memory: fbank = 512-point radix-2 FFT in LDS,
-// log-mel = 400-point direct DFT (400 is not a power of two; 4 frames share each twiddle load).
+// Log-mel and the stack are HBM-trivial (320 B in, 320-512 B out per 10 ms frame); the log-mel kernel keeps its
+// frames' working set in LDS and is bounded by LDS/VALU, not memory: a 400-point direct DFT (400 is not a power of
+// two; 4 frames share each twiddle load).
 #include "common.h"
-#include <float.h>
 
 namespace tn {
-
-constexpr int kWin = 400, kShift = 160, kPad = 512, kBins = 257;
-constexpr float kSr = 16000.f;
-
-__device__ __forceinline__ int bitrev9(int x) { return (int)(__brev((unsigned)x) >> 23); }
-
-__global__ __launch_bounds__(256) void kaldi_fbank_kernel(const float* __restrict__ wav, float* __restrict__ feat,
-                                                          int n_frames, int n_mels) {
-  __shared__ float re[kPad], im[kPad], twc[kPad / 2], tws[kPad / 2], win[kWin], melk[kBins + 3], pw[kBins + 3];
-  __shared__ float red[4];
-  const int tid = threadIdx.x;
-  {  // per-block constants
-    float s, c;
-    sincospif((float)tid / 256.f, &s, &c);  // angle = 2*pi*tid/512
-    twc[tid] = c;
-    tws[tid] = -s;
-    for (int n = tid; n < kWin; n += 256)
-      win[n] = powf(0.5f - 0.5f * cospif(2.f * (float)n / (float)(kWin - 1)), 0.85f);
-    for (int k = tid; k < kBins; k += 256) melk[k] = 1127.f * logf(1.f + (kSr / kPad) * (float)k / 700.f);
-  }
-  const float mel_lo = 1127.f * logf(1.f + 20.f / 700.f);
-  const float mel_hi = 1127.f * logf(1.f + (0.5f * kSr) / 700.f);
-  const float mdelta = (mel_hi - mel_lo) / (float)(n_mels + 1);
-  __syncthreads();
-
-  for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
-    const float* src = wav + (size_t)f * kShift;
-    float part = 0.f;
-    for (int n = tid; n < kWin; n += 256) {
-      const float x = src[n] * 32768.f;
-      im[n] = x;  // raw samples parked in `im`
-      part += x;
-    }
-    const float mean = block_sum(part, red) / (float)kWin;  // (contains the barriers that publish im[])
-    for (int n = tid; n < kPad; n += 256) {
-      float y = 0.f;
-      if (n < kWin) {
-        const float cur = im[n] - mean;
-        const float prev = (n > 0 ? im[n - 1] : im[0]) - mean;
-        y = (cur - 0.97f * prev) * win[n];
-      }
-      re[bitrev9(n)] = y;
-    }
-    __syncthreads();
-    for (int n = tid; n < kPad; n += 256) im[n] = 0.f;
-    __syncthreads();
-#pragma unroll 1
-    for (int s = 1; s <= 9; ++s) {
-      const int half = 1 << (s - 1);
-      const int pos = tid & (half - 1);
-      const int i = ((tid >> (s - 1)) << s) + pos;
-      const int j = i + half;
-      const int tw = pos << (9 - s);
-      const float c = twc[tw], sn = tws[tw];
-      const float br = re[j] * c - im[j] * sn, bi = re[j] * sn + im[j] * c;
-      const float ar = re[i], ai = im[i];
-      re[i] = ar + br;
-      im[i] = ai + bi;
-      re[j] = ar - br;
-      im[j] = ai - bi;
-      __syncthreads();
-    }
-    for (int k = tid; k < kBins; k += 256) pw[k] = re[k] * re[k] + im[k] * im[k];
-    __syncthreads();
-    if (tid < n_mels) {
-      const float left = mel_lo + (float)tid * mdelta, center = left + mdelta, right = center + mdelta;
-      float acc = 0.f;
-      for (int k = 0; k < kPad / 2; ++k) {  // bin 256 carries zero weight (torchaudio pads one zero column)
-        const float m = melk[k];
-        const float w = fminf((m - left) / (center - left), (right - m) / (right - center));
-        if (w > 0.f) acc += w * pw[k];
-      }
-      feat[(size_t)f * n_mels + tid] = logf(fmaxf(acc, FLT_EPSILON));
-    }
-    __syncthreads();
-  }
-}
 
 // ---------------------------------------------------------------------------------------------- log-mel
 constexpr int kNfft = 400, kHop = 160, kFreq = 201, kFr = 4;
@@ -240,33 +164,6 @@ __global__ __launch_bounds__(256) void feat_augment_kernel(const float* __restri
   y[i] = zero ? 0.f : x[(size_t)src * F + f];
 }
 
-// ---------------------------------------------------------------------------------------------- speed perturbation
-// touchnet/data/functions.py:99-114: sox `speed s` + `rate sr` = the waveform resampled by the factor 1/s (pitch and tempo
-// change together).  libsox's polyphase resampler is a third-party binary algorithm that cannot be restated bit for bit
-// (and torchaudio is not in this image to compare with): this kernel evaluates the band-limited interpolation
-//     y[n] = sum_k x[k] h(n s - k),   h(t) = c sinc(c t) kaiser(t / W),  c = 0.95 min(1, 1/s)
-// from a polyphase table the host builds in float64 for the rational speed p / q (touchnet_amd/functional.py): output n sits
-// at input position (n p) / q -> integer part i, phase r = (n p) mod q, and y[n] = sum_j x[i - half + 1 + j] tab[r][j].
-// PARITY UNPINNED against libsox (stated in DESIGN.md); held to a float64 evaluation of the same formula (oracle/frontend.py).
-__global__ __launch_bounds__(256) void resample_polyphase_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                 const float* __restrict__ tab, long long n_in,
-                                                                 long long n_out, int p, int q, int ntap) {
-  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (n >= n_out) return;
-  const long long pos = n * p;
-  const long long i = pos / q;
-  const int r = (int)(pos - i * q);
-  const float* t = tab + (size_t)r * ntap;
-  const long long k0 = i - ntap / 2 + 1;
-  float acc = 0.f;
-  for (int j = 0; j < ntap; ++j) {
-    const long long k = k0 + j;
-    const float xv = (k >= 0 && k < n_in) ? x[k] : 0.f;
-    acc = fmaf(xv, t[j], acc);
-  }
-  y[n] = acc;
-}
-
 // int16 PCM -> float32 in [-1, 1): x * 2^-15, exactly numpy's `astype(float32) / 32768.0` of the reference's
 // datapipe (touchnet/data/datapipe.py:164).  Lets the caller upload 2 bytes per sample.
 __global__ __launch_bounds__(256) void pcm16_to_f32_kernel(const int16_t* __restrict__ in, float* __restrict__ out,
@@ -295,18 +192,6 @@ __global__ __launch_bounds__(256) void pcm16_to_f32_kernel(const int16_t* __rest
 using namespace tn;
 
 extern "C" {
-
-int tn_fbank_frames(int n_samples) { return n_samples < kWin ? 0 : 1 + (n_samples - kWin) / kShift; }
-
-int tn_kaldi_fbank(const float* wav, float* feat, int n_samples, int n_mels, void* stream) {
-  const int nf = tn_fbank_frames(n_samples);
-  if (n_mels <= 0 || n_mels > 256) return TN_EINVAL;
-  if (nf == 0) return TN_OK;
-  hipLaunchKernelGGL(kaldi_fbank_kernel, dim3(nf < 2048 ? nf : 2048), dim3(256), 0, (hipStream_t)stream, wav, feat,
-                     nf, n_mels);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
-}
 
 // scratch_max: device float[1]
 int tn_log_mel(const float* wav, const float* mel_fb, float* feat, float* scratch_max, int n_samples, int n_mels,
@@ -354,16 +239,6 @@ int tn_feat_augment(const float* x, float* y, int T, int F, int out_rows, const 
   const long long n = (long long)out_rows * F;
   hipLaunchKernelGGL(feat_augment_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, F,
                      n, plan);
-  TN_LAUNCH_CHECK();
-  return TN_OK;
-}
-
-// x [n_in] -> y [n_out] at the rational rate p / q input samples per output sample; tab: device float [q][ntap] (ntap even).
-int tn_resample_polyphase(const float* x, float* y, const float* tab, long long n_in, long long n_out, int p, int q,
-                          int ntap, void* stream) {
-  if (n_in <= 0 || n_out <= 0 || p <= 0 || q <= 0 || ntap <= 0 || (ntap & 1) || x == y) return TN_EINVAL;
-  hipLaunchKernelGGL(resample_polyphase_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     x, y, tab, n_in, n_out, p, q, ntap);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }

@@ -1,7 +1,6 @@
 // Kaldi log-fbank and MFCC at any sample rate and frame geometry: the `audio_compute_fbank` / `audio_compute_mfcc` stages,
 // touchnet/data/functions.py:117-156 (`torchaudio.compliance.kaldi.fbank` / `.mfcc`, snip_edges, dither 0, waveform * 32768,
-// use_energy false).  The recipes' own geometry (16 kHz, 25 ms / 10 ms, 20 Hz .. Nyquist) keeps its kernel,
-// csrc/frontend.hip::kaldi_fbank_kernel; this one takes what that one hard-codes as arguments and tables.
+// use_energy false).  The one Kaldi feature kernel: the recipes' 16 kHz 25 ms / 10 ms fbank is one geometry among the rest.
 //
 // Per frame f (one workgroup of 256 threads, grid-stride over the frames):
 //     x[n]   = wav[f shift + n] * 32768,  n < win                       win = int(sr frame_length_ms / 1000)

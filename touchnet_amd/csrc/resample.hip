@@ -3,8 +3,8 @@
 // lowpass_filter_width 6, rolloff 0.99).
 //
 // torchaudio's algorithm is a closed formula — a Hann-windowed sinc evaluated per output phase and applied as a strided
-// convolution over the zero-padded waveform — so, unlike libsox's speed perturbation beside it (csrc/frontend.hip), it can
-// be restated exactly.  With o = orig / gcd, n = new / gcd, output m sits at input position (m o) / n: integer part i,
+// convolution over the zero-padded waveform — so, unlike libsox's speed perturbation (below), it can be restated
+// exactly.  With o = orig / gcd, n = new / gcd, output m sits at input position (m o) / n: integer part i,
 // phase r = (m o) mod n, and
 //     y[m] = sum_j tab[r][j] * x[i - ntap / 2 + 1 + j],          x = 0 outside [0, n_in)
 // where tab [n][ntap] holds the non-zero columns of torchaudio's kernel, rounded to float32 by the host
@@ -15,9 +15,18 @@
 // [i(m0) - ntap / 2 + 1, i(m0 + per - 1) + ntap / 2], at most (per - 1) o / n + 2 + ntap of them; the workgroup stages
 // that span through LDS once, converted, with the part outside [0, n_in) zero-filled, so the tap loop has neither bounds
 // checks nor conversions and neighbouring outputs share their samples on chip.  Measured against the same sum read
-// straight from global memory (the shape of resample_polyphase_kernel) the staging is 1.5x - 3x faster on 30 s clips
-// (profiles/resample_bench_plain_vs_lds.log), so it is the one kernel.  Every position is 64-bit:
-// m * o passes 2^31 after five minutes of 44.1 kHz audio.
+// straight from global memory, one bounds-checked load per tap, the staging is 1.5x - 3x faster on 30 s clips
+// (profiles/resample_bench_plain_vs_lds.log) and 3.4x - 4.0x on speed perturbation's 68 and 76 taps
+// (profiles/frontend_one_kernel.log), so it is the one kernel: functional.py::speed_perturb runs on it with its own
+// table, o / n = the speed p / q.
+// Every position is 64-bit: m * o passes 2^31 after five minutes of 44.1 kHz audio.
+//
+// Speed perturbation, touchnet/data/functions.py:99-114: sox `speed s` + `rate sr` = the waveform resampled by the
+// factor 1 / s (pitch and tempo change together).  libsox's polyphase resampler is a third-party binary algorithm that
+// cannot be restated bit for bit, so the host builds the table of the band-limited interpolation
+//     y[m] = sum_k x[k] h(m s - k),   h(t) = c sinc(c t) kaiser(t / W),  c = 0.95 min(1, 1 / s)
+// in float64 for the rational speed p / q (functional.py::speed_filter_bank) and this kernel sums it.  PARITY UNPINNED
+// against libsox (stated in DESIGN.md); held to a float64 evaluation of the same formula (oracle/frontend.py).
 #include "common.h"
 
 namespace tn {

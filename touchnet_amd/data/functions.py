@@ -53,17 +53,14 @@ def _refuse_dither(config, stage):
 
 
 def audio_compute_fbank(data, config):
-    """functions.py:117-134.  At the recipes' geometry (16 kHz, 25 ms / 10 ms) the frame geometry is compiled into
-    `kaldi_fbank`; a sample of any other rate, or any other frame length / shift, goes to the kernel that takes them as
-    arguments (functional.kaldi_fbank_general, 20 Hz .. Nyquist as torchaudio's defaults)."""
+    """functions.py:117-134: Kaldi log-fbank at the sample's own rate and the config's frame length / shift (20 Hz ..
+    Nyquist as torchaudio's defaults), in one launch per utterance."""
     for sample in data:
         _refuse_dither(config, "audio_compute_fbank")
-        if sample["sample_rate"] == 16000 and config.audiofeat_frame_length == 25 and config.audiofeat_frame_shift == 10:
-            sample["audiofeat"] = ops().kaldi_fbank(_dev_wave(sample), config.audiofeat_num_mel_bins)
-        else:
-            sample["audiofeat"] = ops().kaldi_fbank_general(_dev_wave(sample), sample["sample_rate"],
-                                                            config.audiofeat_num_mel_bins, config.audiofeat_frame_length,
-                                                            config.audiofeat_frame_shift)
+        sample["audiofeat"] = ops().kaldi_fbank(_dev_wave(sample), config.audiofeat_num_mel_bins,
+                                                sample_rate=sample["sample_rate"],
+                                                frame_length=config.audiofeat_frame_length,
+                                                frame_shift=config.audiofeat_frame_shift)
         yield sample
 
 

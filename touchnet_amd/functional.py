@@ -1589,11 +1589,6 @@ def slaney_mel_filters(n_mels: int, device) -> torch.Tensor:
     return _MEL_CACHE[key]
 
 
-def kaldi_fbank(wav: torch.Tensor, num_mel_bins: int = 80) -> torch.Tensor:
-    """wav fp32 [N] in [-1, 1) at 16 kHz -> fp32 [frames, num_mel_bins] (functions.py:117-134)."""
-    return L.kaldi_fbank(_c(wav).float().view(-1), int(num_mel_bins))
-
-
 KALDI_MIN_PADDED, KALDI_MAX_PADDED = 32, 2048     # FFT sizes of csrc/kaldi_feats.hip (8 .. 48 kHz at 25 ms, 16 kHz to 128 ms)
 KALDI_MIN_BINS, KALDI_MAX_BINS = 4, 256           # torchaudio asks for more than 3 bins; one thread per bin
 KALDI_LIFTER = 22.0                               # torchaudio's / Kaldi's cepstral_lifter
@@ -1690,13 +1685,13 @@ def _kaldi_wave(wav, what):
     return _c(wav).float().view(-1)
 
 
-def kaldi_fbank_general(wav: torch.Tensor, sample_rate: int, num_mel_bins: int, frame_length, frame_shift,
-                        low_freq: float = 20.0, high_freq: float = 0.0) -> torch.Tensor:
+def kaldi_fbank(wav: torch.Tensor, num_mel_bins: int = 80, sample_rate: int = 16000, frame_length=25.0, frame_shift=10.0,
+                low_freq: float = 20.0, high_freq: float = 0.0) -> torch.Tensor:
     """wav fp32 [N] in [-1, 1) at `sample_rate` Hz -> Kaldi log-fbank fp32 [frames, num_mel_bins] with windows of
-    `frame_length` ms every `frame_shift` ms (functions.py:117-134 at any rate and geometry; `kaldi_fbank` is the
-    recipes' 16 kHz 25 / 10 kernel)."""
+    `frame_length` ms every `frame_shift` ms (functions.py:117-134 at any rate and geometry; the defaults are the
+    recipes' 16 kHz 25 / 10, 20 Hz .. Nyquist)."""
     key = (int(sample_rate), frame_length, frame_shift, int(num_mel_bins), float(low_freq), float(high_freq), None)
-    wav = _kaldi_wave(wav, "kaldi_fbank_general")
+    wav = _kaldi_wave(wav, "kaldi_fbank")
     shift, window, idx, w, _ = _kaldi_device_tables(wav.device, *key)
     return L.kaldi_feats(wav, window, idx, w, key[0], shift, key[4], key[5])
 
@@ -1747,6 +1742,7 @@ def bestrq_tokenize(feat: torch.Tensor, quantizer: torch.Tensor, codebook: torch
 SPEED_ZEROS = 32            # zero crossings of the interpolation kernel on each side (at the cutoff's scale)
 SPEED_ROLLOFF = 0.95        # pass band as a fraction of the narrower Nyquist band
 SPEED_BETA = 14.769656459379492   # Kaiser window: ~ -150 dB side lobes
+RESAMPLE_MAX_SPAN = 12288  # samples a workgroup of csrc/resample.hip stages (48 KiB of LDS): ntap + 2 of them for one output
 _SPEED_TABLES = {}
 
 
@@ -1778,10 +1774,13 @@ def speed_perturb(wave: torch.Tensor, speed: float) -> torch.Tensor:
     key = (float(speed), wave.device)
     if key not in _SPEED_TABLES:
         p_, q_, tab = speed_filter_bank(speed)
+        if tab.shape[1] + 2 > RESAMPLE_MAX_SPAN:
+            raise ValueError(f"speed_perturb: speed = {speed} needs {tab.shape[1]} filter taps, more than the "
+                             f"{RESAMPLE_MAX_SPAN - 2} tn_resample_sinc stages for one output")
         _SPEED_TABLES[key] = (p_, q_, torch.from_numpy(tab).to(torch.float32).to(wave.device).contiguous())
     p_, q_, tab = _SPEED_TABLES[key]
     n_out = (wave.numel() * q_) // p_
-    return L.resample_polyphase(_c(wave).float(), tab, p_, q_, max(n_out, 1))
+    return L.resample_sinc(_c(wave).float(), tab, p_, q_, max(n_out, 1))
 
 
 RESAMPLE_WIDTH = 6          # torchaudio's lowpass_filter_width: zero crossings of the sinc on each side
@@ -1810,7 +1809,7 @@ def sinc_resample_table(orig: int, new: int):
         base = 0.99 min(o, n), width = ceil(6 o / base), j < n, k < 2 width + o,
     applied to the waveform padded by (width, width + o) at stride o.  Row r of the table is phase j = r o^-1 mod n of K
     — the phase of every output m with (m o) mod n = r — cut to the ntap = 2 floor(6 o / base) + 2 columns around input
-    floor(m o / n) in the layout of tn_resample_polyphase; each entry is K's expression evaluated in K's order at its
+    floor(m o / n) in the layout of tn_resample_sinc; each entry is K's expression evaluated in K's order at its
     (j, k), and the columns left out are exactly 0 once rounded to float32 (|t| clamps to 6 there, where the window is
     cos(pi / 2)^2 ~ 4e-33)."""
     import numpy as np

@@ -714,20 +714,6 @@ def _(nll, hit, labels, sentence_lens, num_sentence, ignore_index):
 
 
 # ===================================================================================================== audio frontend
-@custom_op(f"{NS}::kaldi_fbank", mutates_args=(), device_types="cuda")
-def kaldi_fbank(wav: Tensor, num_mel_bins: int) -> Tensor:
-    nf = _lib().tn_fbank_frames(wav.numel())
-    feat = torch.empty(nf, num_mel_bins, dtype=torch.float32, device=wav.device)
-    _C.check(_lib().tn_kaldi_fbank(_p(wav), _p(feat), wav.numel(), num_mel_bins, _cur()), "tn_kaldi_fbank")
-    return feat
-
-
-@kaldi_fbank.register_fake
-def _(wav, num_mel_bins):
-    n = wav.numel()
-    return wav.new_empty(max(0, 1 + (n - 400) // 160) if n >= 400 else 0, num_mel_bins)
-
-
 @custom_op(f"{NS}::log_mel", mutates_args=(), device_types="cuda")
 def log_mel(wav: Tensor, mel_fb: Tensor, num_mel_bins: int) -> Tensor:
     feat = torch.empty(wav.numel() // 160, num_mel_bins, dtype=torch.float32, device=wav.device)
@@ -754,14 +740,6 @@ def audiofeat_stack(feat: Tensor, stack: int, stride: int, normalize: bool) -> T
 @audiofeat_stack.register_fake
 def _(feat, stack, stride, normalize):
     return feat.new_empty((feat.shape[0] + stride - 1) // stride, feat.shape[1] * stack)
-
-
-def resample_polyphase(wave: Tensor, tab: Tensor, p: int, q: int, n_out: int) -> Tensor:
-    """tn_resample_polyphase on a 1-D fp32 device waveform"""
-    out = torch.empty(n_out, dtype=torch.float32, device=wave.device)
-    _C.check(_lib().tn_resample_polyphase(_p(wave), _p(out), _p(tab), wave.numel(), int(n_out), int(p), int(q),
-                                          int(tab.shape[1]), _cur()), "tn_resample_polyphase")
-    return out
 
 
 def resample_sinc(wave: Tensor, tab: Tensor, orig: int, new: int, n_out: int) -> Tensor:
@@ -1366,7 +1344,7 @@ OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fw
        "gelu_bwd", "rope_apply", "attn_fwd", "attn_bwd", "attn_fwd_bidir", "attn_bwd_bidir", "attn_bwd_stacked",
        "attn_bwd_rope", "attn_build_meta", "attn_fwd_seg", "attn_fwd_seg_chunks", "attn_merge", "attn_bwd_seg", "ce_fwd",
        "ce_bwd", "ce_bwd_", "gemm_tn", "rope_table", "transpose_bf16_", "colsum_bf16", "swiglu_fwd_t", "swiglu_bwd_t",
-       "ce_fwd_rows", "ce_reduce", "kaldi_fbank", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
+       "ce_fwd_rows", "ce_reduce", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
        "constrain_logits_", "token_scores", "token_scores_")
