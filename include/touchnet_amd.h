@@ -207,6 +207,37 @@ int tn_resample_sinc(const void* x, int x_is_pcm16, float* y, const float* tab, 
 int tn_kaldi_feats(const float* wav, float* out, long long n_samples, int sample_rate, int win, int shift, int padded,
                    int num_mel_bins, int num_ceps, float low_freq, float high_freq, const float* window,
                    const int* bank_idx, const float* bank_w, int n_bank_w, const float* dct, void* stream);
+/* Voice-activity detection for recordings longer than one utterance: the energy rule of Kaldi's `compute-vad-energy`.
+ * This goes beyond the reference, whose inference scripts cut every waveform at 30 s
+ * (touchnet/models/qwen2_audio/inference_qwen2_audio.py:101, touchnet/models/kimi_audio/processing_kimi_audio.py:73).
+ * Framing as tn_kaldi_feats: frame t = samples [t shift, t shift + win), T = n < win ? 0 : 1 + (n - win) / shift.
+ * vad_log_energy: x [n] fp32 in [-1, 1) or int16 PCM (x_is_pcm16) -> loge fp32 [T] = log(max(sum_j (s_j - mean)^2,
+ *      FLT_EPSILON)) over the frame's samples s on the int16 scale (int16 as is, fp32 times 32768: the same bits), mean
+ *      first and squared deviations second, in fp32 in a fixed order; a frame of equal samples is log(FLT_EPSILON)
+ *      exactly.  partials double [ceil(T / tn_vad_frames_per_block(win, shift))]: each workgroup's fp64 sum of its frames'
+ *      loge.  A workgroup stages the samples of its frames through LDS once; all sample positions are 64-bit.  One
+ *      launch (none for T == 0, whatever the pointers), no allocation, no synchronisation.
+ *      -22 before any launch for win outside [1, 4096], shift < 1 (shift > win is legal), n < 0, T >= 2^31, and with
+ *      T > 0 a NULL pointer, loge == x, or x / loge / partials not aligned to their elements.
+ * vad_runs: thr = energy_threshold + mean_scale * sum(partials[0 .. n_partials)) / T (fp64, fixed order); for every t,
+ *      den = the frames of [t - ctx, t + ctx] inside [0, T), num = those with loge > thr, voiced_u8[t] = (num >=
+ *      den * proportion), evaluated in fp64; runs int [capacity][2] = the maximal intervals of voiced frames as ordered
+ *      (start, end) pairs, end exclusive, count[0] their number; rows from count on are not written.  loge is an input:
+ *      any decision pattern can be handed in, with partials = {its sum}.  workspace: tn_vad_runs_workspace_bytes(T)
+ *      bytes, 8-byte aligned.  Four launches ordered by the stream (threshold; vote and per-workgroup run counts;
+ *      exclusive scan; starts and ends): no workgroup waits on another, no floating-point atomics, bit-identical repeats.
+ *      T == 0: count[0] = 0, nothing else is read or written.
+ *      -22 before any launch for T outside [0, 2^31), ctx outside [0, 64], proportion outside (0, 1], a NaN threshold or
+ *      scale, capacity < T / 2 + 1, count NULL, and with T > 0 any other NULL or misaligned pointer or n_partials < 1.
+ * tn_vad_frames_per_block: the frames one workgroup of vad_log_energy owns (at most 64; fewer when their samples pass
+ *      48 KiB of LDS); -1 outside the limits of win and shift.  tn_vad_runs_workspace_bytes: -1 for T outside [0, 2^31). */
+int tn_vad_frames_per_block(int win, int shift);
+long long tn_vad_runs_workspace_bytes(long long T);
+int tn_vad_log_energy(const void* x, int x_is_pcm16, float* loge, double* partials, long long n, int win, int shift,
+                      void* stream);
+int tn_vad_runs(const float* loge, long long T, const double* partials, long long n_partials, double energy_threshold,
+                double mean_scale, int ctx, double proportion, unsigned char* voiced_u8, int* runs, int* count,
+                long long capacity, void* workspace, void* stream);
 
 /* ---- fused AdamW on fp32 master weights with bf16 shadow write-back and device-side
  *      skip-on-nonfinite — touchnet/utils/optimizer.py:157-172 + touchnet/bin/train.py:458-474.

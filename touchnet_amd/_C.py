@@ -50,6 +50,10 @@ PROTOTYPES = {
     "tn_audiofeat_stack": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
     "tn_resample_sinc": [_vp, _i, _vp, _vp, _ll, _ll, _i, _i, _i, _vp],
     "tn_kaldi_feats": [_vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp, _vp],
+    "tn_vad_frames_per_block": [_i, _i],
+    "tn_vad_runs_workspace_bytes": [_ll],
+    "tn_vad_log_energy": [_vp, _i, _vp, _vp, _ll, _i, _i, _vp],
+    "tn_vad_runs": [_vp, _ll, _vp, _ll, C.c_double, C.c_double, _i, C.c_double, _vp, _vp, _vp, _ll, _vp, _vp],
     "tn_feat_augment": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp],
     "tn_sumsq_scratch_floats": [],
     "tn_sumsq": [_vp, _vp, _vp, _ll, _i, _vp],
@@ -113,7 +117,8 @@ _RESTYPE = {"tn_gemm_set_persistent": None, "tn_version": C.c_char_p, "tn_sumsq_
             "tn_colsum_workspace_floats": C.c_longlong, "tn_gemm_splitk_workspace_bytes": C.c_longlong,
             "tn_gemm_grouped_workspace_bytes": C.c_longlong, "tn_gemm_grouped_table_bytes": C.c_longlong,
             "tn_attn_decode_workspace_bytes": C.c_longlong, "tn_beam_step_workspace_bytes": C.c_longlong,
-            "tn_edit_align_ws_words": C.c_longlong, "tn_philox4x32_10": None}
+            "tn_edit_align_ws_words": C.c_longlong, "tn_vad_runs_workspace_bytes": C.c_longlong,
+            "tn_philox4x32_10": None}
 
 # kernel-development entry points: exported by the library, deliberately NOT part of the C ABI (include/touchnet_amd.h)
 DEV_PROTOTYPES = {

@@ -22,6 +22,11 @@ Confidences and N-best lists: `--output_scores` adds "confidence", "token_logpro
 (one entry per generated token up to and including the eos), `--top_alternatives K` adds "alternatives" ([[id, logp], ...]
 per token), `--nbest N` (with --num_beams >= N) adds "nbest", the N best finished hypotheses; see DESIGN 9.7.  Without
 these flags the output file is what it was.
+Long recordings: `--long_form` cuts a recording longer than `--max_segment_s` (30) into segments with an energy VAD on the
+device (`--vad_*`: Kaldi's compute-vad-energy defaults and common segmenting values, which nobody has tuned for this use),
+decodes the segments of a batch pooled, and writes "predict_ids" / "predict" of their concatenation plus "segments"
+(start, end in seconds and each segment's own fields); see longform.transcribe_long and DESIGN 9.9.  Records of shorter
+recordings, and every record without the flag, are what they were.
 """
 from __future__ import annotations
 
@@ -36,8 +41,9 @@ import numpy as np
 import torch
 
 from touchnet_amd.data import functions as stages
-from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_score_arguments,
-                                     constraints_from_args)
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_longform_arguments,
+                                     add_score_arguments, constraints_from_args)
+from touchnet_amd.longform import longform_from_args, touch_audio_decoder, transcribe_long
 from touchnet_amd.models.backend import ops
 from touchnet_amd.models.touch_audio import TouchAudioConfig, TouchAudioForCausalLM
 from touchnet_amd.models.touch_audio.inference_touch_audio import transcribe
@@ -144,7 +150,7 @@ def record_line(item, ids, extra: dict, tokenizer=None) -> str:
     return json.dumps(rec, ensure_ascii=False) + "\n"
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model_path", required=True)
     ap.add_argument("--data_list", required=True)
@@ -161,7 +167,23 @@ def main(argv=None):
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
     add_score_arguments(ap)
-    args = ap.parse_args(argv)
+    add_longform_arguments(ap)
+    return ap
+
+
+def generation_config(args, tokenizer=None) -> GenerationConfig:
+    cfg = GenerationConfig(max_new_tokens=args.max_new_tokens, repetition_penalty=args.repetition_penalty,
+                           no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
+                           length_penalty=args.length_penalty,
+                           early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
+                           sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0,
+                           output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
+    cfg.check_beams()
+    return cfg
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -174,20 +196,24 @@ def main(argv=None):
     with open(args.data_list) as f:
         items = [json.loads(line) for line in f if line.strip()]
     items = items[args.shard_index::args.num_shards]
-    cfg = GenerationConfig(max_new_tokens=args.max_new_tokens, repetition_penalty=args.repetition_penalty,
-                           no_repeat_ngram_size=args.no_repeat_ngram_size, num_beams=args.num_beams,
-                           length_penalty=args.length_penalty,
-                           early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
-                           sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0,
-                           output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
-    cfg.check_beams()
+    cfg = generation_config(args, tokenizer)
+    long_cfg = longform_from_args(args)
+    rate = int(dcfg.audio_resample_rate)
+    text = None if tokenizer is None else (
+        lambda row: tokenizer.decode(row, skip_special_tokens=True, clean_up_tokenization_spaces=False))
     os.makedirs(args.output_dir, exist_ok=True)
     out_path = os.path.join(args.output_dir, f"part_{args.shard_index + 1}_of_{args.num_shards}")
     with open(out_path, "w") as writer:
         for i in range(0, len(items), args.batch_size):
             batch = items[i:i + args.batch_size]
-            feats = features([read_wav(it["wav"], int(dcfg.audio_resample_rate)) for it in batch], dcfg)
-            ids, extras = transcribe(model, feats, cfg, details=True)
+            wavs = [read_wav(it["wav"], rate) for it in batch]
+            if long_cfg is not None:
+                done = transcribe_long(touch_audio_decoder(model, cfg, lambda ws: features(ws, dcfg)), wavs, rate, long_cfg,
+                                       args.batch_size, to_text=text, nbest=cfg.nbest, output_scores=cfg.wants_scores,
+                                       device=device)
+                ids, extras = [d["predict_ids"] for d in done], [d["extra"] for d in done]
+            else:
+                ids, extras = transcribe(model, features(wavs, dcfg), cfg, details=True)
             for it, row, extra in zip(batch, ids, extras):
                 writer.write(record_line(it, row, extra, tokenizer))
     return out_path

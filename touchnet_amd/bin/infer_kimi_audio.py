@@ -14,6 +14,11 @@ trust_remote_code as in the reference).  `data.list`: one JSON object per line w
 other than 16 kHz is resampled on the device, infer_asr.read_wav).
 Output: OUT/part_{i+1}_of_{n}, one JSON line per utterance, {"label": the input line, "predict": text}.  The draws of a
 sampled run are keyed by the utterance's line number in the data list, so it decodes the same whatever its batch or shard.
+Long recordings: `--long_form` cuts a recording longer than `--max_segment_s` (30: what the feature extractor keeps) into
+segments with an energy VAD on the device (`--vad_*`, untuned defaults; infer_asr's docstring and DESIGN 9.9), decodes
+them pooled and writes the "predict" of their concatenation plus "segments".  Segment i of line n draws with the key
+n + (i + 1) 2^40, and a sampled run (--text_temperature above 1e-6) decodes one segment per call.  Other records, and
+every record without the flag, are what they were.
 """
 from __future__ import annotations
 
@@ -25,7 +30,8 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import KimiGenerationConfig, add_score_arguments
+from touchnet_amd.generation import KimiGenerationConfig, add_longform_arguments, add_score_arguments
+from touchnet_amd.longform import kimi_audio_decoder, longform_from_args, transcribe_long
 from touchnet_amd.models.kimi_audio import KimiAudioConfig, KimiAudioPackedForCausalLM
 from touchnet_amd.models.kimi_audio.inference_kimi_audio import transcribe
 from touchnet_amd.models.kimi_audio.processing_kimi_audio import BLANK, DEFAULT_INSTRUCT, EOS
@@ -55,7 +61,7 @@ def special_id(tokenizer, token: str, default: int) -> int:
     return int(default) if i is None or i == getattr(tokenizer, "unk_token_id", None) else int(i)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model_path", required=True)
     ap.add_argument("--instruct", default=DEFAULT_INSTRUCT)
@@ -71,12 +77,22 @@ def main(argv=None):
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     add_score_arguments(ap, nbest=False)
-    args = ap.parse_args(argv)
-    cfg = KimiGenerationConfig(text_temperature=args.text_temperature, text_top_k=args.text_top_k,
-                               text_repetition_penalty=args.text_repetition_penalty,
-                               text_repetition_window_size=args.text_repetition_window_size,
-                               max_new_tokens=args.max_new_tokens, seed=args.seed, output_scores=args.output_scores,
-                               top_alternatives=args.top_alternatives)
+    add_longform_arguments(ap)
+    return ap
+
+
+def generation_config(args) -> KimiGenerationConfig:
+    return KimiGenerationConfig(text_temperature=args.text_temperature, text_top_k=args.text_top_k,
+                                text_repetition_penalty=args.text_repetition_penalty,
+                                text_repetition_window_size=args.text_repetition_window_size,
+                                max_new_tokens=args.max_new_tokens, seed=args.seed, output_scores=args.output_scores,
+                                top_alternatives=args.top_alternatives)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    cfg = generation_config(args)
+    long_cfg = longform_from_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("infer_kimi_audio needs the MI355X (there is no CPU path)")
     from transformers import AutoTokenizer
@@ -95,7 +111,14 @@ def main(argv=None):
             batch = items[i:i + args.batch_size]
             wavs = [read_wav(it["wav"]) for _, it in batch]
             keys = torch.tensor([n for n, _ in batch], dtype=torch.int64)
-            _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
+            if long_cfg is not None:
+                to_text = getattr(tokenizer, "detokenize", None) or tokenizer.decode
+                done = transcribe_long(kimi_audio_decoder(model, tokenizer, args.instruct, cfg), wavs, 16000, long_cfg,
+                                       args.batch_size, row_keys=keys.tolist(), to_text=to_text,
+                                       output_scores=cfg.wants_scores, sampled=cfg.text_temperature > 1e-6, device=device)
+                texts, extras = [d["predict"] for d in done], [d["extra"] for d in done]
+            else:
+                _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
             for (_, it), text, extra in zip(batch, texts, extras):
                 writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text, **extra},
                                         ensure_ascii=False) + "\n")

@@ -25,6 +25,11 @@ Confidences and N-best lists: `--output_scores` adds "confidence", "token_logpro
 (one entry per generated token up to and including the eos), `--top_alternatives K` adds "alternatives" ([[id, logp], ...]
 per token), `--nbest N` (beam search with at least N beams) adds "nbest", the N best finished hypotheses with their ids;
 see DESIGN 9.7.  Without these flags the output file is what it was.
+Long recordings: `--long_form` cuts a recording longer than `--max_segment_s` (30: what the feature extractor keeps) into
+segments with an energy VAD on the device (`--vad_*`, untuned defaults; infer_asr's docstring and DESIGN 9.9), decodes
+them pooled and writes the "predict" of their concatenation plus "segments".  Segment i of line n draws with the key
+n + (i + 1) 2^40 and a sampled run decodes one segment per call, so it does not depend on --batch_size.  Other records
+are what they were.
 """
 from __future__ import annotations
 
@@ -36,8 +41,9 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_score_arguments,
-                                     constraints_from_args)
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_longform_arguments,
+                                     add_score_arguments, constraints_from_args)
+from touchnet_amd.longform import longform_from_args, qwen2_audio_decoder, transcribe_long
 from touchnet_amd.models.qwen2_audio import Qwen2AudioConfig, Qwen2AudioPackedForConditionalGeneration
 from touchnet_amd.models.qwen2_audio.inference_qwen2_audio import build_prompts, transcribe, valid_frames
 from touchnet_amd.models.qwen2_audio.processing_qwen2_audio import DEFAULT_INSTRUCT
@@ -83,7 +89,7 @@ def load_model(model_path: str, device) -> Qwen2AudioPackedForConditionalGenerat
     return model.to(device).to(torch.bfloat16).eval()
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model_path", required=True)
     ap.add_argument("--instruct", default=DEFAULT_INSTRUCT)
@@ -100,13 +106,11 @@ def main(argv=None):
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
     add_score_arguments(ap)
-    args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("infer_qwen2_audio needs the MI355X (there is no CPU path)")
-    from transformers import AutoTokenizer
-    device = torch.device("cuda", torch.cuda.current_device())
-    model = load_model(args.model_path, device)
-    tokenizer = AutoTokenizer.from_pretrained(args.model_path)
+    add_longform_arguments(ap)
+    return ap
+
+
+def generation_config(args, tokenizer=None) -> GenerationConfig:
     over = dict(max_length=args.max_length, seed=args.seed)
     if args.output_scores or args.top_alternatives or args.nbest != 1:
         over.update(output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
@@ -123,6 +127,20 @@ def main(argv=None):
     cfg.sequence_bias = constraints_from_args(args, tokenizer, cfg.sequence_bias)
     if args.min_new_tokens is not None:
         cfg.min_new_tokens = args.min_new_tokens
+    return cfg
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("infer_qwen2_audio needs the MI355X (there is no CPU path)")
+    from transformers import AutoTokenizer
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = load_model(args.model_path, device)
+    tokenizer = AutoTokenizer.from_pretrained(args.model_path)
+    cfg = generation_config(args, tokenizer)
+    long_cfg = longform_from_args(args)
+    to_text = lambda r: tokenizer.decode(r, skip_special_tokens=True, clean_up_tokenization_spaces=False)
     with open(args.data_list) as f:
         items = [(n, json.loads(line)) for n, line in enumerate(f) if line.strip()]
     items = items[args.shard_index::args.num_shards]
@@ -138,7 +156,13 @@ def main(argv=None):
                 print(f"longest prompt {longest} > max_length {args.max_length}, skip")
                 continue
             keys = torch.tensor([n for n, _ in batch], dtype=torch.int64)
-            _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
+            if long_cfg is not None:
+                done = transcribe_long(qwen2_audio_decoder(model, tokenizer, args.instruct, cfg), wavs, 16000, long_cfg,
+                                       args.batch_size, row_keys=keys.tolist(), to_text=to_text, nbest=cfg.nbest,
+                                       output_scores=cfg.wants_scores, sampled=cfg.do_sample, device=device)
+                texts, extras = [d["predict"] for d in done], [d["extra"] for d in done]
+            else:
+                _, texts, extras = transcribe(model, wavs, tokenizer, args.instruct, cfg, row_keys=keys, details=True)
             for (_, it), text, extra in zip(batch, texts, extras):
                 writer.write(json.dumps({"label": json.dumps(it, ensure_ascii=False), "predict": text, **extra},
                                         ensure_ascii=False) + "\n")

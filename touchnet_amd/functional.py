@@ -1708,6 +1708,69 @@ def kaldi_mfcc(wav: torch.Tensor, sample_rate: int, num_mel_bins: int, num_ceps:
     return L.kaldi_mfcc(wav, window, idx, w, dct, key[0], shift, key[4], key[5])
 
 
+VAD_MAX_WIN, VAD_MAX_CTX = L.VAD_MAX_WIN, L.VAD_MAX_CTX       # limits of csrc/vad.hip
+
+
+@dataclass
+class VadConfig:
+    """The options of Kaldi's `compute-vad-energy` with that program's defaults, and the frame geometry of its features.
+    Nobody has tuned these values for cutting long recordings into segments for the decoders here: they are Kaldi's
+    defaults for its own use (dropping silence frames before speaker recognition), a starting point and no more."""
+    frame_length: float = 25.0               # ms
+    frame_shift: float = 10.0                # ms
+    energy_threshold: float = 5.0            # constant term of the threshold on the log-energy
+    energy_mean_scale: float = 0.5           # the threshold rises by this times the recording's mean log-energy
+    frames_context: int = 0                  # frames on each side that vote on a frame
+    proportion_threshold: float = 0.6        # share of the voting frames above the threshold that makes a frame voiced
+
+
+def vad_geometry(sample_rate, cfg: VadConfig):
+    """(win, shift) of a VAD configuration in samples at `sample_rate` Hz — `win = int(sr frame_length / 1000)` as
+    kaldi_feature_geometry — or a ValueError that names the field csrc/vad.hip cannot take.  Pure host arithmetic."""
+    sr = int(sample_rate)
+    if sr < 1 or sr != sample_rate:
+        raise ValueError(f"sample_rate = {sample_rate}: a positive integer number of Hz")
+    win, shift = int(sr * cfg.frame_length * 0.001), int(sr * cfg.frame_shift * 0.001)
+    if not 1 <= win <= VAD_MAX_WIN:
+        raise ValueError(f"frame_length = {cfg.frame_length} ms at {sr} Hz is a window of {win} samples: the MI355X VAD "
+                         f"kernel takes 1 .. {VAD_MAX_WIN}")
+    if shift < 1:
+        raise ValueError(f"frame_shift = {cfg.frame_shift} ms is less than one sample at {sr} Hz")
+    ctx = cfg.frames_context
+    if isinstance(ctx, bool) or ctx != int(ctx) or not 0 <= ctx <= VAD_MAX_CTX:
+        raise ValueError(f"frames_context = {ctx!r} must be an integer in [0, {VAD_MAX_CTX}]")
+    if not 0.0 < cfg.proportion_threshold <= 1.0:
+        raise ValueError(f"proportion_threshold = {cfg.proportion_threshold} must be in (0, 1]")
+    if not (math.isfinite(cfg.energy_threshold) and math.isfinite(cfg.energy_mean_scale)):
+        raise ValueError(f"energy_threshold = {cfg.energy_threshold} / energy_mean_scale = {cfg.energy_mean_scale} must be "
+                         "finite")
+    return win, shift
+
+
+def vad_energy(wave: torch.Tensor, sample_rate: int, cfg: Optional[VadConfig] = None):
+    """Kaldi's energy VAD of one recording on the device (csrc/vad.hip): wave fp32 in [-1, 1) or int16 PCM, [N] or
+    [1, N], at `sample_rate` Hz -> (runs int64 [R, 2] on the HOST: the maximal intervals [start, end) of voiced frames in
+    order; voiced uint8 [T] and loge fp32 [T] on the device).  Frame t covers the samples [t shift, t shift + win) of
+    vad_geometry.  One host read per recording: the run count and the runs, in one buffer.  A recording shorter than one
+    window has no frame: empty results, nothing launched."""
+    cfg = cfg or VadConfig()
+    win, shift = vad_geometry(sample_rate, cfg)
+    if not wave.is_cuda:
+        raise RuntimeError("vad_energy: expects a device waveform (there is no CPU path)")
+    if wave.dtype != torch.int16:
+        wave = wave.float()
+    wave = _c(wave).view(-1)
+    if wave.numel() < win:
+        return (torch.empty(0, 2, dtype=torch.int64), torch.empty(0, dtype=torch.uint8, device=wave.device),
+                torch.empty(0, dtype=torch.float32, device=wave.device))
+    loge, partials = L.vad_log_energy(wave, win, shift)
+    voiced, buf = L.vad_runs(loge, partials, float(cfg.energy_threshold), float(cfg.energy_mean_scale),
+                             int(cfg.frames_context), float(cfg.proportion_threshold))
+    host = buf.cpu()
+    n = int(host[0])
+    return host[1:1 + 2 * n].to(torch.int64).view(n, 2), voiced, loge
+
+
 def log_mel_spectrogram(wav: torch.Tensor, num_mel_bins: int = 128, padding: int = 0) -> torch.Tensor:
     """wav fp32 [N] at 16 kHz -> fp32 [N // 160, num_mel_bins] (functions.py:159-190)."""
     wav = _c(wav).float().view(-1)

@@ -1001,6 +1001,25 @@ def add_score_arguments(ap, nbest: bool = True) -> None:
                              "utterance that finished fewer lists fewer")
 
 
+def add_longform_arguments(ap, switch: bool = True) -> None:
+    """--long_form and the knobs of longform.LongFormConfig (longform.longform_from_args reads them back).  The defaults
+    are Kaldi's compute-vad-energy defaults and common segmenting values; nobody has tuned them for these decoders."""
+    if switch:
+        ap.add_argument("--long_form", action="store_true",
+                        help="recordings longer than --max_segment_s are cut into segments by an energy VAD on the device "
+                             'and decoded segment by segment; their records gain "segments".  Shorter recordings and '
+                             "runs without this flag are decoded as before")
+    ap.add_argument("--max_segment_s", type=float, default=30.0, help="longest segment, and the length from which a "
+                                                                      "recording is segmented at all")
+    ap.add_argument("--vad_energy_threshold", type=float, default=5.0)
+    ap.add_argument("--vad_energy_mean_scale", type=float, default=0.5)
+    ap.add_argument("--vad_frames_context", type=int, default=0)
+    ap.add_argument("--vad_proportion_threshold", type=float, default=0.6)
+    ap.add_argument("--vad_min_silence_ms", type=float, default=300.0, help="shorter gaps between voiced runs are closed")
+    ap.add_argument("--vad_min_speech_ms", type=float, default=100.0, help="shorter voiced runs are dropped")
+    ap.add_argument("--vad_pad_ms", type=float, default=100.0, help="every voiced run grows by this on both sides")
+
+
 def _json_number(x: float):
     return x if math.isfinite(x) else None
 

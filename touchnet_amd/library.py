@@ -800,6 +800,80 @@ def _(wav, window, bank_idx, bank_w, dct, sample_rate, shift, low_freq, high_fre
     return wav.new_empty(_kaldi_frames(wav.numel(), window.shape[0], shift), dct.shape[0])
 
 
+VAD_MAX_WIN, VAD_MAX_CTX = 4096, 64                # tn_vad_log_energy's and tn_vad_runs' limits
+
+
+def vad_frames_per_block(win: int, shift: int) -> int:
+    """frames one workgroup of tn_vad_log_energy owns (partials holds one double per workgroup); -1 for a geometry the
+    kernel does not take"""
+    return int(_lib().tn_vad_frames_per_block(int(win), int(shift)))
+
+
+def _vad_partials(frames: int, win: int, shift: int) -> int:
+    fpb = vad_frames_per_block(win, shift)
+    if fpb < 1:
+        raise _C.KernelError(f"vad_log_energy: win = {win} must be in [1, {VAD_MAX_WIN}] and shift = {shift} >= 1")
+    return -(-frames // fpb)
+
+
+@custom_op(f"{NS}::vad_log_energy", mutates_args=(), device_types="cuda")
+def vad_log_energy(wave: Tensor, win: int, shift: int) -> Tuple[Tensor, Tensor]:
+    """Kaldi's raw log-energy per frame (tn_vad_log_energy, csrc/vad.hip): wave 1-D fp32 in [-1, 1) or int16 PCM ->
+    loge fp32 [T] with Kaldi's snip_edges frame count and partials fp64 [workgroups], each workgroup's sum of its frames'
+    loge.  No frame: two empty tensors, nothing launched."""
+    if wave.dim() != 1 or wave.dtype not in (torch.float32, torch.int16):
+        raise _C.KernelError("vad_log_energy: a 1-D fp32 or int16 device waveform")
+    wave = _c(wave)
+    T = _kaldi_frames(wave.numel(), win, shift)
+    loge = torch.empty(T, dtype=torch.float32, device=wave.device)
+    partials = torch.empty(_vad_partials(T, win, shift), dtype=torch.float64, device=wave.device)
+    if T:
+        _C.check(_lib().tn_vad_log_energy(_p(wave), int(wave.dtype == torch.int16), _p(loge), _p(partials), wave.numel(),
+                                          int(win), int(shift), _cur()), "tn_vad_log_energy")
+    return loge, partials
+
+
+@vad_log_energy.register_fake
+def _(wave, win, shift):
+    T = _kaldi_frames(wave.numel(), win, shift)
+    return wave.new_empty(T, dtype=torch.float32), wave.new_empty(_vad_partials(T, win, shift), dtype=torch.float64)
+
+
+@custom_op(f"{NS}::vad_runs", mutates_args=(), device_types="cuda")
+def vad_runs(loge: Tensor, partials: Tensor, energy_threshold: float, mean_scale: float, ctx: int,
+             proportion: float) -> Tuple[Tensor, Tensor]:
+    """Threshold, vote and runs of the energy VAD (tn_vad_runs): loge fp32 [T], partials fp64 [>= 1] whose sum is loge's
+    -> voiced uint8 [T] and runs int32 [1 + 2 (T // 2 + 1)]: element 0 is the number of runs R, elements 1 + 2 r and
+    2 + 2 r the first frame of run r and the frame behind its last; what lies behind the R-th pair is not written.  One
+    buffer, so that one host read fetches the count and the runs."""
+    if loge.dim() != 1 or loge.dtype != torch.float32 or partials.dim() != 1 or partials.dtype != torch.float64:
+        raise _C.KernelError("vad_runs: loge fp32 [T] and partials fp64 [n]")
+    if not 0 <= ctx <= VAD_MAX_CTX:
+        raise _C.KernelError(f"vad_runs: frames_context = {ctx} must be in [0, {VAD_MAX_CTX}]")
+    if not 0.0 < proportion <= 1.0:
+        raise _C.KernelError(f"vad_runs: proportion_threshold = {proportion} must be in (0, 1]")
+    loge, partials = _c(loge), _c(partials)
+    T, dev = loge.numel(), loge.device
+    capacity = T // 2 + 1
+    voiced = torch.empty(T, dtype=torch.uint8, device=dev)
+    if T == 0:
+        return voiced, torch.zeros(1 + 2 * capacity, dtype=torch.int32, device=dev)
+    if partials.numel() < 1:
+        raise _C.KernelError("vad_runs: partials needs at least one element")
+    buf = torch.empty(1 + 2 * capacity, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(_lib().tn_vad_runs_workspace_bytes(T)) // 8, dtype=torch.float64, device=dev)
+    _C.check(_lib().tn_vad_runs(_p(loge), T, _p(partials), partials.numel(), float(energy_threshold), float(mean_scale),
+                                int(ctx), float(proportion), _p(voiced), _p(buf[1:]), _p(buf), capacity, _p(ws), _cur()),
+             "tn_vad_runs")
+    return voiced, buf
+
+
+@vad_runs.register_fake
+def _(loge, partials, energy_threshold, mean_scale, ctx, proportion):
+    T = loge.numel()
+    return loge.new_empty(T, dtype=torch.uint8), loge.new_empty(1 + 2 * (T // 2 + 1), dtype=torch.int32)
+
+
 def feat_augment(feat: Tensor, t_masks, f_masks, subs, out_rows: int) -> Tensor:
     """tn_feat_augment: the draws travel as kernel arguments (host int arrays), so this is a plain function, not a
     registered op (no tensor carries them)."""
@@ -1347,4 +1421,4 @@ OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fw
        "ce_fwd_rows", "ce_reduce", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
-       "constrain_logits_", "token_scores", "token_scores_")
+       "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs")
