@@ -487,7 +487,11 @@ int tn_greedy_step(const void* logits, int* hist, int* hist_len, int* cache_len,
  *      u in [0, 1) from Philox4x32-10 keyed by `seed` with counter (hist_len[b], row_key[b]) — or uniforms[b] when
  *      `uniforms` (fp32 [B]) is not NULL; row_key int64 [B] (NULL: the row index).  Without do_sample: argmax (lowest id
  *      on ties).  A finished row emits `pad`; then the bookkeeping of greedy_step, with up to 8 `eos_ids` (host array)
- *      finishing a row.  n_kept (int32 [B], may be NULL): tokens left after top-k / top-p.  No host synchronisation.
+ *      finishing a row.  n_kept (int32 [B], may be NULL): tokens left after top-k / top-p — exact whenever the threshold
+ *      lies less than 1023/16 below the row's maximum (after penalty and temperature); when the k-th largest value lies
+ *      farther down, every token below that distance is counted too (weight zero: they can be kept but are never drawn),
+ *      so the count is between the exact one and V and the token is unaffected.  1 for a row without a finite maximum or
+ *      without do_sample, 0 for a finished row.  No host synchronisation.
  *      -22 before any launch for NULL or misaligned pointers, V or S_hist out of range, penalty <= 0, n_eos outside
  *      [0, 8], and with do_sample temperature <= 0, top_k < 0 or top_p outside (0, 1]. */
 int tn_sample_step(const void* logits, int* hist, int* hist_len, int* cache_len, int* finished, int* n_unfinished,
