@@ -304,7 +304,8 @@ int tn_pcm16_to_f32(const void* pcm_int16, float* out, long long n, void* stream
  *      BestRQTokenizer.tokenize, touchnet/tokenizer/tokenizer.py:289-299 (called per utterance from
  *      batch_audio_packed, touchnet/models/touch_audio/processing_touch_audio.py:97).
  *      feat [T, F], quantizer [F, E], codebook [V, E] (already L2-normalised, 16-byte aligned) fp32; codes int64 [T];
- *      E in {8, 16, 32} (else -22).  First index wins ties, like torch.argmin. */
+ *      E in {8, 16, 32} (else -22).  First index wins ties, like torch.argmin.  A frame with no finite winner (a NaN
+ *      or inf feature: every distance is NaN) gets code 0, as torch.argmin gives; every code lies in [0, V). */
 int tn_bestrq_tokenize(const float* feat, const float* quantizer, const float* codebook, long long* codes, int T,
                        int F, int E, int V, void* stream);
 

@@ -84,7 +84,9 @@ __global__ __launch_bounds__(256) void log_mel_kernel(const float* __restrict__ 
         const float* w = fb + (size_t)m * kFreq;
         float acc = 0.f;
         for (int k = 0; k < kFreq; ++k) acc += w[k] * pws[f][k];
-        const float v = log10f(fmaxf(acc, 1e-10f));
+        // log10(max(acc, 1e-10)): the floor's logarithm is -10 to 6e-9, which the reference's log10 rounds to -10.f
+        // and the device's log10f to the float above it; silence must come out as exactly (-10 + 4) / 4
+        const float v = acc > 1e-10f ? log10f(acc) : -10.f;
         feat[(size_t)(t0 + f) * n_mels + m] = v;
         lmax = fmaxf(lmax, v);
       }

@@ -6,6 +6,11 @@
 // fp32 throughout and the same formulation (explicit differences, sqrt, strict-less argmin in ascending v), so the
 // codes agree with the reference wherever its own best/second-best margin exceeds fp32 round-off.
 //
+// Non-finite frames: a NaN or inf feature makes the frame's projection, and with it every distance, NaN; no `d < best`
+// holds and the running index keeps its sentinel.  Such a frame gets code 0 — what torch.argmin returns over a row
+// of NaN — so every code lies in [0, V) and the loss kernels never read a target outside the vocabulary.  The
+// sentinel is replaced at the final store only: frames with a finite winner are untouched.
+//
 // Not GEMM-shaped enough for MFMA at fp32 (E = 16): VALU-bound.  One 256-thread workgroup owns FR = 32 frames:
 //   1. projection: feature tile and projection chunk staged through LDS (coalesced 16-byte loads), each thread
 //      accumulates FR*E/256 outputs in ascending-k fma order;
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(256) void bestrq_tokenize_kernel(const float* __res
         ix = oi;
       }
     }
-    codes[f0 + tid] = ix;
+    codes[f0 + tid] = ix == 0x7fffffff ? 0 : ix;   // no distance was below +inf (NaN / inf frame): torch.argmin's 0
   }
 }
 
