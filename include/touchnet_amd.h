@@ -469,6 +469,29 @@ int tn_gemm_get_persistent(void);
 long long tn_attn_decode_workspace_bytes(int B, int Nh, int Nkv, int D, int S_max);
 int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
                    void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream);
+/* gemm_smallm: the linear products of one decode step — q_proj / k_proj / v_proj + apply_rotary_pos_emb, o_proj, down_proj
+ *      and lm_head on B (x num_beams) rows (transformers/models/llama/modeling_llama.py:243-285 LlamaAttention.forward and
+ *      :174-176 LlamaMLP.forward under use_cache=True, driven by touchnet/models/touch_audio/inference_touch_audio.py:177-192)
+ *      — on a kernel that streams every weight row once (csrc/gemm_smallm.hip) instead of the library's small GEMMs.
+ *      y_i[M, N_i] = x[M, K] w_i[N_i, K]^T (+ bias_i[N_i]) for nseg = 1..3 segments that share x, ONE launch; all bf16,
+ *      fp32 accumulation; x with row pitch ldx, w_i with ldw[i], y_i with ldy[i] (elements; nothing outside [M, N_i] of y_i
+ *      is written, no row of x behind M - 1 is read).  bias: NULL, or an array whose entries may be NULL.  Segments whose
+ *      bit is set in rope_mask are returned rotated: cos_t / sin_t bf16 [M, head_dim / 2] (tn_rope_table, one table row per
+ *      row of x), N_i a whole number of heads of head_dim 64 or 128 — bit-identical to the plain segment followed by
+ *      tn_rope_apply.  The order in which the K terms of an output are summed depends on K alone: a row's result does not
+ *      change with M, its index or the other rows.  Only enqueues on the stream.
+ *      -22 before any launch unless 1 <= M <= 128, K % 64 == 0, every N_i % 16 == 0, pitches % 8 == 0 and >= the rows they
+ *      span, every tensor (tables and biases too) non-NULL where required and 16-byte aligned, rope_mask within nseg bits. */
+int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                   const void* const* bias, void* const* y, const long long* ldy, const int* N, const void* cos_t,
+                   const void* sin_t, int head_dim, int rope_mask, void* stream);
+/*      ... and the decode step's gate_proj / up_proj + SwiGLU (modeling_llama.py:174-176: act_fn(gate_proj(x)) *
+ *      up_proj(x)): act[M, I] = silu(x w_gate^T) * (x w_up^T) from one launch — bit-identical to tn_swiglu_fwd on the two
+ *      bf16 products; gate, up and act^T are never stored.  w_gate / w_up [I, K] of one pitch ldw, act with pitch ldact.
+ *      Only enqueues on the stream.  -22 before any launch unless 1 <= M <= 128, K % 64 == 0, I % 16 == 0, pitches % 8 == 0
+ *      and >= the rows they span, 16-byte aligned non-NULL tensors. */
+int tn_gemm_smallm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K,
+                          long long ldx, long long ldw, long long ldact, void* stream);
 /* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
  *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
  *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history

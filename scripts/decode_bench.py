@@ -530,6 +530,103 @@ def bench_token_scores(K, B, steps=32, iters=200):
     return rows
 
 
+DECODER_WIDTHS = {      # (model_type, H, I, heads, kv heads, head_dim, layers, V) of the three decoders modelled above
+    "llama_asr_1b": ("llama", 2048, 8192, 32, 8, 64, 16, 128256),
+    "qwen2_audio_7b": ("qwen2", 4096, 11008, 32, 32, 128, 32, 156032),
+    "kimi_audio_7b": ("qwen2", 3584, 18944, 28, 4, 128, 28, 168448),
+}
+COPY_RATE = 6.3e12      # bytes / s: the copy rate DESIGN.md §9 measures every byte bound against
+
+
+def bench_decode_gemm(name, B, steps=24, iters=40):
+    """TN_DECODE_GEMM own against lib at one decoder's widths: every product family of a decode step at M = 1, 12, 48, 96
+    (weights cycled through > 768 MB of copies, so no call finds its weights in L2 / MALL), then the whole step at B rows
+    with the switch alternated lib, own, lib, own, .. inside this process."""
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G, library as L
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    kind, H, I, Nh, Nkv, D, layers, V = DECODER_WIDTHS[name]
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: (torch.randn(*s, device=DEV, generator=g) * 0.02).to(torch.bfloat16)
+    bias = kind == "qwen2"
+    rows = []
+
+    def copies(*shapes):            # enough sets of the family's weights that a set has left the caches when its turn returns
+        per = sum(n * k * 2 for n, k in shapes)
+        return [[rnd(n, k) for n, k in shapes] for _ in range(max(2, min(48, -(-768 * 2 ** 20 // per))))]
+
+    def timed(fn, sets):
+        it = [0]
+
+        def call():
+            fn(sets[it[0] % len(sets)])
+            it[0] += 1
+        for _ in range(len(sets) + 2):      # every set and every shape warm before the window
+            call()
+        torch.cuda.synchronize()
+        return _events_time(call, iters)
+
+    with torch.no_grad():
+        fam_sets = {"qkv+rope": copies((Nh * D, H), (Nkv * D, H), (Nkv * D, H)), "o": copies((H, Nh * D)),
+                    "gate/up+swiglu": copies((I, H), (I, H)), "down": copies((H, I)), "lm_head": copies((V, H))}
+        # what one call costs the host and the queue with next to nothing to compute: a family at this figure is launch-bound
+        F.DECODE_GEMM = "own"
+        tiny = timed(lambda ws: F.linear_smallm(ws[0][:1], [(ws[0], None)]), [[rnd(16, 64)]] * 2)
+        print(json.dumps(dict(decode_gemm=name, launch_floor_us=round(tiny, 2))), flush=True)
+        for M in (1, 12, 48, 96):
+            x, xi, xo = rnd(M, H), rnd(M, I), rnd(M, Nh * D)
+            pos = torch.arange(M, device=DEV)[None] + 300
+            cos, sin = F.rope_tables(pos, F.rope_inv_freq(D, 10000.0, device=DEV), torch.bfloat16)
+            bs = [rnd(n) if bias else None for n in (Nh * D, Nkv * D, Nkv * D)]
+            # own: the kernel's entry itself, whatever the router's row limit; lib: `linear_group` with the switch at lib
+            pair = lambda inp, rope=None, b=(None,) * 3: ((lambda ws: F.linear_smallm(inp, list(zip(ws, b)), rope)),
+                                                          (lambda ws: F.linear_group(inp, list(zip(ws, b)), rope=rope)))
+            # the current route of `swiglu_mlp`: the node's library body at M % 8 == 0, else composed of the single ops
+            lib_swiglu = (lambda ws: L.swiglu_fwd_t(torch.nn.functional.linear(x, ws[0]), torch.nn.functional.linear(x, ws[1]))) \
+                if M % 8 == 0 else (lambda ws: F.swiglu(*F.linear_group(x, [(ws[0], None), (ws[1], None)])))
+            fams = {"qkv+rope": (*pair(x, (cos, sin, D, (0, 1)), bs), x, (Nh + 2 * Nkv) * D),
+                    "o": (*pair(xo), xo, H), "gate/up+swiglu": (lambda ws: F.swiglu_smallm(x, *ws), lib_swiglu, x, I),
+                    "down": (*pair(xi), xi, H), "lm_head": (*pair(x), x, V)}
+            F.DECODE_GEMM = "lib"
+            for fam, (own_fn, lib_fn, inp, n_out) in fams.items():
+                sets = fam_sets[fam]
+                nbytes = sum(w.numel() for w in sets[0]) * 2 + inp.numel() * 2 + M * n_out * 2
+                us_own = timed(own_fn, sets)
+                us_lib = timed(lib_fn, sets)
+                rows.append(dict(decode_gemm=name, family=fam, M=M, bytes=nbytes, us_own=round(us_own, 2),
+                                 tbps_own=round(nbytes / us_own / 1e6, 3), us_at_copy_rate=round(nbytes / COPY_RATE * 1e6, 2),
+                                 us_lib=round(us_lib, 2), own_over_lib=round(us_own / us_lib, 3)))
+                print(json.dumps(rows[-1]), flush=True)
+        del fam_sets
+        torch.cuda.empty_cache()
+        text = DecoderConfig.from_dict(dict(model_type=kind, hidden_size=H, intermediate_size=I, num_attention_heads=Nh,
+                                            num_key_value_heads=Nkv, head_dim=D, num_hidden_layers=layers, vocab_size=V,
+                                            rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=kind == "llama",
+                                            initializer_range=0.02, eos_token_id=1, pad_token_id=1))
+        torch.manual_seed(0)
+        with torch.device(DEV):
+            lm = PackedCausalLM(text)
+        lm.post_init()
+        lm = lm.to(torch.bfloat16).eval()
+        prompts = G.Prompts([torch.randint(2, 100000, (300,)) for _ in range(B)])
+        cache = G.KVCache.allocate(layers, B, 300 + 10 * steps + 8, Nkv, D, DEV)
+        logits = G._prefill(lm, None, prompts, cache, DEV)
+        greedy = lambda lg: F.greedy_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
+                                          1.0, 0, -1, 1)
+        greedy(logits)
+        arms = []
+        for arm in ("lib", "own") * 4:                     # the first pair warms both arms' shapes and is not reported
+            F.DECODE_GEMM = arm
+            greedy(G.decode_logits(lm, cache))
+            arms.append((arm, round(_events_time(lambda: greedy(G.decode_logits(lm, cache)), steps) / 1e3, 3)))
+        F.DECODE_GEMM = "lib"
+    lib_ms, own_ms = [t for a, t in arms[2:] if a == "lib"], [t for a, t in arms[2:] if a == "own"]
+    rows.append(dict(e2e=f"{name}_decode_step", B=B, layers=layers, ms_lib=lib_ms, ms_own=own_ms,
+                     own_worst_beats_lib_best=max(own_ms) < min(lib_ms)))
+    print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -543,12 +640,18 @@ def main():
     ap.add_argument("--hotwords", type=int, default=0, help="N > 0: tn_logits_constrain with N phrases x 4 prefixes")
     ap.add_argument("--token-scores", type=int, nargs="?", const=8, default=None, metavar="K",
                     help="tn_token_scores with k = 0 and k = K (default 8) alternatives")
+    ap.add_argument("--decode-gemm", nargs="?", const="all", default=None, metavar="DECODER",
+                    help="TN_DECODE_GEMM own against lib: per product family and per step (one of DECODER_WIDTHS, default all)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.decode_gemm is not None:
+        for name in (DECODER_WIDTHS if a.decode_gemm == "all" else [a.decode_gemm]):
+            bench_decode_gemm(name, a.batch)
+        return
     if a.token_scores is not None:
         for r in bench_token_scores(a.token_scores, a.batch):
             print(json.dumps(r), flush=True)

@@ -815,6 +815,93 @@ def _fwd_own(a, b, bias=None) -> bool:
             and (bias is None or bias.dtype == torch.bfloat16))
 
 
+# Which GEMM runs the decode step's products (generation.decode_logits: M = B or B x num_beams rows, far below `_own`'s 96
+# tiles):
+#   "own"  the weight-streaming small-M kernel of csrc/gemm_smallm.hip: q/k/v + RoPE as one launch, gate/up + SwiGLU as one
+#          launch, o_proj, down_proj and lm_head one launch each; a row's product does not depend on the batch it is in.
+#   "lib"  hipBLASLt through torch, RoPE and SwiGLU as row kernels behind the products.
+# TN_DECODE_GEMM selects; the default is "lib" although "own" wins the A/B, because two beam-search tests lose their
+# decision margin under it.  WHO ANSWERS: `_decode_own`, asked with the
+# tensors at `linear_group`'s entry (q/k/v with rope, o_proj), at `swiglu_mlp`'s entry (gate/up + SwiGLU, then down_proj)
+# and by generation.decode_logits for lm_head — nowhere else.  It is false whenever autograd is on and above 128 rows, so
+# training and prefill never see it.
+DECODE_GEMM = os.environ.get("TN_DECODE_GEMM", "lib")
+SMALLM_MAX_ROWS = 128
+_DECODE_OWN_MAX_ROWS = 48     # routed up to here: at 96 rows the library wins the 7B widths' layers (DESIGN.md §9.10's table)
+
+
+def smallm_supported(M: int, Ns, K: int) -> bool:
+    """Shapes tn_gemm_smallm takes: 1..128 rows, a contraction of whole 64-deep chunks, 1..3 segments of whole 16-row strips."""
+    return (1 <= M <= SMALLM_MAX_ROWS and K > 0 and K % 64 == 0 and 1 <= len(Ns) <= 3
+            and all(n > 0 and n % 16 == 0 for n in Ns))
+
+
+def _smallm_rope_ok(M: int, Ns, rope) -> bool:
+    cos, sin, D, which = rope[:4]
+    return (D in (64, 128) and all(0 <= i < len(Ns) and Ns[i] % D == 0 for i in which)
+            and all(t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == (M, D // 2) and t.is_contiguous()
+                    and t.data_ptr() % 16 == 0 for t in (cos, sin)))
+
+
+def _decode_own(x, ws, bs=(), rope=None) -> bool:
+    """The small-M kernel runs ``x w_i^T (+ b_i)`` (rotated as ``rope`` of `linear_group` says) and is the configured choice."""
+    if DECODE_GEMM != "own" or torch.is_grad_enabled() or x.dim() != 2 or not _bf16_rows(x, *ws):
+        return False
+    M, K = x.shape
+    Ns = [w.shape[0] for w in ws]
+    return (M <= _DECODE_OWN_MAX_ROWS and smallm_supported(M, Ns, K) and all(w.shape[1] == K for w in ws)
+            and all(b is None or (b.is_cuda and b.dtype == torch.bfloat16 and b.dim() == 1 and b.is_contiguous()
+                                  and b.data_ptr() % 16 == 0) for b in bs)
+            and (rope is None or _smallm_rope_ok(M, Ns, rope)))
+
+
+def _smallm_operands(name: str, x, ws):
+    """by-name refusal of what tn_gemm_smallm would answer with -22"""
+    if x.dim() != 2 or not _bf16_rows(x, *ws) or any(w.shape[1] != x.shape[1] for w in ws):
+        raise _C.KernelError(f"{name}: bf16 device matrices x [M, K], w [N, K] with contiguous 16-byte aligned rows")
+    if not smallm_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
+        raise _C.KernelError(f"{name}: 1 <= M <= {SMALLM_MAX_ROWS}, K % 64 == 0, 1..3 weights with N % 16 == 0 (got M = "
+                             f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
+
+
+def linear_smallm(x: torch.Tensor, layers, rope=None, outs=None):
+    """``layers``: 1..3 (weight [N_i, K], bias [N_i] | None) sharing x [M, K], M <= 128 -> list of ``x W_i^T + b_i`` from ONE
+    launch of the weight-streaming kernel (tn_gemm_smallm).  ``rope = (cos, sin, head_dim, (i, j, ..))`` as for
+    `linear_group`: those outputs are returned rotated, bit-identical to `apply_rope` of the plain ones.  ``outs``: bf16
+    [M, N_i] views to write (row pitch >= N_i; nothing else of their buffers is touched).  Inference only."""
+    ws = [w for w, _ in layers]
+    bs = [b for _, b in layers]
+    _smallm_operands("linear_smallm", x, ws)
+    M = x.shape[0]
+    for w, b in layers:
+        if b is not None and not (b.is_cuda and b.dtype == torch.bfloat16 and tuple(b.shape) == (w.shape[0],)
+                                  and b.is_contiguous() and b.data_ptr() % 16 == 0):
+            raise _C.KernelError("linear_smallm: bias bf16 [N], contiguous, 16-byte aligned")
+    cos = sin = None
+    D = mask = 0
+    if rope is not None and len(rope[3]):
+        if not _smallm_rope_ok(M, [w.shape[0] for w in ws], rope):
+            raise _C.KernelError("linear_smallm: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
+                                 "outputs of whole heads)")
+        cos, sin, D = rope[:3]
+        mask = sum(1 << int(i) for i in set(rope[3]))
+    if outs is None:
+        return list(L.linear_smallm(x, ws, bs, cos, sin, int(D), mask))
+    if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
+        raise _C.KernelError("linear_smallm: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
+    L.linear_smallm_launch(x, ws, bs, outs, cos, sin, int(D), mask)
+    return list(outs)
+
+
+def swiglu_smallm(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> torch.Tensor:
+    """``silu(x w_gate^T) * (x w_up^T)`` [M, I], M <= 128, from ONE launch (tn_gemm_smallm_swiglu): bit-identical to `swiglu`
+    of the two products; neither of them is stored.  Inference only."""
+    _smallm_operands("swiglu_smallm", x, [w_gate, w_up])
+    if w_gate.shape != w_up.shape or w_gate.stride(0) != w_up.stride(0):
+        raise _C.KernelError("swiglu_smallm: w_gate / w_up [I, K] of one row pitch")
+    return L.swiglu_smallm(x, w_gate, w_up)
+
+
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
            accumulate: bool = False) -> torch.Tensor:
     """``a @ b.T (+ bias)`` (``out += ...`` if accumulate) for contraction-contiguous a [M, K], b [N, K]."""
@@ -1331,6 +1418,8 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
         raise _C.KernelError("linear_group: device tensors only (the product path has no CPU fallback)")
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
+    if _decode_own(x, ws, bs, rope):          # a decode step's rows: the small-M kernel, rotation in its epilogue
+        return linear_smallm(x, layers, rope)
     if not _norm_src_describes(norm_src, x):
         norm_src = None           # (e.g. under tensor-parallel sequence parallelism x is the gathered sequence): keep x itself
     if rope is not None:
@@ -1554,6 +1643,10 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
     if not (x.is_cuda or x.is_meta):
         raise _C.KernelError("swiglu_mlp: device tensors only (the product path has no CPU fallback)")
     M = x.numel() // x.shape[-1]
+    if _decode_own(x, (w_gate, w_up)) and w_gate.stride(0) == w_up.stride(0) and w_gate.shape == w_up.shape \
+            and smallm_supported(M, (w_down.shape[0],), w_down.shape[1]) and _bf16_rows(w_down):
+        # a decode step's rows: gate + up + SwiGLU as one launch of the small-M kernel, then down_proj on it
+        return linear_smallm(swiglu_smallm(x, w_gate, w_up), [(w_down, None)])[0]
     if not _norm_src_describes(norm_src, x):
         norm_src = None
     # (the node's library body transposes x, the weights and dY: `_transposable`)

@@ -732,7 +732,10 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
     for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):
         delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table)
     h, _ = lm.model.norm(delta, residual)
-    return lm.lm_head(h)
+    head = lm.lm_head
+    if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the small-M routing
+        return F.linear_smallm(h, [(head.weight, None)])[0]
+    return head(h)
 
 
 @torch.no_grad()

@@ -956,6 +956,52 @@ def _(q, k_new, v_new, k_cache, v_cache, cache_len, scale):
     return torch.empty_like(q, memory_format=torch.contiguous_format)
 
 
+def linear_smallm_launch(x: Tensor, ws, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                         rope_mask: int) -> None:
+    """tn_gemm_smallm on operands the caller has checked: outs[i][M, N_i] = x ws[i]^T (+ bs[i]), rotated where bit i of
+    rope_mask is set.  Row pitches are the tensors' own."""
+    n = len(ws)
+    arr = lambda ctype, vals: (ctype * n)(*vals)
+    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
+    _C.check(_lib().tn_gemm_smallm(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
+                                   arr(ctypes.c_longlong, [w.stride(0) for w in ws]), addr(bs), addr(outs),
+                                   arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
+                                   arr(ctypes.c_int, [w.shape[0] for w in ws]), _p(cos), _p(sin), int(head_dim),
+                                   int(rope_mask), _cur()), "tn_gemm_smallm")
+
+
+@custom_op(f"{NS}::linear_smallm", mutates_args=(), device_types="cuda")
+def linear_smallm(x: Tensor, ws: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor], sin: Optional[Tensor],
+                  head_dim: int, rope_mask: int) -> List[Tensor]:
+    """The decode step's linear layers on 1..128 rows (tn_gemm_smallm): x [M, K], up to three weights [N_i, K] that share it,
+    optional biases, outputs bit i of rope_mask names rotated by cos / sin [M, head_dim / 2] -> [M, N_i] each, one launch."""
+    _no_grad_inputs("linear_smallm", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_smallm_launch(x, ws, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@linear_smallm.register_fake
+def _(x, ws, bs, cos, sin, head_dim, rope_mask):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+@custom_op(f"{NS}::swiglu_smallm", mutates_args=(), device_types="cuda")
+def swiglu_smallm(x: Tensor, w_gate: Tensor, w_up: Tensor) -> Tensor:
+    """silu(x w_gate^T) * (x w_up^T) [M, I] on 1..128 rows from one launch (tn_gemm_smallm_swiglu); gate and up are not kept."""
+    _no_grad_inputs("swiglu_smallm", x)
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(_lib().tn_gemm_smallm_swiglu(_p(x), _p(w_gate), _p(w_up), _p(act), M, w_gate.shape[0], K, x.stride(0),
+                                          w_gate.stride(0), act.stride(0), _cur()), "tn_gemm_smallm_swiglu")
+    return act
+
+
+@swiglu_smallm.register_fake
+def _(x, w_gate, w_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
 @custom_op(f"{NS}::greedy_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished"),
            device_types="cuda")
 def greedy_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor, n_unfinished: Tensor,
