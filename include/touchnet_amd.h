@@ -469,6 +469,22 @@ int tn_gemm_get_persistent(void);
 long long tn_attn_decode_workspace_bytes(int B, int Nh, int Nkv, int D, int S_max);
 int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
                    void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream);
+/* attn_extend: SEVERAL new rows per sequence over a KV cache — the attention of a forward with past_key_values and more
+ *      than one new position (transformers/models/llama/modeling_llama.py:243-285 with a causal mask behind the cached
+ *      prefix): rescoring hypotheses behind cached prompts, a second chat turn, chunked prefill.  q bf16 [T, Nh, D] and
+ *      k_new / v_new bf16 [T, Nkv, D]: the new rows of R sequences packed one after another (q, k_new rotated);
+ *      seq_start int32 [R + 1] ascending with seq_start[0] = 0 and seq_start[R] = T; caches bf16 [B, S_max, Nkv, D];
+ *      prefix_len int32 [R]; kv_row int32 [R] or NULL (sequence r reads cache row r; needs R <= B).  New row i of sequence
+ *      r (position prefix_len[r] + i) attends to cache[kv_row[r], 0 .. prefix_len[r]) and to the new rows j <= i of its own
+ *      sequence, nothing else; several sequences may name one kv_row.  Writes o bf16 [T, Nh, D] and nothing else: the
+ *      caches are read only, no slot at or past prefix_len[r] is read (appending the new rows is the caller's copy).
+ *      prefix_len[r] outside [0, S_max] or kv_row[r] outside [0, B): the sequence's rows are NaN, no cache slot consulted.
+ *      A sequence without rows writes nothing; T == 0 is a no-op.  No workspace, no atomics: repeats are bit-identical.
+ *      -22 before any launch for NULL or non-16-byte-aligned tensors, NULL or misaligned tables, D not 64 / 128,
+ *      Nh % Nkv != 0, Nh / Nkv > 16, R > B without kv_row, rows without a sequence (T > 0 with R == 0). */
+int tn_attn_extend(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
+                   const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T, int R, int B, int S_max,
+                   int Nh, int Nkv, int D, float scale, void* stream);
 /* gemm_smallm: the linear products of one decode step — q_proj / k_proj / v_proj + apply_rotary_pos_emb, o_proj, down_proj
  *      and lm_head on B (x num_beams) rows (transformers/models/llama/modeling_llama.py:243-285 LlamaAttention.forward and
  *      :174-176 LlamaMLP.forward under use_cache=True, driven by touchnet/models/touch_audio/inference_touch_audio.py:177-192)

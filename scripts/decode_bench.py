@@ -8,6 +8,7 @@ generate() (sdpa, same knobs, same weights).  Prints one JSON object per measure
     python scripts/decode_bench.py --kimi-audio-7b [--batch 12]
     python scripts/decode_bench.py --hotwords 1024 [--batch 12]
     python scripts/decode_bench.py --token-scores [K] [--batch 12]
+    python scripts/decode_bench.py --attn-extend [--layers 16]
 
 --qwen2-audio-7b: the decoder of Qwen2-Audio-7B (32 layers, 32 / 32 heads, D 128, V 156 032, random weights): tn_sample_step
 per call (µs) for top-k + top-p, top-p alone and greedy on bf16 logits [B, 156 032], and ms per decode step end to end
@@ -627,6 +628,59 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
     return rows
 
 
+def bench_attn_extend(layers, rounds=5, iters=100):
+    """tn_attn_extend per call at the rescoring shape (48 continuations of 32 rows behind 12 shared prompts of 750 rows) at
+    both head geometries and at one 750-row turn behind an 8 192-row prefix; then `score_continuations` with and without
+    `cache=` at the rescoring shape on the LlamaForASR-1B-width model, alternated in one process (median of `rounds`).
+    bytes = the cache bytes the launch's workgroups read: per sequence, tiles x prefix_len x Nkv x D x 2 (K, V) x 2 bytes is
+    what is ASKED of L2; `cache_bytes` counts every prefix once per sequence (what a one-tile-per-sequence kernel would read)
+    and the rate is quoted on that."""
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    bf = dict(device=DEV, dtype=torch.bfloat16)
+    for name, n_seq, n_new, P, B in (("rescoring", 48, 32, 750, 12), ("turn", 1, 750, 8192, 1)):
+        for Nh, Nkv, D in ((32, 8, 64), (28, 4, 128)):
+            T = n_seq * n_new
+            q, kn, vn = (torch.randn(T, h, D, **bf) for h in (Nh, Nkv, Nkv))
+            kc, vc = torch.randn(B, P, Nkv, D, **bf), torch.randn(B, P, Nkv, D, **bf)
+            start = torch.arange(n_seq + 1, dtype=torch.int32, device=DEV) * n_new
+            pre = torch.full((n_seq,), P, dtype=torch.int32, device=DEV)
+            row = torch.arange(n_seq, dtype=torch.int32, device=DEV) % B
+            call = lambda: F.attn_extend(q, kn, vn, kc, vc, start, pre, None, row)
+            with torch.no_grad():
+                for _ in range(10):
+                    call()
+                torch.cuda.synchronize()
+                us = _events_time(call, iters)
+            nbytes = n_seq * P * Nkv * D * 2 * 2
+            tiles = n_seq * ((n_new + 15) // 16)
+            yield dict(what="attn_extend", shape=name, sequences=n_seq, new_rows=n_new, prefix=P, Nh=Nh, Nkv=Nkv, D=D,
+                       workgroups=tiles * Nkv, cache_bytes=nbytes, us=round(us, 2), tbps=round(nbytes / us / 1e6, 3),
+                       tbps_asked_of_l2=round(nbytes * ((n_new + 15) // 16) / us / 1e6, 3))
+    m, _ = _model(layers)
+    g = torch.Generator().manual_seed(0)
+    prompts = G.Prompts([torch.randint(0, 128000, (750,), generator=g) for _ in range(12)])
+    conts = [torch.randint(0, 128000, (32,), generator=g) for _ in range(48)]
+    rows = [i % 12 for i in range(48)]
+    repeated = G.Prompts([prompts.input_ids[r] for r in rows])
+    _, cache = G.generate(m, prompts, G.GenerationConfig(max_new_tokens=2), return_cache=True)
+    packed = lambda: G.score_continuations(m, repeated, conts)
+    cached = lambda: G.score_continuations(m, prompts, conts, cache=cache, cache_row=rows)
+    times = {"packed": [], "cached": []}
+    for i in range(rounds + 1):
+        for label, fn in (("packed", packed), ("cached", cached)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i:                                   # (round 0 warms both up)
+                times[label].append((time.perf_counter() - t0) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    yield dict(what="score_continuations", layers=layers, prompts=12, prompt_rows=750, continuations=48, rows_each=32,
+               ms_packed=round(med["packed"], 2), ms_with_cache=round(med["cached"], 2),
+               ms_packed_all=[round(t, 2) for t in times["packed"]], ms_with_cache_all=[round(t, 2) for t in times["cached"]])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -642,12 +696,18 @@ def main():
                     help="tn_token_scores with k = 0 and k = K (default 8) alternatives")
     ap.add_argument("--decode-gemm", nargs="?", const="all", default=None, metavar="DECODER",
                     help="TN_DECODE_GEMM own against lib: per product family and per step (one of DECODER_WIDTHS, default all)")
+    ap.add_argument("--attn-extend", action="store_true",
+                    help="tn_attn_extend per call and score_continuations with / without cache= (profiles/attn_extend_bench.log)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.attn_extend:
+        for r in bench_attn_extend(a.layers):
+            print(json.dumps(r), flush=True)
+        return
     if a.decode_gemm is not None:
         for name in (DECODER_WIDTHS if a.decode_gemm == "all" else [a.decode_gemm]):
             bench_decode_gemm(name, a.batch)

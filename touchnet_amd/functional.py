@@ -2027,6 +2027,50 @@ def attn_decode(q, k_new, v_new, k_cache, v_cache, cache_len, scale: Optional[fl
     return L.attn_decode_(q, k_new, v_new, k_cache, v_cache, cache_len, float(scale))
 
 
+def attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, scale: Optional[float] = None, kv_row=None):
+    """Attention of SEVERAL new rows per sequence over a KV cache (tn_attn_extend): q [T, Nh, D], k_new / v_new [T, Nkv, D]
+    (q and k rotated) hold the new rows of R sequences packed one after another, sequence r in rows seq_start[r] ..
+    seq_start[r + 1]; new row i of sequence r sits at position prefix_len[r] + i and sees cache[kv_row[r], :prefix_len[r]]
+    and the new rows j <= i of its own sequence.  Caches bf16 [B, S_max, Nkv, D], read only (appending is the caller's
+    copy); kv_row None: sequence r reads cache row r.  Several sequences may share a kv_row.  seq_start / prefix_len /
+    kv_row: int sequences or int tensors; a seq_start that lives on the host is checked here (ascending from 0 to T), one
+    that already lives on the device is trusted (the kernel never leaves q / o whatever it holds).  Returns o [T, Nh, D]."""
+    if q.dim() != 3 or k_cache.dim() != 4:
+        raise ValueError("attn_extend: q must be [T, Nh, D] and the caches [B, S_max, Nkv, D]")
+    T, Nh, D = q.shape
+    B, Nkv = k_cache.shape[0], k_cache.shape[2]
+    if D not in (64, 128):
+        raise ValueError(f"attn_extend: head_dim D = {D} must be 64 or 128")
+    if Nkv <= 0 or Nh % Nkv:
+        raise ValueError(f"attn_extend: Nh = {Nh} query heads must be a multiple of Nkv = {Nkv} key/value heads")
+    if Nh // Nkv > 16:
+        raise ValueError(f"attn_extend: G = Nh / Nkv = {Nh // Nkv} query heads per key/value head exceeds 16")
+    dev = q.device
+    table = lambda t: t if isinstance(t, torch.Tensor) else torch.tensor(list(t), dtype=torch.int32)
+    seq_start, prefix_len = table(seq_start), table(prefix_len)
+    R = int(prefix_len.numel())
+    if seq_start.dim() != 1 or int(seq_start.numel()) != R + 1:
+        raise ValueError(f"attn_extend: seq_start must hold R + 1 = {R + 1} entries for {R} prefix_len entries")
+    if not seq_start.is_cuda:
+        s = seq_start.tolist()
+        if s[0] != 0 or any(b < a for a, b in zip(s, s[1:])):
+            raise ValueError(f"attn_extend: seq_start must be ascending from 0 (got {s})")
+        if s[-1] != T:
+            raise ValueError(f"attn_extend: seq_start[-1] = {s[-1]} must equal the number of new rows T = {T}")
+    if kv_row is None:
+        if R > B:
+            raise ValueError(f"attn_extend: R = {R} sequences need kv_row to share the B = {B} cache rows")
+    else:
+        kv_row = table(kv_row)
+        if int(kv_row.numel()) != R:
+            raise ValueError(f"attn_extend: kv_row must hold R = {R} entries")
+        kv_row = kv_row.to(device=dev, dtype=torch.int32)
+    if scale is None:
+        scale = D ** -0.5
+    return L.attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start.to(device=dev, dtype=torch.int32),
+                         prefix_len.to(device=dev, dtype=torch.int32), kv_row, float(scale))
+
+
 def greedy_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty: float = 1.0, ngram: int = 0,
                 eos: int = -1, pad: int = 0) -> None:
     """Repetition penalty + no-repeat-n-gram ban + argmax of HF generate() on logits [B, V], appended to the device

@@ -738,9 +738,119 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
     return head(h)
 
 
+def _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, prefix_len, kv_row):
+    """`_decode_layer` for T packed new rows of R sequences: the same norm, q / k / v with RoPE, o_proj and MLP calls, with
+    tn_attn_extend in the middle -> (delta, residual, k [T, Nkv, D], v [T, Nkv, D]); the caches are only read."""
+    attn = layer.self_attn
+    T, D = delta.shape[0], attn.head_dim
+    if residual is None:
+        residual = delta
+        x = layer.input_layernorm(delta)
+    else:
+        x, residual = layer.input_layernorm(delta, residual)
+    q, k, v = F.linear_group(x, [(attn.q_proj.weight, attn.q_proj.bias), (attn.k_proj.weight, attn.k_proj.bias),
+                                 (attn.v_proj.weight, attn.v_proj.bias)], rope=(cos, sin, D, (0, 1)))
+    k, v = k.view(T, attn.num_kv_heads, D), v.view(T, attn.num_kv_heads, D)
+    o = F.attn_extend(q.view(T, attn.num_heads, D), k, v, kc, vc, seq_start, prefix_len, attn.scaling, kv_row)
+    a = F.linear_group(o.view(T, attn.num_heads * D), [(attn.o_proj.weight, None)])[0]
+    x, residual = layer.post_attention_layernorm(a, residual)
+    return layer.mlp(x), residual, k, v
+
+
+@torch.no_grad()
+def extend(model, cache, rows, new_ids, embed: Optional[EmbedFn] = None, kv_row=None, append: bool = True,
+           keep_rows=None, prefix_len=None) -> torch.Tensor:
+    """Run the decoder over NEW rows behind what a `KVCache` / `BeamState` already holds (tn_attn_extend): sequence r is
+    new_ids[r] (token ids, possibly none) at positions prefix_len[r] .. behind the first prefix_len[r] cached positions of
+    cache row kv_row[r] (default rows[r]; prefix_len default: cache.cache_len of that row, read from the device).  ->
+    hidden states [len(keep_rows), H] behind the final norm of the packed rows `keep_rows` (default: every non-empty
+    sequence's last row); lm_head is the caller's.
+
+    append=True (a `KVCache`; every sequence its own row, kv_row = rows): the new keys / values are scattered into the cache
+    behind the prefixes, the ids into the history, and the lengths become hist_len = prefix + n, cache_len = hist_len - 1
+    — `_prefill`'s state, which the step kernels advance — after growing the cache where it is too short.  append=False:
+    the cache is left as it is, and several sequences may read one row (rescoring)."""
+    lm, _ = _parts(model)
+    _check_model(model, lm)
+    device = lm.model.embed_tokens.weight.device
+    ids_l = [torch.as_tensor(t, dtype=torch.int64).reshape(-1) for t in new_ids]
+    lens = [int(t.numel()) for t in ids_l]
+    R, T = len(lens), sum(lens)
+    rows_l = None if rows is None else [int(r) for r in rows]
+    kv_l = rows_l if kv_row is None else [int(r) for r in kv_row]
+    if kv_l is None or len(kv_l) != R or (rows_l is not None and len(rows_l) != R):
+        raise ValueError(f"extend: {R} sequences need {R} cache rows (rows and / or kv_row)")
+    n_rows = cache.k[0].shape[0]
+    if any(not 0 <= r < n_rows for r in kv_l):
+        raise ValueError(f"extend: cache rows {kv_l} outside [0, {n_rows})")
+    pre = cache.cache_len[torch.tensor(kv_l, device=device)].tolist() if prefix_len is None else [int(p) for p in prefix_len]
+    if len(pre) != R or any(not 0 <= p <= cache.capacity for p in pre):
+        raise ValueError(f"extend: prefix_len {pre} must hold one entry in [0, {cache.capacity}] per sequence")
+    if append:
+        if isinstance(cache, BeamState):
+            raise ValueError("extend: append=True needs a KVCache (a BeamState's rows are shared through its table)")
+        if rows_l is None or kv_l != rows_l or len(set(rows_l)) != R:
+            raise ValueError("extend: append=True writes every sequence behind its own cache row (distinct rows, kv_row = rows)")
+        cache.grow(max(p + n for p, n in zip(pre, lens)))
+    H = lm.model.embed_tokens.weight.shape[1]
+    if T == 0:
+        return torch.empty(0, H, dtype=lm.model.embed_tokens.weight.dtype, device=device)
+    starts = [0]
+    for n in lens:
+        starts.append(starts[-1] + n)
+    pos = torch.cat([torch.arange(n) + p for p, n in zip(pre, lens)])
+    keep = torch.tensor([s - 1 for s, n in zip(starts[1:], lens) if n], dtype=torch.int64) if keep_rows is None \
+        else torch.as_tensor(keep_rows, dtype=torch.int64).reshape(-1)
+    ids, pos, keep = (x.to(device, non_blocking=True) for x in (torch.cat(ids_l), pos, keep))
+    seq_start, pre_d, kv_d = (torch.tensor(x, dtype=torch.int32, device=device) for x in (starts, pre, kv_l))
+    x = embed(ids, lens, T) if embed is not None else lm.model.embed_tokens(ids)             # [T, H]
+    cos, sin = lm.model.rotary_emb(pos, x.dtype)
+    if append:
+        S = cache.capacity
+        dst = torch.cat([torch.arange(n) + (r * S + p) for r, p, n in zip(rows_l, pre, lens)]).to(device)
+    delta, residual = x, None
+    for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):
+        delta, residual, k, v = _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, pre_d, kv_d)
+        if append:                                  # behind the layer's attention: nothing reads a slot that is written
+            kc.view(-1, *k.shape[1:]).index_copy_(0, dst, k)
+            vc.view(-1, *v.shape[1:]).index_copy_(0, dst, v)
+    h, _ = lm.model.norm(delta.index_select(0, keep), residual.index_select(0, keep))
+    if append:
+        cache.hist.view(-1).index_copy_(0, dst, ids.to(torch.int32))
+        live = torch.tensor([r for r, n in zip(rows_l, lens) if n], dtype=torch.int64, device=device)
+        total = torch.tensor([p + n for p, n in zip(pre, lens) if n], dtype=torch.int32, device=device)
+        cache.hist_len.index_copy_(0, live, total)
+        cache.cache_len.index_copy_(0, live, total - 1)
+    return h
+
+
+def next_turn(past: KVCache, turn_ids, eos: Sequence[int], pad: int) -> Prompts:
+    """The ids `generate(..., past=past)` places behind a finished generation for a follow-up turn: per row the history's
+    newest token, whose key / value the loop has not cached yet, then turn_ids[b].  A row that finished early went on
+    emitting `pad` behind its eos: those pads are dropped, and the row's hist_len / cache_len are set back to the eos."""
+    hist, n = past.hist.cpu(), past.hist_len.tolist()
+    stop = {int(e) for e in eos} | {int(pad)}
+    out, m_all = [], []
+    for b, turn in enumerate(turn_ids):
+        row = hist[b, :n[b]].tolist()
+        m = len(row)
+        while m > 1 and row[m - 1] == pad and row[m - 2] in stop:
+            m -= 1
+        if m < 1:
+            raise ValueError(f"next_turn: row {b} of the cache holds no history")
+        m_all.append(m)
+        out.append(torch.cat([torch.tensor(row[m - 1:m], dtype=torch.int64),
+                              torch.as_tensor(turn, dtype=torch.int64).reshape(-1)]))
+    m_d = torch.tensor(m_all, dtype=torch.int32, device=past.hist_len.device)
+    past.hist_len[:len(m_all)].copy_(m_d)
+    past.cache_len[:len(m_all)].copy_(m_d - 1)
+    return Prompts(input_ids=out)
+
+
 @torch.no_grad()
 def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, return_cache: bool = False,
-             row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None, return_scores: bool = False):
+             row_keys: Optional[torch.Tensor] = None, embed: Optional[EmbedFn] = None, return_scores: bool = False,
+             past: Optional[KVCache] = None):
     """Greedy, sampled or beam-search generation for a batch of prompts -> int64 [B, N] generated ids (the prompt
     excluded), `pad` after a row's eos — the tensor HF generate() returns behind the prompt columns.  `model`: TouchAudioForCausalLM,
     Qwen2AudioPackedForConditionalGeneration (with its `embed` builder) or PackedCausalLM, bf16, on the device.
@@ -756,8 +866,16 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     the last element, (ids, scores) or (ids, cache, scores) — one tn_token_scores launch per step on the raw logits (when a
     `sequence_bias` plan edits the logits, it edits a copy).  cfg.nbest > 1 (beam search): (ids [B, nbest, N], scores
     [B, nbest], count [B]) of `BeamState.nbest` in place of ids, the TokenScores then [B * nbest, N] in that order.  With
-    no knob set nothing of this runs."""
+    no knob set nothing of this runs.
+
+    `past`: a `KVCache` an earlier call handed out (`return_cache`), one row per prompt.  prompts.input_ids[b] are then the
+    ids to place behind the first past.cache_len[b] cached positions of row b (`next_turn` builds them for a chat turn);
+    they are prefilled by `extend` instead of the packed forward, the loop goes on in `past`, and the result is what this
+    call generated.  Greedy search and sampling only."""
     cfg = cfg or GenerationConfig()
+    if past is not None and int(cfg.num_beams) != 1:
+        raise ValueError(f"generate: past= with num_beams = {cfg.num_beams} is not supported (beam search shares its cache "
+                         "rows through a table of its own; continue a cache with greedy search or sampling)")
     cfg.check_scores()
     scored = bool(return_scores) or cfg.wants_scores
     n_alt = int(cfg.top_alternatives)
@@ -772,6 +890,10 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     c = lm.config
     B = len(prompts)
     lens = [int(t.numel()) for t in prompts.input_ids]
+    if past is not None:
+        if not isinstance(past, KVCache) or past.cache_len.shape[0] != B:
+            raise ValueError(f"generate: past must be a KVCache of {B} rows, one per prompt")
+        lens = [p + n for p, n in zip(past.cache_len.tolist(), lens)]      # a row's positions once its ids are placed
     n_new = cfg.new_tokens(max(lens))
     if n_new <= 0:
         if scored or int(cfg.nbest) > 1:
@@ -793,8 +915,12 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         if tuple(row_keys.shape) != (B,):
             raise ValueError(f"generate: row_keys must have shape [{B}]")
     chunk = max(1, int(cfg.cache_chunk))
-    cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
-                             device)
+    if past is None:
+        cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
+                                 device)
+    else:
+        cache = past
+        cache.grow(max(lens) + min(n_new, chunk))
     S_full = max(lens) + n_new
     plan = ConstraintPlan.build(cfg.sequence_bias, cfg.min_new_tokens, eos, int(c.vocab_size), device)
     prompt_len = torch.tensor(lens, dtype=torch.int32, device=device) if plan is not None else None
@@ -815,7 +941,13 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
         if scored:                                 # the token the step kernel has just appended, in its history column
             F.token_scores_(raw, cache.hist, cache.hist_len, scores, n_alt)
 
-    step(_prefill(lm, proj_w, prompts, cache, device, embed))
+    if past is None:
+        step(_prefill(lm, proj_w, prompts, cache, device, embed))
+    else:
+        h = extend(model, cache, range(B), prompts.input_ids, embed=embed)
+        cache.finished.zero_()
+        cache.n_unfinished.fill_(B)
+        step(lm.lm_head(h))
     steps = 1
     while steps < n_new:
         if steps % max(1, int(cfg.check_every)) == 0 and int(cache.n_unfinished.item()) == 0:
@@ -916,14 +1048,21 @@ def with_continuations(prompts: Prompts, continuations) -> Prompts:
 
 @torch.no_grad()
 def score_continuations(model, prompts: Prompts, continuations, k: int = 0, embed: Optional[EmbedFn] = None,
-                        rows_per_chunk: int = 4096) -> TokenScores:
+                        rows_per_chunk: int = 4096, cache=None, cache_row=None, prefix_len=None) -> TokenScores:
     """Teacher-forced scores of given continuations — the rescoring entry point: `TokenScores` [B, N] (N the longest
     continuation; columns behind a shorter one read 0 / -1) of continuation b (token ids, possibly none) behind prompt b.
     One packed, document-masked forward over prompt + continuation, the prefill's construction with `keep_rows` = the row
     in front of every continuation token; lm_head runs on at most `rows_per_chunk` of those rows at a time and
     tn_token_scores (token mode) scores each chunk, so the [rows, V] logits never exist as a whole.  `confidence` is
     exp(mean logp) over the whole continuation (1 for an empty one).  `model` as for `generate`; `embed`: the embedding
-    builder of the documents `with_continuations(prompts, continuations)` (Qwen2-Audio: audio_embedder over them)."""
+    builder of the documents `with_continuations(prompts, continuations)` (Qwen2-Audio: audio_embedder over them).
+
+    `cache`: the `KVCache` / `BeamState` a `generate(..., return_cache=True)` over `prompts` has left.  The prompts are then
+    not recomputed: continuation i is scored behind the first prefix_len[i] positions (default: the whole prompt) of cache
+    row cache_row[i] (default: prompt i's row), through `extend(..., append=False)`; there may be more continuations than
+    prompts, and the cache is left as it is.  The row in front of a continuation's first token — the prefix's last
+    position, its id read from the cache's history — is the first new row, so the scored rows are the packed
+    construction's.  `embed` is not consulted on this path: that row must be a token row."""
     _check_alternatives("score_continuations", k)
     if int(rows_per_chunk) < 1:
         raise ValueError(f"score_continuations: rows_per_chunk = {rows_per_chunk} must be >= 1")
@@ -934,6 +1073,9 @@ def score_continuations(model, prompts: Prompts, continuations, k: int = 0, embe
     if any(int(t.numel()) == 0 for t in prompts.input_ids):
         raise ValueError("score_continuations: empty prompt")
     device = lm.model.embed_tokens.weight.device
+    if cache is not None:
+        return _score_behind_cache(model, lm, proj_w, prompts, continuations, int(k), int(rows_per_chunk), cache, cache_row,
+                                   prefix_len, device)
     docs = with_continuations(prompts, continuations)
     plens = [int(t.numel()) for t in prompts.input_ids]
     lens = [int(t.numel()) for t in docs.input_ids]
@@ -965,14 +1107,65 @@ def score_continuations(model, prompts: Prompts, continuations, k: int = 0, embe
     else:
         emb = _embed_touch_audio(lm, proj_w, docs, ids, lens, Tp, device)
     h = lm.model(inputs_embeds=emb[None], position_ids=pos[None], attention_mask=doc[None], keep_rows=rows)[0]   # [n_rows, H]
-    step = int(rows_per_chunk)
-    for a in range(0, n_rows, step):
-        logp, ent, alt_id, alt_logp = F.token_scores(lm.lm_head(h[a:a + step]), toks[a:a + step], int(k))
+    _score_rows(lm, h, toks, slot, result, int(k), int(rows_per_chunk))
+    return result.close(torch.tensor(clens))
+
+
+def _score_rows(lm, h, toks, slot, result: TokenScores, k: int, step: int) -> None:
+    """lm_head and tn_token_scores (token mode) over the kept rows h [n_rows, H], `step` rows at a time, into the flat
+    slots `slot` of `result`."""
+    cells = result.logp.numel()
+    for a in range(0, h.shape[0], step):
+        logp, ent, alt_id, alt_logp = F.token_scores(lm.lm_head(h[a:a + step]), toks[a:a + step], k)
         at = slot[a:a + step]
         result.logp.view(-1).index_copy_(0, at, logp)
         result.entropy.view(-1).index_copy_(0, at, ent)
-        result.alt_id.view(B * N, -1).index_copy_(0, at, alt_id)
-        result.alt_logp.view(B * N, -1).index_copy_(0, at, alt_logp)
+        result.alt_id.view(cells, result.k).index_copy_(0, at, alt_id)
+        result.alt_logp.view(cells, result.k).index_copy_(0, at, alt_logp)
+
+
+def _score_behind_cache(model, lm, proj_w, prompts, continuations, k, rows_per_chunk, cache, cache_row, prefix_len, device):
+    """`score_continuations` with `cache=`: the new rows of continuation i are the prefix's last position and all but the
+    continuation's last token, behind prefix_len[i] - 1 cached positions; every one of them is kept."""
+    conts = [torch.as_tensor(c, dtype=torch.int64).reshape(-1).cpu() for c in continuations]
+    stride = cache.num_beams if isinstance(cache, BeamState) else 1        # where `_prefill` put prompt p: row p * stride
+    B = len(conts)
+    if cache_row is None:
+        if B != len(prompts):
+            raise ValueError(f"score_continuations: {B} continuations for {len(prompts)} cached prompts need cache_row")
+        cache_row = [i * stride for i in range(B)]
+    cache_row = [int(r) for r in cache_row]
+    if len(cache_row) != B or any(r % stride or not 0 <= r // stride < len(prompts) for r in cache_row):
+        raise ValueError(f"score_continuations: cache_row must name the cache row of one of the {len(prompts)} prompts "
+                         "per continuation")
+    plens = [int(prompts.input_ids[r // stride].numel()) for r in cache_row]
+    prefix_len = plens if prefix_len is None else [int(p) for p in prefix_len]
+    if len(prefix_len) != B or any(not 1 <= p <= n for p, n in zip(prefix_len, plens)):
+        raise ValueError("score_continuations: prefix_len must hold one entry in [1, prompt length] per continuation")
+    clens = [int(c.numel()) for c in conts]
+    N = max(clens)
+    result = TokenScores.buffers(B, N, k, device)
+    if sum(clens) == 0:
+        return result.close(torch.tensor(clens))
+    hist = cache.hist.cpu()
+    first = [int(hist[r, p - 1]) for r, p in zip(cache_row, prefix_len)]
+    new_ids = [torch.cat([torch.tensor([t]), c[:-1]]) if c.numel() else c for t, c in zip(first, conts)]
+    embed = None
+    if proj_w is not None and prompts.input_features is not None:
+        at = [o for o, n in zip(torch.tensor([0] + clens[:-1]).cumsum(0).tolist(), clens) if n]
+        feat = torch.stack([prompts.input_features[r // stride][p - 1]
+                            for r, p, n in zip(cache_row, prefix_len, clens) if n]).to(device=device, dtype=proj_w.dtype)
+        at = torch.tensor(at, dtype=torch.int64, device=device)
+
+        def embed(ids, lens, T):                   # TouchAudio: embed(ids) + projector(features); continuation rows have none
+            feats = torch.zeros(T, proj_w.shape[1], dtype=proj_w.dtype, device=device).index_copy_(0, at, feat)
+            return torch.addmm(lm.model.embed_tokens(ids), feats, proj_w.t())
+    T = sum(clens)
+    h = extend(model, cache, None, new_ids, embed=embed, kv_row=cache_row, append=False, keep_rows=torch.arange(T),
+               prefix_len=[p - 1 for p in prefix_len])
+    toks = torch.cat(conts).to(torch.int32).to(device)
+    slot = torch.cat([torch.arange(c) + i * N for i, c in enumerate(clens)]).to(device)
+    _score_rows(lm, h, toks, slot, result, k, rows_per_chunk)
     return result.close(torch.tensor(clens))
 
 

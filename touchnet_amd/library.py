@@ -956,6 +956,37 @@ def _(q, k_new, v_new, k_cache, v_cache, cache_len, scale):
     return torch.empty_like(q, memory_format=torch.contiguous_format)
 
 
+@custom_op(f"{NS}::attn_extend", mutates_args=(), device_types="cuda")
+def attn_extend(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, seq_start: Tensor,
+                prefix_len: Tensor, kv_row: Optional[Tensor], scale: float) -> Tensor:
+    """Several new rows per sequence over a KV cache (tn_attn_extend): q [T, Nh, D], k_new / v_new [T, Nkv, D] (q, k rotated)
+    packed by seq_start int32 [R + 1]; caches [B, S_max, Nkv, D] bf16, read only; prefix_len int32 [R]; kv_row int32 [R] or
+    None.  Returns o [T, Nh, D]."""
+    _no_grad_inputs("attn_extend", q, k_new, v_new, k_cache, v_cache)
+    T, Nh, D = q.shape
+    B, S_max, Nkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    R = prefix_len.shape[0]
+    if (any(t.dtype != torch.bfloat16 for t in (q, k_new, v_new, k_cache, v_cache))
+            or any(t.dtype != torch.int32 for t in (seq_start, prefix_len) + (() if kv_row is None else (kv_row,)))
+            or tuple(k_new.shape) != (T, Nkv, D) or tuple(v_new.shape) != (T, Nkv, D)
+            or tuple(k_cache.shape) != (B, S_max, Nkv, D) or tuple(v_cache.shape) != (B, S_max, Nkv, D)
+            or tuple(seq_start.shape) != (R + 1,) or (kv_row is not None and tuple(kv_row.shape) != (R,))
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous()):
+        raise _C.KernelError("attn_extend: bf16 q [T, Nh, D], k_new / v_new [T, Nkv, D], contiguous caches "
+                             "[B, S_max, Nkv, D], int32 seq_start [R + 1], prefix_len [R], kv_row [R] or None")
+    q, k_new, v_new, seq_start, prefix_len = _c(q), _c(k_new), _c(v_new), _c(seq_start), _c(prefix_len)
+    kv_row = None if kv_row is None else _c(kv_row)
+    o = torch.empty_like(q)
+    _C.check(_lib().tn_attn_extend(_p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(seq_start), _p(prefix_len),
+                                   _p(kv_row), _p(o), T, R, B, S_max, Nh, Nkv, D, float(scale), _cur()), "tn_attn_extend")
+    return o
+
+
+@attn_extend.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, kv_row, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
 def linear_smallm_launch(x: Tensor, ws, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
                          rope_mask: int) -> None:
     """tn_gemm_smallm on operands the caller has checked: outs[i][M, N_i] = x ws[i]^T (+ bs[i]), rotated where bit i of
@@ -1467,4 +1498,4 @@ OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fw
        "ce_fwd_rows", "ce_reduce", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
-       "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs")
+       "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs", "attn_extend")
