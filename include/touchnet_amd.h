@@ -485,6 +485,33 @@ int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_
 int tn_attn_extend(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
                    const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T, int R, int B, int S_max,
                    int Nh, int Nkv, int D, float scale, void* stream);
+/* FP8 KV cache (csrc/kv_fp8.h): the past_key_values of transformers/models/llama/modeling_llama.py:243-285 held as OCP
+ *      e4m3 codes uint8 [.., Nkv, D] (torch.float8_e4m3fn's bits) with one fp32 power-of-two scale per key [.., Nkv]:
+ *      scale = 2^e, e the smallest integer with amax <= 448 * 2^e, never below -100 (amax == 0: e = -100, codes 0);
+ *      code = e4m3(x * 2^-e), round to nearest even; a key holding a NaN or an infinity gets scale NaN and codes 0.
+ *      code * scale is exact in bf16: every kernel below computes what its bf16 sibling computes on the dequantised cache.
+ * kv_quantize: x bf16 [T, Nkv, D] -> codes uint8 [T, Nkv, D], scales fp32 [T, Nkv].  A key's result depends on its own D
+ *      elements only.  T == 0 is a no-op.  -22 before any launch for NULL or misaligned tensors (x 16, codes 8, scales 4
+ *      bytes), D not 64 / 128.
+ * attn_decode_fp8 / attn_decode_beam_fp8: tn_attn_decode / tn_attn_decode_beam with k_cache / v_cache uint8 codes
+ *      [B, S_max, Nkv, D] and k_scale / v_scale fp32 [B, S_max, Nkv].  k_new / v_new stay bf16: they are quantised by the
+ *      rule above, codes and scale go to slot cache_len[b], and the row attends to their DEQUANTISED values, so the output
+ *      depends only on what the cache holds after the call.  Splits, workspace, NaN poisoning (a refused length leaves
+ *      codes and scales untouched), table rules and limits as for the bf16 entries; -22 also for a NULL or misaligned scale.
+ * attn_extend_fp8: tn_attn_extend with the caches AND the new rows as codes and scales (k_new / v_new uint8 [T, Nkv, D],
+ *      k_new_scale / v_new_scale fp32 [T, Nkv]: tn_kv_quantize's output).  Reads only; rules and limits as for
+ *      attn_extend. */
+int tn_kv_quantize(const void* x, void* codes, float* scales, long long T, int Nkv, int D, void* stream);
+int tn_attn_decode_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* k_scale,
+                       float* v_scale, const int* cache_len, void* o, void* workspace, int B, int Nh, int Nkv, int D,
+                       int S_max, float scale, void* stream);
+int tn_attn_decode_beam_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                            float* k_scale, float* v_scale, const int* cache_len, const int* src, void* o, void* workspace,
+                            int R, int Nh, int Nkv, int D, int S_max, float scale, void* stream);
+int tn_attn_extend_fp8(const void* q, const void* k_new, const void* v_new, const float* k_new_scale,
+                       const float* v_new_scale, const void* k_cache, const void* v_cache, const float* k_scale,
+                       const float* v_scale, const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T,
+                       int R, int B, int S_max, int Nh, int Nkv, int D, float scale, void* stream);
 /* gemm_smallm: the linear products of one decode step — q_proj / k_proj / v_proj + apply_rotary_pos_emb, o_proj, down_proj
  *      and lm_head on B (x num_beams) rows (transformers/models/llama/modeling_llama.py:243-285 LlamaAttention.forward and
  *      :174-176 LlamaMLP.forward under use_cache=True, driven by touchnet/models/touch_audio/inference_touch_audio.py:177-192)

@@ -33,6 +33,13 @@ with and without the plan), and tn_beam_step with and without the edit list (K 4
 and k = K (default 8), rows/s in token mode on [4096, V] (the rescoring shape), and its share of the Qwen2-Audio-7B sampled
 decode step timed in the same run (with an A/B of the whole step with and without the launch).
 
+--kv-fp8: the FP8 (e4m3) KV cache beside the bf16 kernels of the same build, alternated in one process (medians of 5 rounds):
+tn_attn_decode_fp8 against tn_attn_decode at B rows behind 750 and 8 192 positions (32 / 8 heads at D 64, 28 / 4 at D 128),
+tn_attn_extend_fp8 against tn_attn_extend at --attn-extend's two shapes (with and without the two tn_kv_quantize launches
+of the new rows), tn_kv_quantize at a 12 x 750-row prefill, the largest logit difference between an fp8 and a bf16 cache
+over one teacher-forced generation of a random-weight model (a recorded number, not a gate), and ms per decode step at
+Qwen2-Audio-7B's widths behind 750 and 8 192 cached positions (profiles/kv_fp8_bench.log).
+
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
 """
@@ -681,6 +688,124 @@ def bench_attn_extend(layers, rounds=5, iters=100):
                ms_packed_all=[round(t, 2) for t in times["packed"]], ms_with_cache_all=[round(t, 2) for t in times["cached"]])
 
 
+def _alternate(calls, rounds=5, iters=50):
+    """{label: fn} -> {label: median over `rounds` of the µs per call}, the labels alternated round by round in one process"""
+    with torch.no_grad():
+        for fn in calls.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in calls}
+        for _ in range(rounds):
+            for k, fn in calls.items():
+                t[k].append(_events_time(fn, iters))
+    return {k: round(sorted(v)[len(v) // 2], 2) for k, v in t.items()}
+
+
+def _random_fp8(*shape):
+    """codes without the two NaN patterns, scales 2^-4 .. 2^-1"""
+    codes = torch.randint(0, 256, shape, device=DEV, dtype=torch.uint8) & 0xF7
+    return codes, torch.exp2(-torch.randint(1, 5, shape[:-1], device=DEV).float())
+
+
+def bench_kv_fp8(B, rounds=5):
+    """The FP8 KV cache beside the bf16 kernels, alternated in one process (medians of `rounds`): tn_attn_decode(_fp8) at B
+    rows behind 750 and 8 192 positions at both head geometries, tn_attn_extend(_fp8) at bench_attn_extend's two shapes,
+    tn_kv_quantize at a 12 x 750-row prefill, the whole decode step at Qwen2-Audio-7B's widths, and the largest logit
+    difference between an fp8 and a bf16 cache over one teacher-forced generation of a random-weight two-layer model.
+    bytes: the cache bytes a call must read (K and V, codes and scales)."""
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    bf = dict(device=DEV, dtype=torch.bfloat16)
+    geoms = ((32, 8, 64), (28, 4, 128))
+    for L in (750, 8192):
+        for Nh, Nkv, D in geoms:
+            S = L + 1
+            q, kn = torch.randn(B, Nh, D, **bf), torch.randn(B, Nkv, D, **bf)
+            kc, vc = torch.randn(B, S, Nkv, D, **bf), torch.randn(B, S, Nkv, D, **bf)
+            (k8, ks), (v8, vs) = _random_fp8(B, S, Nkv, D), _random_fp8(B, S, Nkv, D)
+            cl = torch.full((B,), L - 1, dtype=torch.int32, device=DEV)
+            us = _alternate({"bf16": lambda: F.attn_decode(q, kn, kn, kc, vc, cl),
+                             "fp8": lambda: F.attn_decode_fp8(q, kn, kn, k8, v8, ks, vs, cl)}, rounds, 100)
+            nb = B * L * Nkv * 2
+            yield dict(what="attn_decode", B=B, L=L, Nh=Nh, Nkv=Nkv, D=D, us_bf16=us["bf16"], us_fp8=us["fp8"],
+                       fp8_over_bf16=round(us["fp8"] / us["bf16"], 3), tbps_bf16=round(nb * 2 * D / us["bf16"] / 1e6, 3),
+                       tbps_fp8=round(nb * (D + 4) / us["fp8"] / 1e6, 3))
+    for name, n_seq, n_new, P, rows in (("rescoring", 48, 32, 750, 12), ("turn", 1, 750, 8192, 1)):
+        for Nh, Nkv, D in geoms:
+            T = n_seq * n_new
+            q, kn, vn = (torch.randn(T, h, D, **bf) for h in (Nh, Nkv, Nkv))
+            kc, vc = torch.randn(rows, P, Nkv, D, **bf), torch.randn(rows, P, Nkv, D, **bf)
+            (k8, ks), (v8, vs) = _random_fp8(rows, P, Nkv, D), _random_fp8(rows, P, Nkv, D)
+            (kn8, kns), (vn8, vns) = F.kv_quantize(kn), F.kv_quantize(vn)
+            start = torch.arange(n_seq + 1, dtype=torch.int32, device=DEV) * n_new
+            pre = torch.full((n_seq,), P, dtype=torch.int32, device=DEV)
+            row = torch.arange(n_seq, dtype=torch.int32, device=DEV) % rows
+            us = _alternate({"bf16": lambda: F.attn_extend(q, kn, vn, kc, vc, start, pre, None, row),
+                             "fp8": lambda: F.attn_extend_fp8(q, kn8, vn8, kns, vns, k8, v8, ks, vs, start, pre, None, row),
+                             "fp8_with_quantize": lambda: (F.kv_quantize(kn), F.kv_quantize(vn), F.attn_extend_fp8(
+                                 q, kn8, vn8, kns, vns, k8, v8, ks, vs, start, pre, None, row))}, rounds, 50)
+            yield dict(what="attn_extend", shape=name, sequences=n_seq, new_rows=n_new, prefix=P, Nh=Nh, Nkv=Nkv, D=D,
+                       us_bf16=us["bf16"], us_fp8=us["fp8"], us_fp8_with_quantize=us["fp8_with_quantize"],
+                       fp8_over_bf16=round(us["fp8"] / us["bf16"], 3))
+    for Nh, Nkv, D in geoms + ((32, 32, 128),):
+        x = torch.randn(12 * 750, Nkv, D, **bf)
+        us = _alternate({"q": lambda: F.kv_quantize(x)}, rounds, 100)["q"]
+        yield dict(what="kv_quantize", rows=12 * 750, Nkv=Nkv, D=D, us=us,
+                   tbps_read_and_written=round(x.numel() * (3 + 4 / D) / us / 1e6, 3))
+    # the largest logit difference over one teacher-forced greedy generation (random weights, LlamaForASR-1B widths, 2 layers)
+    m, _ = _model(2)
+    g = torch.Generator().manual_seed(0)
+    prompts = G.Prompts([torch.randint(0, 128000, (n,), generator=g) for n in (300, 750, 520)])
+    lens = [300, 750, 520]
+    with torch.no_grad():
+        caches = {d: G.KVCache.allocate(2, 3, 750 + 34, 8, 64, DEV, kv_dtype=d) for d in G.KV_CACHE_DTYPES}
+        logits = {d: G._prefill(m.language_model, None, prompts, c, DEV).float() for d, c in caches.items()}
+        worst, scale, flips = 0.0, 0.0, 0
+        for _ in range(32):
+            worst = max(worst, float((logits["bf16"] - logits["fp8_e4m3"]).abs().max()))
+            scale = max(scale, float(logits["bf16"].abs().max()))
+            tok = logits["bf16"].argmax(1).to(torch.int32)                   # both caches follow the bf16 run's tokens
+            flips += int((logits["fp8_e4m3"].argmax(1) != tok).sum())
+            for c in caches.values():
+                c.hist.scatter_(1, c.hist_len.to(torch.int64)[:, None], tok[:, None])
+                c.hist_len += 1
+                c.cache_len += 1
+            logits = {d: G.decode_logits(m.language_model, c).float() for d, c in caches.items()}
+    yield dict(what="logit_difference_fp8_vs_bf16_cache", model="random weights, 2 layers, hidden 2048, 32 / 8 heads, D 64",
+               prompts=lens, steps=32, max_abs_difference=round(worst, 4), largest_logit=round(scale, 3),
+               argmax_flips=flips, of=32 * 3)
+    del m, caches, logits
+    # the whole decode step at Qwen2-Audio-7B's widths, B rows behind 750 and 8 192 cached positions (random cache contents)
+    text = DecoderConfig.from_dict(dict(model_type="qwen2", hidden_size=4096, intermediate_size=11008, num_attention_heads=32,
+                                        num_key_value_heads=32, head_dim=128, num_hidden_layers=32, vocab_size=156032,
+                                        rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=False,
+                                        initializer_range=0.02, eos_token_id=151643, pad_token_id=151643))
+    torch.manual_seed(0)
+    with torch.device(DEV):
+        lm = PackedCausalLM(text)
+    lm.post_init()
+    lm = lm.to(torch.bfloat16).eval()
+    for P in (750, 8192):
+        caches = {}
+        for d in G.KV_CACHE_DTYPES:
+            c = G.KVCache.allocate(32, B, P + 8, 32, 128, DEV, kv_dtype=d)
+            for i in range(32):
+                if d == "bf16":
+                    c.k[i].normal_(), c.v[i].normal_()
+                else:
+                    (c.k[i], c.k_scale[i]), (c.v[i], c.v_scale[i]) = _random_fp8(B, P + 8, 32, 128), _random_fp8(B, P + 8, 32, 128)
+            c.hist_len.fill_(P + 1), c.cache_len.fill_(P)
+            caches[d] = c
+        us = _alternate({d: (lambda c=c: G.decode_logits(lm, c)) for d, c in caches.items()}, 3, 8)
+        kv_gb = lambda d: round(B * P * 32 * 32 * 2 * (256 if d == "bf16" else 132) / 1e9, 2)
+        yield dict(what="decode_step_qwen2_audio_7b_widths", B=B, prefix=P, ms_bf16=round(us["bf16"] / 1e3, 3),
+                   ms_fp8=round(us["fp8_e4m3"] / 1e3, 3), fp8_over_bf16=round(us["fp8_e4m3"] / us["bf16"], 3),
+                   cache_gb_bf16=kv_gb("bf16"), cache_gb_fp8=kv_gb("fp8_e4m3"))
+        del caches
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -698,12 +823,18 @@ def main():
                     help="TN_DECODE_GEMM own against lib: per product family and per step (one of DECODER_WIDTHS, default all)")
     ap.add_argument("--attn-extend", action="store_true",
                     help="tn_attn_extend per call and score_continuations with / without cache= (profiles/attn_extend_bench.log)")
+    ap.add_argument("--kv-fp8", action="store_true",
+                    help="the FP8 KV cache beside the bf16 kernels, alternated in one process (profiles/kv_fp8_bench.log)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench needs the MI355X")
     from touchnet_amd import build
     build.build()
     print(json.dumps(dict(device=torch.cuda.get_device_name(0))), flush=True)
+    if a.kv_fp8:
+        for r in bench_kv_fp8(a.batch):
+            print(json.dumps(r), flush=True)
+        return
     if a.attn_extend:
         for r in bench_attn_extend(a.layers):
             print(json.dumps(r), flush=True)

@@ -99,6 +99,10 @@ PROTOTYPES = {
     "tn_attn_decode_workspace_bytes": [_i, _i, _i, _i, _i],
     "tn_attn_decode": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "tn_attn_extend": [_vp] * 9 + [_i] * 7 + [_f, _vp],
+    "tn_kv_quantize": [_vp, _vp, _vp, _ll, _i, _i, _vp],
+    "tn_attn_decode_fp8": [_vp] * 10 + [_i] * 5 + [_f, _vp],
+    "tn_attn_decode_beam_fp8": [_vp] * 11 + [_i] * 5 + [_f, _vp],
+    "tn_attn_extend_fp8": [_vp] * 13 + [_i] * 7 + [_f, _vp],
     "tn_gemm_smallm": [_vp, _ll, _i, _i, _i, C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_ll),
                        C.POINTER(_i), _vp, _vp, _i, _i, _vp],
     "tn_gemm_smallm_swiglu": [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _vp],

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from touchnet_amd.data import functions as stages
-from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_longform_arguments,
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_kv_cache_argument, add_longform_arguments,
                                      add_score_arguments, constraints_from_args)
 from touchnet_amd.longform import longform_from_args, touch_audio_decoder, transcribe_long
 from touchnet_amd.models.backend import ops
@@ -167,6 +167,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
     add_score_arguments(ap)
+    add_kv_cache_argument(ap)
     add_longform_arguments(ap)
     return ap
 
@@ -177,7 +178,8 @@ def generation_config(args, tokenizer=None) -> GenerationConfig:
                            length_penalty=args.length_penalty,
                            early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
                            sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0,
-                           output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
+                           output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest,
+                           kv_cache_dtype=args.kv_cache_dtype)
     cfg.check_beams()
     return cfg
 

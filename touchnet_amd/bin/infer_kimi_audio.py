@@ -30,7 +30,7 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import KimiGenerationConfig, add_longform_arguments, add_score_arguments
+from touchnet_amd.generation import KimiGenerationConfig, add_kv_cache_argument, add_longform_arguments, add_score_arguments
 from touchnet_amd.longform import kimi_audio_decoder, longform_from_args, transcribe_long
 from touchnet_amd.models.kimi_audio import KimiAudioConfig, KimiAudioPackedForCausalLM
 from touchnet_amd.models.kimi_audio.inference_kimi_audio import transcribe
@@ -77,6 +77,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--shard_index", type=int, default=0)
     ap.add_argument("--num_shards", type=int, default=1)
     add_score_arguments(ap, nbest=False)
+    add_kv_cache_argument(ap)
     add_longform_arguments(ap)
     return ap
 
@@ -86,7 +87,7 @@ def generation_config(args) -> KimiGenerationConfig:
                                 text_repetition_penalty=args.text_repetition_penalty,
                                 text_repetition_window_size=args.text_repetition_window_size,
                                 max_new_tokens=args.max_new_tokens, seed=args.seed, output_scores=args.output_scores,
-                                top_alternatives=args.top_alternatives)
+                                top_alternatives=args.top_alternatives, kv_cache_dtype=args.kv_cache_dtype)
 
 
 def main(argv=None):

@@ -41,7 +41,7 @@ import os
 import torch
 
 from touchnet_amd.bin.infer_asr import read_wav
-from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_longform_arguments,
+from touchnet_amd.generation import (GenerationConfig, add_constraint_arguments, add_kv_cache_argument, add_longform_arguments,
                                      add_score_arguments, constraints_from_args)
 from touchnet_amd.longform import longform_from_args, qwen2_audio_decoder, transcribe_long
 from touchnet_amd.models.qwen2_audio import Qwen2AudioConfig, Qwen2AudioPackedForConditionalGeneration
@@ -106,12 +106,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_shards", type=int, default=1)
     add_constraint_arguments(ap)
     add_score_arguments(ap)
+    add_kv_cache_argument(ap)
     add_longform_arguments(ap)
     return ap
 
 
 def generation_config(args, tokenizer=None) -> GenerationConfig:
-    over = dict(max_length=args.max_length, seed=args.seed)
+    over = dict(max_length=args.max_length, seed=args.seed, kv_cache_dtype=args.kv_cache_dtype)
     if args.output_scores or args.top_alternatives or args.nbest != 1:
         over.update(output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
     if args.num_beams is not None:

@@ -20,9 +20,19 @@
 // workspace and a second launch combines them.  Split boundaries depend only on (B, Nkv, S_max) and cache_len: results are
 // bit-reproducible.  The slot cache_len[b] is read by nobody: the key at index cache_len[b] is taken from k_new / v_new,
 // and only the workgroup whose split contains that index writes the slot.
+//
+// FP8 cache (tn_attn_decode_fp8 / tn_attn_decode_beam_fp8; KV = kvq::fp8_t): k_cache / v_cache hold e4m3 codes uint8
+// [B, S_max, Nkv, D] and k_scale / v_scale fp32 [B, S_max, Nkv] hold one power-of-two scale per key (kv_fp8.h).  Grid,
+// splits, lane layout, the order of every floating-point operation, merge and combine are the bf16 kernel's; a lane's 8
+// elements of a key are now 8 bytes plus the key's scale (the D / 8 lanes of the key read the same 4 bytes: one
+// broadcast fetch), expanded exactly into the fp32 values the bf16 kernel unpacks.  Half the bytes per load, so UF = 2 U
+// = 4 iterations are in flight per lane instead of 2: the same bytes in flight.  The owner of slot cache_len[b] quantises the
+// new bf16 key / value in registers (kv_fp8.h's rule, the one tn_kv_quantize applies), stores codes and scale, and
+// attends to the DEQUANTISED values: the key at index cache_len[b] is taken from those registers as codes, like any other
+// key, so a row's output depends only on what the cache holds after the call.
 #include <type_traits>
 
-#include "common.h"
+#include "kv_fp8.h"
 
 namespace tn {
 namespace decode {
@@ -78,17 +88,25 @@ struct NoTable {};                        // the dense kernel's `src`: an empty 
 struct Table {
   const int* __restrict__ p;
 };
+struct NoScales {};                       // the bf16 kernels' scales: an empty argument as well
+struct Scales {
+  float* __restrict__ k;
+  float* __restrict__ v;
+};
 
-template <int D, int G, bool BEAM = false>
+template <int D, int G, bool BEAM = false, typename KV = bf16_t>
 __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_new, const bf16_t* __restrict__ v_new,
-    bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache, const int* __restrict__ cache_len, bf16_t* __restrict__ o,
+    KV* __restrict__ k_cache, KV* __restrict__ v_cache, const int* __restrict__ cache_len, bf16_t* __restrict__ o,
     float* __restrict__ ws_o, float* __restrict__ ws_lse, int Nkv, int S_max, int nsplit, float scale_log2,
-    std::conditional_t<BEAM, Table, NoTable> src) {
+    std::conditional_t<BEAM, Table, NoTable> src, std::conditional_t<std::is_same_v<KV, bf16_t>, NoScales, Scales> sc) {
+  constexpr bool FP8 = !std::is_same_v<KV, bf16_t>;
   constexpr int LPK = D / 8;              // lanes per key row
   constexpr int KPW = 64 / LPK;           // keys per wave per iteration
   constexpr int KPI = KPW * kWaves;       // keys per workgroup per iteration
-  constexpr int U = 2;                    // iterations in flight per lane
+  constexpr int U = 2;                    // iterations in flight per lane on a bf16 cache: 32 bytes of K and of V
+  constexpr int UF = FP8 ? 2 * U : U;     // ... and on this cache: a lane's 8 codes are 8 bytes, so twice as many
+  using Raw = std::conditional_t<FP8, uint2, uint4>;    // a lane's 8 elements of a key as they are loaded
   const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int part = lane % LPK, kg = lane / LPK;
@@ -97,8 +115,8 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
   const bool overflow = len < 0 || len >= S_max;
 
   const size_t row_stride = (size_t)Nkv * D;                           // one cache position
-  const bf16_t* kc = k_cache + (size_t)b * S_max * row_stride + (size_t)kvh * D + part * 8;
-  const bf16_t* vc = v_cache + (size_t)b * S_max * row_stride + (size_t)kvh * D + part * 8;
+  [[maybe_unused]] const KV* kc = k_cache + (size_t)b * S_max * row_stride + (size_t)kvh * D + part * 8;
+  [[maybe_unused]] const KV* vc = v_cache + (size_t)b * S_max * row_stride + (size_t)kvh * D + part * 8;
   const bf16_t* kn = k_new + ((size_t)b * Nkv + kvh) * D + part * 8;
   const bf16_t* vn = v_new + ((size_t)b * Nkv + kvh) * D + part * 8;
 
@@ -119,7 +137,26 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
   const int k1 = min(k0 + chunk, total);
 
   // the owner of the new key's index stores it into the slot (nobody else touches that slot in this launch)
-  if (len >= k0 && len < k1 && wave == 0 && kg == 0) {
+  [[maybe_unused]] uint2 kn_c = make_uint2(0u, 0u), vn_c = make_uint2(0u, 0u);      // FP8: the new key / value as codes
+  [[maybe_unused]] float kn_s = 0.f, vn_s = 0.f;                                    // ... and their scales
+  if constexpr (FP8) {
+    if (len >= k0 && len < k1) {          // (uniform in the workgroup: every lane of every key group takes part)
+      float f[8];
+      unpack8(*reinterpret_cast<const uint4*>(kn), f);
+      kvq::quantize_key<LPK>(f, kn_c, kn_s);
+      unpack8(*reinterpret_cast<const uint4*>(vn), f);
+      kvq::quantize_key<LPK>(f, vn_c, vn_s);
+      if (wave == 0 && kg == 0) {
+        const size_t slot = (size_t)b * S_max + len;
+        *reinterpret_cast<uint2*>(k_cache + slot * row_stride + (size_t)kvh * D + part * 8) = kn_c;
+        *reinterpret_cast<uint2*>(v_cache + slot * row_stride + (size_t)kvh * D + part * 8) = vn_c;
+        if (part == 0) {
+          sc.k[slot * Nkv + kvh] = kn_s;
+          sc.v[slot * Nkv + kvh] = vn_s;
+        }
+      }
+    }
+  } else if (len >= k0 && len < k1 && wave == 0 && kg == 0) {
     *reinterpret_cast<uint4*>(k_cache + ((size_t)b * S_max + len) * row_stride + (size_t)kvh * D + part * 8) =
         *reinterpret_cast<const uint4*>(kn);
     *reinterpret_cast<uint4*>(v_cache + ((size_t)b * S_max + len) * row_stride + (size_t)kvh * D + part * 8) =
@@ -150,39 +187,66 @@ __global__ void __launch_bounds__(kThreads) attn_decode_split_kernel(
     for (int e = 0; e < 8; ++e) acc[h][e] = 0.f;
   }
 
-  for (int base = k0; base < k1; base += U * KPI) {
-    uint4 kr[U], vr[U];
-    int jj[U];
+  for (int base = k0; base < k1; base += UF * KPI) {
+    Raw kr[UF], vr[UF];
+    [[maybe_unused]] float ks[UF], vs[UF];
+    int jj[UF];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
+    for (int u = 0; u < UF; ++u) {
       const int j = base + u * KPI + wave * KPW + kg;
       jj[u] = j;
       const int js = j < k1 ? j : k0;                                       // (in-bounds filler, never used)
-      const bf16_t *kp, *vp;
-      if constexpr (BEAM) {
+      if constexpr (FP8) {
         int r = b;
-        if (js != len) {
-          r = srow[js];
-          if (r < 0 || r >= R) {
-            bad = true;
-            r = b;
+        if constexpr (BEAM) {
+          if (js != len) {
+            r = srow[js];
+            if (r < 0 || r >= R) {
+              bad = true;
+              r = b;
+            }
           }
         }
-        const size_t off = ((size_t)r * S_max + js) * row_stride + (size_t)kvh * D + part * 8;
-        kp = js == len ? kn : k_cache + off;
-        vp = js == len ? vn : v_cache + off;
+        kr[u] = kn_c, vr[u] = vn_c, ks[u] = kn_s, vs[u] = vn_s;
+        if (js != len) {
+          const size_t pos = (size_t)r * S_max + js;
+          kr[u] = *reinterpret_cast<const uint2*>(k_cache + pos * row_stride + (size_t)kvh * D + part * 8);
+          vr[u] = *reinterpret_cast<const uint2*>(v_cache + pos * row_stride + (size_t)kvh * D + part * 8);
+          ks[u] = sc.k[pos * Nkv + kvh];
+          vs[u] = sc.v[pos * Nkv + kvh];
+        }
       } else {
-        kp = js == len ? kn : kc + (size_t)js * row_stride;
-        vp = js == len ? vn : vc + (size_t)js * row_stride;
+        const bf16_t *kp, *vp;
+        if constexpr (BEAM) {
+          int r = b;
+          if (js != len) {
+            r = srow[js];
+            if (r < 0 || r >= R) {
+              bad = true;
+              r = b;
+            }
+          }
+          const size_t off = ((size_t)r * S_max + js) * row_stride + (size_t)kvh * D + part * 8;
+          kp = js == len ? kn : k_cache + off;
+          vp = js == len ? vn : v_cache + off;
+        } else {
+          kp = js == len ? kn : kc + (size_t)js * row_stride;
+          vp = js == len ? vn : vc + (size_t)js * row_stride;
+        }
+        kr[u] = *reinterpret_cast<const uint4*>(kp);
+        vr[u] = *reinterpret_cast<const uint4*>(vp);
       }
-      kr[u] = *reinterpret_cast<const uint4*>(kp);
-      vr[u] = *reinterpret_cast<const uint4*>(vp);
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
+    for (int u = 0; u < UF; ++u) {
       float kf[8], vf[8];
-      unpack8(kr[u], kf);
-      unpack8(vr[u], vf);
+      if constexpr (FP8) {
+        kvq::decode8(kr[u], ks[u], kf);
+        kvq::decode8(vr[u], vs[u], vf);
+      } else {
+        unpack8(kr[u], kf);
+        unpack8(vr[u], vf);
+      }
       const bool valid = jj[u] < k1;
 #pragma unroll
       for (int h = 0; h < G; ++h) {
@@ -303,21 +367,24 @@ __global__ void __launch_bounds__(kThreads) attn_decode_combine_kernel(const flo
   }
 }
 
-template <int D, int G>
-static int launch(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
-                  const int* src, void* o, void* workspace, int B, int Nkv, int S_max, float scale, hipStream_t st) {
+template <int D, int G, typename KV>
+static int launch(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* k_scale,
+                  float* v_scale, const int* cache_len, const int* src, void* o, void* workspace, int B, int Nkv, int S_max,
+                  float scale, hipStream_t st) {
   const int nsplit = num_splits(B, Nkv, S_max);
   float* ws_o = (float*)workspace;
   float* ws_lse = ws_o ? ws_o + (size_t)B * Nkv * nsplit * G * D : nullptr;
   const float sl2 = scale * kLog2e;
+  std::conditional_t<std::is_same_v<KV, bf16_t>, NoScales, Scales> sc{};
+  if constexpr (!std::is_same_v<KV, bf16_t>) sc = Scales{k_scale, v_scale};
   if (src)
-    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, true>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
-                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache,
-                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, Table{src});
+    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, true, KV>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
+                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (KV*)k_cache, (KV*)v_cache,
+                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, Table{src}, sc);
   else
-    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, false>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
-                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (bf16_t*)k_cache, (bf16_t*)v_cache,
-                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, NoTable{});
+    hipLaunchKernelGGL((attn_decode_split_kernel<D, G, false, KV>), dim3(nsplit, Nkv, B), dim3(kThreads), 0, st,
+                       (const bf16_t*)q, (const bf16_t*)k_new, (const bf16_t*)v_new, (KV*)k_cache, (KV*)v_cache,
+                       cache_len, (bf16_t*)o, ws_o, ws_lse, Nkv, S_max, nsplit, sl2, NoTable{}, sc);
   TN_LAUNCH_CHECK();
   if (nsplit > 1) {
     hipLaunchKernelGGL((attn_decode_combine_kernel<D, G>), dim3(Nkv, B), dim3(kThreads), 0, st, (const float*)ws_o,
@@ -327,12 +394,14 @@ static int launch(const void* q, const void* k_new, const void* v_new, void* k_c
   return TN_OK;
 }
 
-template <int D>
+template <int D, typename KV>
 static int dispatch_g(int G, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
-                      const int* cache_len, const int* src, void* o, void* ws, int B, int Nkv, int S_max, float scale,
-                      hipStream_t st) {
-#define TN_DECODE_G(g) \
-  case g: return launch<D, g>(q, k_new, v_new, k_cache, v_cache, cache_len, src, o, ws, B, Nkv, S_max, scale, st);
+                      float* k_scale, float* v_scale, const int* cache_len, const int* src, void* o, void* ws, int B,
+                      int Nkv, int S_max, float scale, hipStream_t st) {
+#define TN_DECODE_G(g)                                                                                                  \
+  case g:                                                                                                               \
+    return launch<D, g, KV>(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src, o, ws, B, Nkv, S_max, \
+                            scale, st);
   switch (G) {
     TN_DECODE_G(1) TN_DECODE_G(2) TN_DECODE_G(3) TN_DECODE_G(4) TN_DECODE_G(5) TN_DECODE_G(6) TN_DECODE_G(7)
     TN_DECODE_G(8) TN_DECODE_G(9) TN_DECODE_G(10) TN_DECODE_G(11) TN_DECODE_G(12) TN_DECODE_G(13) TN_DECODE_G(14)
@@ -343,6 +412,7 @@ static int dispatch_g(int G, const void* q, const void* k_new, const void* v_new
 }
 
 static inline bool al16(const void* p) { return p != nullptr && ((uintptr_t)p & 15) == 0; }
+static inline bool al4(const void* p) { return p != nullptr && ((uintptr_t)p & 3) == 0; }
 
 }  // namespace decode
 }  // namespace tn
@@ -356,35 +426,54 @@ long long tn_attn_decode_workspace_bytes(int B, int Nh, int Nkv, int D, int S_ma
   return (long long)B * Nh * ns * (D + 1) * 4;
 }
 
-static int decode_entry(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
-                        const int* cache_len, const int* src, bool beam, void* o, void* workspace, int B, int Nh, int Nkv,
-                        int D, int S_max, float scale, void* stream) {
+// fp8: the caches hold codes and k_scale / v_scale their scales; otherwise the scales are not looked at
+static int decode_entry(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* k_scale,
+                        float* v_scale, bool fp8, const int* cache_len, const int* src, bool beam, void* o,
+                        void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream) {
   using namespace tn::decode;
   if (B <= 0 || Nh <= 0 || Nkv <= 0 || S_max <= 0 || (D != 64 && D != 128) || Nh % Nkv || Nh / Nkv > 16) return TN_EINVAL;
   if (!al16(q) || !al16(k_new) || !al16(v_new) || !al16(k_cache) || !al16(v_cache) || !al16(o) || cache_len == nullptr ||
       ((uintptr_t)cache_len & 3))
     return TN_EINVAL;
+  if (fp8 && (!al4(k_scale) || !al4(v_scale))) return TN_EINVAL;
   if (beam && (src == nullptr || ((uintptr_t)src & 3))) return TN_EINVAL;
   if (num_splits(B, Nkv, S_max) > 1 && !al16(workspace)) return TN_EINVAL;
   const int G = Nh / Nkv;
   hipStream_t st = (hipStream_t)stream;
-  return D == 64
-             ? dispatch_g<64>(G, q, k_new, v_new, k_cache, v_cache, cache_len, src, o, workspace, B, Nkv, S_max, scale, st)
-             : dispatch_g<128>(G, q, k_new, v_new, k_cache, v_cache, cache_len, src, o, workspace, B, Nkv, S_max, scale, st);
+#define TN_DECODE(d, kv) \
+  dispatch_g<d, kv>(G, q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src, o, workspace, B, Nkv, S_max, scale, st)
+  if (fp8) return D == 64 ? TN_DECODE(64, tn::kvq::fp8_t) : TN_DECODE(128, tn::kvq::fp8_t);
+  return D == 64 ? TN_DECODE(64, tn::bf16_t) : TN_DECODE(128, tn::bf16_t);
+#undef TN_DECODE
 }
 
 int tn_attn_decode(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_len,
                    void* o, void* workspace, int B, int Nh, int Nkv, int D, int S_max, float scale, void* stream) {
-  return decode_entry(q, k_new, v_new, k_cache, v_cache, cache_len, nullptr, false, o, workspace, B, Nh, Nkv, D, S_max,
-                      scale, stream);
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, nullptr, nullptr, false, cache_len, nullptr, false, o, workspace,
+                      B, Nh, Nkv, D, S_max, scale, stream);
 }
 
 // as tn_attn_decode on R = B_utt * K rows, reading the cached keys / values through src int32 [R, S_max]
 int tn_attn_decode_beam(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
                         const int* cache_len, const int* src, void* o, void* workspace, int R, int Nh, int Nkv, int D,
                         int S_max, float scale, void* stream) {
-  return decode_entry(q, k_new, v_new, k_cache, v_cache, cache_len, src, true, o, workspace, R, Nh, Nkv, D, S_max, scale,
-                      stream);
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, nullptr, nullptr, false, cache_len, src, true, o, workspace, R,
+                      Nh, Nkv, D, S_max, scale, stream);
+}
+
+// tn_attn_decode on an FP8 cache: k_cache / v_cache uint8 codes [B, S_max, Nkv, D], k_scale / v_scale fp32 [B, S_max, Nkv]
+int tn_attn_decode_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* k_scale,
+                       float* v_scale, const int* cache_len, void* o, void* workspace, int B, int Nh, int Nkv, int D,
+                       int S_max, float scale, void* stream) {
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, true, cache_len, nullptr, false, o, workspace,
+                      B, Nh, Nkv, D, S_max, scale, stream);
+}
+
+int tn_attn_decode_beam_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                            float* k_scale, float* v_scale, const int* cache_len, const int* src, void* o, void* workspace,
+                            int R, int Nh, int Nkv, int D, int S_max, float scale, void* stream) {
+  return decode_entry(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, true, cache_len, src, true, o, workspace, R, Nh,
+                      Nkv, D, S_max, scale, stream);
 }
 
 }  // extern "C"

@@ -29,7 +29,18 @@
 // heads.  Online softmax in fp32, log2 domain (scale * log2(e)), one rescale per stage, P rounded to bf16, row sums from the
 // unrounded P: the packed forward's arithmetic.  Only stages that hold a key beyond the tile's first position take the
 // mask (one compare per score); whole prefix stages run unmasked.  No atomics, no cross-workgroup reduction.
+//
+// FP8 (tn_attn_extend_fp8; KV = kvq::fp8_t): the cache AND the new rows arrive as e4m3 codes uint8 with one fp32
+// power-of-two scale per key (kv_fp8.h; the caller quantises k_new / v_new once with tn_kv_quantize), so the per-chunk
+// choice between cache, new rows and zero stays a choice between like sources.  A thread's chunk of a stage is 8 bytes of
+// codes and the key's scale instead of 16 bytes: half the global bytes are in flight in registers (12 instead of 16
+// registers per stage at D = 64, 24 instead of 32 at D = 128; the freed registers are left free).  The chunk is expanded
+// to bf16 — exactly — on its way into the SAME panel image; from the image on this is the bf16 kernel: lane layout,
+// head sharing, masks, one rescale per stage.
+#include <type_traits>
+
 #include "attn_common.h"
+#include "kv_fp8.h"
 
 namespace tn {
 namespace extend {
@@ -42,12 +53,22 @@ __device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int D, int HPW>
+struct NoScales {};                  // the bf16 kernel's scales: an empty argument, so its code is what it was
+struct Scales {                      // fp32, one per key: new rows [T, Nkv], caches [B, S_max, Nkv]
+  const float* __restrict__ k_new;
+  const float* __restrict__ v_new;
+  const float* __restrict__ k_cache;
+  const float* __restrict__ v_cache;
+};
+
+template <int D, int HPW, typename KV = bf16_t>
 __global__ void __launch_bounds__(kThreads) attn_extend_kernel(
-    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_new, const bf16_t* __restrict__ v_new,
-    const bf16_t* __restrict__ k_cache, const bf16_t* __restrict__ v_cache, const int* __restrict__ seq_start,
+    const bf16_t* __restrict__ q, const KV* __restrict__ k_new, const KV* __restrict__ v_new,
+    const KV* __restrict__ k_cache, const KV* __restrict__ v_cache, const int* __restrict__ seq_start,
     const int* __restrict__ prefix_len, const int* __restrict__ kv_row, bf16_t* __restrict__ o, int T, int R, int B,
-    int S_max, int Nh, int Nkv, float scale_log2) {
+    int S_max, int Nh, int Nkv, float scale_log2, std::conditional_t<std::is_same_v<KV, bf16_t>, NoScales, Scales> sc) {
+  constexpr bool FP8 = !std::is_same_v<KV, bf16_t>;
+  using Raw = std::conditional_t<FP8, uint2, u32x4_t>;     // a 8-element chunk of a key as it is loaded
   using PT = PTile<kStage, D>;
   constexpr int CPR = D / 8;                          // 16-byte chunks per key row
   constexpr int NLD = kStage * CPR / kThreads;        // chunks of K (and of V) per thread and stage
@@ -86,10 +107,17 @@ __global__ void __launch_bounds__(kThreads) attn_extend_kernel(
   const int L = P + i0 + rows;                        // keys of the tile's stream
   const int nst = (L + kStage - 1) / kStage;
   const size_t kv_ld = (size_t)Nkv * D;
-  const bf16_t* kc = k_cache + (size_t)cr * S_max * kv_ld + (size_t)kvh * D;
-  const bf16_t* vc = v_cache + (size_t)cr * S_max * kv_ld + (size_t)kvh * D;
-  const bf16_t* kn = k_new + (size_t)s0 * kv_ld + (size_t)kvh * D;
-  const bf16_t* vn = v_new + (size_t)s0 * kv_ld + (size_t)kvh * D;
+  const KV* kc = k_cache + (size_t)cr * S_max * kv_ld + (size_t)kvh * D;
+  const KV* vc = v_cache + (size_t)cr * S_max * kv_ld + (size_t)kvh * D;
+  const KV* kn = k_new + (size_t)s0 * kv_ld + (size_t)kvh * D;
+  const KV* vn = v_new + (size_t)s0 * kv_ld + (size_t)kvh * D;
+  [[maybe_unused]] const float *kcs = nullptr, *vcs = nullptr, *kns = nullptr, *vns = nullptr;     // scales of key 0
+  if constexpr (FP8) {
+    kcs = sc.k_cache + (size_t)cr * S_max * Nkv + kvh;
+    vcs = sc.v_cache + (size_t)cr * S_max * Nkv + kvh;
+    kns = sc.k_new + (size_t)s0 * Nkv + kvh;
+    vns = sc.v_new + (size_t)s0 * Nkv + kvh;
+  }
 
   // ---- Q fragments of the wave's heads: lane = position s4, slots (g4, e) = d 32 s + 8 g4 + e
   bool on[HPW];
@@ -124,21 +152,40 @@ __global__ void __launch_bounds__(kThreads) attn_extend_kernel(
   for (int p = 0; p < 2; ++p)
     va[p] = (4 * g4 + (s4 >> 2)) * 32 + 8 * ((2 * p + ((s4 & 3) >> 1)) ^ g4) + 4 * (s4 & 1);
 
-  u32x4_t kr[NLD], vr[NLD];
+  Raw kr[NLD], vr[NLD];
+  [[maybe_unused]] float ksc[NLD], vsc[NLD];          // FP8: the scale of each chunk's key (0 for a zero row)
   auto fetch = [&](int st) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + kThreads * i, row = idx / CPR, c = idx % CPR;
       const int j = st * kStage + row;
-      kr[i] = u32x4_t{0u, 0u, 0u, 0u};
-      vr[i] = u32x4_t{0u, 0u, 0u, 0u};
+      kr[i] = Raw{};
+      vr[i] = Raw{};
+      if constexpr (FP8) ksc[i] = vsc[i] = 0.f;
       if (j < P) {
-        kr[i] = *reinterpret_cast<const u32x4_t*>(kc + (size_t)j * kv_ld + c * 8);
-        vr[i] = *reinterpret_cast<const u32x4_t*>(vc + (size_t)j * kv_ld + c * 8);
+        kr[i] = *reinterpret_cast<const Raw*>(kc + (size_t)j * kv_ld + c * 8);
+        vr[i] = *reinterpret_cast<const Raw*>(vc + (size_t)j * kv_ld + c * 8);
+        if constexpr (FP8) {
+          ksc[i] = kcs[(size_t)j * Nkv];
+          vsc[i] = vcs[(size_t)j * Nkv];
+        }
       } else if (j < L) {
-        kr[i] = *reinterpret_cast<const u32x4_t*>(kn + (size_t)(j - P) * kv_ld + c * 8);
-        vr[i] = *reinterpret_cast<const u32x4_t*>(vn + (size_t)(j - P) * kv_ld + c * 8);
+        kr[i] = *reinterpret_cast<const Raw*>(kn + (size_t)(j - P) * kv_ld + c * 8);
+        vr[i] = *reinterpret_cast<const Raw*>(vn + (size_t)(j - P) * kv_ld + c * 8);
+        if constexpr (FP8) {
+          ksc[i] = kns[(size_t)(j - P) * Nkv];
+          vsc[i] = vns[(size_t)(j - P) * Nkv];
+        }
       }
+    }
+  };
+  // a chunk as the 8 bf16 of the panel image
+  auto image = [](const Raw& r, [[maybe_unused]] float s) -> u32x4_t {
+    if constexpr (FP8) {
+      const uint4 t = kvq::decode8_bf16(r, s);
+      return u32x4_t{t.x, t.y, t.z, t.w};
+    } else {
+      return r;
     }
   };
 
@@ -148,8 +195,13 @@ __global__ void __launch_bounds__(kThreads) attn_extend_kernel(
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + kThreads * i, off = PT::chunk_off(idx / CPR, idx % CPR);
-      *reinterpret_cast<u32x4_t*>(ks + off) = kr[i];
-      *reinterpret_cast<u32x4_t*>(vs + off) = vr[i];
+      if constexpr (FP8) {
+        *reinterpret_cast<u32x4_t*>(ks + off) = image(kr[i], ksc[i]);
+        *reinterpret_cast<u32x4_t*>(vs + off) = image(vr[i], vsc[i]);
+      } else {
+        *reinterpret_cast<u32x4_t*>(ks + off) = kr[i];
+        *reinterpret_cast<u32x4_t*>(vs + off) = vr[i];
+      }
     }
     __syncthreads();
     if (st + 1 < nst) fetch(st + 1);                  // in flight while this stage is computed
@@ -246,28 +298,27 @@ __global__ void __launch_bounds__(kThreads) attn_extend_kernel(
   }
 }
 
-template <int D, int HPW>
+template <int D, int HPW, typename KV>
 static int launch(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
-                  const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T, int R, int B, int S_max,
-                  int Nh, int Nkv, float scale, hipStream_t st) {
+                  const float* const* scales, const int* seq_start, const int* prefix_len, const int* kv_row, void* o,
+                  int T, int R, int B, int S_max, int Nh, int Nkv, float scale, hipStream_t st) {
   // sum_r ceil(n_r / 16) <= (T + 15 R) / 16: the host does not read seq_start
   const long long tiles = ((long long)T + 15ll * R) / kRows;
-  hipLaunchKernelGGL((attn_extend_kernel<D, HPW>), dim3((unsigned)tiles, Nkv), dim3(kThreads), 0, st, (const bf16_t*)q,
-                     (const bf16_t*)k_new, (const bf16_t*)v_new, (const bf16_t*)k_cache, (const bf16_t*)v_cache, seq_start,
-                     prefix_len, kv_row, (bf16_t*)o, T, R, B, S_max, Nh, Nkv, scale * kLog2e);
+  std::conditional_t<std::is_same_v<KV, bf16_t>, NoScales, Scales> sc{};
+  if constexpr (!std::is_same_v<KV, bf16_t>) sc = Scales{scales[0], scales[1], scales[2], scales[3]};
+  hipLaunchKernelGGL((attn_extend_kernel<D, HPW, KV>), dim3((unsigned)tiles, Nkv), dim3(kThreads), 0, st, (const bf16_t*)q,
+                     (const KV*)k_new, (const KV*)v_new, (const KV*)k_cache, (const KV*)v_cache, seq_start, prefix_len,
+                     kv_row, (bf16_t*)o, T, R, B, S_max, Nh, Nkv, scale * kLog2e, sc);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
 static inline bool al(const void* p, uintptr_t a) { return p != nullptr && ((uintptr_t)p & (a - 1)) == 0; }
 
-}  // namespace extend
-}  // namespace tn
-
-extern "C" int tn_attn_extend(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
-                              const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T, int R, int B,
-                              int S_max, int Nh, int Nkv, int D, float scale, void* stream) {
-  using namespace tn::extend;
+// scales: null for the bf16 kernel, else {k_new, v_new, k_cache, v_cache} scales and k / v hold codes
+static int entry(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
+                 const float* const* scales, const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T,
+                 int R, int B, int S_max, int Nh, int Nkv, int D, float scale, void* stream) {
   if (T < 0 || R < 0 || B <= 0 || S_max <= 0 || Nh <= 0 || Nkv <= 0 || (D != 64 && D != 128) || Nh % Nkv || Nh / Nkv > 16)
     return TN_EINVAL;
   if (kv_row == nullptr && R > B) return TN_EINVAL;
@@ -277,14 +328,41 @@ extern "C" int tn_attn_extend(const void* q, const void* k_new, const void* v_ne
   if (!al(q, 16) || !al(k_new, 16) || !al(v_new, 16) || !al(k_cache, 16) || !al(v_cache, 16) || !al(o, 16) ||
       !al(seq_start, 4) || !al(prefix_len, 4) || (kv_row != nullptr && !al(kv_row, 4)))
     return TN_EINVAL;
+  if (scales != nullptr && (!al(scales[0], 4) || !al(scales[1], 4) || !al(scales[2], 4) || !al(scales[3], 4)))
+    return TN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int hpw = (Nh / Nkv + 3) / 4;
 #define TN_EXTEND(d, h)                                                                                                   \
   if (D == d && hpw == h)                                                                                                 \
-    return launch<d, h>(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, kv_row, o, T, R, B, S_max, Nh, Nkv,    \
-                        scale, st);
+    return scales != nullptr                                                                                              \
+               ? launch<d, h, kvq::fp8_t>(q, k_new, v_new, k_cache, v_cache, scales, seq_start, prefix_len, kv_row, o, T, \
+                                          R, B, S_max, Nh, Nkv, scale, st)                                                \
+               : launch<d, h, bf16_t>(q, k_new, v_new, k_cache, v_cache, scales, seq_start, prefix_len, kv_row, o, T, R,  \
+                                      B, S_max, Nh, Nkv, scale, st);
   TN_EXTEND(64, 1) TN_EXTEND(64, 2) TN_EXTEND(64, 3) TN_EXTEND(64, 4)
   TN_EXTEND(128, 1) TN_EXTEND(128, 2) TN_EXTEND(128, 3) TN_EXTEND(128, 4)
 #undef TN_EXTEND
   return TN_EINVAL;
+}
+
+}  // namespace extend
+}  // namespace tn
+
+extern "C" int tn_attn_extend(const void* q, const void* k_new, const void* v_new, const void* k_cache, const void* v_cache,
+                              const int* seq_start, const int* prefix_len, const int* kv_row, void* o, int T, int R, int B,
+                              int S_max, int Nh, int Nkv, int D, float scale, void* stream) {
+  return tn::extend::entry(q, k_new, v_new, k_cache, v_cache, nullptr, seq_start, prefix_len, kv_row, o, T, R, B, S_max, Nh,
+                           Nkv, D, scale, stream);
+}
+
+// tn_attn_extend on FP8 keys / values: k_new / v_new uint8 codes [T, Nkv, D] with k_new_scale / v_new_scale fp32 [T, Nkv],
+// k_cache / v_cache uint8 codes [B, S_max, Nkv, D] with k_scale / v_scale fp32 [B, S_max, Nkv]
+extern "C" int tn_attn_extend_fp8(const void* q, const void* k_new, const void* v_new, const float* k_new_scale,
+                                  const float* v_new_scale, const void* k_cache, const void* v_cache, const float* k_scale,
+                                  const float* v_scale, const int* seq_start, const int* prefix_len, const int* kv_row,
+                                  void* o, int T, int R, int B, int S_max, int Nh, int Nkv, int D, float scale,
+                                  void* stream) {
+  const float* scales[4] = {k_new_scale, v_new_scale, k_scale, v_scale};
+  return tn::extend::entry(q, k_new, v_new, k_cache, v_cache, scales, seq_start, prefix_len, kv_row, o, T, R, B, S_max, Nh,
+                           Nkv, D, scale, stream);
 }

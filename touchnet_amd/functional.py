@@ -2035,6 +2035,14 @@ def attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, scale:
     copy); kv_row None: sequence r reads cache row r.  Several sequences may share a kv_row.  seq_start / prefix_len /
     kv_row: int sequences or int tensors; a seq_start that lives on the host is checked here (ascending from 0 to T), one
     that already lives on the device is trusted (the kernel never leaves q / o whatever it holds).  Returns o [T, Nh, D]."""
+    seq_start, prefix_len, kv_row = _extend_tables(q, k_cache, seq_start, prefix_len, kv_row)
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return L.attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, kv_row, float(scale))
+
+
+def _extend_tables(q, k_cache, seq_start, prefix_len, kv_row):
+    """The geometry and table checks of `attn_extend` / `attn_extend_fp8` -> int32 device (seq_start, prefix_len, kv_row)."""
     if q.dim() != 3 or k_cache.dim() != 4:
         raise ValueError("attn_extend: q must be [T, Nh, D] and the caches [B, S_max, Nkv, D]")
     T, Nh, D = q.shape
@@ -2065,10 +2073,51 @@ def attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, scale:
         if int(kv_row.numel()) != R:
             raise ValueError(f"attn_extend: kv_row must hold R = {R} entries")
         kv_row = kv_row.to(device=dev, dtype=torch.int32)
+    return seq_start.to(device=dev, dtype=torch.int32), prefix_len.to(device=dev, dtype=torch.int32), kv_row
+
+
+# ------------------------------------------------------------------------------------ FP8 KV cache (csrc/kv_fp8.h)
+KV_CODE_DTYPE = L.KV_CODE_DTYPE        # torch.uint8: the storage dtype of the codes
+
+
+def kv_quantize(x):
+    """bf16 keys or values [T, Nkv, D] -> (codes uint8 [T, Nkv, D], scales fp32 [T, Nkv]): OCP e4m3 codes (the bits of
+    torch.float8_e4m3fn) and one power-of-two scale per key, 2^e with e the smallest integer such that amax <= 448 * 2^e
+    (at least -100); a key with a NaN or an infinity gets scale NaN (tn_kv_quantize)."""
+    return L.kv_quantize(x)
+
+
+def kv_dequantize(codes, scales, dtype=torch.bfloat16):
+    """codes uint8 [.., Nkv, D] and scales fp32 [.., Nkv] -> code * scale as `dtype` — exact in bf16 and wider.  Plain
+    torch, on any device: for tests and debugging, not for the hot path (the attention kernels expand codes themselves)."""
+    return (codes.view(torch.float8_e4m3fn).to(torch.float32) * scales[..., None]).to(dtype)
+
+
+def attn_decode_fp8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, scale: Optional[float] = None):
+    """`attn_decode` on an FP8 KV cache: caches uint8 codes [B, S_max, Nkv, D] with k_scale / v_scale fp32 [B, S_max, Nkv].
+    The bf16 k_new / v_new are quantised (`kv_quantize`'s rule) into slot cache_len[b], and the row attends to what the
+    cache then holds: the result is `attn_decode`'s on the dequantised cache and the round-tripped new key / value."""
     if scale is None:
-        scale = D ** -0.5
-    return L.attn_extend(q, k_new, v_new, k_cache, v_cache, seq_start.to(device=dev, dtype=torch.int32),
-                         prefix_len.to(device=dev, dtype=torch.int32), kv_row, float(scale))
+        scale = q.shape[-1] ** -0.5
+    return L.attn_decode_fp8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, float(scale))
+
+
+def attn_decode_beam_fp8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src, scale: Optional[float] = None):
+    """`attn_decode_beam` on an FP8 KV cache: codes and scales are read through the same ancestry table."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return L.attn_decode_beam_fp8(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src, float(scale))
+
+
+def attn_extend_fp8(q, k_new, v_new, k_new_scale, v_new_scale, k_cache, v_cache, k_scale, v_scale, seq_start, prefix_len,
+                    scale: Optional[float] = None, kv_row=None):
+    """`attn_extend` with the new rows (`kv_quantize`'s codes and scales) and the caches alike in the FP8 format: the
+    result is `attn_extend`'s on the dequantised tensors."""
+    seq_start, prefix_len, kv_row = _extend_tables(q, k_cache, seq_start, prefix_len, kv_row)
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    return L.attn_extend_fp8(q, k_new, v_new, k_new_scale, v_new_scale, k_cache, v_cache, k_scale, v_scale, seq_start,
+                             prefix_len, kv_row, float(scale))
 
 
 def greedy_step(logits, hist, hist_len, cache_len, finished, n_unfinished, penalty: float = 1.0, ngram: int = 0,

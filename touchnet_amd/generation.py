@@ -194,6 +194,25 @@ def _check_alternatives(what: str, k) -> None:
         raise ValueError(f"{what}: top_alternatives = {k!r} must be an integer in [0, {MAX_ALTERNATIVES}]")
 
 
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
+
+
+def check_kv_dtype(what: str, value) -> str:
+    if value not in KV_CACHE_DTYPES:
+        raise ValueError(f"{what}: kv_cache_dtype = {value!r} must be one of {KV_CACHE_DTYPES}")
+    return value
+
+
+def _kv_tensors(kv_dtype: str, num_layers: int, rows: int, S_max: int, Nkv: int, D: int, device, dtype):
+    """-> (k, v, k_scale, v_scale) per layer: bf16 [rows, S_max, Nkv, D] without scales, or e4m3 codes (stored as uint8)
+    with fp32 scales [rows, S_max, Nkv]"""
+    fp8 = check_kv_dtype("KV cache", kv_dtype) == "fp8_e4m3"
+    kv = lambda: [torch.empty(rows, S_max, Nkv, D, dtype=F.KV_CODE_DTYPE if fp8 else dtype, device=device)
+                  for _ in range(num_layers)]
+    sc = lambda: [torch.empty(rows, S_max, Nkv, dtype=torch.float32, device=device) for _ in range(num_layers)] if fp8 else None
+    return kv(), kv(), sc(), sc()
+
+
 @dataclass
 class GenerationConfig:
     """The knobs of the reference's generate() call (top_k / top_p / temperature are inert there: do_sample=False).
@@ -221,9 +240,11 @@ class GenerationConfig:
     top_alternatives: int = 0                # 0 .. 8 most likely tokens per position with their log-probabilities (implies output_scores)
     nbest: int = 1                           # beam search: the first `nbest` finished hypotheses (1 .. num_beams) — not HF's
                                              # num_return_sequences key, which from_hf goes on refusing
+    kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3": e4m3 codes + one power-of-two scale per key (KVCache)
 
     def __post_init__(self):
         self.check_scores()
+        check_kv_dtype("generation config", self.kv_cache_dtype)
 
     def check_scores(self) -> None:
         """What the three score knobs accept."""
@@ -278,7 +299,8 @@ class GenerationConfig:
                   min_new_tokens=int(num("min_new_tokens", 0) or 0),
                   # this decoder's own knobs: overrides only (the file's `output_scores` means HF's processed scores)
                   output_scores=bool(overrides.get("output_scores", False)),
-                  top_alternatives=overrides.get("top_alternatives", 0), nbest=overrides.get("nbest", 1))
+                  top_alternatives=overrides.get("top_alternatives", 0), nbest=overrides.get("nbest", 1),
+                  kv_cache_dtype=overrides.get("kv_cache_dtype", "bf16"))
         if cfg.min_new_tokens < 0:
             raise ValueError(f"generation config: min_new_tokens = {cfg.min_new_tokens} must be >= 0")
         if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
@@ -349,6 +371,7 @@ class KimiGenerationConfig:
     seed: int = 0                            # Philox key of the draws (with the row key and the step)
     output_scores: bool = False              # per-token log-probability and entropy of the raw lm_head logits (`TokenScores`)
     top_alternatives: int = 0                # 0 .. 8 most likely tokens per position (implies output_scores)
+    kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3" (GenerationConfig's key; the loop is decode_logits')
 
     def __post_init__(self):
         self.check()
@@ -360,6 +383,7 @@ class KimiGenerationConfig:
     def check(self) -> None:
         """Refuses what tn_kimi_text_step refuses."""
         _check_alternatives("Kimi generation config", self.top_alternatives)
+        check_kv_dtype("Kimi generation config", self.kv_cache_dtype)
         if not self.text_repetition_penalty > 0.0:
             raise ValueError(f"Kimi generation config: text_repetition_penalty {self.text_repetition_penalty} must be > 0")
         if not 1 <= int(self.text_repetition_window_size) <= KIMI_MAX_WINDOW:
@@ -395,7 +419,8 @@ class Prompts:
 class KVCache:
     """L layers of keys / values [B, S_max, Nkv, D] bf16, S_max = longest prompt + max_new_tokens, and the per-row device
     state of the greedy loop (all int32): cache_len [B], hist [B, S_max] (prompt ids then generated ids), hist_len [B],
-    finished [B], n_unfinished [1]."""
+    finished [B], n_unfinished [1].  kv_dtype "fp8_e4m3": k / v hold e4m3 codes (uint8) and k_scale / v_scale, fp32
+    [B, S_max, Nkv] per layer, one power-of-two scale per key (csrc/kv_fp8.h): D + 4 bytes per key instead of 2 D."""
     k: List[torch.Tensor]
     v: List[torch.Tensor]
     cache_len: torch.Tensor
@@ -403,13 +428,20 @@ class KVCache:
     hist_len: torch.Tensor
     finished: torch.Tensor
     n_unfinished: torch.Tensor
+    k_scale: Optional[List[torch.Tensor]] = None
+    v_scale: Optional[List[torch.Tensor]] = None
 
     @classmethod
-    def allocate(cls, num_layers: int, B: int, S_max: int, Nkv: int, D: int, device, dtype=torch.bfloat16) -> "KVCache":
+    def allocate(cls, num_layers: int, B: int, S_max: int, Nkv: int, D: int, device, dtype=torch.bfloat16,
+                 kv_dtype: str = "bf16") -> "KVCache":
         z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=device)
-        return cls(k=[torch.empty(B, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
-                   v=[torch.empty(B, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
+        k, v, ks, vs = _kv_tensors(kv_dtype, num_layers, B, S_max, Nkv, D, device, dtype)
+        return cls(k=k, v=v, k_scale=ks, v_scale=vs,
                    cache_len=z(B), hist=z(B, S_max), hist_len=z(B), finished=z(B), n_unfinished=z(1))
+
+    @property
+    def kv_dtype(self) -> str:
+        return "bf16" if self.k_scale is None else "fp8_e4m3"
 
     @property
     def capacity(self) -> int:
@@ -427,6 +459,9 @@ class KVCache:
         self.k = [bigger(t) for t in self.k]
         self.v = [bigger(t) for t in self.v]
         self.hist = bigger(self.hist)
+        if self.k_scale is not None:
+            self.k_scale = [bigger(t) for t in self.k_scale]
+            self.v_scale = [bigger(t) for t in self.v_scale]
 
 
 @dataclass
@@ -519,15 +554,17 @@ class BeamState:
     n_unfinished: torch.Tensor
     out_ids: torch.Tensor
     out_parent: torch.Tensor
+    k_scale: Optional[List[torch.Tensor]] = None         # kv_dtype "fp8_e4m3" (as in KVCache): fp32 [R, S_max, Nkv] per layer,
+    v_scale: Optional[List[torch.Tensor]] = None         # read through the same table as the codes
 
     @classmethod
     def allocate(cls, num_layers: int, B: int, K: int, S_max: int, Nkv: int, D: int, device,
-                 dtype=torch.bfloat16) -> "BeamState":
+                 dtype=torch.bfloat16, kv_dtype: str = "bf16") -> "BeamState":
         R = B * K
         z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=device)
         first = torch.arange(R, dtype=torch.int32, device=device) // K * K          # the row the prompt is stored in
-        return cls(num_beams=K, k=[torch.empty(R, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
-                   v=[torch.empty(R, S_max, Nkv, D, dtype=dtype, device=device) for _ in range(num_layers)],
+        k, v, ks, vs = _kv_tensors(kv_dtype, num_layers, R, S_max, Nkv, D, device, dtype)
+        return cls(num_beams=K, k=k, v=v, k_scale=ks, v_scale=vs,
                    cache_len=z(R), hist=z(R, S_max), hist_len=z(R), src=first[:, None].repeat(1, S_max),
                    run_score=torch.zeros(R, dtype=torch.float32, device=device), fin_ids=z(R, S_max), fin_len=z(R),
                    fin_score=torch.full((R,), -1.0e9, dtype=torch.float32, device=device), fin_flag=z(R), gen=z(B),
@@ -537,6 +574,10 @@ class BeamState:
     @property
     def finished(self) -> torch.Tensor:
         return self.done
+
+    @property
+    def kv_dtype(self) -> str:
+        return "bf16" if self.k_scale is None else "fp8_e4m3"
 
     @property
     def capacity(self) -> int:
@@ -554,6 +595,9 @@ class BeamState:
         self.k = [bigger(t) for t in self.k]
         self.v = [bigger(t) for t in self.v]
         self.hist, self.fin_ids, self.src = bigger(self.hist), bigger(self.fin_ids), bigger(self.src)
+        if self.k_scale is not None:
+            self.k_scale = [bigger(t) for t in self.k_scale]
+            self.v_scale = [bigger(t) for t in self.v_scale]
 
     def best(self, prompt_lens: Sequence[int], pad: int):
         """-> (ids int64 [B, N] of every utterance's best finished hypothesis behind its prompt, `pad` after its end;
@@ -679,10 +723,14 @@ def _prefill(lm, proj_w, prompts: Prompts, cache, device, embed: Optional[EmbedF
         emb = _embed_touch_audio(lm, proj_w, prompts, ids, lens, Tp, device)
     kv = []
     h = lm.model(inputs_embeds=emb[None], position_ids=pos[None], attention_mask=doc[None], keep_rows=last, kv_out=kv)
-    for (k, v), kc, vc in zip(kv, cache.k, cache.v):
+    for i, ((k, v), kc, vc) in enumerate(zip(kv, cache.k, cache.v)):
         Nkv, D = k.shape[2], k.shape[3]
-        kc.view(-1, Nkv, D).index_copy_(0, dst, k[0].index_select(0, src))
-        vc.view(-1, Nkv, D).index_copy_(0, dst, v[0].index_select(0, src))
+        k, v = k[0].index_select(0, src), v[0].index_select(0, src)
+        if cache.k_scale is not None:
+            _append_fp8(cache, i, dst, F.kv_quantize(k), F.kv_quantize(v))
+            continue
+        kc.view(-1, Nkv, D).index_copy_(0, dst, k)
+        vc.view(-1, Nkv, D).index_copy_(0, dst, v)
     lens_d = torch.tensor(lens, dtype=torch.int32, device=device)
     cache.hist.view(-1).index_copy_(0, torch.cat([torch.arange(n, device=device) + b * row_stride * cache.hist.shape[1]
                                                   for b, n in enumerate(lens)]), ids.index_select(0, src).to(torch.int32))
@@ -693,7 +741,14 @@ def _prefill(lm, proj_w, prompts: Prompts, cache, device, embed: Optional[EmbedF
     return lm.lm_head(h[0])                                                                # [B, V]
 
 
-def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len, table=None):
+def _append_fp8(cache, layer: int, dst, kq, vq):
+    """codes and scales of new keys / values (`kv_quantize`'s pairs) -> the flat cache slots dst of layer `layer`"""
+    for (codes, scales), c, s in ((kq, cache.k[layer], cache.k_scale[layer]), (vq, cache.v[layer], cache.v_scale[layer])):
+        c.view(-1, *codes.shape[1:]).index_copy_(0, dst, codes)
+        s.view(-1, scales.shape[1]).index_copy_(0, dst, scales)
+
+
+def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len, table=None, scales=None):
     attn = layer.self_attn
     B = delta.shape[0]
     if residual is None:
@@ -704,7 +759,11 @@ def _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache_len, table=Non
     q, k, v = F.linear_group(x, [(attn.q_proj.weight, attn.q_proj.bias), (attn.k_proj.weight, attn.k_proj.bias),
                                  (attn.v_proj.weight, attn.v_proj.bias)], rope=(cos, sin, attn.head_dim, (0, 1)))
     D = attn.head_dim
-    if table is None:
+    if scales is not None:                   # an FP8 cache: (k_scale, v_scale) of the layer
+        q, k, v = q.view(B, attn.num_heads, D), k.view(B, attn.num_kv_heads, D), v.view(B, attn.num_kv_heads, D)
+        o = F.attn_decode_fp8(q, k, v, kc, vc, *scales, cache_len, attn.scaling) if table is None else \
+            F.attn_decode_beam_fp8(q, k, v, kc, vc, *scales, cache_len, table, attn.scaling)
+    elif table is None:
         o = F.attn_decode(q.view(B, attn.num_heads, D), k.view(B, attn.num_kv_heads, D), v.view(B, attn.num_kv_heads, D),
                           kc, vc, cache_len, attn.scaling)
     else:
@@ -729,8 +788,9 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
         x = inputs_embeds
     cos, sin = lm.model.rotary_emb(cache.cache_len.to(torch.int64), x.dtype)
     delta, residual = x, None
-    for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):
-        delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table)
+    for i, (layer, kc, vc) in enumerate(zip(lm.model.layers, cache.k, cache.v)):
+        scales = None if cache.k_scale is None else (cache.k_scale[i], cache.v_scale[i])
+        delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table, scales)
     h, _ = lm.model.norm(delta, residual)
     head = lm.lm_head
     if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the small-M routing
@@ -738,9 +798,11 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
     return head(h)
 
 
-def _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, prefix_len, kv_row):
+def _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, prefix_len, kv_row, scales=None):
     """`_decode_layer` for T packed new rows of R sequences: the same norm, q / k / v with RoPE, o_proj and MLP calls, with
-    tn_attn_extend in the middle -> (delta, residual, k [T, Nkv, D], v [T, Nkv, D]); the caches are only read."""
+    tn_attn_extend in the middle -> (delta, residual, k [T, Nkv, D], v [T, Nkv, D]); the caches are only read.  `scales`
+    (an FP8 cache's (k_scale, v_scale) of the layer): k / v are quantised once, tn_attn_extend_fp8 reads them as it reads
+    the cache, and they come back as `kv_quantize`'s (codes, scales) pairs."""
     attn = layer.self_attn
     T, D = delta.shape[0], attn.head_dim
     if residual is None:
@@ -751,7 +813,12 @@ def _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, prefix_le
     q, k, v = F.linear_group(x, [(attn.q_proj.weight, attn.q_proj.bias), (attn.k_proj.weight, attn.k_proj.bias),
                                  (attn.v_proj.weight, attn.v_proj.bias)], rope=(cos, sin, D, (0, 1)))
     k, v = k.view(T, attn.num_kv_heads, D), v.view(T, attn.num_kv_heads, D)
-    o = F.attn_extend(q.view(T, attn.num_heads, D), k, v, kc, vc, seq_start, prefix_len, attn.scaling, kv_row)
+    if scales is not None:
+        k, v = F.kv_quantize(k), F.kv_quantize(v)
+        o = F.attn_extend_fp8(q.view(T, attn.num_heads, D), k[0], v[0], k[1], v[1], kc, vc, *scales, seq_start, prefix_len,
+                              attn.scaling, kv_row)
+    else:
+        o = F.attn_extend(q.view(T, attn.num_heads, D), k, v, kc, vc, seq_start, prefix_len, attn.scaling, kv_row)
     a = F.linear_group(o.view(T, attn.num_heads * D), [(attn.o_proj.weight, None)])[0]
     x, residual = layer.post_attention_layernorm(a, residual)
     return layer.mlp(x), residual, k, v
@@ -809,9 +876,14 @@ def extend(model, cache, rows, new_ids, embed: Optional[EmbedFn] = None, kv_row=
         S = cache.capacity
         dst = torch.cat([torch.arange(n) + (r * S + p) for r, p, n in zip(rows_l, pre, lens)]).to(device)
     delta, residual = x, None
-    for layer, kc, vc in zip(lm.model.layers, cache.k, cache.v):
-        delta, residual, k, v = _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, pre_d, kv_d)
-        if append:                                  # behind the layer's attention: nothing reads a slot that is written
+    for i, (layer, kc, vc) in enumerate(zip(lm.model.layers, cache.k, cache.v)):
+        scales = None if cache.k_scale is None else (cache.k_scale[i], cache.v_scale[i])
+        delta, residual, k, v = _extend_layer(layer, delta, residual, cos, sin, kc, vc, seq_start, pre_d, kv_d, scales)
+        if not append:
+            continue                                # behind the layer's attention: nothing reads a slot that is written
+        if scales is not None:
+            _append_fp8(cache, i, dst, k, v)
+        else:
             kc.view(-1, *k.shape[1:]).index_copy_(0, dst, k)
             vc.view(-1, *v.shape[1:]).index_copy_(0, dst, v)
     h, _ = lm.model.norm(delta.index_select(0, keep), residual.index_select(0, keep))
@@ -893,6 +965,9 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     if past is not None:
         if not isinstance(past, KVCache) or past.cache_len.shape[0] != B:
             raise ValueError(f"generate: past must be a KVCache of {B} rows, one per prompt")
+        if past.kv_dtype != cfg.kv_cache_dtype:
+            raise ValueError(f"generate: past holds a {past.kv_dtype} KV cache but cfg.kv_cache_dtype = "
+                             f"{cfg.kv_cache_dtype!r} (continue a cache with the dtype it was built with)")
         lens = [p + n for p, n in zip(past.cache_len.tolist(), lens)]      # a row's positions once its ids are placed
     n_new = cfg.new_tokens(max(lens))
     if n_new <= 0:
@@ -917,7 +992,7 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     chunk = max(1, int(cfg.cache_chunk))
     if past is None:
         cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
-                                 device)
+                                 device, kv_dtype=cfg.kv_cache_dtype)
     else:
         cache = past
         cache.grow(max(lens) + min(n_new, chunk))
@@ -980,7 +1055,7 @@ def _beam_search(model, lm, proj_w, prompts: Prompts, cfg: GenerationConfig, eos
     K, c = int(cfg.num_beams), lm.config
     chunk = max(1, int(cfg.cache_chunk))
     st = BeamState.allocate(len(lm.model.layers), len(lens), K, max(lens) + min(n_new, chunk), c.num_key_value_heads,
-                            c.head_dim, device)
+                            c.head_dim, device, kv_dtype=cfg.kv_cache_dtype)
     S_full = max(lens) + n_new
     kw = dict(penalty=float(cfg.repetition_penalty), ngram=int(cfg.no_repeat_ngram_size), eos=eos, n_new=n_new,
               length_penalty=float(cfg.length_penalty), early_stopping=cfg.early_stopping)
@@ -1181,6 +1256,14 @@ def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[
 
 
 # ------------------------------------------------------------------------------------ command-line side of the scores
+def add_kv_cache_argument(ap) -> None:
+    """--kv_cache_dtype of the inference command lines."""
+    ap.add_argument("--kv_cache_dtype", default="bf16", choices=list(KV_CACHE_DTYPES),
+                    help="fp8_e4m3: keys / values are cached as e4m3 codes with one power-of-two scale per key, D + 4 bytes "
+                         "per key instead of 2 D (about half the cache memory and cache traffic); its effect on transcripts "
+                         "has not been measured on a trained checkpoint")
+
+
 def add_score_arguments(ap, nbest: bool = True) -> None:
     """--output_scores / --top_alternatives (and --nbest) of the inference command lines."""
     ap.add_argument("--output_scores", action="store_true",

@@ -987,6 +987,129 @@ def _(q, k_new, v_new, k_cache, v_cache, seq_start, prefix_len, kv_row, scale):
     return torch.empty_like(q, memory_format=torch.contiguous_format)
 
 
+KV_CODE_DTYPE = torch.uint8        # the storage dtype of FP8 KV-cache codes (the bits of torch.float8_e4m3fn)
+
+
+@custom_op(f"{NS}::kv_quantize", mutates_args=(), device_types="cuda")
+def kv_quantize(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """bf16 keys or values [T, Nkv, D] -> (e4m3 codes uint8 [T, Nkv, D], fp32 power-of-two scales [T, Nkv]) in the FP8
+    KV-cache format (tn_kv_quantize, csrc/kv_fp8.h)."""
+    _no_grad_inputs("kv_quantize", x)
+    if x.dim() != 3 or x.dtype != torch.bfloat16 or x.shape[2] not in (64, 128):
+        raise _C.KernelError("kv_quantize: bf16 x [T, Nkv, D] with D 64 or 128")
+    x = _c(x)
+    T, Nkv, D = x.shape
+    codes = torch.empty(T, Nkv, D, dtype=KV_CODE_DTYPE, device=x.device)
+    scales = torch.empty(T, Nkv, dtype=torch.float32, device=x.device)
+    _C.check(_lib().tn_kv_quantize(_p(x), _p(codes), _p(scales), T, Nkv, D, _cur()), "tn_kv_quantize")
+    return codes, scales
+
+
+@kv_quantize.register_fake
+def _(x):
+    return (torch.empty(x.shape, dtype=KV_CODE_DTYPE, device=x.device),
+            torch.empty(x.shape[:2], dtype=torch.float32, device=x.device))
+
+
+def _fp8_decode_check(what, q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src=None):
+    B, Nh, D = q.shape
+    S_max, Nkv = k_cache.shape[1], k_cache.shape[2]
+    if (any(t.dtype != torch.bfloat16 for t in (q, k_new, v_new)) or any(t.dtype != KV_CODE_DTYPE for t in (k_cache, v_cache))
+            or any(t.dtype != torch.float32 for t in (k_scale, v_scale)) or cache_len.dtype != torch.int32
+            or tuple(k_new.shape) != (B, Nkv, D) or tuple(v_new.shape) != (B, Nkv, D)
+            or tuple(k_cache.shape) != (B, S_max, Nkv, D) or tuple(v_cache.shape) != (B, S_max, Nkv, D)
+            or tuple(k_scale.shape) != (B, S_max, Nkv) or tuple(v_scale.shape) != (B, S_max, Nkv)
+            or tuple(cache_len.shape) != (B,) or not all(t.is_contiguous() for t in (k_cache, v_cache, k_scale, v_scale))
+            or (src is not None and (src.dtype != torch.int32 or tuple(src.shape) != (B, S_max) or not src.is_contiguous()))):
+        raise _C.KernelError(f"{what}: bf16 q [B, Nh, D], k_new / v_new [B, Nkv, D], contiguous uint8 code caches "
+                             "[B, S_max, Nkv, D] with fp32 scales [B, S_max, Nkv], int32 cache_len [B]"
+                             + ("" if src is None else ", contiguous int32 src [B, S_max]"))
+    return B, Nh, D, S_max, Nkv
+
+
+@custom_op(f"{NS}::attn_decode_fp8", mutates_args=("k_cache", "v_cache", "k_scale", "v_scale"), device_types="cuda")
+def attn_decode_fp8(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, k_scale: Tensor,
+                    v_scale: Tensor, cache_len: Tensor, scale: float) -> Tensor:
+    """`attn_decode_` on an FP8 KV cache (tn_attn_decode_fp8): caches uint8 codes [B, S_max, Nkv, D], k_scale / v_scale fp32
+    [B, S_max, Nkv].  The bf16 k_new / v_new are quantised into slot cache_len[b]; the row attends to what the cache then
+    holds.  Returns o [B, Nh, D]."""
+    _no_grad_inputs("attn_decode_fp8", q, k_new, v_new)
+    B, Nh, D, S_max, Nkv = _fp8_decode_check("attn_decode_fp8", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len)
+    q, k_new, v_new, cache_len = _c(q), _c(k_new), _c(v_new), _c(cache_len)
+    o = torch.empty_like(q)
+    nbytes = int(_lib().tn_attn_decode_workspace_bytes(B, Nh, Nkv, D, S_max))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    _C.check(_lib().tn_attn_decode_fp8(_p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(k_scale), _p(v_scale),
+                                       _p(cache_len), _p(o), _p(ws), B, Nh, Nkv, D, S_max, float(scale), _cur()),
+             "tn_attn_decode_fp8")
+    return o
+
+
+@attn_decode_fp8.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+@custom_op(f"{NS}::attn_decode_beam_fp8", mutates_args=("k_cache", "v_cache", "k_scale", "v_scale"), device_types="cuda")
+def attn_decode_beam_fp8(q: Tensor, k_new: Tensor, v_new: Tensor, k_cache: Tensor, v_cache: Tensor, k_scale: Tensor,
+                         v_scale: Tensor, cache_len: Tensor, src: Tensor, scale: float) -> Tensor:
+    """`attn_decode_beam_` on an FP8 KV cache (tn_attn_decode_beam_fp8): codes and scales of key s of row r are read at
+    [src[r, s], s]."""
+    _no_grad_inputs("attn_decode_beam_fp8", q, k_new, v_new)
+    B, Nh, D, S_max, Nkv = _fp8_decode_check("attn_decode_beam_fp8", q, k_new, v_new, k_cache, v_cache, k_scale, v_scale,
+                                             cache_len, src)
+    q, k_new, v_new, cache_len = _c(q), _c(k_new), _c(v_new), _c(cache_len)
+    o = torch.empty_like(q)
+    nbytes = int(_lib().tn_attn_decode_workspace_bytes(B, Nh, Nkv, D, S_max))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    _C.check(_lib().tn_attn_decode_beam_fp8(_p(q), _p(k_new), _p(v_new), _p(k_cache), _p(v_cache), _p(k_scale), _p(v_scale),
+                                            _p(cache_len), _p(src), _p(o), _p(ws), B, Nh, Nkv, D, S_max, float(scale),
+                                            _cur()), "tn_attn_decode_beam_fp8")
+    return o
+
+
+@attn_decode_beam_fp8.register_fake
+def _(q, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_len, src, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+@custom_op(f"{NS}::attn_extend_fp8", mutates_args=(), device_types="cuda")
+def attn_extend_fp8(q: Tensor, k_new: Tensor, v_new: Tensor, k_new_scale: Tensor, v_new_scale: Tensor, k_cache: Tensor,
+                    v_cache: Tensor, k_scale: Tensor, v_scale: Tensor, seq_start: Tensor, prefix_len: Tensor,
+                    kv_row: Optional[Tensor], scale: float) -> Tensor:
+    """`attn_extend` on FP8 keys / values (tn_attn_extend_fp8): the new rows (`kv_quantize`'s codes [T, Nkv, D] and scales
+    [T, Nkv]) and the caches (codes [B, S_max, Nkv, D], scales [B, S_max, Nkv]) alike; read only.  Returns o [T, Nh, D]."""
+    _no_grad_inputs("attn_extend_fp8", q)
+    T, Nh, D = q.shape
+    B, S_max, Nkv = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    R = prefix_len.shape[0]
+    if (q.dtype != torch.bfloat16 or any(t.dtype != KV_CODE_DTYPE for t in (k_new, v_new, k_cache, v_cache))
+            or any(t.dtype != torch.float32 for t in (k_new_scale, v_new_scale, k_scale, v_scale))
+            or any(t.dtype != torch.int32 for t in (seq_start, prefix_len) + (() if kv_row is None else (kv_row,)))
+            or tuple(k_new.shape) != (T, Nkv, D) or tuple(v_new.shape) != (T, Nkv, D)
+            or tuple(k_new_scale.shape) != (T, Nkv) or tuple(v_new_scale.shape) != (T, Nkv)
+            or tuple(k_cache.shape) != (B, S_max, Nkv, D) or tuple(v_cache.shape) != (B, S_max, Nkv, D)
+            or tuple(k_scale.shape) != (B, S_max, Nkv) or tuple(v_scale.shape) != (B, S_max, Nkv)
+            or tuple(seq_start.shape) != (R + 1,) or (kv_row is not None and tuple(kv_row.shape) != (R,))
+            or not all(t.is_contiguous() for t in (k_cache, v_cache, k_scale, v_scale))):
+        raise _C.KernelError("attn_extend_fp8: bf16 q [T, Nh, D], uint8 codes k_new / v_new [T, Nkv, D] with fp32 scales "
+                             "[T, Nkv], contiguous uint8 code caches [B, S_max, Nkv, D] with fp32 scales [B, S_max, Nkv], "
+                             "int32 seq_start [R + 1], prefix_len [R], kv_row [R] or None")
+    q, k_new, v_new, k_new_scale, v_new_scale = _c(q), _c(k_new), _c(v_new), _c(k_new_scale), _c(v_new_scale)
+    seq_start, prefix_len = _c(seq_start), _c(prefix_len)
+    kv_row = None if kv_row is None else _c(kv_row)
+    o = torch.empty_like(q)
+    _C.check(_lib().tn_attn_extend_fp8(_p(q), _p(k_new), _p(v_new), _p(k_new_scale), _p(v_new_scale), _p(k_cache),
+                                       _p(v_cache), _p(k_scale), _p(v_scale), _p(seq_start), _p(prefix_len), _p(kv_row),
+                                       _p(o), T, R, B, S_max, Nh, Nkv, D, float(scale), _cur()), "tn_attn_extend_fp8")
+    return o
+
+
+@attn_extend_fp8.register_fake
+def _(q, k_new, v_new, k_new_scale, v_new_scale, k_cache, v_cache, k_scale, v_scale, seq_start, prefix_len, kv_row, scale):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
 def linear_smallm_launch(x: Tensor, ws, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
                          rope_mask: int) -> None:
     """tn_gemm_smallm on operands the caller has checked: outs[i][M, N_i] = x ws[i]^T (+ bs[i]), rotated where bit i of
@@ -1498,4 +1621,5 @@ OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fw
        "ce_fwd_rows", "ce_reduce", "log_mel", "audiofeat_stack", "pcm16_to_f32", "bestrq_tokenize",
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
-       "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs", "attn_extend")
+       "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs", "attn_extend",
+       "kv_quantize", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_extend_fp8")

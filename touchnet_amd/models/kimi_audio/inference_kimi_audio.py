@@ -168,7 +168,7 @@ def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfi
         raise ValueError(f"generate_kimi: row_keys must have shape [{B}]")
     chunk = max(1, int(cfg.cache_chunk))
     cache = KVCache.allocate(len(lm.model.layers), B, max(lens) + min(n_new, chunk), c.num_key_value_heads, c.head_dim,
-                             device)
+                             device, kv_dtype=cfg.kv_cache_dtype)
     S_full = max(lens) + n_new
     prompt_len = torch.tensor(lens, dtype=torch.int32, device=device)
     x_next = torch.empty(B, c.hidden_size, dtype=torch.bfloat16, device=device)
