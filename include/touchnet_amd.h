@@ -535,6 +535,29 @@ int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int nseg, const v
  *      and >= the rows they span, 16-byte aligned non-NULL tensors. */
 int tn_gemm_smallm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K,
                           long long ldx, long long ldw, long long ldact, void* stream);
+/* FP8 weight-only decode linears (csrc/weight_fp8.hip, csrc/gemm_smallm.hip): a weight [N, K] held as OCP e4m3 codes uint8
+ *      [N, K] (rows 16-byte aligned) with one fp32 power-of-two scale per output row [N], by the FP8 KV cache's rules
+ *      above with a weight row in a key's place: scale = 2^e, e the smallest integer with amax <= 448 * 2^e, never below
+ *      -100; code = e4m3(w * 2^-e), round to nearest even; code * scale is exact in bf16.
+ * weight_quantize_fp8: w bf16 [N, K] (pitch ldw) -> codes (pitch ldc bytes), scale.  K % 8 == 0.  A row holding a NaN or an
+ *      infinity gets scale NaN and codes 0.  weight_dequantize_fp8: the way back, w = bf16(code * scale).  Both: -22 before
+ *      any launch for NULL or misaligned tensors (w 16, codes 8, scale 4 bytes), N or K <= 0, K % 8, pitches % 8 or < K.
+ * gemm_smallm_fp8 / gemm_smallm_swiglu_fp8: tn_gemm_smallm / tn_gemm_smallm_swiglu with every w_i (w_gate, w_up) as codes
+ *      and scale[i] (scale_gate, scale_up) their row scales; ldw in bytes = elements of codes.  y = rbf(acc * scale + bias)
+ *      with acc the fp32 sum of x . code, then the unchanged RoPE / SwiGLU rule: the bf16 entries' arithmetic on the
+ *      dequantised weights, with the same independence of a row from M, its index and the other rows.  -22 before any
+ *      launch for what the bf16 entries refuse and unless K % 128 == 0, ldw % 16 == 0, every scale non-NULL and 16-byte
+ *      aligned. */
+int tn_weight_quantize_fp8(const void* w, void* codes, float* scale, int N, int K, long long ldw, long long ldc,
+                           void* stream);
+int tn_weight_dequantize_fp8(const void* codes, const float* scale, void* w, int N, int K, long long ldc, long long ldw,
+                             void* stream);
+int tn_gemm_smallm_fp8(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                       const float* const* scale, const void* const* bias, void* const* y, const long long* ldy,
+                       const int* N, const void* cos_t, const void* sin_t, int head_dim, int rope_mask, void* stream);
+int tn_gemm_smallm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
+                              const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                              long long ldact, void* stream);
 /* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
  *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
  *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history

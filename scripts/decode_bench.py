@@ -547,9 +547,11 @@ COPY_RATE = 6.3e12      # bytes / s: the copy rate DESIGN.md §9 measures every 
 
 
 def bench_decode_gemm(name, B, steps=24, iters=40):
-    """TN_DECODE_GEMM own against lib at one decoder's widths: every product family of a decode step at M = 1, 12, 48, 96
-    (weights cycled through > 768 MB of copies, so no call finds its weights in L2 / MALL), then the whole step at B rows
-    with the switch alternated lib, own, lib, own, .. inside this process."""
+    """TN_DECODE_GEMM own against lib, and the FP8 weight variant of the small-M kernel against both, at one decoder's
+    widths: every product family of a decode step at M = 1, 12, 48, 96 (weights cycled through > 768 MB of bf16 copies and
+    their FP8 codes, so no call finds its weights in L2 / MALL), then the whole step at B rows with the arms alternated
+    lib, own, fp8, lib, own, fp8, .. inside this process (fp8: a copy of the model after `quantize_decoder_weights`), and
+    the decoder weight bytes resident before and after."""
     import touchnet_amd.functional as F
     from touchnet_amd import generation as G, library as L
     from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
@@ -575,6 +577,7 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
         return _events_time(call, iters)
 
     with torch.no_grad():
+        fp8_sets = {}
         fam_sets = {"qkv+rope": copies((Nh * D, H), (Nkv * D, H), (Nkv * D, H)), "o": copies((H, Nh * D)),
                     "gate/up+swiglu": copies((I, H), (I, H)), "down": copies((H, I)), "lm_head": copies((V, H))}
         # what one call costs the host and the queue with next to nothing to compute: a family at this figure is launch-bound
@@ -592,20 +595,31 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
             # the current route of `swiglu_mlp`: the node's library body at M % 8 == 0, else composed of the single ops
             lib_swiglu = (lambda ws: L.swiglu_fwd_t(torch.nn.functional.linear(x, ws[0]), torch.nn.functional.linear(x, ws[1]))) \
                 if M % 8 == 0 else (lambda ws: F.swiglu(*F.linear_group(x, [(ws[0], None), (ws[1], None)])))
-            fams = {"qkv+rope": (*pair(x, (cos, sin, D, (0, 1)), bs), x, (Nh + 2 * Nkv) * D),
-                    "o": (*pair(xo), xo, H), "gate/up+swiglu": (lambda ws: F.swiglu_smallm(x, *ws), lib_swiglu, x, I),
-                    "down": (*pair(xi), xi, H), "lm_head": (*pair(x), x, V)}
+            fp8 = lambda inp, rope=None, b=(None,) * 3: (lambda ws: F.linear_smallm_fp8(inp, list(zip(ws, b)), rope))
+            fams = {"qkv+rope": (*pair(x, (cos, sin, D, (0, 1)), bs), fp8(x, (cos, sin, D, (0, 1)), bs), x, (Nh + 2 * Nkv) * D),
+                    "o": (*pair(xo), fp8(xo), xo, H),
+                    "gate/up+swiglu": (lambda ws: F.swiglu_smallm(x, *ws), lib_swiglu, lambda ws: F.swiglu_smallm_fp8(x, *ws), x, I),
+                    "down": (*pair(xi), fp8(xi), xi, H), "lm_head": (*pair(x), fp8(x), x, V)}
             F.DECODE_GEMM = "lib"
-            for fam, (own_fn, lib_fn, inp, n_out) in fams.items():
+            for fam, (own_fn, lib_fn, fp8_fn, inp, n_out) in fams.items():
                 sets = fam_sets[fam]
+                if fam not in fp8_sets:
+                    fp8_sets[fam] = [[F.quantize_weight_fp8(w) for w in ws] for ws in sets]
                 nbytes = sum(w.numel() for w in sets[0]) * 2 + inp.numel() * 2 + M * n_out * 2
+                nbytes8 = nbytes - sum(w.numel() for w in sets[0]) + 4 * sum(w.shape[0] for w in sets[0])
                 us_own = timed(own_fn, sets)
+                us_fp8 = timed(fp8_fn, fp8_sets[fam])
                 us_lib = timed(lib_fn, sets)
+                us_own2 = timed(own_fn, sets)                  # (the bf16 arm again: the spread the fp8 figure is read against)
+                us_fp8_2 = timed(fp8_fn, fp8_sets[fam])
                 rows.append(dict(decode_gemm=name, family=fam, M=M, bytes=nbytes, us_own=round(us_own, 2),
                                  tbps_own=round(nbytes / us_own / 1e6, 3), us_at_copy_rate=round(nbytes / COPY_RATE * 1e6, 2),
-                                 us_lib=round(us_lib, 2), own_over_lib=round(us_own / us_lib, 3)))
+                                 us_lib=round(us_lib, 2), own_over_lib=round(us_own / us_lib, 3), bytes_fp8=nbytes8,
+                                 us_fp8=round(us_fp8, 2), tbps_fp8=round(nbytes8 / us_fp8 / 1e6, 3),
+                                 us_own_again=round(us_own2, 2), us_fp8_again=round(us_fp8_2, 2),
+                                 fp8_over_own=round(us_fp8 / us_own, 3)))
                 print(json.dumps(rows[-1]), flush=True)
-        del fam_sets
+        del fam_sets, fp8_sets
         torch.cuda.empty_cache()
         text = DecoderConfig.from_dict(dict(model_type=kind, hidden_size=H, intermediate_size=I, num_attention_heads=Nh,
                                             num_key_value_heads=Nkv, head_dim=D, num_hidden_layers=layers, vocab_size=V,
@@ -622,15 +636,25 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
         greedy = lambda lg: F.greedy_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
                                           1.0, 0, -1, 1)
         greedy(logits)
+        import copy
+        lm8 = copy.deepcopy(lm)
+        linear_bytes = lambda m: sum(p.numel() * p.element_size() for n, p in m.named_parameters()
+                                     if "embed_tokens" not in n and p.dim() == 2)
+        before = linear_bytes(lm8) + (lm8.lm_head.weight.numel() * 2 if kind == "llama" else 0)      # (a tied head counts once more)
+        G.quantize_decoder_weights(lm8)
+        after = sum(m.weight.codes.numel() + 4 * m.weight.scale.numel() for m in lm8.modules() if isinstance(m, G.Fp8Linear)) \
+            + linear_bytes(lm8)
         arms = []
-        for arm in ("lib", "own") * 4:                     # the first pair warms both arms' shapes and is not reported
-            F.DECODE_GEMM = arm
-            greedy(G.decode_logits(lm, cache))
-            arms.append((arm, round(_events_time(lambda: greedy(G.decode_logits(lm, cache)), steps) / 1e3, 3)))
+        for arm in ("lib", "own", "fp8") * 4:              # the first round warms the arms' shapes and is not reported
+            F.DECODE_GEMM = "lib" if arm == "fp8" else arm
+            m = lm8 if arm == "fp8" else lm
+            greedy(G.decode_logits(m, cache))
+            arms.append((arm, round(_events_time(lambda: greedy(G.decode_logits(m, cache)), steps) / 1e3, 3)))
         F.DECODE_GEMM = "lib"
-    lib_ms, own_ms = [t for a, t in arms[2:] if a == "lib"], [t for a, t in arms[2:] if a == "own"]
-    rows.append(dict(e2e=f"{name}_decode_step", B=B, layers=layers, ms_lib=lib_ms, ms_own=own_ms,
-                     own_worst_beats_lib_best=max(own_ms) < min(lib_ms)))
+    lib_ms, own_ms, fp8_ms = ([t for a, t in arms[3:] if a == arm] for arm in ("lib", "own", "fp8"))
+    rows.append(dict(e2e=f"{name}_decode_step", B=B, layers=layers, ms_lib=lib_ms, ms_own=own_ms, ms_fp8=fp8_ms,
+                     own_worst_beats_lib_best=max(own_ms) < min(lib_ms), fp8_worst_beats_own_best=max(fp8_ms) < min(own_ms),
+                     decoder_linear_bytes_bf16=before, decoder_linear_bytes_fp8=after))
     print(json.dumps(rows[-1]), flush=True)
     return rows
 

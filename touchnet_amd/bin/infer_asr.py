@@ -179,7 +179,7 @@ def generation_config(args, tokenizer=None) -> GenerationConfig:
                            early_stopping={"true": True, "false": False}.get(args.early_stopping, "never"),
                            sequence_bias=constraints_from_args(args, tokenizer), min_new_tokens=args.min_new_tokens or 0,
                            output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest,
-                           kv_cache_dtype=args.kv_cache_dtype)
+                           kv_cache_dtype=args.kv_cache_dtype, weight_dtype=args.weight_dtype)
     cfg.check_beams()
     return cfg
 
@@ -190,6 +190,9 @@ def main(argv=None):
         raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
+    if args.weight_dtype == "fp8_e4m3":
+        from touchnet_amd.generation import quantize_decoder_weights
+        quantize_decoder_weights(model)
     dcfg = data_config(args, model)
     tokenizer = None
     if _first(os.path.join(args.model_path, "tokenizer.json"), os.path.join(args.model_path, "tokenizer_config.json")):

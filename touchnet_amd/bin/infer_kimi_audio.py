@@ -87,7 +87,8 @@ def generation_config(args) -> KimiGenerationConfig:
                                 text_repetition_penalty=args.text_repetition_penalty,
                                 text_repetition_window_size=args.text_repetition_window_size,
                                 max_new_tokens=args.max_new_tokens, seed=args.seed, output_scores=args.output_scores,
-                                top_alternatives=args.top_alternatives, kv_cache_dtype=args.kv_cache_dtype)
+                                top_alternatives=args.top_alternatives, kv_cache_dtype=args.kv_cache_dtype,
+                                weight_dtype=args.weight_dtype)
 
 
 def main(argv=None):
@@ -99,6 +100,9 @@ def main(argv=None):
     from transformers import AutoTokenizer
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
+    if args.weight_dtype == "fp8_e4m3":
+        from touchnet_amd.generation import quantize_decoder_weights
+        quantize_decoder_weights(model)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path, trust_remote_code=True)
     cfg.kimia_text_blank = special_id(tokenizer, BLANK, cfg.kimia_text_blank)
     cfg.kimia_text_eos = special_id(tokenizer, EOS, cfg.kimia_text_eos)

@@ -112,7 +112,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def generation_config(args, tokenizer=None) -> GenerationConfig:
-    over = dict(max_length=args.max_length, seed=args.seed, kv_cache_dtype=args.kv_cache_dtype)
+    over = dict(max_length=args.max_length, seed=args.seed, kv_cache_dtype=args.kv_cache_dtype,
+                weight_dtype=args.weight_dtype)
     if args.output_scores or args.top_alternatives or args.nbest != 1:
         over.update(output_scores=args.output_scores, top_alternatives=args.top_alternatives, nbest=args.nbest)
     if args.num_beams is not None:
@@ -138,6 +139,9 @@ def main(argv=None):
     from transformers import AutoTokenizer
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
+    if args.weight_dtype == "fp8_e4m3":
+        from touchnet_amd.generation import quantize_decoder_weights
+        quantize_decoder_weights(model)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path)
     cfg = generation_config(args, tokenizer)
     long_cfg = longform_from_args(args)

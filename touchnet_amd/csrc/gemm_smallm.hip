@@ -21,7 +21,18 @@
 //    rows are two runs of 8: rows r .. r + 7 and r + head_dim / 2 .. of one head (RoPE), or 8 gate rows and the 8 up rows of
 //    the same features (SwiGLU).  The second run sits in lane groups 2, 3, so the partner of every output is in lane
 //    l ^ 32, same element: one cross-lane exchange, no second pass, no LDS round trip.
-#include "common.h"
+//
+// FP8 weights (F8 = true; tn_gemm_smallm_fp8, tn_gemm_smallm_swiglu_fp8): W is e4m3 codes uint8 [N, K] with
+// one fp32 power-of-two scale per row (weight_fp8.hip, the rules of kv_fp8.h).  A 128-byte line of a weight row now holds
+// 128 contraction steps, so the chunk is 128 deep: lane l still reads bytes 32 (l >> 4) .. + 31 of row l & 15 as two
+// 16-byte loads — 32 codes, expanded exactly to bf16 in registers (v_cvt_pk_f32_fp8 + v_perm_b32 of the high halves), the
+// operands of FOUR MFMAs: MFMA j of a chunk contracts k = 128 c + 32 g + 8 j + s.  X is read with the matching pattern, four
+// 16-byte loads per lane and chunk.  The accumulators hold x . code; the row's scale multiplies them ONCE in the epilogue,
+// own = rbf(acc * scale[f] + bias[f]) (a power of two: the product is exact, so this is the bf16 kernel's arithmetic on
+// the dequantised weights), and everything behind it is unchanged.  F8 = false compiles to the bf16 kernel as before.
+#include <type_traits>
+
+#include "kv_fp8.h"
 
 namespace tn {
 namespace smallm {
@@ -35,8 +46,10 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 
 struct Seg {
-  const bf16_t* W;       // [N, K], pitch ldw (kSwiglu: gate_proj)
-  const bf16_t* W2;      // kSwiglu: up_proj, same pitch
+  const void* W;         // [N, K] bf16 (F8: e4m3 codes), pitch ldw elements (kSwiglu: gate_proj)
+  const void* W2;        // kSwiglu: up_proj, same pitch
+  const float* scale;    // F8: [N] row scales of W (else unused)
+  const float* scale2;   // F8, kSwiglu: those of W2
   const bf16_t* bias;    // [N] or null
   bf16_t* Y;             // [M, N], pitch ldy (kSwiglu: act [M, I])
   long long ldw, ldy;
@@ -57,7 +70,11 @@ struct Frag {            // a lane's 32 bytes of one 64-deep chunk of one row: t
   u32x4_t lo, hi;
 };
 
-__device__ __forceinline__ Frag load_w(const bf16_t* p) {        // streamed: every byte of W is wanted exactly once
+struct Frag4 {           // F8: a lane's 64 bytes of X of one 128-deep chunk, the second operands of the chunk's four MFMAs
+  u32x4_t v[4];
+};
+
+__device__ __forceinline__ Frag load_w(const void* p) {        // streamed: every byte of W is wanted exactly once
   Frag f;
   f.lo = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
   f.hi = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p) + 1);
@@ -71,6 +88,26 @@ __device__ __forceinline__ Frag load_x(const bf16_t* p, bool row_ok) {
     f.hi = *(reinterpret_cast<const u32x4_t*>(p) + 1);
   }
   return f;
+}
+
+__device__ __forceinline__ Frag4 load_x4(const bf16_t* p, bool row_ok) {
+  Frag4 f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) f.v[j] = row_ok ? *(reinterpret_cast<const u32x4_t*>(p) + j) : u32x4_t{0, 0, 0, 0};
+  return f;
+}
+
+// 16 codes -> their 16 bf16 values as the operands of two MFMAs (exact: a code has 4 significant bits).  kv_fp8.h's decode8
+// with scale 1 (the multiplication folds away), then the high halves of each pair of fp32 in one v_perm_b32.
+__device__ __forceinline__ void expand16(const u32x4_t c, u32x4_t& a, u32x4_t& b) {
+  float f[8], h[8];
+  kvq::decode8(make_uint2(c[0], c[1]), 1.0f, f);
+  kvq::decode8(make_uint2(c[2], c[3]), 1.0f, h);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    a[i] = __builtin_amdgcn_perm(__float_as_uint(f[2 * i + 1]), __float_as_uint(f[2 * i]), 0x07060302u);
+    b[i] = __builtin_amdgcn_perm(__float_as_uint(h[2 * i + 1]), __float_as_uint(h[2 * i]), 0x07060302u);
+  }
 }
 
 __device__ __forceinline__ float rbf(float v) { return bf2f(f2bf(v)); }
@@ -96,21 +133,24 @@ __device__ __forceinline__ int run_base(int mode, int head_dim, int j, bool seco
   return (j / per) * head_dim + 8 * (j % per) + (second ? head_dim >> 1 : 0);
 }
 
-template <int MT, int S>
+template <int MT, int S, bool F8>
 __global__ __launch_bounds__(kWaves * 64) void kernel(const Params p) {
+  using w_t = std::conditional_t<F8, kvq::fp8_t, bf16_t>;      // one stored element of W
+  using XFrag = std::conditional_t<F8, Frag4, Frag>;
+  constexpr int kDepth = F8 ? 128 : 64;                          // contraction steps of a chunk: one 128-byte line of W
   __shared__ f32x4_t red[kWaves][MT][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
   const int strip0 = blockIdx.x * S;
 
   // a workgroup past the last whole group of S re-reads the last strip and stores nothing for it
-  const bf16_t* wp[S];
+  const w_t* wp[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     int j;
     const Seg& sg = p.seg[locate(p, min(strip0 + s, p.nstrip - 1), j)];
     const bool second = l15 >= 8;
-    const bf16_t* base = (sg.mode == kSwiglu && second) ? sg.W2 : sg.W;
-    wp[s] = base + (long long)(run_base(sg.mode, p.head_dim, j, second) + (l15 & 7)) * sg.ldw + 16 * g;
+    const w_t* base = static_cast<const w_t*>((sg.mode == kSwiglu && second) ? sg.W2 : sg.W);
+    wp[s] = base + (long long)(run_base(sg.mode, p.head_dim, j, second) + (l15 & 7)) * sg.ldw + (kDepth / 4) * g;
   }
   const bf16_t* xp[MT];
   bool xok[MT];
@@ -118,7 +158,7 @@ __global__ __launch_bounds__(kWaves * 64) void kernel(const Params p) {
   for (int t = 0; t < MT; ++t) {
     const int m = 16 * t + l15;
     xok[t] = m < p.M;
-    xp[t] = p.X + (long long)(xok[t] ? m : 0) * p.ldx + 16 * g;
+    xp[t] = p.X + (long long)(xok[t] ? m : 0) * p.ldx + (kDepth / 4) * g;
   }
 
   f32x4_t acc[S][MT];
@@ -128,34 +168,53 @@ __global__ __launch_bounds__(kWaves * 64) void kernel(const Params p) {
     for (int t = 0; t < MT; ++t) acc[s][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // A wave moves through its chunks U at a time (chunks c, c + 4, .., still in ascending order): with few strips and
-  // tiles one chunk is only 2 KiB per wave, too little in flight to cover the HBM latency.
+  // tiles one chunk is only 2 KiB per wave, too little in flight to cover the HBM latency.  (F8: a chunk of a strip is the
+  // same 16 lines of 128 bytes, so the same U keeps the same bytes of W in flight per wave.)
   constexpr int U = S + MT <= 2 ? 4 : S + MT <= 4 ? 2 : 1, kStep = U * kWaves;
-  const int nch = p.K >> 6;
-  Frag wa[U][S], xa[U][MT], wb[U][S], xb[U][MT];
-  auto load = [&](Frag (&w)[U][S], Frag (&x)[U][MT], int c) {
+  const int nch = p.K / kDepth;
+  Frag wa[U][S], wb[U][S];
+  XFrag xa[U][MT], xb[U][MT];
+  auto load = [&](Frag (&w)[U][S], XFrag (&x)[U][MT], int c) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int cu = c + u * kWaves;
       if (cu < nch) {
 #pragma unroll
-        for (int s = 0; s < S; ++s) w[u][s] = load_w(wp[s] + 64 * (long long)cu);
+        for (int s = 0; s < S; ++s) w[u][s] = load_w(wp[s] + (128 / (int)sizeof(w_t)) * (long long)cu);
 #pragma unroll
-        for (int t = 0; t < MT; ++t) x[u][t] = load_x(xp[t] + 64 * (long long)cu, xok[t]);
+        for (int t = 0; t < MT; ++t) {
+          if constexpr (F8)
+            x[u][t] = load_x4(xp[t] + kDepth * (long long)cu, xok[t]);
+          else
+            x[u][t] = load_x(xp[t] + kDepth * (long long)cu, xok[t]);
+        }
       }
     }
   };
-  auto mac = [&](const Frag (&w)[U][S], const Frag (&x)[U][MT], int c) {
+  auto mac = [&](const Frag (&w)[U][S], const XFrag (&x)[U][MT], int c) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (c + u * kWaves < nch) {
 #pragma unroll
         for (int s = 0; s < S; ++s)
+          if constexpr (F8) {
+            u32x4_t e[4];
+            expand16(w[u][s].lo, e[0], e[1]);
+            expand16(w[u][s].hi, e[2], e[3]);
 #pragma unroll
-          for (int t = 0; t < MT; ++t) {
-            acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[u][s].lo),
-                                                                __builtin_bit_cast(bf16x8_t, x[u][t].lo), acc[s][t], 0, 0, 0);
-            acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[u][s].hi),
-                                                                __builtin_bit_cast(bf16x8_t, x[u][t].hi), acc[s][t], 0, 0, 0);
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, e[j]),
+                                                                    __builtin_bit_cast(bf16x8_t, x[u][t].v[j]), acc[s][t], 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+              acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[u][s].lo),
+                                                                  __builtin_bit_cast(bf16x8_t, x[u][t].lo), acc[s][t], 0, 0, 0);
+              acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[u][s].hi),
+                                                                  __builtin_bit_cast(bf16x8_t, x[u][t].hi), acc[s][t], 0, 0, 0);
+            }
           }
       }
   };
@@ -195,6 +254,8 @@ __global__ __launch_bounds__(kWaves * 64) void kernel(const Params p) {
         float own[4], other[4], y[4];
         u32x2_t bv = {0, 0};
         if (sg.bias != nullptr) bv = *reinterpret_cast<const u32x2_t*>(sg.bias + f0);
+        if constexpr (F8)      // the row scales of the lane's four features: the up rows (second run of a SwiGLU strip) have their own
+          v *= *reinterpret_cast<const f32x4_t*>((mode == kSwiglu && second ? sg.scale2 : sg.scale) + f0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float b = __uint_as_float(e & 1 ? bv[e >> 1] & 0xffff0000u : bv[e >> 1] << 16);
@@ -239,65 +300,67 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // M / (16 S)), fewer give more workgroups: S = 4 while that still leaves two workgroups per CU, never below one strip per
 // four 16-row tiles of X, and two above six tiles (four strips x seven tiles of accumulators and operands no longer fit
 // the register file).  Depends on M and the strip count; the summation order does not depend on S.
+// FP8: a chunk's fragment of X is 16 registers instead of 8 (two register sets: 32 per tile), so four strips stop at
+// four tiles: four strips x five and six tiles compile without scratch, but to 442 and 508 of the 512 registers, over a
+// hundred of them operands parked in AGPRs and copied back for every use (DESIGN.md §9.13's table).  Otherwise the same rule.
 constexpr int kMaxTilesAt4 = 6, kMaxTilesAt1 = 4;      // (only the selectable (tiles, S) pairs are instantiated)
+constexpr int kMaxTilesAt4F8 = 4, kMaxTilesAt1F8 = 4;
+template <bool F8>
 static inline int strips_per_group(int mt, int nstrip) {
-  const int least = mt > kMaxTilesAt1 ? 2 : 1;
-  int s = mt > kMaxTilesAt4 ? 2 : 4;
+  const int least = mt > (F8 ? kMaxTilesAt1F8 : kMaxTilesAt1) ? 2 : 1;
+  int s = mt > (F8 ? kMaxTilesAt4F8 : kMaxTilesAt4) ? 2 : 4;
   while (s > least && (nstrip + s - 1) / s < 2 * 256) s >>= 1;
   return s;
 }
 
-template <int MT>
+template <int MT, bool F8>
 static int launch_s(const Params& p, int S, hipStream_t st) {
   const dim3 block(kWaves * 64);
-  if constexpr (MT <= kMaxTilesAt4) {
+  if constexpr (MT <= (F8 ? kMaxTilesAt4F8 : kMaxTilesAt4)) {
     if (S == 4) {
-      hipLaunchKernelGGL((kernel<MT, 4>), dim3((p.nstrip + 3) / 4), block, 0, st, p);
+      hipLaunchKernelGGL((kernel<MT, 4, F8>), dim3((p.nstrip + 3) / 4), block, 0, st, p);
       TN_LAUNCH_CHECK();
       return TN_OK;
     }
   }
-  if constexpr (MT <= kMaxTilesAt1) {
+  if constexpr (MT <= (F8 ? kMaxTilesAt1F8 : kMaxTilesAt1)) {
     if (S == 1) {
-      hipLaunchKernelGGL((kernel<MT, 1>), dim3(p.nstrip), block, 0, st, p);
+      hipLaunchKernelGGL((kernel<MT, 1, F8>), dim3(p.nstrip), block, 0, st, p);
       TN_LAUNCH_CHECK();
       return TN_OK;
     }
   }
-  hipLaunchKernelGGL((kernel<MT, 2>), dim3((p.nstrip + 1) / 2), block, 0, st, p);
+  hipLaunchKernelGGL((kernel<MT, 2, F8>), dim3((p.nstrip + 1) / 2), block, 0, st, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
+template <bool F8>
 static int launch(const Params& p, hipStream_t st) {
-  const int mt = (p.M + 15) / 16, S = strips_per_group(mt, p.nstrip);
+  const int mt = (p.M + 15) / 16, S = strips_per_group<F8>(mt, p.nstrip);
   switch (mt) {
-    case 1: return launch_s<1>(p, S, st);
-    case 2: return launch_s<2>(p, S, st);
-    case 3: return launch_s<3>(p, S, st);
-    case 4: return launch_s<4>(p, S, st);
-    case 5: return launch_s<5>(p, S, st);
-    case 6: return launch_s<6>(p, S, st);
-    case 7: return launch_s<7>(p, S, st);
-    default: return launch_s<8>(p, S, st);
+    case 1: return launch_s<1, F8>(p, S, st);
+    case 2: return launch_s<2, F8>(p, S, st);
+    case 3: return launch_s<3, F8>(p, S, st);
+    case 4: return launch_s<4, F8>(p, S, st);
+    case 5: return launch_s<5, F8>(p, S, st);
+    case 6: return launch_s<6, F8>(p, S, st);
+    case 7: return launch_s<7, F8>(p, S, st);
+    default: return launch_s<8, F8>(p, S, st);
   }
 }
 
-static bool x_ok(const void* x, int M, int K, long long ldx) {
-  return x != nullptr && aligned16(x) && M >= 1 && M <= kMaxM && K > 0 && K % 64 == 0 && ldx >= K && ldx % 8 == 0;
+// (F8: whole 128-deep chunks; weight pitches are bytes of codes and keep the rows 16-byte aligned)
+static bool x_ok(const void* x, int M, int K, long long ldx, bool f8 = false) {
+  return x != nullptr && aligned16(x) && M >= 1 && M <= kMaxM && K > 0 && K % (f8 ? 128 : 64) == 0 && ldx >= K && ldx % 8 == 0;
 }
 
-}  // namespace smallm
-}  // namespace tn
-
-using namespace tn;
-using namespace tn::smallm;
-
-extern "C" int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int nseg, const void* const* w,
-                              const long long* ldw, const void* const* bias, void* const* y, const long long* ldy,
-                              const int* N, const void* cos_t, const void* sin_t, int head_dim, int rope_mask,
-                              void* stream) {
-  if (!x_ok(x, M, K, ldx) || nseg < 1 || nseg > kMaxSeg || w == nullptr || ldw == nullptr || y == nullptr ||
+// tn_gemm_smallm (scale == nullptr) and tn_gemm_smallm_fp8 (scale[i]: the row scales of w[i])
+static int linear_entry(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                        const float* const* scale, const void* const* bias, void* const* y, const long long* ldy,
+                        const int* N, const void* cos_t, const void* sin_t, int head_dim, int rope_mask, void* stream) {
+  const bool f8 = scale != nullptr;
+  if (!x_ok(x, M, K, ldx, f8) || nseg < 1 || nseg > kMaxSeg || w == nullptr || ldw == nullptr || y == nullptr ||
       ldy == nullptr || N == nullptr || rope_mask < 0 || rope_mask >= (1 << nseg))
     return TN_EINVAL;
   if (rope_mask != 0 && (cos_t == nullptr || sin_t == nullptr || !aligned16(cos_t) || !aligned16(sin_t) ||
@@ -316,11 +379,11 @@ extern "C" int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int ns
     const bool rope = (rope_mask >> i) & 1;
     const void* b = bias != nullptr ? bias[i] : nullptr;
     if (w[i] == nullptr || y[i] == nullptr || !aligned16(w[i]) || !aligned16(y[i]) || (b != nullptr && !aligned16(b)) ||
-        N[i] <= 0 || N[i] % 16 != 0 || ldw[i] < K || ldw[i] % 8 != 0 || ldy[i] < N[i] || ldy[i] % 8 != 0 ||
-        (rope && N[i] % head_dim != 0))
+        N[i] <= 0 || N[i] % 16 != 0 || ldw[i] < K || ldw[i] % (f8 ? 16 : 8) != 0 || ldy[i] < N[i] || ldy[i] % 8 != 0 ||
+        (rope && N[i] % head_dim != 0) || (f8 && (scale[i] == nullptr || !aligned16(scale[i]))))
       return TN_EINVAL;
     strips += N[i] / 16;
-    p.seg[i] = Seg{static_cast<const bf16_t*>(w[i]), nullptr, static_cast<const bf16_t*>(b), static_cast<bf16_t*>(y[i]),
+    p.seg[i] = Seg{w[i], nullptr, f8 ? scale[i] : nullptr, nullptr, static_cast<const bf16_t*>(b), static_cast<bf16_t*>(y[i]),
                    ldw[i], ldy[i], strips, rope ? kRope : kPlain};
   }
   for (int i = nseg; i < kMaxSeg; ++i) {
@@ -328,13 +391,15 @@ extern "C" int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int ns
     p.seg[i].strip_end = 0x7fffffff;
   }
   p.nstrip = strips;
-  return launch(p, static_cast<hipStream_t>(stream));
+  return f8 ? launch<true>(p, static_cast<hipStream_t>(stream)) : launch<false>(p, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int tn_gemm_smallm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K,
-                                     long long ldx, long long ldw, long long ldact, void* stream) {
-  if (!x_ok(x, M, K, ldx) || w_gate == nullptr || w_up == nullptr || act == nullptr || !aligned16(w_gate) ||
-      !aligned16(w_up) || !aligned16(act) || I <= 0 || I % 16 != 0 || ldw < K || ldw % 8 != 0 || ldact < I || ldact % 8 != 0)
+// tn_gemm_smallm_swiglu (no scales) and tn_gemm_smallm_swiglu_fp8
+static int swiglu_entry(const void* x, const void* w_gate, const void* w_up, const float* s_gate, const float* s_up, bool f8,
+                        void* act, int M, int I, int K, long long ldx, long long ldw, long long ldact, void* stream) {
+  if (!x_ok(x, M, K, ldx, f8) || w_gate == nullptr || w_up == nullptr || act == nullptr || !aligned16(w_gate) ||
+      !aligned16(w_up) || !aligned16(act) || I <= 0 || I % 16 != 0 || ldw < K || ldw % (f8 ? 16 : 8) != 0 || ldact < I ||
+      ldact % 8 != 0 || (f8 && (s_gate == nullptr || s_up == nullptr || !aligned16(s_gate) || !aligned16(s_up))))
     return TN_EINVAL;
   Params p = {};
   p.X = static_cast<const bf16_t*>(x);
@@ -344,7 +409,40 @@ extern "C" int tn_gemm_smallm_swiglu(const void* x, const void* w_gate, const vo
   p.head_dim = 64;
   p.nstrip = I / 8;                  // a strip = 8 rows of gate_proj + the same 8 of up_proj -> 8 features of act
   for (int i = 0; i < kMaxSeg; ++i)
-    p.seg[i] = Seg{static_cast<const bf16_t*>(w_gate), static_cast<const bf16_t*>(w_up), nullptr, static_cast<bf16_t*>(act),
-                   ldw, ldact, i == 0 ? p.nstrip : 0x7fffffff, kSwiglu};
-  return launch(p, static_cast<hipStream_t>(stream));
+    p.seg[i] = Seg{w_gate, w_up, s_gate, s_up, nullptr, static_cast<bf16_t*>(act), ldw, ldact, i == 0 ? p.nstrip : 0x7fffffff,
+                   kSwiglu};
+  return f8 ? launch<true>(p, static_cast<hipStream_t>(stream)) : launch<false>(p, static_cast<hipStream_t>(stream));
+}
+
+}  // namespace smallm
+}  // namespace tn
+
+using namespace tn;
+using namespace tn::smallm;
+
+
+extern "C" int tn_gemm_smallm(const void* x, long long ldx, int M, int K, int nseg, const void* const* w,
+                              const long long* ldw, const void* const* bias, void* const* y, const long long* ldy,
+                              const int* N, const void* cos_t, const void* sin_t, int head_dim, int rope_mask,
+                              void* stream) {
+  return linear_entry(x, ldx, M, K, nseg, w, ldw, nullptr, bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask, stream);
+}
+
+extern "C" int tn_gemm_smallm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K,
+                                     long long ldx, long long ldw, long long ldact, void* stream) {
+  return swiglu_entry(x, w_gate, w_up, nullptr, nullptr, false, act, M, I, K, ldx, ldw, ldact, stream);
+}
+
+extern "C" int tn_gemm_smallm_fp8(const void* x, long long ldx, int M, int K, int nseg, const void* const* w,
+                                  const long long* ldw, const float* const* scale, const void* const* bias, void* const* y,
+                                  const long long* ldy, const int* N, const void* cos_t, const void* sin_t, int head_dim,
+                                  int rope_mask, void* stream) {
+  if (scale == nullptr) return TN_EINVAL;
+  return linear_entry(x, ldx, M, K, nseg, w, ldw, scale, bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask, stream);
+}
+
+extern "C" int tn_gemm_smallm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
+                                         const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                                         long long ldact, void* stream) {
+  return swiglu_entry(x, w_gate, w_up, scale_gate, scale_up, true, act, M, I, K, ldx, ldw, ldact, stream);
 }

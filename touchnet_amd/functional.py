@@ -902,6 +902,120 @@ def swiglu_smallm(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> 
     return L.swiglu_smallm(x, w_gate, w_up)
 
 
+# FP8 (e4m3) weight-only decode linears (csrc/weight_fp8.hip, the FP8 variant of csrc/gemm_smallm.hip).
+# WHO ANSWERS: `linear_group`, `swiglu_mlp` and generation.decode_logits look for an `Fp8Weight` at their entry.  Up to 128
+# rows with autograd off run on the FP8 small-M kernel whatever TN_DECODE_GEMM says (there is no library arm for codes);
+# anything else — prefill, an extend with more rows, a shape the kernel does not take — dequantises the weight to bf16 for the
+# call and takes the existing path.  Autograd on is refused.
+class Fp8Weight:
+    """A weight [N, K] as OCP e4m3 ``codes`` uint8 [N, K] and one fp32 power-of-two ``scale`` per output row [N]
+    (`quantize_weight_fp8`); ``codes * scale`` is exact in bf16."""
+    __slots__ = ("codes", "scale")
+
+    def __init__(self, codes: torch.Tensor, scale: torch.Tensor):
+        self.codes, self.scale = codes, scale
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+
+def quantize_weight_fp8(w: torch.Tensor) -> Fp8Weight:
+    """bf16 device weight [N, K], K % 8 == 0 -> `Fp8Weight`: per output row scale = 2^e with e the smallest integer such
+    that the row's amax <= 448 * 2^e (at least -100), codes = e4m3(w / scale), round to nearest even
+    (tn_weight_quantize_fp8).  A weight that holds a NaN or an infinity is refused."""
+    if w.dim() != 2 or not _bf16_rows(w) or w.shape[0] < 1 or w.shape[1] < 8 or w.shape[1] % 8:
+        raise _C.KernelError("quantize_weight_fp8: a bf16 device matrix [N, K], K % 8 == 0, with contiguous 16-byte aligned rows")
+    if not bool(torch.isfinite(w).all()):          # (weights are static: one host read per weight at load time)
+        raise _C.KernelError("quantize_weight_fp8: the weight holds a NaN or an infinity")
+    return Fp8Weight(*L.weight_quantize_fp8(w.detach()))
+
+
+def _fp8_weight_ok(w, align: int = 16) -> bool:
+    """codes and scale as the small-M kernel reads them (16-byte aligned rows; the converters take 8)"""
+    c, s = w.codes, w.scale
+    return (c.is_cuda and c.dtype == L.KV_CODE_DTYPE and c.dim() == 2 and c.stride(1) == 1 and c.stride(0) % align == 0
+            and c.data_ptr() % align == 0 and s.is_cuda and s.dtype == torch.float32 and tuple(s.shape) == (c.shape[0],)
+            and s.is_contiguous() and s.data_ptr() % 16 == 0)
+
+
+def dequantize_weight_fp8(w: Fp8Weight) -> torch.Tensor:
+    """-> the bf16 weight ``codes * scale`` [N, K], exactly (tn_weight_dequantize_fp8)."""
+    if not isinstance(w, Fp8Weight) or not _fp8_weight_ok(w, 8) or w.shape[1] % 8:
+        raise _C.KernelError("dequantize_weight_fp8: an Fp8Weight (uint8 codes [N, K], K % 8 == 0, with 8-byte aligned rows, "
+                             "fp32 scale [N])")
+    return L.weight_dequantize_fp8(w.codes, w.scale)
+
+
+def smallm_fp8_supported(M: int, Ns, K: int) -> bool:
+    """Shapes tn_gemm_smallm_fp8 takes: `smallm_supported`'s, with a contraction of whole 128-deep chunks."""
+    return smallm_supported(M, Ns, K) and K % 128 == 0
+
+
+def _smallm_fp8_operands(name: str, x, ws):
+    """by-name refusal of what tn_gemm_smallm_fp8 would answer with -22"""
+    if (x.dim() != 2 or not _bf16_rows(x) or not all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in ws)
+            or any(w.shape[1] != x.shape[1] for w in ws)):
+        raise _C.KernelError(f"{name}: bf16 device matrix x [M, K] and Fp8Weights [N, K] (uint8 codes with contiguous 16-byte "
+                             "aligned rows, fp32 scale [N])")
+    if not smallm_fp8_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
+        raise _C.KernelError(f"{name}: 1 <= M <= {SMALLM_MAX_ROWS}, K % 128 == 0, 1..3 weights with N % 16 == 0 (got M = "
+                             f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
+
+
+def _smallm_bias_ok(w, b) -> bool:
+    return b is None or (b.is_cuda and b.dtype == torch.bfloat16 and tuple(b.shape) == (w.shape[0],) and b.is_contiguous()
+                         and b.data_ptr() % 16 == 0)
+
+
+def linear_smallm_fp8(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_smallm` on FP8 weights: ``layers`` = 1..3 (`Fp8Weight` [N_i, K], bias bf16 [N_i] | None) sharing x [M, K],
+    M <= 128, K % 128 == 0 -> list of ``bf16(x codes_i^T * scale_i + b_i)`` from ONE launch (tn_gemm_smallm_fp8): the bf16
+    kernel's arithmetic on the dequantised weights.  ``rope`` and ``outs`` as there.  Inference only."""
+    ws = [w for w, _ in layers]
+    bs = [b for _, b in layers]
+    _smallm_fp8_operands("linear_smallm_fp8", x, ws)
+    M = x.shape[0]
+    if not all(_smallm_bias_ok(w, b) for w, b in layers):
+        raise _C.KernelError("linear_smallm_fp8: bias bf16 [N], contiguous, 16-byte aligned")
+    cos = sin = None
+    D = mask = 0
+    if rope is not None and len(rope[3]):
+        if not _smallm_rope_ok(M, [w.shape[0] for w in ws], rope):
+            raise _C.KernelError("linear_smallm_fp8: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
+                                 "outputs of whole heads)")
+        cos, sin, D = rope[:3]
+        mask = sum(1 << int(i) for i in set(rope[3]))
+    codes, scales = [w.codes for w in ws], [w.scale for w in ws]
+    if outs is None:
+        return list(L.linear_smallm_fp8(x, codes, scales, bs, cos, sin, int(D), mask))
+    if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
+        raise _C.KernelError("linear_smallm_fp8: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
+    L.linear_smallm_fp8_launch(x, codes, scales, bs, outs, cos, sin, int(D), mask)
+    return list(outs)
+
+
+def swiglu_smallm_fp8(x: torch.Tensor, w_gate: Fp8Weight, w_up: Fp8Weight) -> torch.Tensor:
+    """`swiglu_smallm` on FP8 weights, ONE launch (tn_gemm_smallm_swiglu_fp8): bit-identical to `swiglu` of the two
+    `linear_smallm_fp8` products.  Inference only."""
+    _smallm_fp8_operands("swiglu_smallm_fp8", x, [w_gate, w_up])
+    if w_gate.shape != w_up.shape or w_gate.codes.stride(0) != w_up.codes.stride(0):
+        raise _C.KernelError("swiglu_smallm_fp8: w_gate / w_up [I, K] of one row pitch")
+    return L.swiglu_smallm_fp8(x, w_gate.codes, w_gate.scale, w_up.codes, w_up.scale)
+
+
+def _fp8_rows(name: str, x):
+    """The entry check of a product on `Fp8Weight`s -> x as rows [M, K] if the FP8 small-M kernel takes them, else None."""
+    if torch.is_grad_enabled():
+        raise _C.KernelError(f"{name}: an Fp8Weight takes no autograd (FP8 weights are inference only: run under torch.no_grad())")
+    x2 = x.reshape(-1, x.shape[-1])
+    return x2 if x2.shape[0] <= SMALLM_MAX_ROWS and _bf16_rows(x2) else None
+
+
+def _bf16_weight(w):
+    return dequantize_weight_fp8(w) if isinstance(w, Fp8Weight) else w
+
+
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
            accumulate: bool = False) -> torch.Tensor:
     """``a @ b.T (+ bias)`` (``out += ...`` if accumulate) for contraction-contiguous a [M, K], b [N, K]."""
@@ -1418,6 +1532,16 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
         raise _C.KernelError("linear_group: device tensors only (the product path has no CPU fallback)")
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
+    if any(isinstance(w, Fp8Weight) for w in ws):
+        x2 = _fp8_rows("linear_group", x)
+        if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) and w.shape[1] == x2.shape[1] for w in ws)
+                and smallm_fp8_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1])
+                and all(_smallm_bias_ok(w, b) for w, b in layers)
+                and (rope is None or _smallm_rope_ok(x2.shape[0], [w.shape[0] for w in ws], rope))):
+            return [y.view(*x.shape[:-1], -1) for y in linear_smallm_fp8(x2, layers, rope)]
+        # prefill, or an extend with more rows: one conversion per weight and call, then the bf16 path
+        return linear_group(x, [(_bf16_weight(w), b) for w, b in layers], wgrad, dgrad_tn, norm_src, rope,
+                            rope_grad_in_attention)
     if _decode_own(x, ws, bs, rope):          # a decode step's rows: the small-M kernel, rotation in its epilogue
         return linear_smallm(x, layers, rope)
     if not _norm_src_describes(norm_src, x):
@@ -1643,6 +1767,15 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
     if not (x.is_cuda or x.is_meta):
         raise _C.KernelError("swiglu_mlp: device tensors only (the product path has no CPU fallback)")
     M = x.numel() // x.shape[-1]
+    if any(isinstance(w, Fp8Weight) for w in (w_gate, w_up, w_down)):
+        x2 = _fp8_rows("swiglu_mlp", x)
+        if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in (w_gate, w_up))
+                and w_gate.shape == w_up.shape and w_gate.codes.stride(0) == w_up.codes.stride(0)
+                and w_gate.shape[1] == x2.shape[1] and smallm_fp8_supported(M, (w_gate.shape[0],), x2.shape[1])):
+            # a decode step's rows: gate + up + SwiGLU as one launch of the FP8 small-M kernel; down_proj asks for itself
+            act = swiglu_smallm_fp8(x2, w_gate, w_up)
+            return linear_group(act, [(w_down, None)])[0].view(*x.shape[:-1], -1)
+        return swiglu_mlp(x, _bf16_weight(w_gate), _bf16_weight(w_up), _bf16_weight(w_down), norm_src)
     if _decode_own(x, (w_gate, w_up)) and w_gate.stride(0) == w_up.stride(0) and w_gate.shape == w_up.shape \
             and smallm_supported(M, (w_down.shape[0],), w_down.shape[1]) and _bf16_rows(w_down):
         # a decode step's rows: gate + up + SwiGLU as one launch of the small-M kernel, then down_proj on it

@@ -203,6 +203,57 @@ def check_kv_dtype(what: str, value) -> str:
     return value
 
 
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
+
+
+def check_weight_dtype(what: str, value) -> str:
+    if value not in WEIGHT_DTYPES:
+        raise ValueError(f"{what}: weight_dtype = {value!r} must be one of {WEIGHT_DTYPES}")
+    return value
+
+
+class Fp8Linear(torch.nn.Module):
+    """What `quantize_decoder_weights` leaves in an nn.Linear's place: ``weight`` is a functional.Fp8Weight (codes and row
+    scales, no Parameter), ``bias`` the layer's own.  The decoder's callers read `.weight` / `.bias` and hand them to
+    functional.linear_group / swiglu_mlp, which route on the weight's type."""
+
+    def __init__(self, linear: torch.nn.Linear):
+        super().__init__()
+        self.in_features, self.out_features = linear.in_features, linear.out_features
+        self.weight = F.quantize_weight_fp8(linear.weight.detach())
+        self.bias = linear.bias
+
+    def forward(self, x):
+        return F.linear_group(x, [(self.weight, self.bias)])[0]
+
+
+@torch.no_grad()
+def quantize_decoder_weights(model) -> int:
+    """Replaces the seven linear layers of every decoder layer (q / k / v / o_proj, gate / up / down_proj) and lm_head of
+    `model` (a PackedCausalLM, or a model that holds one as `.language_model`, or Kimi-Audio's) by `Fp8Linear`s: e4m3 codes
+    with one power-of-two scale per output row, half the bytes a decode step streams and a card holds.  Layers whose
+    shapes the FP8 small-M kernel does not take (in_features % 128, out_features % 16) stay bf16, and so does
+    embed_tokens — a tied lm_head gets codes of its own.  The bf16 weights are dropped.  Idempotent.  -> bytes freed."""
+    lm = getattr(model, "language_model", None) or model
+    freed = 0
+
+    def swap(owner, name):
+        nonlocal freed
+        lin = getattr(owner, name, None)
+        if (isinstance(lin, torch.nn.Linear) and lin.weight.is_cuda and lin.weight.dtype == torch.bfloat16
+                and F.smallm_fp8_supported(1, (lin.out_features,), lin.in_features)):
+            setattr(owner, name, Fp8Linear(lin))
+            tied = lin.weight is lm.model.embed_tokens.weight       # (its bf16 rows live on as the embedding)
+            freed += (0 if tied else 2 * lin.weight.numel()) - lin.weight.numel() - 4 * lin.out_features
+    for layer in lm.model.layers:
+        for name in ("q_proj", "k_proj", "v_proj", "o_proj"):
+            swap(layer.self_attn, name)
+        for name in ("gate_proj", "up_proj", "down_proj"):
+            swap(layer.mlp, name)
+    swap(lm, "lm_head")
+    return freed
+
+
 def _kv_tensors(kv_dtype: str, num_layers: int, rows: int, S_max: int, Nkv: int, D: int, device, dtype):
     """-> (k, v, k_scale, v_scale) per layer: bf16 [rows, S_max, Nkv, D] without scales, or e4m3 codes (stored as uint8)
     with fp32 scales [rows, S_max, Nkv]"""
@@ -241,10 +292,12 @@ class GenerationConfig:
     nbest: int = 1                           # beam search: the first `nbest` finished hypotheses (1 .. num_beams) — not HF's
                                              # num_return_sequences key, which from_hf goes on refusing
     kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3": e4m3 codes + one power-of-two scale per key (KVCache)
+    weight_dtype: str = "bf16"               # "fp8_e4m3": generate() runs `quantize_decoder_weights` on the model first
 
     def __post_init__(self):
         self.check_scores()
         check_kv_dtype("generation config", self.kv_cache_dtype)
+        check_weight_dtype("generation config", self.weight_dtype)
 
     def check_scores(self) -> None:
         """What the three score knobs accept."""
@@ -300,7 +353,8 @@ class GenerationConfig:
                   # this decoder's own knobs: overrides only (the file's `output_scores` means HF's processed scores)
                   output_scores=bool(overrides.get("output_scores", False)),
                   top_alternatives=overrides.get("top_alternatives", 0), nbest=overrides.get("nbest", 1),
-                  kv_cache_dtype=overrides.get("kv_cache_dtype", "bf16"))
+                  kv_cache_dtype=overrides.get("kv_cache_dtype", "bf16"),
+                  weight_dtype=overrides.get("weight_dtype", "bf16"))
         if cfg.min_new_tokens < 0:
             raise ValueError(f"generation config: min_new_tokens = {cfg.min_new_tokens} must be >= 0")
         if cfg.max_new_tokens is None and "max_new_tokens" in overrides:
@@ -372,6 +426,7 @@ class KimiGenerationConfig:
     output_scores: bool = False              # per-token log-probability and entropy of the raw lm_head logits (`TokenScores`)
     top_alternatives: int = 0                # 0 .. 8 most likely tokens per position (implies output_scores)
     kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3" (GenerationConfig's key; the loop is decode_logits')
+    weight_dtype: str = "bf16"               # "bf16" or "fp8_e4m3" (GenerationConfig's key: `quantize_decoder_weights`)
 
     def __post_init__(self):
         self.check()
@@ -384,6 +439,7 @@ class KimiGenerationConfig:
         """Refuses what tn_kimi_text_step refuses."""
         _check_alternatives("Kimi generation config", self.top_alternatives)
         check_kv_dtype("Kimi generation config", self.kv_cache_dtype)
+        check_weight_dtype("Kimi generation config", self.weight_dtype)
         if not self.text_repetition_penalty > 0.0:
             raise ValueError(f"Kimi generation config: text_repetition_penalty {self.text_repetition_penalty} must be > 0")
         if not 1 <= int(self.text_repetition_window_size) <= KIMI_MAX_WINDOW:
@@ -793,6 +849,8 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
         delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table, scales)
     h, _ = lm.model.norm(delta, residual)
     head = lm.lm_head
+    if isinstance(head.weight, F.Fp8Weight):                         # FP8 codes: `linear_group` routes them
+        return F.linear_group(h, [(head.weight, head.bias)])[0]
     if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the small-M routing
         return F.linear_smallm(h, [(head.weight, None)])[0]
     return head(h)
@@ -951,6 +1009,8 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     cfg.check_scores()
     scored = bool(return_scores) or cfg.wants_scores
     n_alt = int(cfg.top_alternatives)
+    if cfg.weight_dtype == "fp8_e4m3":
+        quantize_decoder_weights(model)
     lm, proj_w = _parts(model)
     _check_model(model, lm)
     if len(prompts) == 0:
@@ -1257,7 +1317,12 @@ def trim_at_eos(ids: torch.Tensor, eos: Union[int, Sequence[int]]) -> List[List[
 
 # ------------------------------------------------------------------------------------ command-line side of the scores
 def add_kv_cache_argument(ap) -> None:
-    """--kv_cache_dtype of the inference command lines."""
+    """--kv_cache_dtype and --weight_dtype of the inference command lines."""
+    ap.add_argument("--weight_dtype", default="bf16", choices=list(WEIGHT_DTYPES),
+                    help="fp8_e4m3: the decoder layers' linear weights and lm_head are converted once after loading to e4m3 "
+                         "codes with one power-of-two scale per output row (half their memory and half the bytes a decode "
+                         "step streams); independent of --kv_cache_dtype; its effect on transcripts has not been measured "
+                         "on a trained checkpoint")
     ap.add_argument("--kv_cache_dtype", default="bf16", choices=list(KV_CACHE_DTYPES),
                     help="fp8_e4m3: keys / values are cached as e4m3 codes with one power-of-two scale per key, D + 4 bytes "
                          "per key instead of 2 D (about half the cache memory and cache traffic); its effect on transcripts "

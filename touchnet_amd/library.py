@@ -1156,6 +1156,86 @@ def _(x, w_gate, w_up):
     return x.new_empty(x.shape[0], w_gate.shape[0])
 
 
+@custom_op(f"{NS}::weight_quantize_fp8", mutates_args=(), device_types="cuda")
+def weight_quantize_fp8(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """bf16 weight [N, K], K % 8 == 0 -> (e4m3 codes uint8 [N, K], fp32 power-of-two scales [N], one per output row)
+    (tn_weight_quantize_fp8: csrc/kv_fp8.h's rules with a weight row in a key's place)."""
+    _no_grad_inputs("weight_quantize_fp8", w)
+    N, K = w.shape
+    codes = torch.empty(N, K, dtype=KV_CODE_DTYPE, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    _C.check(_lib().tn_weight_quantize_fp8(_p(w), _p(codes), _p(scale), N, K, w.stride(0), K, _cur()),
+             "tn_weight_quantize_fp8")
+    return codes, scale
+
+
+@weight_quantize_fp8.register_fake
+def _(w):
+    return (torch.empty(w.shape, dtype=KV_CODE_DTYPE, device=w.device),
+            torch.empty(w.shape[0], dtype=torch.float32, device=w.device))
+
+
+@custom_op(f"{NS}::weight_dequantize_fp8", mutates_args=(), device_types="cuda")
+def weight_dequantize_fp8(codes: Tensor, scale: Tensor) -> Tensor:
+    """codes uint8 [N, K] and scales fp32 [N] -> the bf16 weight code * scale [N, K], exactly (tn_weight_dequantize_fp8)."""
+    N, K = codes.shape
+    w = torch.empty(N, K, dtype=torch.bfloat16, device=codes.device)
+    _C.check(_lib().tn_weight_dequantize_fp8(_p(codes), _p(scale), _p(w), N, K, codes.stride(0), K, _cur()),
+             "tn_weight_dequantize_fp8")
+    return w
+
+
+@weight_dequantize_fp8.register_fake
+def _(codes, scale):
+    return torch.empty(codes.shape, dtype=torch.bfloat16, device=codes.device)
+
+
+def linear_smallm_fp8_launch(x: Tensor, ws, ss, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                             rope_mask: int) -> None:
+    """tn_gemm_smallm_fp8 on operands the caller has checked: `linear_smallm_launch` with ws[i] e4m3 codes [N_i, K] and
+    ss[i] their row scales [N_i]."""
+    n = len(ws)
+    arr = lambda ctype, vals: (ctype * n)(*vals)
+    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
+    _C.check(_lib().tn_gemm_smallm_fp8(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
+                                       arr(ctypes.c_longlong, [w.stride(0) for w in ws]), addr(ss), addr(bs), addr(outs),
+                                       arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
+                                       arr(ctypes.c_int, [w.shape[0] for w in ws]), _p(cos), _p(sin), int(head_dim),
+                                       int(rope_mask), _cur()), "tn_gemm_smallm_fp8")
+
+
+@custom_op(f"{NS}::linear_smallm_fp8", mutates_args=(), device_types="cuda")
+def linear_smallm_fp8(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor],
+                      sin: Optional[Tensor], head_dim: int, rope_mask: int) -> List[Tensor]:
+    """`linear_smallm` on FP8 weights (tn_gemm_smallm_fp8): ws[i] e4m3 codes uint8 [N_i, K], ss[i] fp32 row scales [N_i]."""
+    _no_grad_inputs("linear_smallm_fp8", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_smallm_fp8_launch(x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@linear_smallm_fp8.register_fake
+def _(x, ws, ss, bs, cos, sin, head_dim, rope_mask):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+@custom_op(f"{NS}::swiglu_smallm_fp8", mutates_args=(), device_types="cuda")
+def swiglu_smallm_fp8(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_smallm` on FP8 weights (tn_gemm_smallm_swiglu_fp8): codes [I, K] of one pitch with their row scales [I]."""
+    _no_grad_inputs("swiglu_smallm_fp8", x)
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(_lib().tn_gemm_smallm_swiglu_fp8(_p(x), _p(w_gate), _p(w_up), _p(s_gate), _p(s_up), _p(act), M, w_gate.shape[0],
+                                              K, x.stride(0), w_gate.stride(0), act.stride(0), _cur()),
+             "tn_gemm_smallm_swiglu_fp8")
+    return act
+
+
+@swiglu_smallm_fp8.register_fake
+def _(x, w_gate, s_gate, w_up, s_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
 @custom_op(f"{NS}::greedy_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished"),
            device_types="cuda")
 def greedy_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor, n_unfinished: Tensor,

@@ -53,7 +53,8 @@ def transcribe(model, feats: List[torch.Tensor], cfg: Optional[GenerationConfig]
                             bos_token_id=bos, check_every=cfg.check_every, num_beams=cfg.num_beams,
                             length_penalty=cfg.length_penalty, early_stopping=cfg.early_stopping,
                             sequence_bias=cfg.sequence_bias, min_new_tokens=cfg.min_new_tokens,
-                            output_scores=cfg.output_scores, top_alternatives=cfg.top_alternatives, nbest=cfg.nbest)
+                            output_scores=cfg.output_scores, top_alternatives=cfg.top_alternatives, nbest=cfg.nbest,
+                            kv_cache_dtype=cfg.kv_cache_dtype, weight_dtype=cfg.weight_dtype)
     out = generate(model, build_prompts(feats, pad, bos), gcfg)
     ids, extras = record_fields(out, gcfg, [eos])
     return (ids, extras) if details else ids
