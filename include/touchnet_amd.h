@@ -558,6 +558,23 @@ int tn_gemm_smallm_fp8(const void* x, long long ldx, int M, int K, int nseg, con
 int tn_gemm_smallm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
                               const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
                               long long ldact, void* stream);
+/* gemm_midm, gemm_midm_swiglu, gemm_midm_fp8, gemm_midm_swiglu_fp8: the four entries above for 1 <= M <= 256 rows, on the
+ *      kernel of csrc/gemm_midm.hip — beam search over a batch, large decode batches and chunked extends.  Same arguments,
+ *      same arithmetic rule (bf16-rounded sum + bias, then the RoPE / SwiGLU rule; FP8: the sum times the row scale first),
+ *      same refusals with 256 in 128's place.  A wave walks the whole contraction of its strips in ascending order, so the
+ *      order of an output's K terms again depends on K alone — but it is NOT the small-M entries' order: the two families
+ *      agree bit for bit on integer data only.  X is read once per workgroup and staged through LDS. */
+int tn_gemm_midm(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                 const void* const* bias, void* const* y, const long long* ldy, const int* N, const void* cos_t,
+                 const void* sin_t, int head_dim, int rope_mask, void* stream);
+int tn_gemm_midm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K, long long ldx,
+                        long long ldw, long long ldact, void* stream);
+int tn_gemm_midm_fp8(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                     const float* const* scale, const void* const* bias, void* const* y, const long long* ldy, const int* N,
+                     const void* cos_t, const void* sin_t, int head_dim, int rope_mask, void* stream);
+int tn_gemm_midm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
+                            const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                            long long ldact, void* stream);
 /* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
  *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
  *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history

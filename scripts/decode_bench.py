@@ -548,8 +548,9 @@ COPY_RATE = 6.3e12      # bytes / s: the copy rate DESIGN.md §9 measures every 
 
 def bench_decode_gemm(name, B, steps=24, iters=40):
     """TN_DECODE_GEMM own against lib, and the FP8 weight variant of the small-M kernel against both, at one decoder's
-    widths: every product family of a decode step at M = 1, 12, 48, 96 (weights cycled through > 768 MB of bf16 copies and
-    their FP8 codes, so no call finds its weights in L2 / MALL), then the whole step at B rows with the arms alternated
+    widths: every product family of a decode step at M = 1, 12, 48, 64, 96, 128, 192, 256 (weights cycled through > 768 MB of
+    bf16 copies and their FP8 codes, so no call finds its weights in L2 / MALL) — from 48 rows on with the mid-M kernel's
+    bf16 and FP8 entries (csrc/gemm_midm.hip) beside the library route, and beside the small-M kernel up to its 128 rows —, then the whole step at B rows with the arms alternated
     lib, own, fp8, lib, own, fp8, .. inside this process (fp8: a copy of the model after `quantize_decoder_weights`), and
     the decoder weight bytes resident before and after."""
     import touchnet_amd.functional as F
@@ -584,7 +585,8 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
         F.DECODE_GEMM = "own"
         tiny = timed(lambda ws: F.linear_smallm(ws[0][:1], [(ws[0], None)]), [[rnd(16, 64)]] * 2)
         print(json.dumps(dict(decode_gemm=name, launch_floor_us=round(tiny, 2))), flush=True)
-        for M in (1, 12, 48, 96):
+        for M in (1, 12, 48, 64, 96, 128, 192, 256):
+            small, mid = M <= F.SMALLM_MAX_ROWS, M >= 48
             x, xi, xo = rnd(M, H), rnd(M, I), rnd(M, Nh * D)
             pos = torch.arange(M, device=DEV)[None] + 300
             cos, sin = F.rope_tables(pos, F.rope_inv_freq(D, 10000.0, device=DEV), torch.bfloat16)
@@ -596,6 +598,10 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
             lib_swiglu = (lambda ws: L.swiglu_fwd_t(torch.nn.functional.linear(x, ws[0]), torch.nn.functional.linear(x, ws[1]))) \
                 if M % 8 == 0 else (lambda ws: F.swiglu(*F.linear_group(x, [(ws[0], None), (ws[1], None)])))
             fp8 = lambda inp, rope=None, b=(None,) * 3: (lambda ws: F.linear_smallm_fp8(inp, list(zip(ws, b)), rope))
+            mids = lambda inp, rope=None, b=(None,) * 3: ((lambda ws: F.linear_midm(inp, list(zip(ws, b)), rope)),
+                                                          (lambda ws: F.linear_midm_fp8(inp, list(zip(ws, b)), rope)))
+            mid_fams = {"qkv+rope": mids(x, (cos, sin, D, (0, 1)), bs), "o": mids(xo), "down": mids(xi), "lm_head": mids(x),
+                        "gate/up+swiglu": (lambda ws: F.swiglu_midm(x, *ws), lambda ws: F.swiglu_midm_fp8(x, *ws))}
             fams = {"qkv+rope": (*pair(x, (cos, sin, D, (0, 1)), bs), fp8(x, (cos, sin, D, (0, 1)), bs), x, (Nh + 2 * Nkv) * D),
                     "o": (*pair(xo), fp8(xo), xo, H),
                     "gate/up+swiglu": (lambda ws: F.swiglu_smallm(x, *ws), lib_swiglu, lambda ws: F.swiglu_smallm_fp8(x, *ws), x, I),
@@ -607,6 +613,20 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
                     fp8_sets[fam] = [[F.quantize_weight_fp8(w) for w in ws] for ws in sets]
                 nbytes = sum(w.numel() for w in sets[0]) * 2 + inp.numel() * 2 + M * n_out * 2
                 nbytes8 = nbytes - sum(w.numel() for w in sets[0]) + 4 * sum(w.shape[0] for w in sets[0])
+                if mid:         # every arm twice, alternated: lib, mid-M, mid-M FP8, (small-M FP8,) and again
+                    arms = {"lib": (lib_fn, sets), "midm": (mid_fams[fam][0], sets), "midm_fp8": (mid_fams[fam][1], fp8_sets[fam])}
+                    if small:
+                        arms["smallm_fp8"] = (fp8_fn, fp8_sets[fam])
+                    us = {a: [] for a in arms}
+                    for _ in range(2):
+                        for a, (fn, ws) in arms.items():
+                            us[a].append(round(timed(fn, ws), 2))
+                    rows.append(dict(decode_gemm=name, family=fam, M=M, bytes=nbytes, bytes_fp8=nbytes8,
+                                     **{"us_" + a: v for a, v in us.items()},
+                                     midm_over_lib=round(min(us["midm"]) / min(us["lib"]), 3)))
+                    print(json.dumps(rows[-1]), flush=True)
+                if not small:
+                    continue
                 us_own = timed(own_fn, sets)
                 us_fp8 = timed(fp8_fn, fp8_sets[fam])
                 us_lib = timed(lib_fn, sets)

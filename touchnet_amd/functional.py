@@ -828,12 +828,26 @@ def _fwd_own(a, b, bias=None) -> bool:
 DECODE_GEMM = os.environ.get("TN_DECODE_GEMM", "lib")
 SMALLM_MAX_ROWS = 128
 _DECODE_OWN_MAX_ROWS = 48     # routed up to here: at 96 rows the library wins the 7B widths' layers (DESIGN.md §9.10's table)
+# Rows 49 .. _DECODE_MIDM_MAX_ROWS of the "own" arm go to the mid-M kernel (csrc/gemm_midm.hip).  48 = none: at 48 .. 256
+# rows its layer loses to the library at both 7B widths (DESIGN.md §9.14's table).  FP8 weights have no library arm: above _FP8_SMALLM_MAX_ROWS rows (up to 256) they always
+# run on the mid-M kernel, up to it on the small-M kernel.
+_DECODE_MIDM_MAX_ROWS = 48
+_FP8_SMALLM_MAX_ROWS = 128
+
+
+MIDM_MAX_ROWS = 256
+
+
+def midm_supported(M: int, Ns, K: int, fp8: bool = False) -> bool:
+    """Shapes tn_gemm_midm (fp8: tn_gemm_midm_fp8) takes: 1..256 rows, a contraction of whole 64-deep (128-deep) chunks, 1..3
+    segments of whole 16-row strips."""
+    return (1 <= M <= MIDM_MAX_ROWS and K > 0 and K % (128 if fp8 else 64) == 0 and 1 <= len(Ns) <= 3
+            and all(n > 0 and n % 16 == 0 for n in Ns))
 
 
 def smallm_supported(M: int, Ns, K: int) -> bool:
-    """Shapes tn_gemm_smallm takes: 1..128 rows, a contraction of whole 64-deep chunks, 1..3 segments of whole 16-row strips."""
-    return (1 <= M <= SMALLM_MAX_ROWS and K > 0 and K % 64 == 0 and 1 <= len(Ns) <= 3
-            and all(n > 0 and n % 16 == 0 for n in Ns))
+    """Shapes tn_gemm_smallm takes: `midm_supported`'s up to 128 rows."""
+    return M <= SMALLM_MAX_ROWS and midm_supported(M, Ns, K)
 
 
 def _smallm_rope_ok(M: int, Ns, rope) -> bool:
@@ -844,23 +858,29 @@ def _smallm_rope_ok(M: int, Ns, rope) -> bool:
 
 
 def _decode_own(x, ws, bs=(), rope=None) -> bool:
-    """The small-M kernel runs ``x w_i^T (+ b_i)`` (rotated as ``rope`` of `linear_group` says) and is the configured choice."""
+    """A weight-streaming kernel (`linear_own` says which) runs ``x w_i^T (+ b_i)`` (rotated as ``rope`` of `linear_group`
+    says) and is the configured choice."""
     if DECODE_GEMM != "own" or torch.is_grad_enabled() or x.dim() != 2 or not _bf16_rows(x, *ws):
         return False
     M, K = x.shape
     Ns = [w.shape[0] for w in ws]
-    return (M <= _DECODE_OWN_MAX_ROWS and smallm_supported(M, Ns, K) and all(w.shape[1] == K for w in ws)
+    return (M <= max(_DECODE_OWN_MAX_ROWS, _DECODE_MIDM_MAX_ROWS) and midm_supported(M, Ns, K) and all(w.shape[1] == K for w in ws)
             and all(b is None or (b.is_cuda and b.dtype == torch.bfloat16 and b.dim() == 1 and b.is_contiguous()
                                   and b.data_ptr() % 16 == 0) for b in bs)
             and (rope is None or _smallm_rope_ok(M, Ns, rope)))
 
 
-def _smallm_operands(name: str, x, ws):
-    """by-name refusal of what tn_gemm_smallm would answer with -22"""
+def linear_own(x, layers, rope=None):
+    """What `_decode_own` said yes to, on the kernel that owns the row count: small-M up to 48 rows, mid-M above."""
+    return (linear_smallm if x.shape[0] <= _DECODE_OWN_MAX_ROWS else linear_midm)(x, layers, rope)
+
+
+def _smallm_operands(name: str, x, ws, max_rows: int = SMALLM_MAX_ROWS):
+    """by-name refusal of what tn_gemm_smallm (tn_gemm_midm: max_rows = 256) would answer with -22"""
     if x.dim() != 2 or not _bf16_rows(x, *ws) or any(w.shape[1] != x.shape[1] for w in ws):
         raise _C.KernelError(f"{name}: bf16 device matrices x [M, K], w [N, K] with contiguous 16-byte aligned rows")
-    if not smallm_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
-        raise _C.KernelError(f"{name}: 1 <= M <= {SMALLM_MAX_ROWS}, K % 64 == 0, 1..3 weights with N % 16 == 0 (got M = "
+    if x.shape[0] > max_rows or not midm_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
+        raise _C.KernelError(f"{name}: 1 <= M <= {max_rows}, K % 64 == 0, 1..3 weights with N % 16 == 0 (got M = "
                              f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
 
 
@@ -869,27 +889,30 @@ def linear_smallm(x: torch.Tensor, layers, rope=None, outs=None):
     launch of the weight-streaming kernel (tn_gemm_smallm).  ``rope = (cos, sin, head_dim, (i, j, ..))`` as for
     `linear_group`: those outputs are returned rotated, bit-identical to `apply_rope` of the plain ones.  ``outs``: bf16
     [M, N_i] views to write (row pitch >= N_i; nothing else of their buffers is touched).  Inference only."""
+    return _stream_linear("linear_smallm", SMALLM_MAX_ROWS, x, layers, rope, outs)
+
+
+def _stream_linear(name: str, max_rows: int, x, layers, rope, outs):
+    """`linear_smallm` / `linear_midm` (``name``: the custom op and its ``_launch`` form in `library`)"""
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
-    _smallm_operands("linear_smallm", x, ws)
+    _smallm_operands(name, x, ws, max_rows)
     M = x.shape[0]
-    for w, b in layers:
-        if b is not None and not (b.is_cuda and b.dtype == torch.bfloat16 and tuple(b.shape) == (w.shape[0],)
-                                  and b.is_contiguous() and b.data_ptr() % 16 == 0):
-            raise _C.KernelError("linear_smallm: bias bf16 [N], contiguous, 16-byte aligned")
+    if not all(_smallm_bias_ok(w, b) for w, b in layers):
+        raise _C.KernelError(f"{name}: bias bf16 [N], contiguous, 16-byte aligned")
     cos = sin = None
     D = mask = 0
     if rope is not None and len(rope[3]):
         if not _smallm_rope_ok(M, [w.shape[0] for w in ws], rope):
-            raise _C.KernelError("linear_smallm: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
+            raise _C.KernelError(f"{name}: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
                                  "outputs of whole heads)")
         cos, sin, D = rope[:3]
         mask = sum(1 << int(i) for i in set(rope[3]))
     if outs is None:
-        return list(L.linear_smallm(x, ws, bs, cos, sin, int(D), mask))
+        return list(getattr(L, name)(x, ws, bs, cos, sin, int(D), mask))
     if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
-        raise _C.KernelError("linear_smallm: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
-    L.linear_smallm_launch(x, ws, bs, outs, cos, sin, int(D), mask)
+        raise _C.KernelError(f"{name}: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
+    getattr(L, name + "_launch")(x, ws, bs, outs, cos, sin, int(D), mask)
     return list(outs)
 
 
@@ -904,9 +927,10 @@ def swiglu_smallm(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> 
 
 # FP8 (e4m3) weight-only decode linears (csrc/weight_fp8.hip, the FP8 variant of csrc/gemm_smallm.hip).
 # WHO ANSWERS: `linear_group`, `swiglu_mlp` and generation.decode_logits look for an `Fp8Weight` at their entry.  Up to 128
-# rows with autograd off run on the FP8 small-M kernel whatever TN_DECODE_GEMM says (there is no library arm for codes);
-# anything else — prefill, an extend with more rows, a shape the kernel does not take — dequantises the weight to bf16 for the
-# call and takes the existing path.  Autograd on is refused.
+# rows with autograd off run on the FP8 small-M kernel, 129 .. 256 rows on the FP8 mid-M kernel (csrc/gemm_midm.hip; §9.14),
+# whatever TN_DECODE_GEMM says (there is no library arm for codes); anything else — prefill, an extend with more than 256
+# rows, a shape the kernels do not take — dequantises the weight to bf16 for the call and takes the existing path.
+# Autograd on is refused.
 class Fp8Weight:
     """A weight [N, K] as OCP e4m3 ``codes`` uint8 [N, K] and one fp32 power-of-two ``scale`` per output row [N]
     (`quantize_weight_fp8`); ``codes * scale`` is exact in bf16."""
@@ -952,14 +976,14 @@ def smallm_fp8_supported(M: int, Ns, K: int) -> bool:
     return smallm_supported(M, Ns, K) and K % 128 == 0
 
 
-def _smallm_fp8_operands(name: str, x, ws):
-    """by-name refusal of what tn_gemm_smallm_fp8 would answer with -22"""
+def _smallm_fp8_operands(name: str, x, ws, max_rows: int = SMALLM_MAX_ROWS):
+    """by-name refusal of what tn_gemm_smallm_fp8 (tn_gemm_midm_fp8: max_rows = 256) would answer with -22"""
     if (x.dim() != 2 or not _bf16_rows(x) or not all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in ws)
             or any(w.shape[1] != x.shape[1] for w in ws)):
         raise _C.KernelError(f"{name}: bf16 device matrix x [M, K] and Fp8Weights [N, K] (uint8 codes with contiguous 16-byte "
                              "aligned rows, fp32 scale [N])")
-    if not smallm_fp8_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
-        raise _C.KernelError(f"{name}: 1 <= M <= {SMALLM_MAX_ROWS}, K % 128 == 0, 1..3 weights with N % 16 == 0 (got M = "
+    if x.shape[0] > max_rows or not midm_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1], fp8=True):
+        raise _C.KernelError(f"{name}: 1 <= M <= {max_rows}, K % 128 == 0, 1..3 weights with N % 16 == 0 (got M = "
                              f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
 
 
@@ -972,26 +996,31 @@ def linear_smallm_fp8(x: torch.Tensor, layers, rope=None, outs=None):
     """`linear_smallm` on FP8 weights: ``layers`` = 1..3 (`Fp8Weight` [N_i, K], bias bf16 [N_i] | None) sharing x [M, K],
     M <= 128, K % 128 == 0 -> list of ``bf16(x codes_i^T * scale_i + b_i)`` from ONE launch (tn_gemm_smallm_fp8): the bf16
     kernel's arithmetic on the dequantised weights.  ``rope`` and ``outs`` as there.  Inference only."""
+    return _stream_linear_fp8("linear_smallm_fp8", SMALLM_MAX_ROWS, x, layers, rope, outs)
+
+
+def _stream_linear_fp8(name: str, max_rows: int, x, layers, rope, outs):
+    """`linear_smallm_fp8` / `linear_midm_fp8` (``name``: the custom op and its ``_launch`` form in `library`)"""
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
-    _smallm_fp8_operands("linear_smallm_fp8", x, ws)
+    _smallm_fp8_operands(name, x, ws, max_rows)
     M = x.shape[0]
     if not all(_smallm_bias_ok(w, b) for w, b in layers):
-        raise _C.KernelError("linear_smallm_fp8: bias bf16 [N], contiguous, 16-byte aligned")
+        raise _C.KernelError(f"{name}: bias bf16 [N], contiguous, 16-byte aligned")
     cos = sin = None
     D = mask = 0
     if rope is not None and len(rope[3]):
         if not _smallm_rope_ok(M, [w.shape[0] for w in ws], rope):
-            raise _C.KernelError("linear_smallm_fp8: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
+            raise _C.KernelError(f"{name}: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
                                  "outputs of whole heads)")
         cos, sin, D = rope[:3]
         mask = sum(1 << int(i) for i in set(rope[3]))
     codes, scales = [w.codes for w in ws], [w.scale for w in ws]
     if outs is None:
-        return list(L.linear_smallm_fp8(x, codes, scales, bs, cos, sin, int(D), mask))
+        return list(getattr(L, name)(x, codes, scales, bs, cos, sin, int(D), mask))
     if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
-        raise _C.KernelError("linear_smallm_fp8: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
-    L.linear_smallm_fp8_launch(x, codes, scales, bs, outs, cos, sin, int(D), mask)
+        raise _C.KernelError(f"{name}: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
+    getattr(L, name + "_launch")(x, codes, scales, bs, outs, cos, sin, int(D), mask)
     return list(outs)
 
 
@@ -1004,12 +1033,43 @@ def swiglu_smallm_fp8(x: torch.Tensor, w_gate: Fp8Weight, w_up: Fp8Weight) -> to
     return L.swiglu_smallm_fp8(x, w_gate.codes, w_gate.scale, w_up.codes, w_up.scale)
 
 
+# The mid-M kernel (csrc/gemm_midm.hip): the four entries above up to 256 rows.  A row's result is again
+# independent of M, its index and the other rows, but it is not the small-M kernel's to the last bit (another summation order).
+def linear_midm(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_smallm` for 1 <= M <= 256 rows, ONE launch of tn_gemm_midm: x is staged through LDS once per workgroup and
+    the waves split the output features.  Inference only."""
+    return _stream_linear("linear_midm", MIDM_MAX_ROWS, x, layers, rope, outs)
+
+
+def swiglu_midm(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> torch.Tensor:
+    """`swiglu_smallm` for 1 <= M <= 256 rows (tn_gemm_midm_swiglu): bit-identical to `swiglu` of the two `linear_midm`
+    products.  Inference only."""
+    _smallm_operands("swiglu_midm", x, [w_gate, w_up], MIDM_MAX_ROWS)
+    if w_gate.shape != w_up.shape or w_gate.stride(0) != w_up.stride(0):
+        raise _C.KernelError("swiglu_midm: w_gate / w_up [I, K] of one row pitch")
+    return L.swiglu_midm(x, w_gate, w_up)
+
+
+def linear_midm_fp8(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_smallm_fp8` for 1 <= M <= 256 rows (tn_gemm_midm_fp8): `linear_midm`'s arithmetic on the dequantised weights."""
+    return _stream_linear_fp8("linear_midm_fp8", MIDM_MAX_ROWS, x, layers, rope, outs)
+
+
+def swiglu_midm_fp8(x: torch.Tensor, w_gate: Fp8Weight, w_up: Fp8Weight) -> torch.Tensor:
+    """`swiglu_smallm_fp8` for 1 <= M <= 256 rows (tn_gemm_midm_swiglu_fp8).  Inference only."""
+    _smallm_fp8_operands("swiglu_midm_fp8", x, [w_gate, w_up], MIDM_MAX_ROWS)
+    if w_gate.shape != w_up.shape or w_gate.codes.stride(0) != w_up.codes.stride(0):
+        raise _C.KernelError("swiglu_midm_fp8: w_gate / w_up [I, K] of one row pitch")
+    return L.swiglu_midm_fp8(x, w_gate.codes, w_gate.scale, w_up.codes, w_up.scale)
+
+
 def _fp8_rows(name: str, x):
-    """The entry check of a product on `Fp8Weight`s -> x as rows [M, K] if the FP8 small-M kernel takes them, else None."""
+    """The entry check of a product on `Fp8Weight`s -> x as rows [M, K] if an FP8 kernel takes them (small-M up to 128 rows,
+    mid-M up to 256), else None."""
     if torch.is_grad_enabled():
         raise _C.KernelError(f"{name}: an Fp8Weight takes no autograd (FP8 weights are inference only: run under torch.no_grad())")
     x2 = x.reshape(-1, x.shape[-1])
-    return x2 if x2.shape[0] <= SMALLM_MAX_ROWS and _bf16_rows(x2) else None
+    return x2 if x2.shape[0] <= MIDM_MAX_ROWS and _bf16_rows(x2) else None
 
 
 def _bf16_weight(w):
@@ -1535,15 +1595,16 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
     if any(isinstance(w, Fp8Weight) for w in ws):
         x2 = _fp8_rows("linear_group", x)
         if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) and w.shape[1] == x2.shape[1] for w in ws)
-                and smallm_fp8_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1])
+                and midm_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1], fp8=True)
                 and all(_smallm_bias_ok(w, b) for w, b in layers)
                 and (rope is None or _smallm_rope_ok(x2.shape[0], [w.shape[0] for w in ws], rope))):
-            return [y.view(*x.shape[:-1], -1) for y in linear_smallm_fp8(x2, layers, rope)]
-        # prefill, or an extend with more rows: one conversion per weight and call, then the bf16 path
+            own = linear_smallm_fp8 if x2.shape[0] <= _FP8_SMALLM_MAX_ROWS else linear_midm_fp8
+            return [y.view(*x.shape[:-1], -1) for y in own(x2, layers, rope)]
+        # prefill, or an extend with more than 256 rows: one conversion per weight and call, then the bf16 path
         return linear_group(x, [(_bf16_weight(w), b) for w, b in layers], wgrad, dgrad_tn, norm_src, rope,
                             rope_grad_in_attention)
-    if _decode_own(x, ws, bs, rope):          # a decode step's rows: the small-M kernel, rotation in its epilogue
-        return linear_smallm(x, layers, rope)
+    if _decode_own(x, ws, bs, rope):          # a decode step's rows: a weight-streaming kernel, rotation in its epilogue
+        return linear_own(x, layers, rope)
     if not _norm_src_describes(norm_src, x):
         norm_src = None           # (e.g. under tensor-parallel sequence parallelism x is the gathered sequence): keep x itself
     if rope is not None:
@@ -1771,15 +1832,16 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
         x2 = _fp8_rows("swiglu_mlp", x)
         if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in (w_gate, w_up))
                 and w_gate.shape == w_up.shape and w_gate.codes.stride(0) == w_up.codes.stride(0)
-                and w_gate.shape[1] == x2.shape[1] and smallm_fp8_supported(M, (w_gate.shape[0],), x2.shape[1])):
-            # a decode step's rows: gate + up + SwiGLU as one launch of the FP8 small-M kernel; down_proj asks for itself
-            act = swiglu_smallm_fp8(x2, w_gate, w_up)
+                and w_gate.shape[1] == x2.shape[1] and midm_supported(M, (w_gate.shape[0],), x2.shape[1], fp8=True)):
+            # a decode step's rows: gate + up + SwiGLU as one launch of an FP8 kernel; down_proj asks for itself
+            act = (swiglu_smallm_fp8 if M <= _FP8_SMALLM_MAX_ROWS else swiglu_midm_fp8)(x2, w_gate, w_up)
             return linear_group(act, [(w_down, None)])[0].view(*x.shape[:-1], -1)
         return swiglu_mlp(x, _bf16_weight(w_gate), _bf16_weight(w_up), _bf16_weight(w_down), norm_src)
     if _decode_own(x, (w_gate, w_up)) and w_gate.stride(0) == w_up.stride(0) and w_gate.shape == w_up.shape \
-            and smallm_supported(M, (w_down.shape[0],), w_down.shape[1]) and _bf16_rows(w_down):
-        # a decode step's rows: gate + up + SwiGLU as one launch of the small-M kernel, then down_proj on it
-        return linear_smallm(swiglu_smallm(x, w_gate, w_up), [(w_down, None)])[0]
+            and midm_supported(M, (w_down.shape[0],), w_down.shape[1]) and _bf16_rows(w_down):
+        # a decode step's rows: gate + up + SwiGLU as one launch of a weight-streaming kernel, then down_proj on it
+        act = (swiglu_smallm if M <= _DECODE_OWN_MAX_ROWS else swiglu_midm)(x, w_gate, w_up)
+        return linear_own(act, [(w_down, None)])[0]
     if not _norm_src_describes(norm_src, x):
         norm_src = None
     # (the node's library body transposes x, the weights and dY: `_transposable`)

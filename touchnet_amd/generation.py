@@ -851,8 +851,8 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
     head = lm.lm_head
     if isinstance(head.weight, F.Fp8Weight):                         # FP8 codes: `linear_group` routes them
         return F.linear_group(h, [(head.weight, head.bias)])[0]
-    if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the small-M routing
-        return F.linear_smallm(h, [(head.weight, None)])[0]
+    if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the own-kernel routing
+        return F.linear_own(h, [(head.weight, None)])[0]
     return head(h)
 
 

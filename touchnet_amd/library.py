@@ -1110,18 +1110,24 @@ def _(q, k_new, v_new, k_new_scale, v_new_scale, k_cache, v_cache, k_scale, v_sc
     return torch.empty_like(q, memory_format=torch.contiguous_format)
 
 
+def _stream_gemm_launch(entry: str, x: Tensor, ws, ss, bs, outs, cos, sin, head_dim: int, rope_mask: int) -> None:
+    """One of the weight-streaming linear entries (tn_gemm_smallm / _midm, ss = None; their _fp8 forms, ss = row scales)."""
+    n = len(ws)
+    arr = lambda ctype, vals: (ctype * n)(*vals)
+    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
+    scales = () if ss is None else (addr(ss),)
+    _C.check(getattr(_lib(), entry)(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
+                                    arr(ctypes.c_longlong, [w.stride(0) for w in ws]), *scales, addr(bs), addr(outs),
+                                    arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
+                                    arr(ctypes.c_int, [w.shape[0] for w in ws]), _p(cos), _p(sin), int(head_dim),
+                                    int(rope_mask), _cur()), entry)
+
+
 def linear_smallm_launch(x: Tensor, ws, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
                          rope_mask: int) -> None:
     """tn_gemm_smallm on operands the caller has checked: outs[i][M, N_i] = x ws[i]^T (+ bs[i]), rotated where bit i of
     rope_mask is set.  Row pitches are the tensors' own."""
-    n = len(ws)
-    arr = lambda ctype, vals: (ctype * n)(*vals)
-    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
-    _C.check(_lib().tn_gemm_smallm(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
-                                   arr(ctypes.c_longlong, [w.stride(0) for w in ws]), addr(bs), addr(outs),
-                                   arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
-                                   arr(ctypes.c_int, [w.shape[0] for w in ws]), _p(cos), _p(sin), int(head_dim),
-                                   int(rope_mask), _cur()), "tn_gemm_smallm")
+    _stream_gemm_launch("tn_gemm_smallm", x, ws, None, bs, outs, cos, sin, head_dim, rope_mask)
 
 
 @custom_op(f"{NS}::linear_smallm", mutates_args=(), device_types="cuda")
@@ -1194,14 +1200,7 @@ def linear_smallm_fp8_launch(x: Tensor, ws, ss, bs, outs, cos: Optional[Tensor],
                              rope_mask: int) -> None:
     """tn_gemm_smallm_fp8 on operands the caller has checked: `linear_smallm_launch` with ws[i] e4m3 codes [N_i, K] and
     ss[i] their row scales [N_i]."""
-    n = len(ws)
-    arr = lambda ctype, vals: (ctype * n)(*vals)
-    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
-    _C.check(_lib().tn_gemm_smallm_fp8(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
-                                       arr(ctypes.c_longlong, [w.stride(0) for w in ws]), addr(ss), addr(bs), addr(outs),
-                                       arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
-                                       arr(ctypes.c_int, [w.shape[0] for w in ws]), _p(cos), _p(sin), int(head_dim),
-                                       int(rope_mask), _cur()), "tn_gemm_smallm_fp8")
+    _stream_gemm_launch("tn_gemm_smallm_fp8", x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
 
 
 @custom_op(f"{NS}::linear_smallm_fp8", mutates_args=(), device_types="cuda")
@@ -1232,6 +1231,82 @@ def swiglu_smallm_fp8(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s
 
 
 @swiglu_smallm_fp8.register_fake
+def _(x, w_gate, s_gate, w_up, s_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
+# The mid-M kernel (csrc/gemm_midm.hip, 1..256 rows): the four ops above on its entries, argument for argument.
+def linear_midm_launch(x: Tensor, ws, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                       rope_mask: int) -> None:
+    """tn_gemm_midm on operands the caller has checked (`linear_smallm_launch`'s contract)."""
+    _stream_gemm_launch("tn_gemm_midm", x, ws, None, bs, outs, cos, sin, head_dim, rope_mask)
+
+
+def linear_midm_fp8_launch(x: Tensor, ws, ss, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                           rope_mask: int) -> None:
+    """tn_gemm_midm_fp8 on operands the caller has checked (`linear_smallm_fp8_launch`'s contract)."""
+    _stream_gemm_launch("tn_gemm_midm_fp8", x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+
+
+@custom_op(f"{NS}::linear_midm", mutates_args=(), device_types="cuda")
+def linear_midm(x: Tensor, ws: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor], sin: Optional[Tensor],
+                head_dim: int, rope_mask: int) -> List[Tensor]:
+    """`linear_smallm` on 1..256 rows (tn_gemm_midm): x is staged through LDS once per workgroup."""
+    _no_grad_inputs("linear_midm", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_midm_launch(x, ws, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@linear_midm.register_fake
+def _(x, ws, bs, cos, sin, head_dim, rope_mask):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+@custom_op(f"{NS}::swiglu_midm", mutates_args=(), device_types="cuda")
+def swiglu_midm(x: Tensor, w_gate: Tensor, w_up: Tensor) -> Tensor:
+    """`swiglu_smallm` on 1..256 rows (tn_gemm_midm_swiglu)."""
+    _no_grad_inputs("swiglu_midm", x)
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(_lib().tn_gemm_midm_swiglu(_p(x), _p(w_gate), _p(w_up), _p(act), M, w_gate.shape[0], K, x.stride(0),
+                                        w_gate.stride(0), act.stride(0), _cur()), "tn_gemm_midm_swiglu")
+    return act
+
+
+@swiglu_midm.register_fake
+def _(x, w_gate, w_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
+@custom_op(f"{NS}::linear_midm_fp8", mutates_args=(), device_types="cuda")
+def linear_midm_fp8(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor],
+                    sin: Optional[Tensor], head_dim: int, rope_mask: int) -> List[Tensor]:
+    """`linear_smallm_fp8` on 1..256 rows (tn_gemm_midm_fp8)."""
+    _no_grad_inputs("linear_midm_fp8", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_midm_fp8_launch(x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@linear_midm_fp8.register_fake
+def _(x, ws, ss, bs, cos, sin, head_dim, rope_mask):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+@custom_op(f"{NS}::swiglu_midm_fp8", mutates_args=(), device_types="cuda")
+def swiglu_midm_fp8(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_smallm_fp8` on 1..256 rows (tn_gemm_midm_swiglu_fp8)."""
+    _no_grad_inputs("swiglu_midm_fp8", x)
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(_lib().tn_gemm_midm_swiglu_fp8(_p(x), _p(w_gate), _p(w_up), _p(s_gate), _p(s_up), _p(act), M, w_gate.shape[0],
+                                            K, x.stride(0), w_gate.stride(0), act.stride(0), _cur()),
+             "tn_gemm_midm_swiglu_fp8")
+    return act
+
+
+@swiglu_midm_fp8.register_fake
 def _(x, w_gate, s_gate, w_up, s_up):
     return x.new_empty(x.shape[0], w_gate.shape[0])
 
