@@ -575,6 +575,43 @@ int tn_gemm_midm_fp8(const void* x, long long ldx, int M, int K, int nseg, const
 int tn_gemm_midm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
                             const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
                             long long ldact, void* stream);
+/* MXFP4 weight-only decode linears (csrc/mxfp4.h, csrc/weight_mxfp4.hip, the MXFP4 arms of csrc/gemm_smallm.hip and
+ *      csrc/gemm_midm.hip): a weight [N, K] held in the OCP microscaling FP4 format — codes uint8 [N, K / 2], byte i of a row
+ *      = element 2 i in bits 3:0 and element 2 i + 1 in bits 7:4, each e2m1 (sign, 2 exponent bits, 1 mantissa bit:
+ *      magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; both zeros legal), and scales uint8 [N, K / 32], byte b = 2^(b - 127) for
+ *      elements 32 j .. 32 j + 31 (e8m0; bytes 1 .. 254 are in contract, 0 and 255 are not).
+ * weight_quantize_mxfp4: w bf16 [N, K] (pitch ldw elements) -> codes (pitch ldc bytes), scales (pitch lds bytes), K % 32 == 0.
+ *      Per block of 32: e = the smallest integer >= -100 with amax <= 6 * 2^e, scale byte e + 127, code = e2m1(w * 2^-e),
+ *      round to nearest, ties to the even mantissa bit, the sign bit the input's; an all-zero block gets e = -100 and zero
+ *      codes.  code * scale is exact in bf16.  A block holding a NaN or an infinity gets scale byte 255 and zero codes.
+ *      weight_dequantize_mxfp4: the exact way back, w = bf16(code * scale).  Both: -22 before any launch for NULL or
+ *      misaligned tensors (w and codes 16 bytes), N or K <= 0, K % 32, ldw % 8 or < K, ldc % 16 or < K / 2, lds < K / 32.
+ * gemm_smallm_mxfp4 / gemm_smallm_swiglu_mxfp4 / gemm_midm_mxfp4 / gemm_midm_swiglu_mxfp4: the _fp8 entries with every w_i
+ *      (w_gate, w_up) as MXFP4 codes, ldw in bytes, and scales[i] (scales_gate, scales_up) their block scales with pitch
+ *      lds[i] (lds) in bytes.  Any codes and scales of the format are taken, not only the quantiser's.  Codes are expanded
+ *      exactly to bf16 with their block scale applied in the conversion; y = rbf(acc + bias) with acc the fp32 sum over
+ *      v_mfma_f32_16x16x32_bf16, then the unchanged RoPE / SwiGLU rule: the bf16 entries' arithmetic on the dequantised
+ *      weights, with the same independence of a row from M, its index and the other rows.  -22 before any launch for what
+ *      the bf16 entries refuse and unless K % 128 == 0, ldw >= K / 2, ldw % 16 == 0, every scales pointer non-NULL and
+ *      4-byte aligned, lds >= K / 32 and lds % 4 == 0. */
+int tn_weight_quantize_mxfp4(const void* w, void* codes, void* scales, int N, int K, long long ldw, long long ldc,
+                             long long lds, void* stream);
+int tn_weight_dequantize_mxfp4(const void* codes, const void* scales, void* w, int N, int K, long long ldc, long long lds,
+                               long long ldw, void* stream);
+int tn_gemm_smallm_mxfp4(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                         const unsigned char* const* scales, const long long* lds, const void* const* bias, void* const* y,
+                         const long long* ldy, const int* N, const void* cos_t, const void* sin_t, int head_dim,
+                         int rope_mask, void* stream);
+int tn_gemm_smallm_swiglu_mxfp4(const void* x, const void* w_gate, const void* w_up, const unsigned char* scales_gate,
+                                const unsigned char* scales_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                                long long lds, long long ldact, void* stream);
+int tn_gemm_midm_mxfp4(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                       const unsigned char* const* scales, const long long* lds, const void* const* bias, void* const* y,
+                       const long long* ldy, const int* N, const void* cos_t, const void* sin_t, int head_dim, int rope_mask,
+                       void* stream);
+int tn_gemm_midm_swiglu_mxfp4(const void* x, const void* w_gate, const void* w_up, const unsigned char* scales_gate,
+                              const unsigned char* scales_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                              long long lds, long long ldact, void* stream);
 /* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
  *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
  *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history

@@ -40,6 +40,11 @@ of the new rows), tn_kv_quantize at a 12 x 750-row prefill, the largest logit di
 over one teacher-forced generation of a random-weight model (a recorded number, not a gate), and ms per decode step at
 Qwen2-Audio-7B's widths behind 750 and 8 192 cached positions (profiles/kv_fp8_bench.log).
 
+--decode-gemm-mxfp4 [DECODER]: the MXFP4 arms of the weight-streaming kernels beside the FP8 arms of the same build, alternated
+in one process: the decode step's product families and lm_head at M = 1, 12, 48, 96 (small-M kernel) and 256 (mid-M kernel),
+weights cycled through copies that outgrow L2 / MALL, then the whole step at B rows with lib, own, fp8 and mxfp4 alternated
+(profiles/decode_gemm_mxfp4_bench.log).
+
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
 """
@@ -679,6 +684,99 @@ def bench_decode_gemm(name, B, steps=24, iters=40):
     return rows
 
 
+def bench_decode_gemm_mxfp4(name, B, steps=24, iters=200):
+    """The MXFP4 arm against the FP8 arm per call — every product family of a decode step at M = 1, 12, 48, 96 on the small-M
+    kernel and M = 256 on the mid-M kernel, each arm twice, alternated, on weight sets that outgrow L2 / MALL — then the whole
+    step at B rows with the arms alternated lib, own, fp8, mxfp4 (copies of the model after `quantize_decoder_weights`)."""
+    import copy
+
+    import touchnet_amd.functional as F
+    from touchnet_amd import generation as G
+    from touchnet_amd.models.llama import DecoderConfig, PackedCausalLM
+    kind, H, I, Nh, Nkv, D, layers, V = DECODER_WIDTHS[name]
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: (torch.randn(*s, device=DEV, generator=g) * 0.02).to(torch.bfloat16)
+    bias = kind == "qwen2"
+
+    def timed(fn, sets):
+        it = [0]
+
+        def call():
+            fn(sets[it[0] % len(sets)])
+            it[0] += 1
+        for _ in range(len(sets) + 2):
+            call()
+        torch.cuda.synchronize()
+        return round(_events_time(call, iters), 2)
+
+    with torch.no_grad():
+        shapes = {"qkv+rope": ((Nh * D, H), (Nkv * D, H), (Nkv * D, H)), "o": ((H, Nh * D),), "gate/up+swiglu": ((I, H), (I, H)),
+                  "down": ((H, I),), "lm_head": ((V, H),)}
+        sets = {}
+        for fam, sh in shapes.items():      # (the bf16 weights are dropped as soon as both sets of codes exist)
+            n = max(2, min(48, -(-768 * 2 ** 20 // sum(a * b for a, b in sh))))
+            ws = [[rnd(a, b) for a, b in sh] for _ in range(n)]
+            sets[fam] = ([[F.quantize_weight_fp8(w) for w in s] for s in ws], [[F.quantize_weight_mxfp4(w) for w in s] for s in ws])
+            del ws
+        for M in (1, 12, 48, 96, 256):
+            kern = "smallm" if M <= F.SMALLM_MAX_ROWS else "midm"
+            x, xi, xo = rnd(M, H), rnd(M, I), rnd(M, Nh * D)
+            pos = torch.arange(M, device=DEV)[None] + 300
+            rope = (*F.rope_tables(pos, F.rope_inv_freq(D, 10000.0, device=DEV), torch.bfloat16), D, (0, 1))
+            bs = [rnd(n) if bias else None for n in (Nh * D, Nkv * D, Nkv * D)]
+            for fam, (inp, r, b) in {"qkv+rope": (x, rope, bs), "o": (xo, None, [None]), "gate/up+swiglu": (x, None, None),
+                                     "down": (xi, None, [None]), "lm_head": (x, None, [None])}.items():
+                def arm(fmt, inp=inp, r=r, b=b):
+                    if b is None:
+                        return lambda ws: getattr(F, f"swiglu_{kern}_{fmt}")(inp, *ws)
+                    return lambda ws: getattr(F, f"linear_{kern}_{fmt}")(inp, list(zip(ws, b)), r)
+                us = {"fp8": [], "mxfp4": []}
+                for _ in range(2):
+                    us["fp8"].append(timed(arm("fp8"), sets[fam][0]))
+                    us["mxfp4"].append(timed(arm("mxfp4"), sets[fam][1]))
+                elems = sum(a * b for a, b in shapes[fam])
+                io = inp.numel() * 2 + M * (I if b is None else sum(a for a, _ in shapes[fam])) * 2
+                b8, b4 = elems + 4 * sum(a for a, _ in shapes[fam]) + io, elems // 2 + elems // 32 + io
+                print(json.dumps(dict(decode_gemm_mxfp4=name, kernel=kern, family=fam, M=M, bytes_fp8=b8, bytes_mxfp4=b4,
+                                      us_fp8=us["fp8"], us_mxfp4=us["mxfp4"], tbps_mxfp4=round(b4 / min(us["mxfp4"]) / 1e6, 3),
+                                      mxfp4_over_fp8=round(min(us["mxfp4"]) / min(us["fp8"]), 3),
+                                      bytes_ratio=round(b4 / b8, 3))), flush=True)
+        del sets
+        torch.cuda.empty_cache()
+        text = DecoderConfig.from_dict(dict(model_type=kind, hidden_size=H, intermediate_size=I, num_attention_heads=Nh,
+                                            num_key_value_heads=Nkv, head_dim=D, num_hidden_layers=layers, vocab_size=V,
+                                            rope_theta=10000.0, rms_norm_eps=1e-5, tie_word_embeddings=kind == "llama",
+                                            initializer_range=0.02, eos_token_id=1, pad_token_id=1))
+        torch.manual_seed(0)
+        with torch.device(DEV):
+            lm = PackedCausalLM(text)
+        lm.post_init()
+        lm = lm.to(torch.bfloat16).eval()
+        cache = G.KVCache.allocate(layers, B, 300 + 20 * steps + 8, Nkv, D, DEV)
+        logits = G._prefill(lm, None, G.Prompts([torch.randint(2, 100000, (300,)) for _ in range(B)]), cache, DEV)
+        greedy = lambda lg: F.greedy_step(lg, cache.hist, cache.hist_len, cache.cache_len, cache.finished, cache.n_unfinished,
+                                          1.0, 0, -1, 1)
+        greedy(logits)
+        models = {"lib": lm, "own": lm, "fp8": copy.deepcopy(lm), "mxfp4": copy.deepcopy(lm)}
+        G.quantize_decoder_weights(models["fp8"], "fp8_e4m3")
+        G.quantize_decoder_weights(models["mxfp4"], "mxfp4")
+        code_bytes = lambda m: sum(w.codes.numel() + F._scales_of(w).numel() * F._scales_of(w).element_size()
+                                   for w in (mod.weight for mod in m.modules() if isinstance(mod, (G.Fp8Linear, G.Mxfp4Linear))))
+        ms = {a: [] for a in models}
+        for rnd_i in range(4):              # the first round warms the arms' shapes and is not reported
+            for a, m in models.items():
+                F.DECODE_GEMM = "own" if a == "own" else "lib"
+                greedy(G.decode_logits(m, cache))
+                t = round(_events_time(lambda: greedy(G.decode_logits(m, cache)), steps) / 1e3, 3)
+                if rnd_i:
+                    ms[a].append(t)
+        F.DECODE_GEMM = "lib"
+    print(json.dumps(dict(e2e=f"{name}_decode_step", B=B, layers=layers, **{"ms_" + a: v for a, v in ms.items()},
+                          mxfp4_over_fp8=round(min(ms["mxfp4"]) / min(ms["fp8"]), 3),
+                          mxfp4_over_own=round(min(ms["mxfp4"]) / min(ms["own"]), 3),
+                          code_bytes_fp8=code_bytes(models["fp8"]), code_bytes_mxfp4=code_bytes(models["mxfp4"]))), flush=True)
+
+
 def bench_attn_extend(layers, rounds=5, iters=100):
     """tn_attn_extend per call at the rescoring shape (48 continuations of 32 rows behind 12 shared prompts of 750 rows) at
     both head geometries and at one 750-row turn behind an 8 192-row prefix; then `score_continuations` with and without
@@ -865,6 +963,8 @@ def main():
                     help="tn_token_scores with k = 0 and k = K (default 8) alternatives")
     ap.add_argument("--decode-gemm", nargs="?", const="all", default=None, metavar="DECODER",
                     help="TN_DECODE_GEMM own against lib: per product family and per step (one of DECODER_WIDTHS, default all)")
+    ap.add_argument("--decode-gemm-mxfp4", nargs="?", const="qwen2_audio_7b", default=None, metavar="DECODER",
+                    help="the MXFP4 arms against the FP8 arms per call, and the whole step (profiles/decode_gemm_mxfp4_bench.log)")
     ap.add_argument("--attn-extend", action="store_true",
                     help="tn_attn_extend per call and score_continuations with / without cache= (profiles/attn_extend_bench.log)")
     ap.add_argument("--kv-fp8", action="store_true",
@@ -882,6 +982,9 @@ def main():
     if a.attn_extend:
         for r in bench_attn_extend(a.layers):
             print(json.dumps(r), flush=True)
+        return
+    if a.decode_gemm_mxfp4 is not None:
+        bench_decode_gemm_mxfp4(a.decode_gemm_mxfp4, a.batch)
         return
     if a.decode_gemm is not None:
         for name in (DECODER_WIDTHS if a.decode_gemm == "all" else [a.decode_gemm]):

@@ -190,9 +190,9 @@ def main(argv=None):
         raise RuntimeError("infer_asr needs the MI355X (there is no CPU path)")
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
-    if args.weight_dtype == "fp8_e4m3":
+    if args.weight_dtype != "bf16":
         from touchnet_amd.generation import quantize_decoder_weights
-        quantize_decoder_weights(model)
+        quantize_decoder_weights(model, args.weight_dtype)
     dcfg = data_config(args, model)
     tokenizer = None
     if _first(os.path.join(args.model_path, "tokenizer.json"), os.path.join(args.model_path, "tokenizer_config.json")):

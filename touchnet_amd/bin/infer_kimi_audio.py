@@ -100,9 +100,9 @@ def main(argv=None):
     from transformers import AutoTokenizer
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
-    if args.weight_dtype == "fp8_e4m3":
+    if args.weight_dtype != "bf16":
         from touchnet_amd.generation import quantize_decoder_weights
-        quantize_decoder_weights(model)
+        quantize_decoder_weights(model, args.weight_dtype)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path, trust_remote_code=True)
     cfg.kimia_text_blank = special_id(tokenizer, BLANK, cfg.kimia_text_blank)
     cfg.kimia_text_eos = special_id(tokenizer, EOS, cfg.kimia_text_eos)

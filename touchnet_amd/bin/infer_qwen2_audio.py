@@ -139,9 +139,9 @@ def main(argv=None):
     from transformers import AutoTokenizer
     device = torch.device("cuda", torch.cuda.current_device())
     model = load_model(args.model_path, device)
-    if args.weight_dtype == "fp8_e4m3":
+    if args.weight_dtype != "bf16":
         from touchnet_amd.generation import quantize_decoder_weights
-        quantize_decoder_weights(model)
+        quantize_decoder_weights(model, args.weight_dtype)
     tokenizer = AutoTokenizer.from_pretrained(args.model_path)
     cfg = generation_config(args, tokenizer)
     long_cfg = longform_from_args(args)

@@ -24,6 +24,12 @@
 //  * One fragment of X read from LDS feeds the MFMAs of S strips; accumulators are MT x S x 4 fp32 per lane.
 //  * Epilogues are gemm_stream.h's, per wave on its own strips straight from the accumulators.
 //
+// MXFP4 weights (F = kMxfp4): the chunk stays 128 deep, a 64-byte half line per weight row, so the stage of
+// X, its swizzle and the four LDS reads per tile are the FP8 arm's.  A lane's fragment of W is ONE 16-byte load (32 codes,
+// one scale block) and ONE scale byte, block 4 c + (l >> 4) of its row, issued together; gemm_stream.h's expand32 applies the
+// scale in the conversion.  A fragment is 5 registers, so the ring holds FIVE sets: chunks c + 1 .. c + 4 are in flight under
+// the MFMAs of chunk c, the FP8 ring's bytes, and both halves of a line are asked for by one wave one chunk apart.
+//
 // Every barrier is reached by all four waves: the chunk loop's trip count depends on K alone, a wave whose strips lie past
 // the last one re-reads the last strip and stores nothing, and there is no barrier behind the loop.
 #include <type_traits>
@@ -36,12 +42,20 @@ using namespace wstream;
 
 constexpr int kWaves = 4, kThreads = kWaves * 64;
 constexpr int kMaxM = 256;
-constexpr int kRing = 3;           // fragment sets of W per strip: chunk c + 2 is loaded under the MFMAs of chunk c
+// fragment sets of W per strip: chunk c + kRing - 1 is loaded under the MFMAs of chunk c
+template <Format F> constexpr int kRingOf = F == kMxfp4 ? 5 : 3;
 
-template <int MT, int S, bool F8>
+struct FragM {           // kMxfp4: a lane's 16 bytes of one 64-byte chunk of a weight row, and the scale byte of those 32 codes
+  u32x4_t c;
+  uint32_t sb;
+};
+
+template <int MT, int S, Format F>
 __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
-  using w_t = std::conditional_t<F8, kvq::fp8_t, bf16_t>;      // one stored element of W
-  constexpr int kDepth = F8 ? 128 : 64;                          // contraction steps of a chunk
+  constexpr bool F8 = F != kBf16, F4 = F == kMxfp4;              // (F8: codes, 128-deep chunks and 256-byte rows of X)
+  using w_t = std::conditional_t<F == kBf16, bf16_t, uint8_t>;   // one stored element of W (kMxfp4: a byte of two codes)
+  using WFrag = std::conditional_t<F4, FragM, Frag>;
+  constexpr int kDepth = kDepthOf<F>, kLane = kLaneBytesOf<F>, kRing = kRingOf<F>;
   constexpr int kRowBytes = 2 * kDepth, kSlots = kRowBytes / 16; // a row of X of one chunk, in 16-byte slots
   constexpr int kStage = 16 * MT * kRowBytes;
   constexpr int kRowStep = kThreads / kSlots;                    // rows between a thread's slots of a stage: 32 | 16
@@ -54,11 +68,13 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
 
   // a wave past the last strip re-reads the last strip and stores nothing for it
   const w_t* wp[S];
+  const uint8_t* sp[F4 ? S : 1];
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     int j;
     const Seg& sg = p.seg[locate(p, min(strip0 + s, p.nstrip - 1), j)];
-    wp[s] = strip_row<w_t>(sg, p.head_dim, j, lane);
+    wp[s] = strip_row<w_t, kLane>(sg, p.head_dim, j, lane);
+    if constexpr (F4) sp[s] = strip_scale_row(sg, p.head_dim, j, lane);
   }
 
   // the fill: slot `fslot` of rows frow + kRowStep r.  (swz(row) does not change with r: kRowStep / 2 % 8 == 0 | kRowStep % 16 == 0.)
@@ -90,16 +106,25 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
     for (int t = 0; t < MT; ++t) acc[s][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int nch = p.K / kDepth;
-  Frag w[kRing][S];
-  auto load = [&](Frag (&f)[S], int c) {
+  WFrag w[kRing][S];
+  auto load = [&](WFrag (&f)[S], int c) {
 #pragma unroll
-    for (int s = 0; s < S; ++s) f[s] = load_w(wp[s] + (128 / (int)sizeof(w_t)) * (long long)c);
+    for (int s = 0; s < S; ++s) {
+      if constexpr (F4) {
+        f[s].c = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wp[s] + 64 * (long long)c));
+        f[s].sb = sp[s][4 * (long long)c];
+      } else {
+        f[s] = load_w(wp[s] + (128 / (int)sizeof(w_t)) * (long long)c);
+      }
+    }
   };
-  auto mac = [&](const Frag (&f)[S], const unsigned char* stage) {
+  auto mac = [&](const WFrag (&f)[S], const unsigned char* stage) {
     u32x4_t e[S][kFrag];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      if constexpr (F8) {
+      if constexpr (F4) {
+        expand32(f[s].c, f[s].sb, e[s]);
+      } else if constexpr (F8) {
         expand16(f[s].lo, e[s][0], e[s][1]);
         expand16(f[s].hi, e[s][2], e[s][3]);
       } else {
@@ -121,8 +146,9 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
     }
   };
 
-  load(w[0], 0);
-  if (nch > 1) load(w[1], 1);
+#pragma unroll
+  for (int u = 0; u + 1 < kRing; ++u)
+    if (u < nch) load(w[u], u);
   fetch(0);
 #pragma unroll
   for (int r = 0; r < kPer; ++r)          // the rows behind M of both stages: zeros, once
@@ -139,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
       if (cu >= nch) break;
       __syncthreads();          // stage cu & 1 is filled; nobody reads the other stage any more
       if (cu + 1 < nch) fetch(cu + 1);
-      if (cu + 2 < nch) load(w[(u + 2) % kRing], cu + 2);
+      if (cu + kRing - 1 < nch) load(w[(u + kRing - 1) % kRing], cu + kRing - 1);
       mac(w[u], xs + (cu & 1) * kStage);
       if (cu + 1 < nch) put((cu + 1) & 1);
     }
@@ -153,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
       const Seg& sg = p.seg[locate(p, st, j)];
 #pragma unroll
       for (int t = 0; t < MT; ++t)
-        if (16 * t < p.M) tile_epilogue<F8>(p, sg, j, t, lane, acc[s][t]);
+        if (16 * t < p.M) tile_epilogue<F>(p, sg, j, t, lane, acc[s][t]);
     }
   }
 }
@@ -164,28 +190,33 @@ __global__ __launch_bounds__(kThreads) void kernel(const Params p) {
 // the summation order does not depend on S.
 static inline int strips_per_wave(int nstrip) { return (nstrip + 2 * kWaves - 1) / (2 * kWaves) >= 256 ? 2 : 1; }
 
-template <int MT, bool F8>
+template <int MT, Format F>
 static int launch_mt(const Params& p, hipStream_t st) {
   const int S = strips_per_wave(p.nstrip);
   const dim3 grid((p.nstrip + kWaves * S - 1) / (kWaves * S)), block(kThreads);
   if (S == 2)
-    hipLaunchKernelGGL((kernel<MT, 2, F8>), grid, block, 0, st, p);
+    hipLaunchKernelGGL((kernel<MT, 2, F>), grid, block, 0, st, p);
   else
-    hipLaunchKernelGGL((kernel<MT, 1, F8>), grid, block, 0, st, p);
+    hipLaunchKernelGGL((kernel<MT, 1, F>), grid, block, 0, st, p);
   TN_LAUNCH_CHECK();
   return TN_OK;
 }
 
 // tile counts 4, 6, 8, 12, 16: M rounds up to the next one (the rows behind M are zeros in LDS and cost MFMAs, not traffic)
-static int run(int rc, const Params& p, bool f8, void* stream) {
+template <Format F>
+static int launch(const Params& p, hipStream_t st) {
+  const int mt = (p.M + 15) / 16;
+  if (mt <= 4) return launch_mt<4, F>(p, st);
+  if (mt <= 6) return launch_mt<6, F>(p, st);
+  if (mt <= 8) return launch_mt<8, F>(p, st);
+  if (mt <= 12) return launch_mt<12, F>(p, st);
+  return launch_mt<16, F>(p, st);
+}
+
+static int run(int rc, const Params& p, Format f, void* stream) {
   if (rc != TN_OK) return rc;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int mt = (p.M + 15) / 16;
-  if (mt <= 4) return f8 ? launch_mt<4, true>(p, st) : launch_mt<4, false>(p, st);
-  if (mt <= 6) return f8 ? launch_mt<6, true>(p, st) : launch_mt<6, false>(p, st);
-  if (mt <= 8) return f8 ? launch_mt<8, true>(p, st) : launch_mt<8, false>(p, st);
-  if (mt <= 12) return f8 ? launch_mt<12, true>(p, st) : launch_mt<12, false>(p, st);
-  return f8 ? launch_mt<16, true>(p, st) : launch_mt<16, false>(p, st);
+  return f == kMxfp4 ? launch<kMxfp4>(p, st) : f == kFp8 ? launch<kFp8>(p, st) : launch<kBf16>(p, st);
 }
 
 }  // namespace midm
@@ -198,30 +229,50 @@ extern "C" int tn_gemm_midm(const void* x, long long ldx, int M, int K, int nseg
                             const void* const* bias, void* const* y, const long long* ldy, const int* N, const void* cos_t,
                             const void* sin_t, int head_dim, int rope_mask, void* stream) {
   Params p;
-  return run(linear_params(p, kMaxM, x, ldx, M, K, nseg, w, ldw, nullptr, bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask),
-             p, false, stream);
+  return run(linear_params(p, kMaxM, kBf16, x, ldx, M, K, nseg, w, ldw, nullptr, nullptr, bias, y, ldy, N, cos_t, sin_t,
+                           head_dim, rope_mask),
+             p, kBf16, stream);
 }
 
 extern "C" int tn_gemm_midm_swiglu(const void* x, const void* w_gate, const void* w_up, void* act, int M, int I, int K,
                                    long long ldx, long long ldw, long long ldact, void* stream) {
   Params p;
-  return run(swiglu_params(p, kMaxM, x, w_gate, w_up, nullptr, nullptr, false, act, M, I, K, ldx, ldw, ldact), p, false, stream);
+  return run(swiglu_params(p, kMaxM, kBf16, x, w_gate, w_up, nullptr, nullptr, 0, act, M, I, K, ldx, ldw, ldact), p, kBf16,
+             stream);
 }
 
 extern "C" int tn_gemm_midm_fp8(const void* x, long long ldx, int M, int K, int nseg, const void* const* w,
                                 const long long* ldw, const float* const* scale, const void* const* bias, void* const* y,
                                 const long long* ldy, const int* N, const void* cos_t, const void* sin_t, int head_dim,
                                 int rope_mask, void* stream) {
-  if (scale == nullptr) return TN_EINVAL;
   Params p;
-  return run(linear_params(p, kMaxM, x, ldx, M, K, nseg, w, ldw, scale, bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask),
-             p, true, stream);
+  return run(linear_params(p, kMaxM, kFp8, x, ldx, M, K, nseg, w, ldw, reinterpret_cast<const void* const*>(scale), nullptr,
+                           bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask),
+             p, kFp8, stream);
 }
 
 extern "C" int tn_gemm_midm_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
                                        const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
                                        long long ldact, void* stream) {
   Params p;
-  return run(swiglu_params(p, kMaxM, x, w_gate, w_up, scale_gate, scale_up, true, act, M, I, K, ldx, ldw, ldact), p, true,
+  return run(swiglu_params(p, kMaxM, kFp8, x, w_gate, w_up, scale_gate, scale_up, 0, act, M, I, K, ldx, ldw, ldact), p, kFp8,
              stream);
+}
+
+extern "C" int tn_gemm_midm_mxfp4(const void* x, long long ldx, int M, int K, int nseg, const void* const* w,
+                                  const long long* ldw, const unsigned char* const* scales, const long long* lds,
+                                  const void* const* bias, void* const* y, const long long* ldy, const int* N,
+                                  const void* cos_t, const void* sin_t, int head_dim, int rope_mask, void* stream) {
+  Params p;
+  return run(linear_params(p, kMaxM, kMxfp4, x, ldx, M, K, nseg, w, ldw, reinterpret_cast<const void* const*>(scales), lds,
+                           bias, y, ldy, N, cos_t, sin_t, head_dim, rope_mask),
+             p, kMxfp4, stream);
+}
+
+extern "C" int tn_gemm_midm_swiglu_mxfp4(const void* x, const void* w_gate, const void* w_up, const unsigned char* scales_gate,
+                                         const unsigned char* scales_up, void* act, int M, int I, int K, long long ldx,
+                                         long long ldw, long long lds, long long ldact, void* stream) {
+  Params p;
+  return run(swiglu_params(p, kMaxM, kMxfp4, x, w_gate, w_up, scales_gate, scales_up, lds, act, M, I, K, ldx, ldw, ldact), p,
+             kMxfp4, stream);
 }

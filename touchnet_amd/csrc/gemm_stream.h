@@ -1,28 +1,36 @@
 // What the two weight-streaming decode GEMMs share (gemm_smallm.hip: up to 128 rows, the waves split K; gemm_midm.hip: up to
 // 256 rows, the waves split N and X is staged through LDS): how a launch's strips map to weights and outputs, the lane
-// pattern of a weight fragment, the exact FP8 expansion, the epilogue of one 16 x 16 tile, and the host's entry checks.
+// pattern of a weight fragment, the exact FP8 and MXFP4 expansions, the epilogue of one 16 x 16 tile, and the host's entry
+// checks.
 // Both kernels take W as the 16-row MFMA operand, so a lane holds FOUR output features of ONE row of X (lane l, element e =
 // feature row 4 (l >> 4) + e of the strip, X row l & 15) and everything below holds for both.
 #pragma once
 #include "kv_fp8.h"
+#include "mxfp4.h"
 
 namespace tn {
 namespace wstream {
 
 constexpr int kMaxSeg = 3;
 enum Mode { kPlain = 0, kRope = 1, kSwiglu = 2 };
+// How W is stored.  kBf16: bf16 [N, K].  kFp8: e4m3 codes [N, K] with one fp32 scale per row (kv_fp8.h), applied in the
+// epilogue.  kMxfp4: e2m1 codes [N, K / 2] with one e8m0 scale byte per 32 elements of K (mxfp4.h), applied in the expansion.
+enum Format { kBf16 = 0, kFp8 = 1, kMxfp4 = 2 };
+// contraction steps of a chunk, and the bytes of a weight row's chunk a lane reads (the four lanes of a row cover it)
+template <Format F> constexpr int kDepthOf = F == kBf16 ? 64 : 128;
+template <Format F> constexpr int kLaneBytesOf = F == kMxfp4 ? 16 : 32;
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 
 struct Seg {
-  const void* W;         // [N, K] bf16 (F8: e4m3 codes), pitch ldw elements (kSwiglu: gate_proj)
+  const void* W;         // [N, K] bf16 (kFp8: e4m3 codes; kMxfp4: [N, K / 2] bytes of two codes), pitch ldw elements | bytes
   const void* W2;        // kSwiglu: up_proj, same pitch
-  const float* scale;    // F8: [N] row scales of W (else unused)
-  const float* scale2;   // F8, kSwiglu: those of W2
+  const void* scale;     // kFp8: fp32 [N] row scales of W; kMxfp4: uint8 [N, K / 32] block scales, pitch lds (else unused)
+  const void* scale2;    // kFp8 / kMxfp4, kSwiglu: those of W2
   const bf16_t* bias;    // [N] or null
   bf16_t* Y;             // [M, N], pitch ldy (kSwiglu: act [M, I])
-  long long ldw, ldy;
+  long long ldw, ldy, lds;
   int strip_end;         // strips of segments 0 .. this one
   int mode;
 };
@@ -60,6 +68,14 @@ __device__ __forceinline__ void expand16(const u32x4_t c, u32x4_t& a, u32x4_t& b
   }
 }
 
+// kMxfp4: a lane's 16 bytes of a weight row's 64-byte chunk are 32 codes under ONE scale byte `sb`, the operands of four
+// MFMAs: dword j -> MFMA j, its 8 codes element for element where an FP8 lane's 8 codes sit (mxfp4.h's expand8)
+__device__ __forceinline__ void expand32(const u32x4_t c, uint32_t sb, u32x4_t (&e)[4]) {
+  const float sc = mx4::scale_f32(sb);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) e[j] = mx4::expand8(c[j], sc);
+}
+
 __device__ __forceinline__ float rbf(float v) { return bf2f(f2bf(v)); }
 
 // where strip `st` of the launch lives: its segment and its index inside it
@@ -83,19 +99,28 @@ __device__ __forceinline__ int run_base(int mode, int head_dim, int j, bool seco
   return (j / per) * head_dim + 8 * (j % per) + (second ? head_dim >> 1 : 0);
 }
 
-// the lane's address in strip j of `sg` for a chunk's fragment: row l & 15 of the strip, bytes 32 (l >> 4) .. of its line
-template <typename w_t>
+// the lane's address in strip j of `sg` for a chunk's fragment: row l & 15 of the strip, bytes LB (l >> 4) .. of its chunk
+// (LB = 32: a 128-byte line; kMxfp4's 16: half a line)
+template <typename w_t, int LB = 32>
 __device__ __forceinline__ const w_t* strip_row(const Seg& sg, int head_dim, int j, int lane) {
   const int l15 = lane & 15;
   const bool second = l15 >= 8;
   const w_t* base = static_cast<const w_t*>((sg.mode == kSwiglu && second) ? sg.W2 : sg.W);
-  return base + (long long)(run_base(sg.mode, head_dim, j, second) + (l15 & 7)) * sg.ldw + (32 / (int)sizeof(w_t)) * (lane >> 4);
+  return base + (long long)(run_base(sg.mode, head_dim, j, second) + (l15 & 7)) * sg.ldw + (LB / (int)sizeof(w_t)) * (lane >> 4);
+}
+
+// kMxfp4: ... and of its scale byte: block (l >> 4) of the row's first chunk (a chunk is four blocks, one per lane group)
+__device__ __forceinline__ const uint8_t* strip_scale_row(const Seg& sg, int head_dim, int j, int lane) {
+  const int l15 = lane & 15;
+  const bool second = l15 >= 8;
+  const uint8_t* base = static_cast<const uint8_t*>((sg.mode == kSwiglu && second) ? sg.scale2 : sg.scale);
+  return base + (long long)(run_base(sg.mode, head_dim, j, second) + (l15 & 7)) * sg.lds + (lane >> 4);
 }
 
 // The epilogue of tile t (rows 16 t .. + 15 of X) of strip j of `sg`, run by one whole wave with the finished sums `v` in the
-// MFMA's layout: (F8: x row scale,) + bias, rounded to bf16, then the row kernels' RoPE / SwiGLU rule with the partner of
+// MFMA's layout: (kFp8: x row scale,) + bias, rounded to bf16, then the row kernels' RoPE / SwiGLU rule with the partner of
 // every output in lane l ^ 32, and the store of the rows below M.
-template <bool F8>
+template <Format F>
 __device__ __forceinline__ void tile_epilogue(const Params& p, const Seg& sg, int j, int t, int lane, f32x4_t v) {
   const int l15 = lane & 15, g = lane >> 4, mode = sg.mode;
   const bool second = g >= 2;
@@ -105,8 +130,8 @@ __device__ __forceinline__ void tile_epilogue(const Params& p, const Seg& sg, in
   float own[4], other[4], y[4];
   u32x2_t bv = {0, 0};
   if (sg.bias != nullptr) bv = *reinterpret_cast<const u32x2_t*>(sg.bias + f0);
-  if constexpr (F8)      // the row scales of the lane's four features: the up rows (second run of a SwiGLU strip) have their own
-    v *= *reinterpret_cast<const f32x4_t*>((mode == kSwiglu && second ? sg.scale2 : sg.scale) + f0);
+  if constexpr (F == kFp8)      // the row scales of the lane's four features: the up rows (second run of a SwiGLU strip) have their own
+    v *= *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(mode == kSwiglu && second ? sg.scale2 : sg.scale) + f0);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float b = __uint_as_float(e & 1 ? bv[e >> 1] & 0xffff0000u : bv[e >> 1] << 16);
@@ -143,19 +168,28 @@ __device__ __forceinline__ void tile_epilogue(const Params& p, const Seg& sg, in
 // ---- host: the entries' checks, one set for both kernels (max_m: 128 or 256) -------------------------------------------------
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// (F8: whole 128-deep chunks; weight pitches are bytes of codes and keep the rows 16-byte aligned)
-static inline bool x_ok(const void* x, int M, int max_m, int K, long long ldx, bool f8) {
-  return x != nullptr && aligned16(x) && M >= 1 && M <= max_m && K > 0 && K % (f8 ? 128 : 64) == 0 && ldx >= K && ldx % 8 == 0;
+static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// (codes: whole 128-deep chunks; their weight pitches are bytes and keep the rows 16-byte aligned)
+static inline bool x_ok(const void* x, int M, int max_m, int K, long long ldx, Format f) {
+  return x != nullptr && aligned16(x) && M >= 1 && M <= max_m && K > 0 && K % (f == kBf16 ? 64 : 128) == 0 && ldx >= K && ldx % 8 == 0;
 }
 
-// the linear entries (scale == nullptr: bf16 weights; else scale[i] = the row scales of codes w[i]) -> TN_OK and `p`, or -22
-static inline int linear_params(Params& p, int max_m, const void* x, long long ldx, int M, int K, int nseg,
-                                const void* const* w, const long long* ldw, const float* const* scale,
+// a weight's row pitch, and its scales: kFp8 fp32 [N], 16-byte aligned; kMxfp4 bytes [N, K / 32], 4-byte aligned rows
+static inline bool w_ok(Format f, int K, long long ldw, const void* scale, long long lds) {
+  if (f == kBf16) return ldw >= K && ldw % 8 == 0;
+  if (f == kFp8) return ldw >= K && ldw % 16 == 0 && scale != nullptr && aligned16(scale);
+  return ldw >= K / 2 && ldw % 16 == 0 && scale != nullptr && aligned4(scale) && lds >= K / 32 && lds % 4 == 0;
+}
+
+// the linear entries (scale[i]: the scales of codes w[i], lds[i] their pitch, by `f`; kBf16: both unused) -> TN_OK and `p`, or -22
+static inline int linear_params(Params& p, int max_m, Format f, const void* x, long long ldx, int M, int K, int nseg,
+                                const void* const* w, const long long* ldw, const void* const* scale, const long long* lds,
                                 const void* const* bias, void* const* y, const long long* ldy, const int* N,
                                 const void* cos_t, const void* sin_t, int head_dim, int rope_mask) {
-  const bool f8 = scale != nullptr;
-  if (!x_ok(x, M, max_m, K, ldx, f8) || nseg < 1 || nseg > kMaxSeg || w == nullptr || ldw == nullptr || y == nullptr ||
-      ldy == nullptr || N == nullptr || rope_mask < 0 || rope_mask >= (1 << nseg))
+  if (!x_ok(x, M, max_m, K, ldx, f) || nseg < 1 || nseg > kMaxSeg || w == nullptr || ldw == nullptr || y == nullptr ||
+      ldy == nullptr || N == nullptr || rope_mask < 0 || rope_mask >= (1 << nseg) || (f != kBf16 && scale == nullptr) ||
+      (f == kMxfp4 && lds == nullptr))
     return TN_EINVAL;
   if (rope_mask != 0 && (cos_t == nullptr || sin_t == nullptr || !aligned16(cos_t) || !aligned16(sin_t) ||
                          (head_dim != 64 && head_dim != 128)))
@@ -172,13 +206,15 @@ static inline int linear_params(Params& p, int max_m, const void* x, long long l
   for (int i = 0; i < nseg; ++i) {
     const bool rope = (rope_mask >> i) & 1;
     const void* b = bias != nullptr ? bias[i] : nullptr;
+    const void* sc = f != kBf16 ? scale[i] : nullptr;
+    const long long sp = f == kMxfp4 ? lds[i] : 0;
     if (w[i] == nullptr || y[i] == nullptr || !aligned16(w[i]) || !aligned16(y[i]) || (b != nullptr && !aligned16(b)) ||
-        N[i] <= 0 || N[i] % 16 != 0 || ldw[i] < K || ldw[i] % (f8 ? 16 : 8) != 0 || ldy[i] < N[i] || ldy[i] % 8 != 0 ||
-        (rope && N[i] % head_dim != 0) || (f8 && (scale[i] == nullptr || !aligned16(scale[i]))))
+        N[i] <= 0 || N[i] % 16 != 0 || !w_ok(f, K, ldw[i], sc, sp) || ldy[i] < N[i] || ldy[i] % 8 != 0 ||
+        (rope && N[i] % head_dim != 0))
       return TN_EINVAL;
     strips += N[i] / 16;
-    p.seg[i] = Seg{w[i], nullptr, f8 ? scale[i] : nullptr, nullptr, static_cast<const bf16_t*>(b), static_cast<bf16_t*>(y[i]),
-                   ldw[i], ldy[i], strips, rope ? kRope : kPlain};
+    p.seg[i] = Seg{w[i], nullptr, sc, nullptr, static_cast<const bf16_t*>(b), static_cast<bf16_t*>(y[i]), ldw[i], ldy[i], sp,
+                   strips, rope ? kRope : kPlain};
   }
   for (int i = nseg; i < kMaxSeg; ++i) {
     p.seg[i] = p.seg[nseg - 1];
@@ -188,13 +224,13 @@ static inline int linear_params(Params& p, int max_m, const void* x, long long l
   return TN_OK;
 }
 
-// the SwiGLU entries (f8: codes with their row scales)
-static inline int swiglu_params(Params& p, int max_m, const void* x, const void* w_gate, const void* w_up, const float* s_gate,
-                                const float* s_up, bool f8, void* act, int M, int I, int K, long long ldx, long long ldw,
-                                long long ldact) {
-  if (!x_ok(x, M, max_m, K, ldx, f8) || w_gate == nullptr || w_up == nullptr || act == nullptr || !aligned16(w_gate) ||
-      !aligned16(w_up) || !aligned16(act) || I <= 0 || I % 16 != 0 || ldw < K || ldw % (f8 ? 16 : 8) != 0 || ldact < I ||
-      ldact % 8 != 0 || (f8 && (s_gate == nullptr || s_up == nullptr || !aligned16(s_gate) || !aligned16(s_up))))
+// the SwiGLU entries (codes: s_gate / s_up their scales, of one pitch lds)
+static inline int swiglu_params(Params& p, int max_m, Format f, const void* x, const void* w_gate, const void* w_up,
+                                const void* s_gate, const void* s_up, long long lds, void* act, int M, int I, int K,
+                                long long ldx, long long ldw, long long ldact) {
+  if (!x_ok(x, M, max_m, K, ldx, f) || w_gate == nullptr || w_up == nullptr || act == nullptr || !aligned16(w_gate) ||
+      !aligned16(w_up) || !aligned16(act) || I <= 0 || I % 16 != 0 || !w_ok(f, K, ldw, s_gate, lds) ||
+      !w_ok(f, K, ldw, s_up, lds) || ldact < I || ldact % 8 != 0)
     return TN_EINVAL;
   p = Params{};
   p.X = static_cast<const bf16_t*>(x);
@@ -204,7 +240,7 @@ static inline int swiglu_params(Params& p, int max_m, const void* x, const void*
   p.head_dim = 64;
   p.nstrip = I / 8;                  // a strip = 8 rows of gate_proj + the same 8 of up_proj -> 8 features of act
   for (int i = 0; i < kMaxSeg; ++i)
-    p.seg[i] = Seg{w_gate, w_up, s_gate, s_up, nullptr, static_cast<bf16_t*>(act), ldw, ldact, i == 0 ? p.nstrip : 0x7fffffff,
+    p.seg[i] = Seg{w_gate, w_up, s_gate, s_up, nullptr, static_cast<bf16_t*>(act), ldw, ldact, lds, i == 0 ? p.nstrip : 0x7fffffff,
                    kSwiglu};
   return TN_OK;
 }

@@ -976,12 +976,15 @@ def smallm_fp8_supported(M: int, Ns, K: int) -> bool:
     return smallm_supported(M, Ns, K) and K % 128 == 0
 
 
-def _smallm_fp8_operands(name: str, x, ws, max_rows: int = SMALLM_MAX_ROWS):
-    """by-name refusal of what tn_gemm_smallm_fp8 (tn_gemm_midm_fp8: max_rows = 256) would answer with -22"""
-    if (x.dim() != 2 or not _bf16_rows(x) or not all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in ws)
+def _smallm_fp8_operands(name: str, x, ws, max_rows: int = SMALLM_MAX_ROWS, cls=None):
+    """by-name refusal of what tn_gemm_smallm_fp8 (tn_gemm_midm_fp8: max_rows = 256; ``cls`` = `Mxfp4Weight`: the _mxfp4
+    entries) would answer with -22"""
+    cls = cls or Fp8Weight
+    if (x.dim() != 2 or not _bf16_rows(x) or not all(isinstance(w, cls) and _codes_ok(w) for w in ws)
             or any(w.shape[1] != x.shape[1] for w in ws)):
-        raise _C.KernelError(f"{name}: bf16 device matrix x [M, K] and Fp8Weights [N, K] (uint8 codes with contiguous 16-byte "
-                             "aligned rows, fp32 scale [N])")
+        raise _C.KernelError(f"{name}: bf16 device matrix x [M, K] and {cls.__name__}s [N, K] (" + (
+            "uint8 codes with contiguous 16-byte aligned rows, fp32 scale [N])" if cls is Fp8Weight else
+            "uint8 codes [N, K / 2] with contiguous 16-byte aligned rows, uint8 scales [N, K / 32] with 4-byte aligned rows)"))
     if x.shape[0] > max_rows or not midm_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1], fp8=True):
         raise _C.KernelError(f"{name}: 1 <= M <= {max_rows}, K % 128 == 0, 1..3 weights with N % 16 == 0 (got M = "
                              f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
@@ -999,11 +1002,12 @@ def linear_smallm_fp8(x: torch.Tensor, layers, rope=None, outs=None):
     return _stream_linear_fp8("linear_smallm_fp8", SMALLM_MAX_ROWS, x, layers, rope, outs)
 
 
-def _stream_linear_fp8(name: str, max_rows: int, x, layers, rope, outs):
-    """`linear_smallm_fp8` / `linear_midm_fp8` (``name``: the custom op and its ``_launch`` form in `library`)"""
+def _stream_linear_fp8(name: str, max_rows: int, x, layers, rope, outs, cls=None):
+    """`linear_smallm_fp8` / `linear_midm_fp8` and their _mxfp4 forms (``name``: the custom op and its ``_launch`` form in
+    `library`; ``cls``: the weight class, `Fp8Weight` if None)"""
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
-    _smallm_fp8_operands(name, x, ws, max_rows)
+    _smallm_fp8_operands(name, x, ws, max_rows, cls)
     M = x.shape[0]
     if not all(_smallm_bias_ok(w, b) for w, b in layers):
         raise _C.KernelError(f"{name}: bias bf16 [N], contiguous, 16-byte aligned")
@@ -1015,7 +1019,7 @@ def _stream_linear_fp8(name: str, max_rows: int, x, layers, rope, outs):
                                  "outputs of whole heads)")
         cos, sin, D = rope[:3]
         mask = sum(1 << int(i) for i in set(rope[3]))
-    codes, scales = [w.codes for w in ws], [w.scale for w in ws]
+    codes, scales = [w.codes for w in ws], [_scales_of(w) for w in ws]
     if outs is None:
         return list(getattr(L, name)(x, codes, scales, bs, cos, sin, int(D), mask))
     if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
@@ -1063,17 +1067,135 @@ def swiglu_midm_fp8(x: torch.Tensor, w_gate: Fp8Weight, w_up: Fp8Weight) -> torc
     return L.swiglu_midm_fp8(x, w_gate.codes, w_gate.scale, w_up.codes, w_up.scale)
 
 
-def _fp8_rows(name: str, x):
-    """The entry check of a product on `Fp8Weight`s -> x as rows [M, K] if an FP8 kernel takes them (small-M up to 128 rows,
-    mid-M up to 256), else None."""
+def _fp8_rows(name: str, x, cls=None):
+    """The entry check of a product on `Fp8Weight`s (``cls``: on `Mxfp4Weight`s) -> x as rows [M, K] if a kernel for codes
+    takes them (small-M up to 128 rows, mid-M up to 256), else None."""
     if torch.is_grad_enabled():
-        raise _C.KernelError(f"{name}: an Fp8Weight takes no autograd (FP8 weights are inference only: run under torch.no_grad())")
+        kind = "MXFP4" if cls is Mxfp4Weight else "FP8"
+        raise _C.KernelError(f"{name}: an {(cls or Fp8Weight).__name__} takes no autograd ({kind} weights are inference only: "
+                             "run under torch.no_grad())")
     x2 = x.reshape(-1, x.shape[-1])
     return x2 if x2.shape[0] <= MIDM_MAX_ROWS and _bf16_rows(x2) else None
 
 
 def _bf16_weight(w):
-    return dequantize_weight_fp8(w) if isinstance(w, Fp8Weight) else w
+    return dequantize_weight_fp8(w) if isinstance(w, Fp8Weight) else dequantize_weight_mxfp4(w) if isinstance(w, Mxfp4Weight) else w
+
+
+# MXFP4 weight-only decode linears (csrc/mxfp4.h, csrc/weight_mxfp4.hip, the MXFP4 arms of both weight-streaming kernels;
+# DESIGN.md §9.15).  WHO ANSWERS: as for `Fp8Weight` — `linear_group`, `swiglu_mlp` and generation.decode_logits route an
+# `Mxfp4Weight` through the same code (`_codes_kernels`): up to 128 rows with autograd off the small-M arm, 129 .. 256 rows
+# the mid-M arm, anything else dequantises for the call, autograd on is refused.
+class Mxfp4Weight:
+    """A weight [N, K] in the OCP MXFP4 format: ``codes`` uint8 [N, K / 2] (element 2 i in bits 3:0 of byte i, element 2 i + 1
+    in bits 7:4; e2m1: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) and ``scales`` uint8 [N, K / 32], byte b = 2^(b - 127) for a
+    block of 32 elements (1 <= b <= 254).  Any codes of the format, not only `quantize_weight_mxfp4`'s."""
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
+        self.codes, self.scales = codes, scales
+
+    @property
+    def shape(self):
+        return torch.Size((self.codes.shape[0], 2 * self.codes.shape[1]))
+
+
+QUANTIZED_WEIGHTS = (Fp8Weight, Mxfp4Weight)
+
+
+def _scales_of(w):
+    return w.scale if isinstance(w, Fp8Weight) else w.scales
+
+
+def _mxfp4_weight_ok(w, scale_align: int = 4) -> bool:
+    """codes and scales as the kernels read them (16-byte aligned code rows, 4-byte aligned scale rows; the converters
+    take scale rows of any pitch)"""
+    c, s = w.codes, w.scales
+    return (c.is_cuda and c.dtype == torch.uint8 and c.dim() == 2 and c.stride(1) == 1 and c.stride(0) % 16 == 0
+            and c.data_ptr() % 16 == 0 and c.shape[1] % 16 == 0 and s.is_cuda and s.dtype == torch.uint8
+            and tuple(s.shape) == (c.shape[0], c.shape[1] // 16) and s.stride(1) == 1 and s.stride(0) % scale_align == 0
+            and s.data_ptr() % scale_align == 0)
+
+
+def _codes_ok(w) -> bool:
+    return _fp8_weight_ok(w) if isinstance(w, Fp8Weight) else _mxfp4_weight_ok(w)
+
+
+def _codes_kernels(cls):
+    """(linear small-M, linear mid-M, swiglu small-M, swiglu mid-M) for a class of quantised weights"""
+    if cls is Mxfp4Weight:
+        return linear_smallm_mxfp4, linear_midm_mxfp4, swiglu_smallm_mxfp4, swiglu_midm_mxfp4
+    return linear_smallm_fp8, linear_midm_fp8, swiglu_smallm_fp8, swiglu_midm_fp8
+
+
+def _codes_class(ws):
+    """the class of the first quantised weight among ``ws`` (one call takes one format), or None"""
+    return next((type(w) for w in ws if isinstance(w, QUANTIZED_WEIGHTS)), None)
+
+
+_MXFP4_MAX_ABS = 2.0 ** 120
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
+    """bf16 device weight [N, K], K % 32 == 0 -> `Mxfp4Weight`: per block of 32 along K the scale byte e + 127 with e the
+    smallest integer >= -100 such that the block's amax <= 6 * 2^e, codes = e2m1(w * 2^-e), round to nearest, ties to the
+    even mantissa bit (tn_weight_quantize_mxfp4).  A weight that holds a NaN, an infinity or any |w| >= 2^120 is refused."""
+    if w.dim() != 2 or not _bf16_rows(w) or w.shape[0] < 1 or w.shape[1] < 32 or w.shape[1] % 32:
+        raise _C.KernelError("quantize_weight_mxfp4: a bf16 device matrix [N, K], K % 32 == 0, with contiguous 16-byte aligned rows")
+    if not bool(torch.isfinite(w).all()):          # (weights are static: one host read per weight at load time)
+        raise _C.KernelError("quantize_weight_mxfp4: the weight holds a NaN or an infinity")
+    if not bool((w.abs() < _MXFP4_MAX_ABS).all()):
+        raise _C.KernelError("quantize_weight_mxfp4: the weight holds an |w| >= 2^120 (its block scale would leave the format)")
+    return Mxfp4Weight(*L.weight_quantize_mxfp4(w.detach()))
+
+
+def dequantize_weight_mxfp4(w: Mxfp4Weight) -> torch.Tensor:
+    """-> the bf16 weight ``codes * scales`` [N, K], exactly (tn_weight_dequantize_mxfp4)."""
+    if not isinstance(w, Mxfp4Weight) or not _mxfp4_weight_ok(w, 1):
+        raise _C.KernelError("dequantize_weight_mxfp4: an Mxfp4Weight (uint8 codes [N, K / 2] with 16-byte aligned rows, uint8 "
+                             "scales [N, K / 32], K % 32 == 0)")
+    return L.weight_dequantize_mxfp4(w.codes, w.scales)
+
+
+def smallm_mxfp4_supported(M: int, Ns, K: int) -> bool:
+    """Shapes tn_gemm_smallm_mxfp4 takes: `smallm_fp8_supported`'s (whole 128-deep chunks, whole 16-row strips)."""
+    return smallm_fp8_supported(M, Ns, K)
+
+
+def midm_mxfp4_supported(M: int, Ns, K: int) -> bool:
+    """Shapes tn_gemm_midm_mxfp4 takes: `midm_supported`'s for codes."""
+    return midm_supported(M, Ns, K, fp8=True)
+
+
+def linear_smallm_mxfp4(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_smallm_fp8` on MXFP4 weights: ``layers`` = 1..3 (`Mxfp4Weight` [N_i, K], bias bf16 [N_i] | None) sharing x
+    [M, K], M <= 128, K % 128 == 0 -> list of ``bf16(x dequantize(w_i)^T + b_i)`` from ONE launch (tn_gemm_smallm_mxfp4): the
+    bf16 kernel's arithmetic on the dequantised weights.  ``rope`` and ``outs`` as there.  Inference only."""
+    return _stream_linear_fp8("linear_smallm_mxfp4", SMALLM_MAX_ROWS, x, layers, rope, outs, Mxfp4Weight)
+
+
+def linear_midm_mxfp4(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_smallm_mxfp4` for 1 <= M <= 256 rows (tn_gemm_midm_mxfp4): `linear_midm`'s arithmetic on the dequantised weights."""
+    return _stream_linear_fp8("linear_midm_mxfp4", MIDM_MAX_ROWS, x, layers, rope, outs, Mxfp4Weight)
+
+
+def _swiglu_mxfp4(name: str, max_rows: int, x, w_gate, w_up):
+    _smallm_fp8_operands(name, x, [w_gate, w_up], max_rows, Mxfp4Weight)
+    if (w_gate.shape != w_up.shape or w_gate.codes.stride(0) != w_up.codes.stride(0)
+            or w_gate.scales.stride(0) != w_up.scales.stride(0)):
+        raise _C.KernelError(f"{name}: w_gate / w_up [I, K] of one code pitch and one scale pitch")
+    return getattr(L, name)(x, w_gate.codes, w_gate.scales, w_up.codes, w_up.scales)
+
+
+def swiglu_smallm_mxfp4(x: torch.Tensor, w_gate: Mxfp4Weight, w_up: Mxfp4Weight) -> torch.Tensor:
+    """`swiglu_smallm` on MXFP4 weights, ONE launch (tn_gemm_smallm_swiglu_mxfp4): bit-identical to `swiglu` of the two
+    `linear_smallm_mxfp4` products.  Inference only."""
+    return _swiglu_mxfp4("swiglu_smallm_mxfp4", SMALLM_MAX_ROWS, x, w_gate, w_up)
+
+
+def swiglu_midm_mxfp4(x: torch.Tensor, w_gate: Mxfp4Weight, w_up: Mxfp4Weight) -> torch.Tensor:
+    """`swiglu_smallm_mxfp4` for 1 <= M <= 256 rows (tn_gemm_midm_swiglu_mxfp4).  Inference only."""
+    return _swiglu_mxfp4("swiglu_midm_mxfp4", MIDM_MAX_ROWS, x, w_gate, w_up)
 
 
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -1592,13 +1714,14 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
         raise _C.KernelError("linear_group: device tensors only (the product path has no CPU fallback)")
     ws = [w for w, _ in layers]
     bs = [b for _, b in layers]
-    if any(isinstance(w, Fp8Weight) for w in ws):
-        x2 = _fp8_rows("linear_group", x)
-        if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) and w.shape[1] == x2.shape[1] for w in ws)
+    cls = _codes_class(ws)
+    if cls is not None:
+        x2 = _fp8_rows("linear_group", x, cls)
+        if (x2 is not None and all(isinstance(w, cls) and _codes_ok(w) and w.shape[1] == x2.shape[1] for w in ws)
                 and midm_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1], fp8=True)
                 and all(_smallm_bias_ok(w, b) for w, b in layers)
                 and (rope is None or _smallm_rope_ok(x2.shape[0], [w.shape[0] for w in ws], rope))):
-            own = linear_smallm_fp8 if x2.shape[0] <= _FP8_SMALLM_MAX_ROWS else linear_midm_fp8
+            own = _codes_kernels(cls)[0 if x2.shape[0] <= _FP8_SMALLM_MAX_ROWS else 1]
             return [y.view(*x.shape[:-1], -1) for y in own(x2, layers, rope)]
         # prefill, or an extend with more than 256 rows: one conversion per weight and call, then the bf16 path
         return linear_group(x, [(_bf16_weight(w), b) for w, b in layers], wgrad, dgrad_tn, norm_src, rope,
@@ -1828,13 +1951,15 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
     if not (x.is_cuda or x.is_meta):
         raise _C.KernelError("swiglu_mlp: device tensors only (the product path has no CPU fallback)")
     M = x.numel() // x.shape[-1]
-    if any(isinstance(w, Fp8Weight) for w in (w_gate, w_up, w_down)):
-        x2 = _fp8_rows("swiglu_mlp", x)
-        if (x2 is not None and all(isinstance(w, Fp8Weight) and _fp8_weight_ok(w) for w in (w_gate, w_up))
+    cls = _codes_class((w_gate, w_up, w_down))
+    if cls is not None:
+        x2 = _fp8_rows("swiglu_mlp", x, cls)
+        if (x2 is not None and all(isinstance(w, cls) and _codes_ok(w) for w in (w_gate, w_up))
                 and w_gate.shape == w_up.shape and w_gate.codes.stride(0) == w_up.codes.stride(0)
+                and _scales_of(w_gate).stride(0) == _scales_of(w_up).stride(0)
                 and w_gate.shape[1] == x2.shape[1] and midm_supported(M, (w_gate.shape[0],), x2.shape[1], fp8=True)):
-            # a decode step's rows: gate + up + SwiGLU as one launch of an FP8 kernel; down_proj asks for itself
-            act = (swiglu_smallm_fp8 if M <= _FP8_SMALLM_MAX_ROWS else swiglu_midm_fp8)(x2, w_gate, w_up)
+            # a decode step's rows: gate + up + SwiGLU as one launch of a kernel for codes; down_proj asks for itself
+            act = _codes_kernels(cls)[2 if M <= _FP8_SMALLM_MAX_ROWS else 3](x2, w_gate, w_up)
             return linear_group(act, [(w_down, None)])[0].view(*x.shape[:-1], -1)
         return swiglu_mlp(x, _bf16_weight(w_gate), _bf16_weight(w_up), _bf16_weight(w_down), norm_src)
     if _decode_own(x, (w_gate, w_up)) and w_gate.stride(0) == w_up.stride(0) and w_gate.shape == w_up.shape \

@@ -203,7 +203,7 @@ def check_kv_dtype(what: str, value) -> str:
     return value
 
 
-WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
+WEIGHT_DTYPES = ("bf16", "fp8_e4m3", "mxfp4")
 
 
 def check_weight_dtype(what: str, value) -> str:
@@ -227,13 +227,30 @@ class Fp8Linear(torch.nn.Module):
         return F.linear_group(x, [(self.weight, self.bias)])[0]
 
 
+class Mxfp4Linear(torch.nn.Module):
+    """`Fp8Linear` with ``weight`` a functional.Mxfp4Weight (e2m1 codes and one e8m0 scale byte per 32 elements of K)."""
+
+    def __init__(self, linear: torch.nn.Linear):
+        super().__init__()
+        self.in_features, self.out_features = linear.in_features, linear.out_features
+        self.weight = F.quantize_weight_mxfp4(linear.weight.detach())
+        self.bias = linear.bias
+
+    forward = Fp8Linear.forward
+
+
 @torch.no_grad()
-def quantize_decoder_weights(model) -> int:
+def quantize_decoder_weights(model, weight_dtype: str = "fp8_e4m3") -> int:
     """Replaces the seven linear layers of every decoder layer (q / k / v / o_proj, gate / up / down_proj) and lm_head of
     `model` (a PackedCausalLM, or a model that holds one as `.language_model`, or Kimi-Audio's) by `Fp8Linear`s: e4m3 codes
-    with one power-of-two scale per output row, half the bytes a decode step streams and a card holds.  Layers whose
-    shapes the FP8 small-M kernel does not take (in_features % 128, out_features % 16) stay bf16, and so does
-    embed_tokens — a tied lm_head gets codes of its own.  The bf16 weights are dropped.  Idempotent.  -> bytes freed."""
+    with one power-of-two scale per output row, half the bytes a decode step streams and a card holds — or, with
+    ``weight_dtype`` "mxfp4", by `Mxfp4Linear`s: e2m1 codes with one scale byte per 32 elements, 0.53 bytes per weight.
+    Layers whose shapes the small-M kernel's arms for codes do not take (in_features % 128, out_features % 16) stay bf16,
+    and so does embed_tokens — a tied lm_head gets codes of its own.  The bf16 weights are dropped.  Idempotent (a layer
+    that holds codes of either format is left alone).  -> bytes freed."""
+    if check_weight_dtype("quantize_decoder_weights", weight_dtype) == "bf16":
+        return 0
+    mx = weight_dtype == "mxfp4"
     lm = getattr(model, "language_model", None) or model
     freed = 0
 
@@ -242,9 +259,10 @@ def quantize_decoder_weights(model) -> int:
         lin = getattr(owner, name, None)
         if (isinstance(lin, torch.nn.Linear) and lin.weight.is_cuda and lin.weight.dtype == torch.bfloat16
                 and F.smallm_fp8_supported(1, (lin.out_features,), lin.in_features)):
-            setattr(owner, name, Fp8Linear(lin))
+            setattr(owner, name, (Mxfp4Linear if mx else Fp8Linear)(lin))
             tied = lin.weight is lm.model.embed_tokens.weight       # (its bf16 rows live on as the embedding)
-            freed += (0 if tied else 2 * lin.weight.numel()) - lin.weight.numel() - 4 * lin.out_features
+            held = lin.weight.numel() // 2 + lin.weight.numel() // 32 if mx else lin.weight.numel() + 4 * lin.out_features
+            freed += (0 if tied else 2 * lin.weight.numel()) - held
     for layer in lm.model.layers:
         for name in ("q_proj", "k_proj", "v_proj", "o_proj"):
             swap(layer.self_attn, name)
@@ -292,7 +310,7 @@ class GenerationConfig:
     nbest: int = 1                           # beam search: the first `nbest` finished hypotheses (1 .. num_beams) — not HF's
                                              # num_return_sequences key, which from_hf goes on refusing
     kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3": e4m3 codes + one power-of-two scale per key (KVCache)
-    weight_dtype: str = "bf16"               # "fp8_e4m3": generate() runs `quantize_decoder_weights` on the model first
+    weight_dtype: str = "bf16"               # "fp8_e4m3" | "mxfp4": generate() runs `quantize_decoder_weights` on the model first
 
     def __post_init__(self):
         self.check_scores()
@@ -426,7 +444,7 @@ class KimiGenerationConfig:
     output_scores: bool = False              # per-token log-probability and entropy of the raw lm_head logits (`TokenScores`)
     top_alternatives: int = 0                # 0 .. 8 most likely tokens per position (implies output_scores)
     kv_cache_dtype: str = "bf16"             # "bf16" or "fp8_e4m3" (GenerationConfig's key; the loop is decode_logits')
-    weight_dtype: str = "bf16"               # "bf16" or "fp8_e4m3" (GenerationConfig's key: `quantize_decoder_weights`)
+    weight_dtype: str = "bf16"               # "bf16", "fp8_e4m3" or "mxfp4" (GenerationConfig's key: `quantize_decoder_weights`)
 
     def __post_init__(self):
         self.check()
@@ -849,7 +867,7 @@ def decode_logits(lm, cache, table: Optional[torch.Tensor] = None,
         delta, residual = _decode_layer(layer, delta, residual, cos, sin, kc, vc, cache.cache_len, table, scales)
     h, _ = lm.model.norm(delta, residual)
     head = lm.lm_head
-    if isinstance(head.weight, F.Fp8Weight):                         # FP8 codes: `linear_group` routes them
+    if isinstance(head.weight, F.QUANTIZED_WEIGHTS):                 # FP8 / MXFP4 codes: `linear_group` routes them
         return F.linear_group(h, [(head.weight, head.bias)])[0]
     if head.bias is None and F._decode_own(h, (head.weight,)):       # the decode rows' share of the own-kernel routing
         return F.linear_own(h, [(head.weight, None)])[0]
@@ -1009,8 +1027,8 @@ def generate(model, prompts: Prompts, cfg: Optional[GenerationConfig] = None, re
     cfg.check_scores()
     scored = bool(return_scores) or cfg.wants_scores
     n_alt = int(cfg.top_alternatives)
-    if cfg.weight_dtype == "fp8_e4m3":
-        quantize_decoder_weights(model)
+    if cfg.weight_dtype != "bf16":
+        quantize_decoder_weights(model, cfg.weight_dtype)
     lm, proj_w = _parts(model)
     _check_model(model, lm)
     if len(prompts) == 0:
@@ -1321,8 +1339,9 @@ def add_kv_cache_argument(ap) -> None:
     ap.add_argument("--weight_dtype", default="bf16", choices=list(WEIGHT_DTYPES),
                     help="fp8_e4m3: the decoder layers' linear weights and lm_head are converted once after loading to e4m3 "
                          "codes with one power-of-two scale per output row (half their memory and half the bytes a decode "
-                         "step streams); independent of --kv_cache_dtype; its effect on transcripts has not been measured "
-                         "on a trained checkpoint")
+                         "step streams); mxfp4: to OCP MXFP4, e2m1 codes with one power-of-two scale byte per 32 "
+                         "elements (0.53 bytes per weight); independent of --kv_cache_dtype; the effect of either on "
+                         "transcripts has not been measured on a trained checkpoint")
     ap.add_argument("--kv_cache_dtype", default="bf16", choices=list(KV_CACHE_DTYPES),
                     help="fp8_e4m3: keys / values are cached as e4m3 codes with one power-of-two scale per key, D + 4 bytes "
                          "per key instead of 2 D (about half the cache memory and cache traffic); its effect on transcripts "

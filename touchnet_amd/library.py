@@ -1111,11 +1111,14 @@ def _(q, k_new, v_new, k_new_scale, v_new_scale, k_cache, v_cache, k_scale, v_sc
 
 
 def _stream_gemm_launch(entry: str, x: Tensor, ws, ss, bs, outs, cos, sin, head_dim: int, rope_mask: int) -> None:
-    """One of the weight-streaming linear entries (tn_gemm_smallm / _midm, ss = None; their _fp8 forms, ss = row scales)."""
+    """One of the weight-streaming linear entries (tn_gemm_smallm / _midm, ss = None; their _fp8 forms, ss = row scales;
+    their _mxfp4 forms, ss = block scales, passed with their row pitches)."""
     n = len(ws)
     arr = lambda ctype, vals: (ctype * n)(*vals)
     addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
     scales = () if ss is None else (addr(ss),)
+    if entry.endswith("_mxfp4"):
+        scales += (arr(ctypes.c_longlong, [t.stride(0) for t in ss]),)
     _C.check(getattr(_lib(), entry)(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
                                     arr(ctypes.c_longlong, [w.stride(0) for w in ws]), *scales, addr(bs), addr(outs),
                                     arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
@@ -1307,6 +1310,111 @@ def swiglu_midm_fp8(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_u
 
 
 @swiglu_midm_fp8.register_fake
+def _(x, w_gate, s_gate, w_up, s_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
+# MXFP4 weights (csrc/mxfp4.h, csrc/weight_mxfp4.hip, the MXFP4 arms of both weight-streaming kernels): the FP8 ops above with
+# codes uint8 [N, K / 2] and block scales uint8 [N, K / 32] in the place of codes [N, K] and row scales [N].
+@custom_op(f"{NS}::weight_quantize_mxfp4", mutates_args=(), device_types="cuda")
+def weight_quantize_mxfp4(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """bf16 weight [N, K], K % 32 == 0 -> (e2m1 codes uint8 [N, K / 2], e8m0 scale bytes uint8 [N, K / 32])
+    (tn_weight_quantize_mxfp4: csrc/mxfp4.h's rules)."""
+    _no_grad_inputs("weight_quantize_mxfp4", w)
+    N, K = w.shape
+    codes = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, K // 32, dtype=torch.uint8, device=w.device)
+    _C.check(_lib().tn_weight_quantize_mxfp4(_p(w), _p(codes), _p(scales), N, K, w.stride(0), K // 2, K // 32, _cur()),
+             "tn_weight_quantize_mxfp4")
+    return codes, scales
+
+
+@weight_quantize_mxfp4.register_fake
+def _(w):
+    return (torch.empty(w.shape[0], w.shape[1] // 2, dtype=torch.uint8, device=w.device),
+            torch.empty(w.shape[0], w.shape[1] // 32, dtype=torch.uint8, device=w.device))
+
+
+@custom_op(f"{NS}::weight_dequantize_mxfp4", mutates_args=(), device_types="cuda")
+def weight_dequantize_mxfp4(codes: Tensor, scales: Tensor) -> Tensor:
+    """codes uint8 [N, K / 2] and scale bytes uint8 [N, K / 32] -> the bf16 weight code * scale [N, K], exactly
+    (tn_weight_dequantize_mxfp4)."""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    w = torch.empty(N, K, dtype=torch.bfloat16, device=codes.device)
+    _C.check(_lib().tn_weight_dequantize_mxfp4(_p(codes), _p(scales), _p(w), N, K, codes.stride(0), scales.stride(0), K,
+                                               _cur()), "tn_weight_dequantize_mxfp4")
+    return w
+
+
+@weight_dequantize_mxfp4.register_fake
+def _(codes, scales):
+    return torch.empty(codes.shape[0], 2 * codes.shape[1], dtype=torch.bfloat16, device=codes.device)
+
+
+def linear_smallm_mxfp4_launch(x: Tensor, ws, ss, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                               rope_mask: int) -> None:
+    """tn_gemm_smallm_mxfp4 on operands the caller has checked: `linear_smallm_launch` with ws[i] MXFP4 codes [N_i, K / 2] and
+    ss[i] their block scales [N_i, K / 32]."""
+    _stream_gemm_launch("tn_gemm_smallm_mxfp4", x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+
+
+def linear_midm_mxfp4_launch(x: Tensor, ws, ss, bs, outs, cos: Optional[Tensor], sin: Optional[Tensor], head_dim: int,
+                             rope_mask: int) -> None:
+    """tn_gemm_midm_mxfp4 on operands the caller has checked (`linear_smallm_mxfp4_launch`'s contract)."""
+    _stream_gemm_launch("tn_gemm_midm_mxfp4", x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+
+
+@custom_op(f"{NS}::linear_smallm_mxfp4", mutates_args=(), device_types="cuda")
+def linear_smallm_mxfp4(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor],
+                        sin: Optional[Tensor], head_dim: int, rope_mask: int) -> List[Tensor]:
+    """`linear_smallm` on MXFP4 weights (tn_gemm_smallm_mxfp4): ws[i] codes uint8 [N_i, K / 2], ss[i] scale bytes [N_i, K / 32]."""
+    _no_grad_inputs("linear_smallm_mxfp4", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_smallm_mxfp4_launch(x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@custom_op(f"{NS}::linear_midm_mxfp4", mutates_args=(), device_types="cuda")
+def linear_midm_mxfp4(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]], cos: Optional[Tensor],
+                      sin: Optional[Tensor], head_dim: int, rope_mask: int) -> List[Tensor]:
+    """`linear_smallm_mxfp4` on 1..256 rows (tn_gemm_midm_mxfp4)."""
+    _no_grad_inputs("linear_midm_mxfp4", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_midm_mxfp4_launch(x, ws, ss, bs, outs, cos, sin, head_dim, rope_mask)
+    return outs
+
+
+@linear_smallm_mxfp4.register_fake
+@linear_midm_mxfp4.register_fake
+def _(x, ws, ss, bs, cos, sin, head_dim, rope_mask):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+def _swiglu_mxfp4(entry: str, x, w_gate, s_gate, w_up, s_up):
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(getattr(_lib(), entry)(_p(x), _p(w_gate), _p(w_up), _p(s_gate), _p(s_up), _p(act), M, w_gate.shape[0], K,
+                                    x.stride(0), w_gate.stride(0), s_gate.stride(0), act.stride(0), _cur()), entry)
+    return act
+
+
+@custom_op(f"{NS}::swiglu_smallm_mxfp4", mutates_args=(), device_types="cuda")
+def swiglu_smallm_mxfp4(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_smallm` on MXFP4 weights (tn_gemm_smallm_swiglu_mxfp4): codes [I, K / 2] of one pitch, scale bytes [I, K / 32]
+    of one pitch."""
+    _no_grad_inputs("swiglu_smallm_mxfp4", x)
+    return _swiglu_mxfp4("tn_gemm_smallm_swiglu_mxfp4", x, w_gate, s_gate, w_up, s_up)
+
+
+@custom_op(f"{NS}::swiglu_midm_mxfp4", mutates_args=(), device_types="cuda")
+def swiglu_midm_mxfp4(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_smallm_mxfp4` on 1..256 rows (tn_gemm_midm_swiglu_mxfp4)."""
+    _no_grad_inputs("swiglu_midm_mxfp4", x)
+    return _swiglu_mxfp4("tn_gemm_midm_swiglu_mxfp4", x, w_gate, s_gate, w_up, s_up)
+
+
+@swiglu_smallm_mxfp4.register_fake
+@swiglu_midm_mxfp4.register_fake
 def _(x, w_gate, s_gate, w_up, s_up):
     return x.new_empty(x.shape[0], w_gate.shape[0])
 

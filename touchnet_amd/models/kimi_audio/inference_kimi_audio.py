@@ -141,8 +141,8 @@ def generate_kimi(model, prompts: KimiPrompts, cfg: Optional[KimiGenerationConfi
     cfg.check()
     scored = bool(return_scores) or cfg.wants_scores
     n_alt = int(cfg.top_alternatives)
-    if cfg.weight_dtype == "fp8_e4m3":
-        G.quantize_decoder_weights(model)
+    if cfg.weight_dtype != "bf16":
+        G.quantize_decoder_weights(model, cfg.weight_dtype)
     lm = _TextDecoder(model)
     G._check_model(model, lm)
     B = len(prompts)
