@@ -612,6 +612,27 @@ int tn_gemm_midm_mxfp4(const void* x, long long ldx, int M, int K, int nseg, con
 int tn_gemm_midm_swiglu_mxfp4(const void* x, const void* w_gate, const void* w_up, const unsigned char* scales_gate,
                               const unsigned char* scales_up, void* act, int M, int I, int K, long long ldx, long long ldw,
                               long long lds, long long ldact, void* stream);
+/* gemm_prefill_fp8 / _mxfp4 / _swiglu_fp8 / _swiglu_mxfp4: the linear and SwiGLU entries above on FP8 / MXFP4 codes for ANY
+ *      M >= 1 — prefill and long extends — on the tiled, LDS-staged MFMA kernel of csrc/gemm_codes.hip: X (bf16) and the
+ *      codes of W reach LDS by LDS-DMA in 128-deep chunks, and a code is expanded (exactly) to bf16 when its fragment is read
+ *      from LDS.  Same operands, pitches, alignment rules and arithmetic rule as the _midm entries (bf16 products, fp32 sums,
+ *      FP8: times the row scale, + bias, one rounding to bf16; SwiGLU: tn_swiglu_fwd's rule on the two rounded products),
+ *      without the RoPE arguments: a caller that wants q / k rotated runs tn_rope_apply on the result, which is the same
+ *      bits.  The order of an output's K terms depends on K alone (not on M, N, the row or the tile), but it is not the
+ *      streaming kernels' order.  -22 before any launch for what those entries refuse (except M > 256) and for a pitch
+ *      or K >= 2^23.  Only enqueues on the stream. */
+int tn_gemm_prefill_fp8(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                        const float* const* scale, const void* const* bias, void* const* y, const long long* ldy,
+                        const int* N, void* stream);
+int tn_gemm_prefill_mxfp4(const void* x, long long ldx, int M, int K, int nseg, const void* const* w, const long long* ldw,
+                          const unsigned char* const* scales, const long long* lds, const void* const* bias, void* const* y,
+                          const long long* ldy, const int* N, void* stream);
+int tn_gemm_prefill_swiglu_fp8(const void* x, const void* w_gate, const void* w_up, const float* scale_gate,
+                               const float* scale_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                               long long ldact, void* stream);
+int tn_gemm_prefill_swiglu_mxfp4(const void* x, const void* w_gate, const void* w_up, const unsigned char* scales_gate,
+                                 const unsigned char* scales_up, void* act, int M, int I, int K, long long ldx, long long ldw,
+                                 long long lds, long long ldact, void* stream);
 /* greedy_step: logits [B, V] (`dtype`), V <= 262144; hist int32 [B, S_hist] with hist_len [B]; finished int32 [B];
  *      n_unfinished int32[1].  Per row: fp32 logits, repetition penalty over the ids of hist[b, :hist_len[b]]
  *      (l < 0 ? l * penalty : l / penalty, once per id), -inf on ids that complete an `ngram`-gram of the history

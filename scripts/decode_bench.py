@@ -45,6 +45,11 @@ in one process: the decode step's product families and lm_head at M = 1, 12, 48,
 weights cycled through copies that outgrow L2 / MALL, then the whole step at B rows with lib, own, fp8 and mxfp4 alternated
 (profiles/decode_gemm_mxfp4_bench.log).
 
+--prefill-codes [DECODER]: one decoder layer's seven products (q/k/v + RoPE, o_proj, gate/up + SwiGLU, down_proj) on FP8 and
+MXFP4 weights at M = 257 .. 8192 rows, through `linear_group` / `swiglu_mlp` with the router's row bound at 256 (dequantise per
+call, then the bf16 path) and unbounded (the prefill kernel for codes, csrc/gemm_codes.hip), alternated in one process on weight
+sets cycled past L2 / MALL; achieved TF/s and weight TB/s of the new route beside it (profiles/prefill_codes_bench.log).
+
 bytes per attention call = sum_b (len_b + 1) * Nkv * D * 2 (K and V) * 2 bytes — the cache read; q / o and the appended
 row are noise beside it.
 """
@@ -948,6 +953,53 @@ def bench_kv_fp8(B, rounds=5):
         del caches
 
 
+def bench_prefill_codes(name, rounds=2):
+    """Per format and M: µs of one layer's seven products on the parent route (a: `_CODES_PREFILL_MAX_ROWS` = 256) and on the
+    prefill kernel for codes (b: unbounded), each `rounds` times, alternated a b a b; b / a from the minima."""
+    import touchnet_amd.functional as F
+    kind, H, I, Nh, Nkv, D, _, _ = DECODER_WIDTHS[name]
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: (torch.randn(*s, device=DEV, generator=g) * 0.02).to(torch.bfloat16)
+    shapes = ((Nh * D, H), (Nkv * D, H), (Nkv * D, H), (H, Nh * D), (I, H), (I, H), (H, I))
+    elems = sum(a * b for a, b in shapes)
+    bound = F._CODES_PREFILL_MAX_ROWS
+    with torch.no_grad():
+        for fmt, quant in (("fp8", F.quantize_weight_fp8), ("mxfp4", F.quantize_weight_mxfp4)):
+            nsets = max(2, -(-512 * 2 ** 20 // (elems if fmt == "fp8" else elems // 2)))      # codes cycled past the 256 MB MALL
+            sets = [[quant(rnd(a, b)) for a, b in shapes] for _ in range(nsets)]
+            wbytes = elems + 4 * sum(a for a, _ in shapes) if fmt == "fp8" else elems // 2 + elems // 32
+            for M in (257, 512, 1024, 2048, 4096, 8192):
+                x, xo = rnd(M, H), rnd(M, Nh * D)
+                pos = torch.arange(M, device=DEV)[None] % 750
+                rope = (*F.rope_tables(pos, F.rope_inv_freq(D, 10000.0, device=DEV), torch.bfloat16), D, (0, 1))
+                bs = [rnd(n) if kind == "qwen2" else None for n in (Nh * D, Nkv * D, Nkv * D)]
+                it = [0]
+
+                def layer():
+                    q, k, v, o, wg, wu, wd = sets[it[0] % nsets]
+                    it[0] += 1
+                    F.linear_group(x, [(q, bs[0]), (k, bs[1]), (v, bs[2])], rope=rope)
+                    F.linear_group(xo, [(o, None)])
+                    F.swiglu_mlp(x, wg, wu, wd)
+                flop = 2 * M * elems
+                iters = max(10, min(400, int(2e14 / flop)))       # windows of 0.1 s and more
+                us = {"a": [], "b": []}
+                for _ in range(rounds):
+                    for arm, rows in (("a", 256), ("b", 1 << 30)):
+                        F._CODES_PREFILL_MAX_ROWS = rows
+                        for _ in range(nsets + 1):
+                            layer()
+                        torch.cuda.synchronize()
+                        us[arm].append(round(_events_time(layer, iters), 1))
+                F._CODES_PREFILL_MAX_ROWS = bound
+                b = min(us["b"])
+                print(json.dumps(dict(prefill_codes=name, fmt=fmt, M=M, us_dequant_then_bf16=us["a"], us_codes_kernel=us["b"],
+                                      b_over_a=round(b / min(us["a"]), 3), tflops_codes_kernel=round(flop / b / 1e6, 1),
+                                      weight_tbps_codes_kernel=round(wbytes / b / 1e6, 3))), flush=True)
+            del sets
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-hf", action="store_true")
@@ -965,6 +1017,8 @@ def main():
                     help="TN_DECODE_GEMM own against lib: per product family and per step (one of DECODER_WIDTHS, default all)")
     ap.add_argument("--decode-gemm-mxfp4", nargs="?", const="qwen2_audio_7b", default=None, metavar="DECODER",
                     help="the MXFP4 arms against the FP8 arms per call, and the whole step (profiles/decode_gemm_mxfp4_bench.log)")
+    ap.add_argument("--prefill-codes", nargs="?", const="all", default=None, metavar="DECODER",
+                    help="the prefill kernel for codes against dequantise + bf16 per layer (profiles/prefill_codes_bench.log)")
     ap.add_argument("--attn-extend", action="store_true",
                     help="tn_attn_extend per call and score_continuations with / without cache= (profiles/attn_extend_bench.log)")
     ap.add_argument("--kv-fp8", action="store_true",
@@ -982,6 +1036,10 @@ def main():
     if a.attn_extend:
         for r in bench_attn_extend(a.layers):
             print(json.dumps(r), flush=True)
+        return
+    if a.prefill_codes is not None:
+        for name in (DECODER_WIDTHS if a.prefill_codes == "all" else [a.prefill_codes]):
+            bench_prefill_codes(name)
         return
     if a.decode_gemm_mxfp4 is not None:
         bench_decode_gemm_mxfp4(a.decode_gemm_mxfp4, a.batch)

@@ -125,6 +125,12 @@ PROTOTYPES = {
     "tn_gemm_midm_mxfp4": [_vp, _ll, _i, _i, _i, C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_vp), C.POINTER(_ll),
                            C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_i), _vp, _vp, _i, _i, _vp],
     "tn_gemm_midm_swiglu_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _ll, _vp],
+    "tn_gemm_prefill_fp8": [_vp, _ll, _i, _i, _i, C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_vp), C.POINTER(_vp),
+                            C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_i), _vp],
+    "tn_gemm_prefill_mxfp4": [_vp, _ll, _i, _i, _i, C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_vp), C.POINTER(_ll),
+                              C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_ll), C.POINTER(_i), _vp],
+    "tn_gemm_prefill_swiglu_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _vp],
+    "tn_gemm_prefill_swiglu_mxfp4": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _ll, _ll, _ll, _vp],
     "tn_greedy_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _i, _vp],
     "tn_sample_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _i, _f, _ull, _vp, _i, _i, _i,
                        _vp],

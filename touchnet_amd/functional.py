@@ -928,8 +928,9 @@ def swiglu_smallm(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor) -> 
 # FP8 (e4m3) weight-only decode linears (csrc/weight_fp8.hip, the FP8 variant of csrc/gemm_smallm.hip).
 # WHO ANSWERS: `linear_group`, `swiglu_mlp` and generation.decode_logits look for an `Fp8Weight` at their entry.  Up to 128
 # rows with autograd off run on the FP8 small-M kernel, 129 .. 256 rows on the FP8 mid-M kernel (csrc/gemm_midm.hip; §9.14),
-# whatever TN_DECODE_GEMM says (there is no library arm for codes); anything else — prefill, an extend with more than 256
-# rows, a shape the kernels do not take — dequantises the weight to bf16 for the call and takes the existing path.
+# whatever TN_DECODE_GEMM says (there is no library arm for codes), 257 .. _CODES_PREFILL_MAX_ROWS rows on the prefill kernel
+# for codes (csrc/gemm_codes.hip; §9.16); anything else — more rows, a shape the kernels do not take — dequantises the weight
+# to bf16 for the call and takes the existing path.
 # Autograd on is refused.
 class Fp8Weight:
     """A weight [N, K] as OCP e4m3 ``codes`` uint8 [N, K] and one fp32 power-of-two ``scale`` per output row [N]
@@ -1075,7 +1076,12 @@ def _fp8_rows(name: str, x, cls=None):
         raise _C.KernelError(f"{name}: an {(cls or Fp8Weight).__name__} takes no autograd ({kind} weights are inference only: "
                              "run under torch.no_grad())")
     x2 = x.reshape(-1, x.shape[-1])
-    return x2 if x2.shape[0] <= MIDM_MAX_ROWS and _bf16_rows(x2) else None
+    return x2 if x2.shape[0] <= max(MIDM_MAX_ROWS, _CODES_PREFILL_MAX_ROWS) and _bf16_rows(x2) else None
+
+
+def _codes_arm(M: int) -> int:
+    """which of `_codes_kernels`' linear kernels owns M rows (its SwiGLU form: + 2 | + 1): small-M, mid-M, prefill"""
+    return 0 if M <= _FP8_SMALLM_MAX_ROWS else 1 if M <= MIDM_MAX_ROWS else 4
 
 
 def _bf16_weight(w):
@@ -1122,10 +1128,12 @@ def _codes_ok(w) -> bool:
 
 
 def _codes_kernels(cls):
-    """(linear small-M, linear mid-M, swiglu small-M, swiglu mid-M) for a class of quantised weights"""
+    """(linear small-M, linear mid-M, swiglu small-M, swiglu mid-M, linear prefill, swiglu prefill) for a class of quantised
+    weights"""
     if cls is Mxfp4Weight:
-        return linear_smallm_mxfp4, linear_midm_mxfp4, swiglu_smallm_mxfp4, swiglu_midm_mxfp4
-    return linear_smallm_fp8, linear_midm_fp8, swiglu_smallm_fp8, swiglu_midm_fp8
+        return (linear_smallm_mxfp4, linear_midm_mxfp4, swiglu_smallm_mxfp4, swiglu_midm_mxfp4, linear_prefill_mxfp4,
+                swiglu_prefill_mxfp4)
+    return linear_smallm_fp8, linear_midm_fp8, swiglu_smallm_fp8, swiglu_midm_fp8, linear_prefill_fp8, swiglu_prefill_fp8
 
 
 def _codes_class(ws):
@@ -1196,6 +1204,97 @@ def swiglu_smallm_mxfp4(x: torch.Tensor, w_gate: Mxfp4Weight, w_up: Mxfp4Weight)
 def swiglu_midm_mxfp4(x: torch.Tensor, w_gate: Mxfp4Weight, w_up: Mxfp4Weight) -> torch.Tensor:
     """`swiglu_smallm_mxfp4` for 1 <= M <= 256 rows (tn_gemm_midm_swiglu_mxfp4).  Inference only."""
     return _swiglu_mxfp4("swiglu_midm_mxfp4", MIDM_MAX_ROWS, x, w_gate, w_up)
+
+
+# The prefill kernel for codes (csrc/gemm_codes.hip; DESIGN.md §9.16): a tiled, LDS-staged MFMA GEMM that reads FP8 / MXFP4
+# codes directly, for ANY row count.  WHO ANSWERS: the two fallback branches of `linear_group` and `swiglu_mlp` send
+# 257 .. _CODES_PREFILL_MAX_ROWS rows here instead of dequantising; up to 256 rows stay on the streaming kernels.
+# 512: the largest measured row count up to which one decoder layer on this kernel stays within 1.05 of dequantise + bf16 at
+# all three decoder widths (DESIGN.md §9.16's table: 0.51 - 0.82 of it at 512 rows, 1.16 - 1.20 at Kimi-Audio's widths at 1024).
+_CODES_PREFILL_MAX_ROWS = 512
+
+
+def prefill_codes_supported(M: int, Ns, K: int) -> bool:
+    """Shapes tn_gemm_prefill_fp8 / _mxfp4 take: `smallm_fp8_supported`'s (whole 128-deep chunks, 1..3 weights of whole 16-row
+    strips) at any M >= 1."""
+    return M >= 1 and midm_supported(1, Ns, K, fp8=True)
+
+
+def _prefill_operands(name: str, x, ws, cls):
+    """by-name refusal of what tn_gemm_prefill_fp8 / _mxfp4 would answer with -22"""
+    if (x.dim() != 2 or not _bf16_rows(x) or not all(isinstance(w, cls) and _codes_ok(w) for w in ws)
+            or any(w.shape[1] != x.shape[1] for w in ws)):
+        raise _C.KernelError(f"{name}: bf16 device matrix x [M, K] and {cls.__name__}s [N, K] (" + (
+            "uint8 codes with contiguous 16-byte aligned rows, fp32 scale [N])" if cls is Fp8Weight else
+            "uint8 codes [N, K / 2] with contiguous 16-byte aligned rows, uint8 scales [N, K / 32] with 4-byte aligned rows)"))
+    if not prefill_codes_supported(x.shape[0], [w.shape[0] for w in ws], x.shape[1]):
+        raise _C.KernelError(f"{name}: M >= 1, K % 128 == 0, 1..3 weights with N % 16 == 0 (got M = "
+                             f"{x.shape[0]}, K = {x.shape[1]}, N = {[w.shape[0] for w in ws]})")
+
+
+def _prefill_linear(name: str, cls, x, layers, rope, outs):
+    ws = [w for w, _ in layers]
+    bs = [b for _, b in layers]
+    _prefill_operands(name, x, ws, cls)
+    M = x.shape[0]
+    if not all(_smallm_bias_ok(w, b) for w, b in layers):
+        raise _C.KernelError(f"{name}: bias bf16 [N], contiguous, 16-byte aligned")
+    which = ()
+    if rope is not None and len(rope[3]):
+        if not _smallm_rope_ok(M, [w.shape[0] for w in ws], rope):
+            raise _C.KernelError(f"{name}: rope = (cos, sin bf16 [M, head_dim / 2], head_dim 64 | 128, indices of "
+                                 "outputs of whole heads)")
+        which = sorted(set(int(i) for i in rope[3]))
+    codes, scales = [w.codes for w in ws], [_scales_of(w) for w in ws]
+    if outs is None:
+        ys = list(getattr(L, name)(x, codes, scales, bs))
+    else:
+        if len(outs) != len(ws) or not _bf16_rows(*outs) or any(tuple(o.shape) != (M, w.shape[0]) for o, w in zip(outs, ws)):
+            raise _C.KernelError(f"{name}: outs bf16 [M, N_i] device views with contiguous 16-byte aligned rows")
+        getattr(L, name + "_launch")(x, codes, scales, bs, outs)
+        ys = list(outs)
+    # RoPE: the rotary row kernel on the plain product (rounded to bf16, then rotated: the epilogues' rule, the same bits)
+    for i in range(0, len(which), 2):
+        cos, sin, D = rope[:3]
+        a = ys[which[i]]
+        b = ys[which[i + 1]] if i + 1 < len(which) else a.new_empty(M, 0)
+        ra, rb = apply_rope(a.view(1, M, -1, D), b.view(1, M, -1, D), cos, sin)
+        for j, r in zip(which[i:i + 2], (ra, rb)):
+            ys[j] = r.view(M, -1) if outs is None else outs[j].copy_(r.view(M, -1))
+    return ys
+
+
+def linear_prefill_fp8(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_midm_fp8` for ANY M >= 1 rows on the tiled kernel for codes (tn_gemm_prefill_fp8): ``layers`` = 1..3
+    (`Fp8Weight` [N_i, K], bias bf16 [N_i] | None) sharing x [M, K], K % 128 == 0 -> list of ``bf16(x codes_i^T * scale_i +
+    b_i)`` from ONE launch; a row's result does not depend on M, its index or the other rows.  ``rope``: those outputs are
+    rotated by the rotary row kernel behind the launch — bit-identical to `apply_rope` of the plain ones.  Inference only."""
+    return _prefill_linear("linear_prefill_fp8", Fp8Weight, x, layers, rope, outs)
+
+
+def linear_prefill_mxfp4(x: torch.Tensor, layers, rope=None, outs=None):
+    """`linear_prefill_fp8` on `Mxfp4Weight`s (tn_gemm_prefill_mxfp4)."""
+    return _prefill_linear("linear_prefill_mxfp4", Mxfp4Weight, x, layers, rope, outs)
+
+
+def _prefill_swiglu(name: str, cls, x, w_gate, w_up):
+    _prefill_operands(name, x, [w_gate, w_up], cls)
+    if (w_gate.shape != w_up.shape or w_gate.codes.stride(0) != w_up.codes.stride(0)
+            or (cls is Mxfp4Weight and w_gate.scales.stride(0) != w_up.scales.stride(0))):
+        raise _C.KernelError(f"{name}: w_gate / w_up [I, K] of one code pitch" + (" and one scale pitch" if cls is Mxfp4Weight
+                                                                                    else ""))
+    return getattr(L, name)(x, w_gate.codes, _scales_of(w_gate), w_up.codes, _scales_of(w_up))
+
+
+def swiglu_prefill_fp8(x: torch.Tensor, w_gate: Fp8Weight, w_up: Fp8Weight) -> torch.Tensor:
+    """``silu(x w_gate^T) * (x w_up^T)`` [M, I] for ANY M >= 1 from ONE launch (tn_gemm_prefill_swiglu_fp8): bit-identical to
+    `swiglu` of the two `linear_prefill_fp8` products; neither of them is stored.  Inference only."""
+    return _prefill_swiglu("swiglu_prefill_fp8", Fp8Weight, x, w_gate, w_up)
+
+
+def swiglu_prefill_mxfp4(x: torch.Tensor, w_gate: Mxfp4Weight, w_up: Mxfp4Weight) -> torch.Tensor:
+    """`swiglu_prefill_fp8` on `Mxfp4Weight`s (tn_gemm_prefill_swiglu_mxfp4)."""
+    return _prefill_swiglu("swiglu_prefill_mxfp4", Mxfp4Weight, x, w_gate, w_up)
 
 
 def _mm_tn(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -1718,12 +1817,13 @@ def linear_group(x, layers, wgrad: str = "tn", dgrad_tn: bool = True, norm_src=N
     if cls is not None:
         x2 = _fp8_rows("linear_group", x, cls)
         if (x2 is not None and all(isinstance(w, cls) and _codes_ok(w) and w.shape[1] == x2.shape[1] for w in ws)
-                and midm_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1], fp8=True)
+                and prefill_codes_supported(x2.shape[0], [w.shape[0] for w in ws], x2.shape[1])
                 and all(_smallm_bias_ok(w, b) for w, b in layers)
                 and (rope is None or _smallm_rope_ok(x2.shape[0], [w.shape[0] for w in ws], rope))):
-            own = _codes_kernels(cls)[0 if x2.shape[0] <= _FP8_SMALLM_MAX_ROWS else 1]
+            own = _codes_kernels(cls)[_codes_arm(x2.shape[0])]
             return [y.view(*x.shape[:-1], -1) for y in own(x2, layers, rope)]
-        # prefill, or an extend with more than 256 rows: one conversion per weight and call, then the bf16 path
+        # more rows than _CODES_PREFILL_MAX_ROWS, or a shape no kernel for codes takes: one conversion per weight and call,
+        # then the bf16 path
         return linear_group(x, [(_bf16_weight(w), b) for w, b in layers], wgrad, dgrad_tn, norm_src, rope,
                             rope_grad_in_attention)
     if _decode_own(x, ws, bs, rope):          # a decode step's rows: a weight-streaming kernel, rotation in its epilogue
@@ -1957,9 +2057,10 @@ def swiglu_mlp(x, w_gate, w_up, w_down, norm_src=None):
         if (x2 is not None and all(isinstance(w, cls) and _codes_ok(w) for w in (w_gate, w_up))
                 and w_gate.shape == w_up.shape and w_gate.codes.stride(0) == w_up.codes.stride(0)
                 and _scales_of(w_gate).stride(0) == _scales_of(w_up).stride(0)
-                and w_gate.shape[1] == x2.shape[1] and midm_supported(M, (w_gate.shape[0],), x2.shape[1], fp8=True)):
-            # a decode step's rows: gate + up + SwiGLU as one launch of a kernel for codes; down_proj asks for itself
-            act = _codes_kernels(cls)[2 if M <= _FP8_SMALLM_MAX_ROWS else 3](x2, w_gate, w_up)
+                and w_gate.shape[1] == x2.shape[1] and prefill_codes_supported(M, (w_gate.shape[0],), x2.shape[1])):
+            # gate + up + SwiGLU as one launch of the kernel for codes that owns M rows; down_proj asks for itself
+            arm = _codes_arm(M)
+            act = _codes_kernels(cls)[arm + 2 if arm < 4 else 5](x2, w_gate, w_up)
             return linear_group(act, [(w_down, None)])[0].view(*x.shape[:-1], -1)
         return swiglu_mlp(x, _bf16_weight(w_gate), _bf16_weight(w_up), _bf16_weight(w_down), norm_src)
     if _decode_own(x, (w_gate, w_up)) and w_gate.stride(0) == w_up.stride(0) and w_gate.shape == w_up.shape \

@@ -1419,6 +1419,78 @@ def _(x, w_gate, s_gate, w_up, s_up):
     return x.new_empty(x.shape[0], w_gate.shape[0])
 
 
+# The prefill kernel for codes (csrc/gemm_codes.hip, any M >= 1): the FP8 / MXFP4 ops above on its entries, without RoPE.
+def _prefill_gemm_launch(entry: str, x: Tensor, ws, ss, bs, outs) -> None:
+    """tn_gemm_prefill_fp8 / _mxfp4 on operands the caller has checked (`_stream_gemm_launch` without the RoPE arguments)."""
+    n = len(ws)
+    arr = lambda ctype, vals: (ctype * n)(*vals)
+    addr = lambda ts: arr(ctypes.c_void_p, [None if t is None else _p(t).value for t in ts])
+    scales = (addr(ss),) + ((arr(ctypes.c_longlong, [t.stride(0) for t in ss]),) if entry.endswith("_mxfp4") else ())
+    _C.check(getattr(_lib(), entry)(_p(x), x.stride(0), x.shape[0], x.shape[1], n, addr(ws),
+                                    arr(ctypes.c_longlong, [w.stride(0) for w in ws]), *scales, addr(bs), addr(outs),
+                                    arr(ctypes.c_longlong, [o.stride(0) for o in outs]),
+                                    arr(ctypes.c_int, [w.shape[0] for w in ws]), _cur()), entry)
+
+
+def linear_prefill_fp8_launch(x: Tensor, ws, ss, bs, outs) -> None:
+    """tn_gemm_prefill_fp8 on operands the caller has checked: outs[i][M, N_i] = x (ws[i] * ss[i])^T (+ bs[i])."""
+    _prefill_gemm_launch("tn_gemm_prefill_fp8", x, ws, ss, bs, outs)
+
+
+def linear_prefill_mxfp4_launch(x: Tensor, ws, ss, bs, outs) -> None:
+    """tn_gemm_prefill_mxfp4 on operands the caller has checked (`linear_prefill_fp8_launch` with block scales)."""
+    _prefill_gemm_launch("tn_gemm_prefill_mxfp4", x, ws, ss, bs, outs)
+
+
+@custom_op(f"{NS}::linear_prefill_fp8", mutates_args=(), device_types="cuda")
+def linear_prefill_fp8(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]]) -> List[Tensor]:
+    """`linear_midm_fp8` without RoPE on any M >= 1 rows (tn_gemm_prefill_fp8): the tiled kernel for prefill."""
+    _no_grad_inputs("linear_prefill_fp8", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_prefill_fp8_launch(x, ws, ss, bs, outs)
+    return outs
+
+
+@custom_op(f"{NS}::linear_prefill_mxfp4", mutates_args=(), device_types="cuda")
+def linear_prefill_mxfp4(x: Tensor, ws: List[Tensor], ss: List[Tensor], bs: List[Optional[Tensor]]) -> List[Tensor]:
+    """`linear_midm_mxfp4` without RoPE on any M >= 1 rows (tn_gemm_prefill_mxfp4)."""
+    _no_grad_inputs("linear_prefill_mxfp4", x)
+    outs = [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+    linear_prefill_mxfp4_launch(x, ws, ss, bs, outs)
+    return outs
+
+
+@linear_prefill_fp8.register_fake
+@linear_prefill_mxfp4.register_fake
+def _(x, ws, ss, bs):
+    return [x.new_empty(x.shape[0], w.shape[0]) for w in ws]
+
+
+@custom_op(f"{NS}::swiglu_prefill_fp8", mutates_args=(), device_types="cuda")
+def swiglu_prefill_fp8(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_midm_fp8` on any M >= 1 rows (tn_gemm_prefill_swiglu_fp8)."""
+    _no_grad_inputs("swiglu_prefill_fp8", x)
+    M, K = x.shape
+    act = x.new_empty(M, w_gate.shape[0])
+    _C.check(_lib().tn_gemm_prefill_swiglu_fp8(_p(x), _p(w_gate), _p(w_up), _p(s_gate), _p(s_up), _p(act), M,
+                                               w_gate.shape[0], K, x.stride(0), w_gate.stride(0), act.stride(0), _cur()),
+             "tn_gemm_prefill_swiglu_fp8")
+    return act
+
+
+@custom_op(f"{NS}::swiglu_prefill_mxfp4", mutates_args=(), device_types="cuda")
+def swiglu_prefill_mxfp4(x: Tensor, w_gate: Tensor, s_gate: Tensor, w_up: Tensor, s_up: Tensor) -> Tensor:
+    """`swiglu_midm_mxfp4` on any M >= 1 rows (tn_gemm_prefill_swiglu_mxfp4)."""
+    _no_grad_inputs("swiglu_prefill_mxfp4", x)
+    return _swiglu_mxfp4("tn_gemm_prefill_swiglu_mxfp4", x, w_gate, s_gate, w_up, s_up)
+
+
+@swiglu_prefill_fp8.register_fake
+@swiglu_prefill_mxfp4.register_fake
+def _(x, w_gate, s_gate, w_up, s_up):
+    return x.new_empty(x.shape[0], w_gate.shape[0])
+
+
 @custom_op(f"{NS}::greedy_step_", mutates_args=("hist", "hist_len", "cache_len", "finished", "n_unfinished"),
            device_types="cuda")
 def greedy_step_(logits: Tensor, hist: Tensor, hist_len: Tensor, cache_len: Tensor, finished: Tensor, n_unfinished: Tensor,
@@ -1885,4 +1957,5 @@ OPS = ("rmsnorm_fwd","rmsnorm_bwd", "layernorm_fwd", "layernorm_bwd", "swiglu_fw
        "attn_decode_", "greedy_step_", "sample_step_", "attn_block_causal_fwd", "vq_nearest", "attn_decode_beam_",
        "beam_step_", "kimi_text_step_", "kaldi_feats", "kaldi_mfcc", "edit_align", "beam_step_edits_",
        "constrain_logits_", "token_scores", "token_scores_", "vad_log_energy", "vad_runs", "attn_extend",
-       "kv_quantize", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_extend_fp8")
+       "kv_quantize", "attn_decode_fp8", "attn_decode_beam_fp8", "attn_extend_fp8",
+       "linear_prefill_fp8", "linear_prefill_mxfp4", "swiglu_prefill_fp8", "swiglu_prefill_mxfp4")
